@@ -21,6 +21,13 @@ end to end. cpu_baseline = the reference libzstd 1.5.7 (oracle/_ref) on host thr
   N > 1: either `python bench.py --gpus N ...` (it starts its own N ranks through torch.distributed.run on 127.0.0.1) or the driver's
   `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...`;
   --dry-launch stops after the process group is formed and the partition agreed (tests/test_distributed_gloo.py runs it at N = 2 on CPU).
+
+A plain run (decompress / compress) does only what its headline needs: it prepares the inputs, warms up, times --steps steps and prints the
+line (metric, value, unit, higher_is_better, dtype, ms_per_step, config). --full adds everything else: the full-size correctness gates, the
+compress / combined / host_api / dict / roundtrip / blocks objects, rooflines, per-kernel times and the CPU baselines.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float64 / float32, ~20 MB): sizes and status of
+every item, two checksums of every item's bytes, and the bytes of a fixed, seeded sample of items. The inputs depend on the arguments only,
+so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -127,11 +134,12 @@ def cpu_model():
 USE_DIST = False      # set by main(): world > 1 (or forced, see there)
 
 
-def emit(line):
+def emit(line, checked=True):
     """rank 0's one JSON line. A run with ZHIP_BENCH_NO_VERIFY (diagnostic kernel variants that produce wrong bytes on purpose) skipped the
-    full-size correctness gates: its line says so and carries no claim of exactness."""
+    full-size correctness gates: its line says so and carries no claim of exactness. A plain run (checked=False) has no gates:
+    its `verified` is null."""
     verified = not os.environ.get("ZHIP_BENCH_NO_VERIFY")
-    line["verified"] = verified
+    line["verified"] = verified if checked else None
     if not verified:
         line["metric"] = "UNVERIFIED DIAGNOSTIC RUN (ZHIP_BENCH_NO_VERIFY): " + line.get("metric", "")
         for k in ("round_trip_exact", "bit_exact_vs_libzstd"):
@@ -403,8 +411,9 @@ SPAN_NAME = "zhip_decode_pipeline_span"
 ENC_KERNELS = (1, 5, 6, 8)
 
 
-def run_decompress(job, ctx, frames, csizes, raw, item, steps, warmup):
-    """the decode direction on `frames` (list of bytes) whose originals are raw [F, item] in HBM. Returns (elapsed, ktimes)."""
+def run_decompress(job, ctx, frames, csizes, raw, item, steps, warmup, check=True, outputs=None):
+    """the decode direction on `frames` (list of bytes) whose originals are raw [F, item] in HBM. Returns (elapsed, ktimes, out_sizes).
+    check=False skips the correctness gate; a dict `outputs` receives the buffers the last step wrote (dst, sizes, status)."""
     F = len(frames)
     dev = job.dev
     offs = np.zeros(F, dtype=np.int64)
@@ -416,7 +425,9 @@ def run_decompress(job, ctx, frames, csizes, raw, item, steps, warmup):
     out_sizes = torch.zeros(F, dtype=torch.int64, device=dev)
     status = torch.zeros(F, dtype=torch.int32, device=dev)
     elapsed, ktimes = job.timed(lambda: ctx.decompress(src, src_segs, dst, dst_segs, out_sizes, status), ctx, DEC_KERNELS, steps, warmup)
-    if os.environ.get("ZHIP_BENCH_NO_VERIFY"):                     # diagnostic kernel variants that produce wrong bytes on purpose: the line says so (main())
+    if outputs is not None:
+        outputs.update(dst=dst.view(F, item), sizes=out_sizes, status=status)
+    if not check or os.environ.get("ZHIP_BENCH_NO_VERIFY"):                   # diagnostic kernel variants that produce wrong bytes on purpose: the line says so (main())
         return elapsed, ktimes, out_sizes
     # correctness gate at full size: every frame decoded, every byte equals the original input
     assert int(status.abs().max().item()) == 0, "a frame failed to decode"
@@ -425,8 +436,9 @@ def run_decompress(job, ctx, frames, csizes, raw, item, steps, warmup):
     return elapsed, ktimes, out_sizes
 
 
-def run_compress(job, ctx, raw, frames, item, steps, warmup):
-    """the encode direction on raw [F, item]: every frame must be byte-identical to libzstd's (`frames`). Returns (elapsed, total, ktimes)."""
+def run_compress(job, ctx, raw, frames, item, steps, warmup, check=True, outputs=None):
+    """the encode direction on raw [F, item]: every frame must be byte-identical to libzstd's (`frames`). Returns (elapsed, total, ktimes).
+    check=False skips the per-frame comparison; a dict `outputs` receives the buffers the last step wrote (dst, sizes, status)."""
     F = raw.shape[0]
     dev = job.dev
     bound = (item + (item >> 8) + 64 + 15) & ~15
@@ -437,6 +449,10 @@ def run_compress(job, ctx, raw, frames, item, steps, warmup):
     status = torch.zeros(F, dtype=torch.int32, device=dev)
     src = raw.reshape(-1)
     elapsed, ktimes = job.timed(lambda: ctx.compress(src, src_segs, dst, dst_segs, out_sizes, status), ctx, ENC_KERNELS, steps, warmup)
+    if outputs is not None:
+        outputs.update(dst=dst.view(F, bound), sizes=out_sizes, status=status)
+    if not check:
+        return elapsed, int(out_sizes.sum().item()), ktimes
     assert int(status.abs().max().item()) == 0, "a frame failed to compress"
     sizes = out_sizes.cpu().numpy()
     out = dst.view(F, bound).cpu().numpy()
@@ -444,6 +460,48 @@ def run_compress(job, ctx, raw, frames, item, steps, warmup):
         assert out[i, : sizes[i]].tobytes() == frames[i], "frame %d differs from libzstd 1.5.7" % i
     del dst
     return elapsed, int(sizes.sum()), ktimes
+
+
+DUMP_SEED = 20261016          # --dump-outputs: which items are written out whole
+DUMP_SAMPLE_ITEMS = 32
+DUMP_CHUNK = 256              # rows per checksum pass on the device
+
+
+def item_checksums(rows, lens):
+    """per row of rows [F, W] (uint8, on any device): the sum of the bytes rows[i, :lens[i]] and their sum weighted by (position % 8191) + 1
+    -- exact in float64 (at most 255 * 8191 * W per row) -- so that every byte of every item enters the dump. Returns two float64 arrays."""
+    F, W = rows.shape
+    pos = torch.arange(W, dtype=torch.int32, device=rows.device)
+    weight = pos % 8191 + 1
+    s, ws = [], []
+    for a in range(0, F, DUMP_CHUNK):
+        x = rows[a:a + DUMP_CHUNK].to(torch.int32)
+        x = x * (pos[None, :] < lens[a:a + DUMP_CHUNK, None]).to(torch.int32)
+        s.append(x.sum(1, dtype=torch.int64))
+        ws.append((x * weight).sum(1, dtype=torch.int64))
+    return torch.cat(s).cpu().numpy().astype(np.float64), torch.cat(ws).cpu().numpy().astype(np.float64)
+
+
+def dump_outputs(out_dir, prefix, outputs, rank, world):
+    """--dump-outputs: what the last timed step handed its caller (outputs: dst [F, W] uint8, sizes [F] int64, status [F] int32) as float
+    .npy files under out_dir: <prefix>_sizes, status, <prefix>_sum and <prefix>_weighted_sum over every item, and a fixed, seeded sample of
+    DUMP_SAMPLE_ITEMS whole items (<prefix>_sample, float32 [n, W], zero past each item's size; sample_index = their item numbers)."""
+    dst, sizes, status = outputs["dst"], outputs["sizes"], outputs["status"]
+    F, W = dst.shape
+    lens = sizes.clamp(0, W)
+    total, weighted = item_checksums(dst, lens)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(F, size=min(F, DUMP_SAMPLE_ITEMS), replace=False))
+    it = torch.from_numpy(idx).to(dst.device)
+    rows = dst[it]
+    rows = rows * (torch.arange(W, device=dst.device)[None, :] < lens[it][:, None]).to(rows.dtype)
+    arrays = {prefix + "_sizes": sizes.cpu().numpy().astype(np.float64), "status": status.cpu().numpy().astype(np.float64),
+              prefix + "_sum": total, prefix + "_weighted_sum": weighted,
+              prefix + "_sample": rows.cpu().numpy().astype(np.float32), "sample_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+    return sorted(arrays)
 
 
 def sample_blob(frames, n):
@@ -789,7 +847,16 @@ def main():
     ap.add_argument("--dry-launch", action="store_true", help="form the process group, agree on the partition, exit (no kernels; gloo where there is no GPU)")
     ap.add_argument("--host-api-child", default=None, metavar="SLOTS",
                     help="(internal) measure the host-buffer calls over these device slots ('all' = every visible device, or a ZHIP_DEVICES list) in this process and print the object")
+    ap.add_argument("--full", action="store_true",
+                    help="decompress / compress: also run the correctness gates, the other directions and configs, rooflines, per-kernel times and the CPU baselines "
+                         "(a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="decompress / compress: write what the last timed step computed to DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.config or args.direction or "decompress") not in ("decompress", "compress"):
+        ap.error("--dump-outputs is available for --config decompress and compress")
     if args.host_api_child:
         return host_api_child(args)
     config = args.config or args.direction or "decompress"
@@ -870,13 +937,23 @@ def bench_frames(args, config, rank, world, dev):
             junk = [torch.empty(int(g) << 30, dtype=torch.uint8, device=dev) for g in os.environ["ZHIP_BENCH_PREFRAG"].split(",")]
             for t in junk: t.fill_(1)
             torch.cuda.synchronize(); del junk, t; torch.cuda.empty_cache()
-        elapsed, ctot2, ktimes = run_compress(job, ctx, raw, frames, FRAME, args.steps, args.warmup)
+        outs = {} if args.dump_outputs else None
+        elapsed, ctot2, ktimes = run_compress(job, ctx, raw, frames, FRAME, args.steps, args.warmup, check=args.full, outputs=outs)
         ms = elapsed / args.steps * 1e3
         cfg["workload"] = "multi_compress_to_buffer (device-resident): %d x 128 KiB Silesia-like inputs per GPU, level 3" % F
         line = {"metric": "GB/s uncompressed throughput, batch compress of 128 KiB inputs at level 3 (bit-exact vs libzstd 1.5.7)",
                 "value": round(world * F * FRAME * args.steps / elapsed / 1e9, 3), "unit": "GB/s", "n_gpus": world, "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                 "dtype": "u8", "data": "synthetic", "config": cfg}
+        if outs:
+            line["outputs"] = dump_outputs(args.dump_outputs, "compressed", outs, rank, world)
+            outs.clear()
+        if not args.full:
+            if rank == 0:
+                line["setup_s"] = {"generate": round(t_gen, 1), "host_compress": round(t_comp, 1)}
+                emit(line, checked=False)
+            ctx.close()
+            return
         if rank == 0:
             line["kernels"] = kernels_obj(ctx, ktimes)
             line["regime"] = e1f_regime(ctx, ktimes, F)
@@ -890,7 +967,8 @@ def bench_frames(args, config, rank, world, dev):
             emit(line)
         return
 
-    elapsed, ktimes, out_sizes = run_decompress(job, ctx, frames, csizes, raw, FRAME, args.steps, args.warmup)
+    outs = {} if args.dump_outputs else None
+    elapsed, ktimes, out_sizes = run_decompress(job, ctx, frames, csizes, raw, FRAME, args.steps, args.warmup, check=args.full, outputs=outs)
     if USE_DIST:
         import torch.distributed as dist
         # the only cross-rank exchange the path needs: the segment table of the sharded result (payload stays per GPU)
@@ -906,6 +984,15 @@ def bench_frames(args, config, rank, world, dev):
         "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
         "config": cfg,
     }
+    if outs:
+        line["outputs"] = dump_outputs(args.dump_outputs, "decompressed", outs, rank, world)
+        outs.clear()
+    if not args.full:
+        if rank == 0:
+            line["setup_s"] = {"generate": round(t_gen, 1), "host_compress": round(t_comp, 1)}
+            emit(line, checked=False)
+        ctx.close()
+        return
     sec = frame_sections(frames)
     if rank == 0:
         line["kernels"] = kernels_obj(ctx, ktimes)

@@ -77,7 +77,7 @@ double zo_mt_bench(const char* libpath, int decompress, const uint8_t* src, cons
 double zo_mt_bench_dict(const char* libpath, int decompress, const uint8_t* src, const uint64_t* offs, uint32_t n, size_t maxOut,
                         int level, int threads, int passes, const void* dict, size_t dictSize, double* times)
 {
-    void* h = dlopen(libpath, RTLD_NOW | RTLD_LOCAL);
+    void* h = dlopen(libpath, RTLD_NOW | RTLD_LOCAL | RTLD_DEEPBIND);   /* its own symbols first: see tests/reflib.py */
     if (!h) return -1.0;
     zapi z;
     *(void**)&z.createCCtx = dlsym(h, "ZSTD_createCCtx"); *(void**)&z.freeCCtx = dlsym(h, "ZSTD_freeCCtx");
@@ -161,7 +161,7 @@ static void* prep_worker(void* arg)
 int zo_mt_compress_all(const char* libpath, const uint8_t* src, const uint64_t* offs, uint32_t n, int level, int threads,
                        const void* dict, size_t dictSize, uint8_t* out, size_t slotCap, uint64_t* outSizes)
 {
-    void* h = dlopen(libpath, RTLD_NOW | RTLD_LOCAL);
+    void* h = dlopen(libpath, RTLD_NOW | RTLD_LOCAL | RTLD_DEEPBIND);   /* its own symbols first: see tests/reflib.py */
     if (!h) return -1;
     zapi z; memset(&z, 0, sizeof z);
     *(void**)&z.createCCtx = dlsym(h, "ZSTD_createCCtx"); *(void**)&z.freeCCtx = dlsym(h, "ZSTD_freeCCtx");

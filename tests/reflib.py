@@ -73,7 +73,9 @@ def have_oracle():
 
 class RefZstd:
     def __init__(self):
-        self.lib = L = C.CDLL(REF_SO)
+        # RTLD_DEEPBIND: the library's calls to its own exported functions must reach its own code, not the older libzstd that torch's
+        # libraries bring into the process's global scope (the image copy is not linked -Bsymbolic like oracle/_ref)
+        self.lib = L = C.CDLL(REF_SO, mode=C.RTLD_LOCAL | getattr(os, "RTLD_DEEPBIND", 0))
         for name, res, args in [
             ("ZSTD_versionNumber", C.c_uint, []),
             ("ZSTD_createCCtx", C.c_void_p, []),

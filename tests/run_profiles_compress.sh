@@ -3,7 +3,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; cd $R
 F=${PROF_FRAMES:-32768}
 P=gpurun_out/profc; rm -rf $P; mkdir -p $P/kt $P/fetch $P/write $P/sq $P/tcc
-B="python bench.py --direction compress --frames $F --no-cpu-baseline"
+B="python bench.py --full --direction compress --frames $F --no-cpu-baseline"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $P/kt -- $B --steps 2 --warmup 1 > $P/kt/bench.json 2> $P/kt/err.log
 timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $P/fetch -- $B --steps 1 --warmup 0 > $P/fetch/bench.json 2> $P/fetch/err.log
 timeout 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $P/write -- $B --steps 1 --warmup 0 > $P/write/bench.json 2> $P/write/err.log

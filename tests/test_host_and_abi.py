@@ -219,6 +219,37 @@ def test_bench_line_shape_for_the_driver():
         assert '"%s"' % k in tail, k
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float .npy files only, sizes / status as returned, both checksums of every item over its first `size` bytes
+    (several checksum chunks), the seeded sample whole and zero past each size, the same files from the same outputs, well under 64 MB"""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_CHUNK", 16)
+    g = torch.Generator().manual_seed(7)
+    F, W = 100, 300
+    dst = torch.randint(0, 256, (F, W), dtype=torch.uint8, generator=g)
+    sizes = torch.randint(0, W + 1, (F,), dtype=torch.int64, generator=g)
+    status = torch.zeros(F, dtype=torch.int32); status[3] = -20
+    outs = {"dst": dst, "sizes": sizes, "status": status}
+    names = bench.dump_outputs(str(tmp_path / "a"), "decompressed", outs, 0, 1)
+    bench.dump_outputs(str(tmp_path / "b"), "decompressed", outs, 0, 1)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in names}
+    assert sorted(os.listdir(str(tmp_path / "a"))) == sorted(n + ".npy" for n in names)
+    for n, a in got.items():
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, np.load(str(tmp_path / "b" / (n + ".npy")))), n
+    assert sum(os.path.getsize(str(tmp_path / "a" / (n + ".npy"))) for n in names) < 64 << 20
+    d, ln = dst.numpy().astype(np.int64), sizes.numpy()
+    mask = np.arange(W)[None, :] < ln[:, None]
+    assert np.array_equal(got["decompressed_sizes"], ln.astype(np.float64)) and got["status"][3] == -20
+    assert np.array_equal(got["decompressed_sum"], (d * mask).sum(1).astype(np.float64))
+    assert np.array_equal(got["decompressed_weighted_sum"], (d * mask * (np.arange(W) % 8191 + 1)).sum(1).astype(np.float64))
+    idx = got["sample_index"].astype(np.int64)
+    assert len(idx) == bench.DUMP_SAMPLE_ITEMS and len(set(idx.tolist())) == len(idx)
+    assert np.array_equal(got["decompressed_sample"], (d * mask)[idx].astype(np.float32))
+
+
 def test_c_partition_rule_is_the_references(zstd):
     """zhip_partition_by_bytes (what zhip_compress_batch / zhip_decompress_batch cut a batch over the node's devices with) against the reference's
     dispatcher loop restated here line by line (c-ext/compressor.c:1127-1216: bytesPerWorker = total / threadCount, a worker's run closes once its
