@@ -159,7 +159,10 @@ void      zhip_ctx_set_size_hint(zhip_ctx*, uint64_t maxItemBytes);
 int zhip_decompress_batch_device(zhip_ctx*, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
                                  void* d_dst, const zhip_segment* d_dstSegs,
                                  uint64_t* d_outSizes, int32_t* d_status, void* stream);
-/* d_dstSegs[i].length must be >= zhip_compress_bound(d_srcSegs[i].length). */
+/* d_dstSegs[i].length must be >= zhip_compress_bound(d_srcSegs[i].length): every kernel that may serve an item (one-block sources, sources of
+ * several blocks, any batch size) refuses a smaller slot with d_status[i] = 70 (Destination buffer is too small) and writes nothing into it,
+ * however small the frame would have come out. Segments need no alignment and may come in any order; several items may name one source.
+ * Nothing outside [offset, offset + length) of an item's destination segment is written, in either direction. */
 int zhip_compress_batch_device(zhip_ctx*, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
                                void* d_dst, const zhip_segment* d_dstSegs,
                                uint64_t* d_outSizes, int32_t* d_status, void* stream);

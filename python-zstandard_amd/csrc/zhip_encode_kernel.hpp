@@ -2596,6 +2596,13 @@ ZH_DEVFN void ze_split_body(const ZhipEncodeArgs& a, ZeLDS& L)
     ze_fence();
 }
 
+// ZSTD_compressBound (zstd.h:249) == zhip_compress_bound: every frame encoder refuses a destination slot below it with ZE_DST_TOO_SMALL before
+// writing anything, whatever kernel serves the source and however small the frame would come out (include/zstd_hip.h states the rule)
+ZH_DEV uint64_t ze_compress_bound(uint64_t n)
+{
+    return n + (n >> 8) + (n < (128u << 10) ? (((128u << 10) - n) >> 11) : 0);
+}
+
 // A frame of several blocks (ZSTD_compress_frameChunk, zstd.c:27545): sources above 128 KiB. All lanes call.
 // useFlat: take the flat match kernel's sequences where it left some (ZeMbBlock, zhip_format.hpp) -- returns ZE_MB_RETRY when what really
 // happened to the blocks is not what that search assumed; the caller then runs the frame again with useFlat = false.
@@ -2610,7 +2617,7 @@ ZH_DEVFN int ze_frame_multi_impl(const ZhipEncodeArgs& a, ZeLDS& L, ZeLDSMulti* 
     const uint64_t cap64 = a.dstSegs[2 * (size_t)f + 1];
     if (srcSize64 >= (1ull << 31)) return ZE_PARAM_UNSUPPORTED;                   // index overflow correction: not implemented
     const uint32_t srcSize = (uint32_t)srcSize64;
-    if (cap64 < (uint64_t)srcSize + (srcSize >> 8)) return ZE_DST_TOO_SMALL;
+    if (cap64 < ze_compress_bound(srcSize)) return ZE_DST_TOO_SMALL;
     ZePar cp;
     const int e = ze_get_cparams(cp, a.rows, srcSize);
     if (e) return e;
@@ -2725,8 +2732,7 @@ ZH_DEVFN int ze_frame(const ZhipEncodeArgs& a, ZeLDS& L, uint32_t f, uint8_t* ws
         else return ZE_PARAM_UNSUPPORTED;
     }
     const uint32_t srcSize = (uint32_t)srcSize64;
-    const uint32_t bound = srcSize + (srcSize >> 8) + (srcSize < (128u << 10) ? (((128u << 10) - srcSize) >> 11) : 0);
-    if (cap64 < bound) return ZE_DST_TOO_SMALL;
+    if (cap64 < ze_compress_bound(srcSize)) return ZE_DST_TOO_SMALL;
     const uint32_t cap = cap64 > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)cap64;
     ZePar cp;
     const int e = ze_get_cparams(cp, a.rows, srcSize);
