@@ -137,7 +137,29 @@ void zhip_free_payload(void* data);     /* a zhip_outbuf.data pointer: back to t
 /* ---- device-resident batch API (all pointers are HBM addresses on the current device) ----
  * A context owns the per-launch scratch (literal buffers, hash tables, work counters, status words) so repeated
  * calls allocate nothing. `stream` is a hipStream_t passed as void* (NULL = default stream). Calls are asynchronous;
- * zhip_ctx_sync() waits and returns the first failing frame (lowest index) like the reference's workers do. */
+ * zhip_ctx_sync() waits and returns the first failing frame (lowest index) like the reference's workers do.
+ *
+ * Ordering and threads (pinned by tests/test_gpu_streams.py and tests/test_gpu_concurrent_callers.py):
+ *   Stream order.   zhip_decompress_batch_device, zhip_compress_batch_device and zhip_compact_device are ordered after everything queued on
+ *                   `stream` before the call, and everything queued on `stream` after the call returns sees all of its outputs (d_dst,
+ *                   d_outSizes, d_status): producers and consumers on the same stream need no host synchronisation, a blocking or a
+ *                   non-blocking stream alike. The library's internal streams (the decode pipeline's chunk slots and their side streams) are
+ *                   joined to `stream` at both ends of every call and never show to the caller. Work on OTHER streams is the caller's to order.
+ *                   A call may wait on the host while it (re)allocates scratch or -- the first compress launch of 16 384 sources or more -- picks
+ *                   its tables; it never needs the caller to.
+ *   One call sequence per context.  A context is one queue of calls: calls on it may follow each other with nothing waited for in between
+ *                   when they are made from one host thread at a time and on one stream (scratch is reused in stream order). Two host threads on
+ *                   one context, or two streams on one context with work in flight on both, need the caller's own ordering. Different
+ *                   contexts are independent: any threads, any streams.
+ *   Setters.        zhip_ctx_set_ddict and zhip_ctx_set_cparams may be called between asynchronous calls without waiting for them: a setter that
+ *                   uploads or digests anything (another dictionary, the same dictionary for other parameters) first waits for ALL work in
+ *                   flight on the device, so calls queued before it finish with the tables they were queued with and calls made after it use
+ *                   the new ones. A setter that finds its dictionary already digested (the fingerprint matches), clears the dictionary or
+ *                   changes only level / flags / format / size hint touches host state, which every call reads when it is made, and does not wait.
+ *   Host-buffer calls.  zhip_compress_batch / zhip_decompress_batch and zhip_thread_memory_size may be called from any number of threads
+ *                   concurrently (contexts are per thread, the pinned pool and the device slots' worker threads are shared and serialise
+ *                   inside); a payload may be released with zhip_free_payload / zhip_free_outbufs on any thread, also after the thread that
+ *                   received it has exited. */
 typedef struct zhip_ctx zhip_ctx;
 zhip_ctx* zhip_ctx_create(void);
 void      zhip_ctx_destroy(zhip_ctx*);

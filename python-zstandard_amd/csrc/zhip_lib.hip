@@ -566,6 +566,10 @@ extern "C" int zhip_ctx_set_ddict(zhip_ctx* c, const void* hostDict, size_t dict
     // unless a full dictionary was demanded, which is then "Dictionary is corrupted"
     const bool hasMagic = dictSize >= 8 && rd32((const uint8_t*)hostDict) == ZF_DICT_MAGIC;
     if (dictType == ZHIP_DICT_FULLDICT && !hasMagic) { c->ddictKey = 0; return -ZE_DICT_CORRUPTED; }
+    // A re-upload waits for everything in flight first (include/zstd_hip.h, "Setters"): the copies below are blocking ones and the digest kernels run on stream 0,
+    // neither ordered against the non-blocking slot streams or a non-blocking caller stream on which an earlier call's kernels may still be reading these buffers.
+    // Re-uploads are rare and the fingerprint hit above returns without it, so the wait is off the hot path.
+    HIP_TRY(hipDeviceSynchronize());
     if (c->dictBlob.reserve(dictSize + 64)) { c->ddictKey = 0; return g_reserveRc; }       // (+ 64: K3 reads whole 32-byte windows)
     if (c->dictEntropy.reserve(sizeof(ZhipDictEntropy))) { c->ddictKey = 0; return g_reserveRc; }
     HIP_TRY(hipMemcpy(c->dictBlob.p, hostDict, dictSize, hipMemcpyHostToDevice));
@@ -647,6 +651,7 @@ extern "C" int zhip_ctx_set_cparams(zhip_ctx* c, const zhip_cparams* p)
         // (what ZSTD_createCDict does on the host in the reference, zstd.c:28490-28614)
         if (p->dictSize > 0x7FFFFFFFu) { g_lastError = "dictionary too large"; return ZHIP_ERR_UNSUPPORTED; }
         const size_t cells = (size_t)1 << ZE_CDICT_MAX_HLOG;
+        HIP_TRY(hipDeviceSynchronize());      // (as in zhip_ctx_set_ddict: an earlier call's kernels may still be reading the buffers written below)
         if (c->cdictBlob.reserve(p->dictSize + 16) || c->cdictEntropy.reserve(sizeof(ZhipDictEntropy)) ||
             c->cdictDigest.reserve(sizeof(ZeCDict)) || c->cdictTables.reserve(3 * cells * sizeof(uint32_t))) return g_reserveRc;
         HIP_TRY(hipMemcpy(c->cdictBlob.p, p->dict, p->dictSize, hipMemcpyHostToDevice));

@@ -260,17 +260,14 @@ def compress_table(corpus, ref):
     return srcs, items, short, _ref_frames(ref, srcs)
 
 
-@pytest.mark.parametrize("arrangement", ["lds", "flat", "several_blocks"])
-def test_compress_segment_tables_with_canaries(zstd, compress_table, arrangement):
-    """Sources in shuffled order at odd offsets with gaps, one source used by three items, empty sources, destination slots of exactly
-    zhip_compress_bound at odd offsets with gaps and in yet another order, three of bound - 1 (an empty, a one-block and a several-block source).
-    Through the LDS-source kernel (a small batch), the flat search (ZHIP_E1LDS_MAX=0) and the several-block flat search (ZHIP_MBC_MIN=0 + a size
-    hint). Every status-0 frame is libzstd's; every short slot is refused with status 70 (include/zstd_hip.h: the rule of every kernel); no byte
-    outside any slot changes."""
-    import torch
-    srcs, items, short, want = compress_table
-    rng = np.random.default_rng(["lds", "flat", "several_blocks"].index(arrangement) + 7)
-    n = len(items)
+COMPRESS_ARRANGEMENTS = ["lds", "flat", "several_blocks"]
+
+
+def _compress_table_layout(table, rng):
+    """where the compress table lies for one call: sources in shuffled order at odd offsets with gaps in an arena of 0x3C, destination slots of
+    zhip_compress_bound (the short ones one byte less) at odd offsets with gaps in yet another order. Returns (source arena, the items' source
+    offsets, the items' source lengths, slot offsets, slot capacities, destination arena size)."""
+    srcs, items, short, _ = table
     slens = np.array([len(s) for s in srcs], dtype=np.int64)
     soffs, sarena = _odd_layout(rng, slens, rng.permutation(len(srcs)))
     src_np = np.full(sarena, 0x3C, dtype=np.uint8)
@@ -278,27 +275,52 @@ def test_compress_segment_tables_with_canaries(zstd, compress_table, arrangement
         src_np[o:o + len(s)] = np.frombuffer(s, dtype=np.uint8)
     caps = np.array([_bound(len(srcs[s])) for s in items], dtype=np.int64)
     caps[short] -= 1
-    doffs, darena = _odd_layout(rng, caps, rng.permutation(n))
+    doffs, darena = _odd_layout(rng, caps, rng.permutation(len(items)))
+    return src_np, soffs[items], slens[items], doffs, caps, darena
+
+
+def _compress_table_context(table, arrangement):
+    """a fresh context that serves the table through the LDS-source kernel (a small batch), the flat search (ZHIP_E1LDS_MAX=0) or the
+    several-block flat search (ZHIP_MBC_MIN=0 + a size hint)"""
+    env = {"lds": {}, "flat": {"ZHIP_E1LDS_MAX": "0"}, "several_blocks": {"ZHIP_MBC_MIN": "0"}}[arrangement]
+    return _context(env, hint=max(len(s) for s in table[0]) if arrangement == "several_blocks" else 0)
+
+
+def _check_compress_table(label, table, st, sz, got, doffs, caps):
+    """every status-0 frame is libzstd's; every short slot is refused with status 70; no byte outside any slot changed"""
+    srcs, items, short, want = table
+    for i, s in enumerate(items):
+        if i in short:
+            assert st[i] == ZE_DST_TOO_SMALL, (label, "slot of bound - 1", i, len(srcs[s]), int(st[i]))
+        else:
+            assert st[i] == 0, (label, i, len(srcs[s]), int(st[i]))
+            assert got[doffs[i]: doffs[i] + sz[i]].tobytes() == want[s], (label, i, len(srcs[s]))
+    ok, where = _outside_slots_untouched(got, doffs, caps)
+    assert ok, (label, "bytes outside the slots changed at", where)
+
+
+@pytest.mark.parametrize("arrangement", COMPRESS_ARRANGEMENTS)
+def test_compress_segment_tables_with_canaries(zstd, compress_table, arrangement):
+    """Sources in shuffled order at odd offsets with gaps, one source used by three items, empty sources, destination slots of exactly
+    zhip_compress_bound at odd offsets with gaps and in yet another order, three of bound - 1 (an empty, a one-block and a several-block source).
+    Through the LDS-source kernel (a small batch), the flat search (ZHIP_E1LDS_MAX=0) and the several-block flat search (ZHIP_MBC_MIN=0 + a size
+    hint). Every status-0 frame is libzstd's; every short slot is refused with status 70 (include/zstd_hip.h: the rule of every kernel); no byte
+    outside any slot changes."""
+    import torch
+    rng = np.random.default_rng(COMPRESS_ARRANGEMENTS.index(arrangement) + 7)
+    n = len(compress_table[1])
+    src_np, soffs, slens, doffs, caps, darena = _compress_table_layout(compress_table, rng)
     dev = _dev()
     dst = torch.full((darena,), CANARY, dtype=torch.uint8, device=dev)
     out_sizes = torch.zeros(n, dtype=torch.int64, device=dev)
     status = torch.full((n,), -1, dtype=torch.int32, device=dev)
-    env = {"lds": {}, "flat": {"ZHIP_E1LDS_MAX": "0"}, "several_blocks": {"ZHIP_MBC_MIN": "0"}}[arrangement]
-    ctx = _context(env, hint=max(slens) if arrangement == "several_blocks" else 0)
+    ctx = _compress_table_context(compress_table, arrangement)
     try:
-        ctx.compress(_t(src_np), _segs(soffs[items], slens[items]), dst, _segs(doffs, caps), out_sizes, status)
+        ctx.compress(_t(src_np), _segs(soffs, slens), dst, _segs(doffs, caps), out_sizes, status)
         torch.cuda.synchronize()
     finally:
         ctx.close()
-    st, sz, got = status.cpu().numpy(), out_sizes.cpu().numpy(), dst.cpu().numpy()
-    for i, s in enumerate(items):
-        if i in short:
-            assert st[i] == ZE_DST_TOO_SMALL, (arrangement, "slot of bound - 1", i, len(srcs[s]), int(st[i]))
-        else:
-            assert st[i] == 0, (arrangement, i, len(srcs[s]), int(st[i]))
-            assert got[doffs[i]: doffs[i] + sz[i]].tobytes() == want[s], (arrangement, i, len(srcs[s]))
-    ok, where = _outside_slots_untouched(got, doffs, caps)
-    assert ok, (arrangement, "bytes outside the slots changed at", where)
+    _check_compress_table(arrangement, compress_table, status.cpu().numpy(), out_sizes.cpu().numpy(), dst.cpu().numpy(), doffs, caps)
 
 
 @pytest.fixture(scope="module")
@@ -589,11 +611,9 @@ def _decode_batch(pool, ref, n, chunk, seed, several_block_mode=False):
     return frames, caps, want, damaged
 
 
-def _decode(ctx, batch, rng):
-    """one ctx.decompress over `batch`: frames at odd offsets with gaps, destination slots of the items' capacities at odd offsets with gaps in
-    shuffled order and canaries around them, status -1 and SIZE_SENTINEL before the call. Returns (launches per timer, status, sizes,
-    destination arena, slot offsets)."""
-    import torch
+def _decode_layout(batch, rng):
+    """where `batch` lies for one call: frames at odd offsets with gaps in an arena of 0x3C, destination slots of the items' capacities at odd
+    offsets with gaps in shuffled order. Returns (source arena, frame offsets, frame lengths, slot offsets, destination arena size)."""
     frames, caps, _, _ = batch
     n = len(frames)
     flens = np.fromiter((len(f) for f in frames), dtype=np.int64, count=n)
@@ -602,6 +622,17 @@ def _decode(ctx, batch, rng):
     for f, o in zip(frames, soffs):
         src_np[o:o + len(f)] = np.frombuffer(f, dtype=np.uint8)
     doffs, darena = _odd_layout(rng, caps, rng.permutation(n))
+    return src_np, soffs, flens, doffs, darena
+
+
+def _decode(ctx, batch, rng):
+    """one ctx.decompress over `batch`: frames at odd offsets with gaps, destination slots of the items' capacities at odd offsets with gaps in
+    shuffled order and canaries around them, status -1 and SIZE_SENTINEL before the call. Returns (launches per timer, status, sizes,
+    destination arena, slot offsets)."""
+    import torch
+    frames, caps, _, _ = batch
+    n = len(frames)
+    src_np, soffs, flens, doffs, darena = _decode_layout(batch, rng)
     dev = _dev()
     src = _t(src_np)
     dst = torch.full((darena,), CANARY, dtype=torch.uint8, device=dev)
