@@ -1546,6 +1546,8 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
                         // step can copy as much as is already final -- the copied length doubles instead of advancing a byte at a time
                         // (what has been written is final and periodic, so the source is simply the `span` bytes before the write
                         // position, span a multiple of the period that doubles while whole spans are copied -- no division)
+                        // (the cap at 32 below cannot bind while ZD_COOP_LEN <= 32 -- only matches up to ZD_COOP_LEN come here, so c <= nLen <= 32 --; it is what
+                        // keeps the four-register copy right should ZD_COOP_LEN grow)
                         uint32_t done = 0, span = myOF;
                         while (done < nLen) {
                             uint32_t c = span; if (c > nLen - done) c = nLen - done; if (c > 32) c = 32;

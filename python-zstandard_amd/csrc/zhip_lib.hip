@@ -531,6 +531,18 @@ extern "C" int zhip_ctx_kernel_time(zhip_ctx* c, int direction, double* avgMs, u
     return 0;
 }
 
+extern "C" int zhip_ctx_decode_fallbacks(zhip_ctx* c, uint64_t* frames)
+{
+    if (!c || !frames) return ZHIP_ERR_UNSUPPORTED;
+    *frames = 0;
+    if (!c->pipeCounters.p) return 0;             // no decompress call yet
+    HIP_TRY(hipDeviceSynchronize());
+    uint32_t v = 0;
+    HIP_TRY(hipMemcpy(&v, c->pipeCounters.p, sizeof v, hipMemcpyDeviceToHost));      // word 0 of the pipeline's counters: the fallback list's length
+    *frames = v;
+    return 0;
+}
+
 extern "C" int zhip_ctx_table_pick(zhip_ctx* c, float* ms3)
 {
     if (!c) return 0;

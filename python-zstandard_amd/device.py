@@ -103,6 +103,13 @@ class DeviceBatchContext:
         self.L.zhip_ctx_kernel_time(self.ctx, direction, C.byref(ms), C.byref(n))
         return ms.value, n.value
 
+    def decode_fallbacks(self):
+        """frames of the last decompress() call that the phase-split kernels handed to the generic kernel (waits for the device)"""
+        n = C.c_uint64(0)
+        if self.L.zhip_ctx_decode_fallbacks(self.ctx, C.byref(n)):
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return n.value
+
     def table_pick(self):
         """(candidate times in ms -- 0 = not tried --, index kept) of the compress direction's table placement pick; zeros while none has happened"""
         ms = (C.c_float * 3)()

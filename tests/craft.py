@@ -203,3 +203,200 @@ def encoding_variants():
         ("treeless literals with nothing to inherit", frm([blk(bytes([0x83, 0x40, 0x01]) + b"\x01\x02\x03\x04\x05" + bytes([0]))]), 8, False),
     ]
     return out
+
+
+# ------------------------------------------------------------------------------------------------ frames from explicit sequences, at any size
+# A frame is DESCRIBED as a list of blocks -- ("seq", literals, [(ll, ml, offset value)], options), ("raw", data), ("rle", byte, n) -- which
+# tests/seqmodel.py executes in plain Python and write_frame() below turns into bytes. Nothing above this line changes (tests/golden/edge_frames.json
+# pins its bytes); the writer here has no size caps: 1/2/3-byte sequence counts, predefined or RLE mode per table, raw / RLE / Huffman literals
+# (one or four streams, direct weights, treeless), every frame-header form. The bit streams are built byte by byte, in linear time.
+class _Bits:
+    """LSB-first bit writer; finish() appends the closing 1 bit. The format's decoders read such a stream from its end, so the fields are added in
+    the REVERSE of reading order and every field's most significant bit is read first."""
+    def __init__(self):
+        self.out = bytearray(); self.acc = 0; self.n = 0
+
+    def add(self, v, nb):
+        self.acc |= v << self.n; self.n += nb
+        while self.n >= 8:
+            self.out.append(self.acc & 255); self.acc >>= 8; self.n -= 8
+
+    def finish(self):
+        self.add(1, 1)
+        if self.n: self.out.append(self.acc); self.acc = 0; self.n = 0
+        return bytes(self.out)
+
+
+_TABS = {}
+
+
+def _seq_table(kind, rle_code=None):
+    """(cells, log, {symbol: [states]}) of the predefined table `kind` (0 LL, 1 OF, 2 ML), or the one-cell table of RLE mode"""
+    if rle_code is not None:
+        return [(rle_code, 0, 0)], 0, {rle_code: [0]}
+    if kind not in _TABS:
+        name, n, log = [("zo_ll_defnorm", 36, 6), ("zo_of_defnorm", 29, 5), ("zo_ml_defnorm", 53, 6)][kind]
+        cells = _decode_table(_defnorm(name, n), log)
+        by = {}
+        for x, c in enumerate(cells): by.setdefault(c[0], []).append(x)
+        _TABS[kind] = (cells, log, by)
+    return _TABS[kind]
+
+
+def seq_codes(ll, ml, ofv):
+    """((code, extra value, extra bits) for LL, OF, ML) of one sequence"""
+    lc = ll if ll < 16 else _code(ll, _LL_BASE)
+    mc = ml - 3 if ml < 35 else _code(ml, _ML_BASE)
+    oc = ofv.bit_length() - 1
+    return (lc, ll - _LL_BASE[lc], _LL_BITS[lc]), (oc, ofv - (1 << oc), oc), (mc, ml - _ML_BASE[mc], _ML_BITS[mc])
+
+
+def sequences_section(seqs, modes=(0, 0, 0), count_bytes=None):
+    """count + modes byte + RLE symbols + bit stream for seqs = [(ll, ml, offset value)]; modes = (LL, OF, ML), each 0 (predefined) or 1 (RLE: every
+    sequence then has the same code in that table); count_bytes forces the 1-, 2- or 3-byte form of the count"""
+    n = len(seqs)
+    if count_bytes is None: count_bytes = 1 if n < 128 else 2 if n < 0x7F00 else 3
+    if count_bytes == 1: assert n < 128; head = bytes([n])
+    elif count_bytes == 2: assert n < 0x7F00; head = bytes([0x80 + (n >> 8), n & 255])
+    else: assert 0x7F00 <= n < 0x7F00 + 65536; head = b"\xff" + (n - 0x7F00).to_bytes(2, "little")
+    if n == 0: return head
+    codes = [seq_codes(*q) for q in seqs]
+    tabs = []
+    for k in range(3):
+        if modes[k]:
+            assert all(c[k][0] == codes[0][k][0] for c in codes), "RLE mode needs one code for every sequence"
+            tabs.append(_seq_table(k, codes[0][k][0]))
+        else: tabs.append(_seq_table(k))
+    head += bytes([(modes[0] << 6) | (modes[1] << 4) | (modes[2] << 2)]) + bytes(codes[0][k][0] for k in range(3) if modes[k])
+    # walk backwards: the last sequence takes any state of its symbols; each earlier one the state of its symbol whose range holds its successor.
+    # Fields in reading order per sequence: OF, ML, LL extra bits, then (not after the last) LL, ML, OF state bits -- added here in reverse.
+    w = _Bits()
+    st = [tabs[k][2][codes[n - 1][k][0]][0] for k in range(3)]
+    for i in range(n - 1, -1, -1):
+        (_, lx, lb), (_, ox, ob), (_, mx, mb) = codes[i]
+        if i < n - 1:
+            upd = []
+            for k in range(3):
+                cells = tabs[k][0]; succ = st[k]
+                x = next(x for x in tabs[k][2][codes[i][k][0]] if cells[x][2] <= succ < cells[x][2] + (1 << cells[x][1]))
+                upd.append((succ - cells[x][2], cells[x][1])); st[k] = x
+            w.add(*upd[1]); w.add(*upd[2]); w.add(*upd[0])
+        w.add(lx, lb); w.add(mx, mb); w.add(ox, ob)
+    w.add(st[2], tabs[2][1]); w.add(st[1], tabs[1][1]); w.add(st[0], tabs[0][1])
+    return head + w.finish()
+
+
+class HufTable:
+    """A canonical Huffman code of the format (RFC 8878 4.2.1) over the byte values in `data` (all <= 128, so the weights fit the direct form;
+    at least two different values), code lengths capped at 11 bits. nbits[s] / code[s] per symbol; description() is the tree as direct weights."""
+    def __init__(self, data):
+        import heapq
+        freq = {}
+        for b in data: freq[b] = freq.get(b, 0) + 1
+        assert len(freq) >= 2 and max(freq) <= 128
+        while True:
+            heap = [(f, s, (s,)) for s, f in freq.items()]
+            heapq.heapify(heap)
+            depth = dict.fromkeys(freq, 0)
+            while len(heap) > 1:
+                fa, sa, ma = heapq.heappop(heap); fb, sb, mb = heapq.heappop(heap)
+                for s in ma + mb: depth[s] += 1
+                heapq.heappush(heap, (fa + fb, min(sa, sb), ma + mb))
+            if max(depth.values()) <= 11: break
+            freq = {s: (f >> 1) + 1 for s, f in freq.items()}                 # flatter counts give a flatter tree
+        self.max_bits = mb_ = max(depth.values())
+        self.weights = [mb_ + 1 - depth[s] if s in depth else 0 for s in range(max(freq) + 1)]
+        self.nbits, self.code, pos = {}, {}, 0
+        for w in range(1, mb_ + 1):                                             # lowest weight (longest code) first, symbols in natural order
+            for s, ws in enumerate(self.weights):
+                if ws == w: self.nbits[s] = mb_ + 1 - w; self.code[s] = pos >> (w - 1); pos += 1 << (w - 1)
+        assert pos == 1 << mb_
+
+    def description(self):
+        ws = self.weights[:-1]                                                  # the last symbol's weight is implied
+        ws = ws + [0] * (len(ws) & 1)
+        return bytes([127 + len(self.weights) - 1]) + bytes((ws[i] << 4) | ws[i + 1] for i in range(0, len(ws), 2))
+
+    def stream(self, data):
+        w = _Bits()
+        for b in reversed(data): w.add(self.code[b], self.nbits[b])
+        return w.finish()
+
+
+def literals_section(lits, mode="raw", hdr=None, table=None):
+    """The literals section of `lits`. mode: "raw" / "rle" (hdr = 1, 2 or 3 header bytes, default the shortest), "huf1" / "huf4" (Huffman with `table`
+    written in front, one or four streams) or "treeless1" / "treeless4" (the previous block's table, `table`, not written)."""
+    n = len(lits)
+    if mode in ("raw", "rle"):
+        t = 0 if mode == "raw" else 1
+        if mode == "rle": assert n > 0 and lits == lits[:1] * n
+        if hdr is None: hdr = 1 if n < 32 else 2 if n < 4096 else 3
+        if hdr == 1: assert n < 32; h = bytes([(n << 3) | t])
+        elif hdr == 2: assert n < 4096; h = ((n << 4) | (1 << 2) | t).to_bytes(2, "little")
+        else: assert n < (1 << 20); h = ((n << 4) | (3 << 2) | t).to_bytes(3, "little")
+        return h + (bytes(lits) if mode == "raw" else bytes(lits[:1]))
+    t = 2 if mode.startswith("huf") else 3
+    body = table.description() if t == 2 else b""
+    if mode.endswith("1"):
+        body += table.stream(lits)
+        assert n < 1024 and len(body) < 1024
+        return (t | (0 << 2) | (n << 4) | (len(body) << 14)).to_bytes(3, "little") + body
+    q = (n + 3) // 4
+    parts = [table.stream(lits[i * q:(i + 1) * q]) for i in range(3)] + [table.stream(lits[3 * q:])]
+    assert n >= 3 * q + 1 and all(len(p) < 65536 for p in parts[:3])
+    body += b"".join(len(p).to_bytes(2, "little") for p in parts[:3]) + b"".join(parts)
+    for sf, bits, size in ((1, 10, 3), (2, 14, 4), (3, 18, 5)):
+        if n < (1 << bits) and len(body) < (1 << bits):
+            return (t | (sf << 2) | (n << 4) | (len(body) << (4 + bits))).to_bytes(size, "little") + body
+    raise AssertionError("literals too large")
+
+
+def block(kind, content, last):
+    """3-byte block header + content; kind 0 raw, 1 RLE (content = the byte, size given as a pair (byte, n)), 2 compressed"""
+    if kind == 1:
+        byte, n = content
+        return ((1 if last else 0) | (1 << 1) | (n << 3)).to_bytes(3, "little") + bytes([byte])
+    assert len(content) < (1 << 21)
+    return ((1 if last else 0) | (kind << 1) | (len(content) << 3)).to_bytes(3, "little") + bytes(content)
+
+
+def frame_header(fcs=None, single_segment=False, window_log=17, dict_id=None, checksum=False, fcs_bytes=None):
+    """magic + frame header: single-segment (needs fcs) or a window descriptor; fcs None = no content size; dict_id None = no field;
+    fcs_bytes forces the width of the content-size field (1 only with single_segment, 2, 4 or 8)"""
+    fhd = (0x20 if single_segment else 0) | (4 if checksum else 0)
+    tail = b""
+    if not single_segment: tail += bytes([(window_log - 10) << 3])
+    else: assert fcs is not None
+    if dict_id is not None:
+        nb = 1 if dict_id < 256 else 2 if dict_id < 65536 else 4
+        fhd |= {1: 1, 2: 2, 4: 3}[nb]; tail += dict_id.to_bytes(nb, "little")
+    if fcs is not None:
+        if fcs_bytes is None: fcs_bytes = 1 if single_segment and fcs < 256 else 2 if 256 <= fcs < 65536 + 256 else 4 if fcs < (1 << 32) else 8
+        if fcs_bytes == 1: assert single_segment and fcs < 256
+        if fcs_bytes == 2: assert 256 <= fcs < 65536 + 256
+        fhd |= {1: 0, 2: 1, 4: 2, 8: 3}[fcs_bytes] << 6
+        tail += (fcs - 256 if fcs_bytes == 2 else fcs).to_bytes(fcs_bytes, "little")
+    return b"\x28\xb5\x2f\xfd" + bytes([fhd]) + tail
+
+
+def write_frame(blocks, fcs="auto", content=None, checksum=None, **header):
+    """A frame of `blocks`: ("seq", literals, seqs, options) / ("raw", data) / ("rle", byte, n). A "seq" block's options: lit = the literals mode
+    of literals_section (default "raw"), lit_hdr, modes, count_bytes; Huffman tables are built per block ("huf*") and inherited ("treeless*").
+    fcs "auto" declares len(content); checksum = the 32-bit trailer to write (the caller computes it: Oracle.xxh64(content) & 0xFFFFFFFF, or a
+    wrong one); other keywords go to frame_header."""
+    if fcs == "auto": fcs = len(content)
+    out = [frame_header(fcs=fcs, checksum=checksum is not None, **header)]
+    table = None
+    for i, b in enumerate(blocks):
+        last = i == len(blocks) - 1
+        if b[0] == "raw": out.append(block(0, b[1], last))
+        elif b[0] == "rle": out.append(block(1, (b[1], b[2]), last))
+        else:
+            lits, seqs = bytes(b[1]), b[2]
+            o = b[3] if len(b) > 3 else {}
+            mode = o.get("lit", "raw")
+            if mode.startswith("huf"): table = HufTable(o.get("huf_from", lits))
+            body = literals_section(lits, mode, o.get("lit_hdr"), table) + sequences_section(seqs, o.get("modes", (0, 0, 0)), o.get("count_bytes"))
+            out.append(block(2, body, last))
+    if checksum is not None: out.append((checksum & 0xFFFFFFFF).to_bytes(4, "little"))
+    return b"".join(out)
