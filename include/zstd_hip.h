@@ -199,7 +199,8 @@ int zhip_compact_device(const void* d_slots, const zhip_segment* d_slotSegs, con
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,
  * 4 K3, 5 / 6 the lane-serial match and the entropy kernels, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,
- * 8 the flat match kernel, 9 "zhip_decode_pipeline_span": not a kernel, a chunk's decode pipeline from K1's start to K3's end (what the overlapping kernels cost together). */
+ * 8 the flat match kernel -- the match stage of a chunk whichever of its forms ran: the double-fast search's and, since the fast strategy has a flat search of its own
+ * (levels 1, 2 and negative levels without a dictionary, sources of one block), that one's; the LDS-source kernels of small batches too --, 9 "zhip_decode_pipeline_span": not a kernel, a chunk's decode pipeline from K1's start to K3's end (what the overlapping kernels cost together). */
 const char* zhip_kernel_name(int k);
 int         zhip_ctx_kernel_time(zhip_ctx*, int direction, double* avgMs, uint64_t* launches);
 /* how many frames of the context's last zhip_decompress_batch_device call the phase-split kernels (K1 -> K2 -> K3) handed to the generic kernel: frames of several

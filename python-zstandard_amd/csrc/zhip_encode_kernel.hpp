@@ -1286,6 +1286,162 @@ ZH_DEV uint32_t ze_dfast_flat(uint64_t* seqs, const uint8_t* src, uint32_t srcSi
     return ze_dfast_flat_np<18, false, 2>(seqs, src, 0, srcSize, hlog, clog, mml, hashLong, hashSmall, nullptr, idle ? idle : src, epoch);
 }
 
+// ------------------------------------------------------------------------------------------ E1, flat form (fast strategy, no dictionary)
+// ZSTD_compressBlock_fast_noDict_generic (zstd.c:31906, restated step for step in ze_fast_g below) for a source of one block, flattened the way
+// ze_dfast_flat_np flattens the double-fast search: one LANE per source, one loop, every trip NPAIR iterations of the reference's pair loop. A pair
+// examines positions A and B = A + 1 against the table and C = A + d against the first repeat offset (d = the step the pair BEFORE it left behind:
+// the reference computes ip2 before it raises `step`, zstd.c:32017-32021), and the next pair starts at C. Per pair, in the reference's order:
+//   table[h(A)] = A;  repcode at C?  -> table[h(B)] = B, match at C;   candidate of A?  -> table[h(B)] = B, match at A;
+//   table[h(B)] = B;  candidate of B?  -> table[h(C)] = C only while step <= 4, match at B;   else the next pair.
+// So the cells of A and B are written whatever a pair decides and the cell of C only after a hit at B. Three memory rounds a trip, each issued whole:
+// own bytes (A, B of every pair, the last C, the repcode bytes), the 2 * NPAIR table cells, the bytes of the plausible candidates. The cell reads see
+// the reference's earlier writes of the same trip through forwarding selects (slot order A0 B0 A1 B1 ..: a slot with the hash of an earlier slot takes
+// that slot's new cell, the latest wins); a pair's writes happen only if every pair before it failed, so pairs after a hit are speculative and dropped.
+// Cells: position + 2 in the low 18 bits, an 8-bit tag of the position's first FOUR bytes above (the reference compares 4 bytes whatever minMatch is;
+// minMatch only feeds the hash), the launch's number in the top 6 -- the layout of ze_dfast_flat_np<18>'s cells, so one allocation serves both and
+// needs no zeroing between launches. A cell with another tag or number is "no match" without a fetch. A source of one block never has a window
+// smaller than itself (ze_get_cparams), so the lowest valid index is 2 throughout. Sequences only: the entropy kernel gathers the literals.
+template <int NPAIR>
+ZH_DEV uint32_t ze_fast_flat_np(uint64_t* seqs, const uint8_t* src, uint32_t srcSize, int hlog, int mml, uint32_t tlen, uint32_t* table, const uint8_t* idle, uint32_t epoch = 0)
+{
+    constexpr uint32_t PB = 18, TB = 8, TM = (1u << TB) - 1;
+    constexpr int NS = 2 * NPAIR;                                      // table slots of a trip
+    const uint32_t EPW = (epoch & 63u) << (PB + TB);
+    const uint32_t sh = 32u - (uint32_t)hlog;
+    const int mls = mml <= 4 ? 4 : mml >= 7 ? 7 : mml;
+    const uint32_t shl = mls == 4 ? 32u : (uint32_t)(64 - 8 * mls);
+    const uint64_t prime = mls == 4 ? 2654435761ull : mls == 5 ? 889523592379ull : mls == 6 ? 227718039650203ull : 58295818150454627ull;
+#define ZF_H(u) ((uint32_t)((((u) << shl) * prime) >> 32) >> sh)
+#define ZF_T(u) ((((((uint32_t)(u) * 2654435761u) >> (sh - TB)) & TM) << PB) | EPW)
+#define ZF_IDX(c) ((c) & ((1u << PB) - 1))
+    if (srcSize < 8) return 0;
+    if (!idle) idle = src;
+    const uint32_t ilimit = srcSize - 8;
+    const uint32_t stepSize = tlen + (tlen == 0 ? 1u : 0u) + 1;
+    uint32_t ip = 1, anchor = 0, rep1 = 1, rep2 = 0, nseq = 0;          // repeat offsets (1, 4) at position 1: the second is larger than the history and parked (zstd.c:31951)
+    uint32_t dist = 0, step = 0, nextStep = 0;
+    bool fresh = true;
+    for (;;) {
+        if (fresh) { step = dist = stepSize; nextStep = ip + 128; }    // _start (zstd.c:31958)
+        // pair k: A = pa[k], C = pa[k + 1] = A + ds[k], `step` = st[k] while it runs
+        uint32_t pa[NPAIR + 1], ds[NPAIR + 1], st[NPAIR + 1], nx[NPAIR + 1];
+        pa[0] = ip; ds[0] = dist; st[0] = step; nx[0] = nextStep;
+#pragma unroll
+        for (int k = 0; k < NPAIR; k++) {
+            pa[k + 1] = pa[k] + ds[k]; ds[k + 1] = st[k]; st[k + 1] = st[k]; nx[k + 1] = nx[k];
+            if (pa[k + 1] + ds[k + 1] >= nx[k]) { st[k + 1]++; nx[k + 1] += 128; }
+        }
+        if (pa[1] + 1 >= ilimit) break;                                 // ip3 >= ilimit, at _start and at the loop's foot alike
+        uint32_t R = 1;                                                 // the pairs that are real if all before them fail
+#pragma unroll
+        for (int k = 1; k < NPAIR; k++) if (R == (uint32_t)k && pa[k + 1] + 1 < ilimit) R = (uint32_t)k + 1;
+        ZE_STAT(10);
+        // round 0: own bytes (positions of pairs that are not real read the last valid position: ignored)
+        uint64_t wA[NPAIR + 1], wB[NPAIR]; uint32_t rv[NPAIR], hs[NS + 1];
+#pragma unroll
+        for (int k = 0; k <= NPAIR; k++) { const uint32_t q = pa[k] <= ilimit ? pa[k] : ilimit; wA[k] = zh_ld64(src + q); }
+#pragma unroll
+        for (int k = 0; k < NPAIR; k++) { const uint32_t q = pa[k] < ilimit ? pa[k] + 1 : ilimit; wB[k] = zh_ld64(src + q); }
+#pragma unroll
+        for (int k = 0; k < NPAIR; k++) { const uint32_t q = pa[k + 1] <= ilimit ? pa[k + 1] : ilimit; rv[k] = zh_ld32(src + q - rep1); }
+#pragma unroll
+        for (int k = 0; k < NPAIR; k++) { hs[2 * k] = ZF_H(wA[k]); hs[2 * k + 1] = ZF_H(wB[k]); }
+        hs[NS] = ZF_H(wA[NPAIR]);
+        // round 1: the table cells, all in flight together; then what each read sees after the reference's earlier writes of this trip
+        uint32_t cell[NS], nw[NS];
+#pragma unroll
+        for (int s = 0; s < NS; s++) cell[s] = table[hs[s]];
+#pragma unroll
+        for (int k = 0; k < NPAIR; k++) { nw[2 * k] = (pa[k] + 2) | ZF_T(wA[k]); nw[2 * k + 1] = (pa[k] + 3) | ZF_T(wB[k]); }
+#pragma unroll
+        for (int s = 1; s < NS; s++) {
+#pragma unroll
+            for (int j = 0; j < s; j++) if (hs[s] == hs[j]) cell[s] = nw[j];
+        }
+        table[hs[0]] = nw[0]; table[hs[1]] = nw[1];            // pair 0 is real: its two writes happen whatever it decides
+        uint32_t idx[NS]; bool pv[NS];
+#pragma unroll
+        for (int s = 0; s < NS; s++) { idx[s] = ZF_IDX(cell[s]); pv[s] = idx[s] >= 2 && (cell[s] >> PB) == (nw[s] >> PB); }
+        // round 2: the bytes of the plausible candidates (the others read one address the whole wave shares)
+        uint32_t cb[NS];
+#pragma unroll
+        for (int s = 0; s < NS; s++) cb[s] = zh_ld32(pv[s] ? src + (idx[s] - 2) : idle);
+#pragma unroll
+        for (int s = 0; s < NS; s++) cb[s] = zh_opaque(cb[s]);                     // no load sinks into a branch
+        int fnd[NPAIR];
+#pragma unroll
+        for (int k = 0; k < NPAIR; k++)
+            fnd[k] = (rep1 > 0 && rv[k] == (uint32_t)wA[k + 1]) ? 1 : (pv[2 * k] && cb[2 * k] == (uint32_t)wA[k]) ? 2 : (pv[2 * k + 1] && cb[2 * k + 1] == (uint32_t)wB[k]) ? 3 : 0;
+        uint32_t P = NPAIR; int found = 0;                                         // the first real pair that hit
+#pragma unroll
+        for (int k = NPAIR - 1; k >= 0; k--) if ((uint32_t)k < R && fnd[k]) { P = (uint32_t)k; found = fnd[k]; }
+        // the writes of the later pairs that really ran: 1 .. P (a hit in P) or 1 .. R - 1 (none), in the reference's order
+#pragma unroll
+        for (int k = 1; k < NPAIR; k++) if ((uint32_t)k <= P && (uint32_t)k < R) { table[hs[2 * k]] = nw[2 * k]; table[hs[2 * k + 1]] = nw[2 * k + 1]; }
+        if (found) {
+            ZE_STAT(11);
+            uint32_t aP = pa[0], cP = pa[1], stP = st[0], iA = idx[0], iB = idx[1], hC = hs[2]; uint64_t wC = wA[1];
+#pragma unroll
+            for (int k = 1; k < NPAIR; k++) if (P == (uint32_t)k) { aP = pa[k]; cP = pa[k + 1]; stP = st[k]; iA = idx[2 * k]; iB = idx[2 * k + 1]; hC = hs[2 * k + 2]; wC = wA[k + 1]; }
+            uint32_t ipm, mpos, mLength, offBase = 1, current0 = aP;
+            if (found == 1) {                                           // repcode at C, one byte backwards (zstd.c:31975-31990)
+                ipm = cP; mpos = cP - rep1;
+                mLength = ze_count_fwd(src, cP + 4, cP + 4 - rep1, srcSize) + 4;
+                if (src[ipm - 1] == src[mpos - 1]) { ipm--; mpos--; mLength++; }
+            } else {
+                if (found == 2) { ipm = aP; mpos = iA - 2; }
+                else { ipm = aP + 1; mpos = iB - 2; current0 = aP + 1; if (stP <= 4) table[hC] = (cP + 2) | ZF_T(wC); }      // the pending write survives only while step <= 4 (zstd.c:32008)
+                const uint32_t offset = ipm - mpos;
+                mLength = ze_count_fwd(src, ipm + 4, mpos + 4, srcSize) + 4;
+                while (ipm > anchor && mpos > 0) {                      // catch up (zstd.c:32034), 8 bytes a round
+                    ZE_STAT(13);
+                    const uint32_t room = ipm - anchor < mpos ? ipm - anchor : mpos;
+                    if (mpos >= 8) {
+                        const uint64_t dd = zh_ld64(src + ipm - 8) ^ zh_ld64(src + mpos - 8);
+                        uint32_t k = dd ? (uint32_t)(zh_clz64(dd) >> 3) : 8u;
+                        if (k > room) k = room;
+                        ipm -= k; mpos -= k; mLength += k;
+                        if (k < 8) break;
+                    } else {
+                        if (src[ipm - 1] != src[mpos - 1]) break;
+                        ipm--; mpos--; mLength++;
+                    }
+                }
+                rep2 = rep1; rep1 = offset; offBase = offset + 3;
+            }
+            seqs[nseq++] = ZE_SEQ_PACK(offBase, ipm - anchor, mLength);
+            ip = ipm + mLength; anchor = ip;
+            if (ip <= ilimit) {
+                const uint32_t pI = current0 + 2;
+                const uint64_t wI = zh_ld64(src + pI), wE = zh_ld64(src + ip - 2);
+                uint64_t wr = zh_ld64(src + ip); uint32_t r2 = zh_ld32(src + ip - rep2);
+                table[ZF_H(wI)] = (pI + 2) | ZF_T(wI);
+                table[ZF_H(wE)] = ip | ZF_T(wE);
+                while (rep2 > 0 && (uint32_t)wr == r2) {                // immediate repeat-offset matches (zstd.c:32062-32074)
+                    ZE_STAT(14);
+                    const uint32_t r = ze_count_fwd(src, ip + 4, ip + 4 - rep2, srcSize) + 4;
+                    const uint32_t t = rep2; rep2 = rep1; rep1 = t;
+                    table[ZF_H(wr)] = (ip + 2) | ZF_T(wr);
+                    seqs[nseq++] = ZE_SEQ_PACK(1, 0, r);
+                    ip += r; anchor = ip;
+                    if (ip > ilimit) break;
+                    wr = zh_ld64(src + ip); r2 = zh_ld32(src + ip - rep2);
+                }
+            }
+            fresh = true;
+        } else {                                                        // every real pair failed: go on from the last one's C
+            ip = pa[1]; dist = ds[1]; step = st[1]; nextStep = nx[1];
+#pragma unroll
+            for (int k = 2; k <= NPAIR; k++) if (R == (uint32_t)k) { ip = pa[k]; dist = ds[k]; step = st[k]; nextStep = nx[k]; }
+            fresh = false;
+        }
+    }
+#undef ZF_H
+#undef ZF_T
+#undef ZF_IDX
+    return nseq;
+}
+
 
 // ------------------------------------------------------------------------------------------ fast strategy (levels 1-2, negative levels)
 // ZSTD_compressBlock_fast_noDict_generic (zstd.c:31906) for a block that is the whole frame: one hash table of hashLog bits over
@@ -3013,7 +3169,10 @@ ZH_DEVFN void ze_match_body(const ZhipEncodeArgs& a)
 
 // E1 flat: one lane per frame, statically assigned, every frame of the chunk in flight (ze_dfast_flat). Frames it does not cover are
 // listed for the lane-serial kernel above (chunk-local index) or, above one block, for the generic kernel.
-template <int NPROBE = 2>
+// FAST = true: the same kernel for the fast strategy (ze_fast_flat_np, NPROBE = its pairs per trip) -- sources whose row says strategy 1, no dictionary, one table
+// per source. An instantiation of its own, so that the double-fast kernels' code and registers are what they were; the host launches it when both one-block
+// rows are fast (zhip_compress_batch_device), and whatever either form declines is the lane-serial kernel's as before.
+template <int NPROBE = 2, bool FAST = false>
 ZH_DEVFN void ze_match_flat_body(const ZhipEncodeArgs& a)
 {
     const uint32_t lane = zh_lane();
@@ -3038,12 +3197,13 @@ ZH_DEVFN void ze_match_flat_body(const ZhipEncodeArgs& a)
             ok = a.cdict->status == 0 && a.cdict->contentSize != 0 && srcSize <= ze_dict_slot_max(a);
             if (ok) ze_dict_cparams(cp, *a.cdict, srcSize);
         }
-        ok = ok && cp.strat == 2 && (size_t)(4u << cp.hlog) + (4u << cp.clog) <= a.tableStride;
+        if (FAST) ok = ok && !dict && cp.strat == 1 && (size_t)(4u << cp.hlog) <= a.tableStride;
+        else ok = ok && cp.strat == 2 && (size_t)(4u << cp.hlog) + (4u << cp.clog) <= a.tableStride;
         if (!ok) { a.e1List[zh_atomic_add(a.e1Count, 1u)] = i; take = false; }    // the lane-serial kernel decides (and reports errors)
     }
     uint32_t* hashLong = (uint32_t*)(a.flatTables + (size_t)(mine ? i : 0u) * a.tableStride);
     uint32_t* hashSmall = hashLong + (take ? (1u << cp.hlog) : 0u);
-    if (dict && a.tabEpoch == 0) {
+    if (!FAST && dict && a.tabEpoch == 0) {
         // dictionary batches without launch numbers in the cells (ZhipEncodeArgs.tabEpoch): the wave zeroes its documents' tables itself, only the part each one uses (the
         // slots are sized for the attach cutoff: a host-side memset of whole slots would write four times what 4 KiB documents need)
         const uint32_t myUnits = take ? ((4u << cp.hlog) + (4u << cp.clog)) / 16u : 0u;
@@ -3063,6 +3223,8 @@ ZH_DEVFN void ze_match_flat_body(const ZhipEncodeArgs& a)
     // (a probe launch of the placement pick searches the sources' first bytes only -- same tables, same parameters, the same scatter over the allocation, a fraction of the time)
     const uint32_t searchSize = a.probeCap && srcSize > a.probeCap ? a.probeCap : srcSize;
     const uint64_t wc0 = a.waveClock ? zd_wall_clock() : 0ull;
+    if (FAST) m.nbSeq = ze_fast_flat_np<NPROBE>((uint64_t*)(fr + ZE_ARENA_SEQ), src, searchSize, cp.hlog, cp.mml, (uint32_t)cp.tlen, hashLong, a.idle, a.tabEpoch);
+    else
     m.nbSeq = dict ? ze_dfast_dict_flat((uint64_t*)(fr + ZE_ARENA_SEQ), src, searchSize, cp, *a.cdict, a.cdictContent, a.cdictHashLong, a.cdictHashSmall, hashLong, hashSmall, a.tabEpoch, a.tabEpochShift)
                    : NPROBE > 2 ? ze_dfast_flatn<NPROBE>((uint64_t*)(fr + ZE_ARENA_SEQ), src, searchSize, cp.hlog, cp.clog, cp.mml, hashLong, hashSmall, a.idle, a.tabEpoch)
                                  : ze_dfast_flat((uint64_t*)(fr + ZE_ARENA_SEQ), src, searchSize, cp.hlog, cp.clog, cp.mml, hashLong, hashSmall, a.idle, a.tabEpoch);
@@ -3119,7 +3281,7 @@ ZH_DEVFN void ze_match_flat_mb_body(const ZhipEncodeArgs& a)
 // for more frames per CU (4 KiB: 32 waves, 16 KiB: 9, 64 KiB: 2, one block: 1). A source above the area (no size hint and a shape picked
 // too small cannot happen -- the host falls back to the one-block shape -- but the kernel does not rely on it) is searched in place.
 template <uint32_t BYTES> struct ZeSrcLDS { uint8_t b[BYTES + 64]; };
-template <int NPROBE = 2>
+template <int NPROBE = 2, bool FAST = false>          // (FAST: the fast strategy's form, as in ze_match_flat_body)
 ZH_DEVFN void ze_match_lds_body(const ZhipEncodeArgs& a, uint8_t* lds, uint32_t ldsBytes)
 {
     const uint32_t lane = zh_lane();
@@ -3132,8 +3294,8 @@ ZH_DEVFN void ze_match_lds_body(const ZhipEncodeArgs& a, uint8_t* lds, uint32_t 
     ZePar cp;
     if (srcSize64 > ZF_BLOCK_MAX) { if (lane == 0) { m.mode = 3; a.meta[i] = m; a.bigList[zh_atomic_add(a.bigCount, 1u)] = f; } return; }
     const uint32_t srcSize = (uint32_t)srcSize64;
-    if (a.cdict || srcSize < 64 || ze_get_cparams(cp, a.rows, srcSize) || cp.strat != 2 ||
-        (size_t)(4u << cp.hlog) + (4u << cp.clog) > a.tableStride) {
+    if (a.cdict || srcSize < 64 || ze_get_cparams(cp, a.rows, srcSize) || cp.strat != (FAST ? 1 : 2) ||
+        (size_t)(4u << cp.hlog) + (FAST ? 0u : (4u << cp.clog)) > a.tableStride) {
         if (lane == 0) a.e1List[zh_atomic_add(a.e1Count, 1u)] = i;        // the lane-serial kernel decides (and reports errors)
         return;
     }
@@ -3156,7 +3318,10 @@ ZH_DEVFN void ze_match_lds_body(const ZhipEncodeArgs& a, uint8_t* lds, uint32_t 
     // stretch every 4.5 probes on the bench corpus and the one-lane search already takes two probes per round trip, so the wave form saves
     // little more than half the round trips and pays shuffles, ballots and a wave-wide match extension for each.)
     if (lane != 0) return;
-    if (NPROBE == 4)
+    if (FAST)
+        m.nbSeq = staged ? ze_fast_flat_np<NPROBE>((uint64_t*)(fr + ZE_ARENA_SEQ), lds, srcSize, cp.hlog, cp.mml, (uint32_t)cp.tlen, hashLong, nullptr, a.tabEpoch)
+                         : ze_fast_flat_np<NPROBE>((uint64_t*)(fr + ZE_ARENA_SEQ), src, srcSize, cp.hlog, cp.mml, (uint32_t)cp.tlen, hashLong, a.idle, a.tabEpoch);
+    else if (NPROBE == 4)
         m.nbSeq = staged ? ze_dfast_flat4((uint64_t*)(fr + ZE_ARENA_SEQ), lds, srcSize, cp.hlog, cp.clog, cp.mml, hashLong, hashSmall, nullptr, a.tabEpoch)
                          : ze_dfast_flat4((uint64_t*)(fr + ZE_ARENA_SEQ), src, srcSize, cp.hlog, cp.clog, cp.mml, hashLong, hashSmall, a.idle, a.tabEpoch);
     else

@@ -118,11 +118,19 @@ ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_flat_kernel(ZhipEncodeArg
 ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_flat4_kernel(ZhipEncodeArgs a) { ze_match_flat_body<4>(a); }
 ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_flat3_kernel(ZhipEncodeArgs a) { ze_match_flat_body<3>(a); }      // three probes: launches of up to 65 536 sources
 ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_flat_mb_kernel(ZhipEncodeArgs a) { ze_match_flat_mb_body(a); }
+// the fast strategy's flat search (ze_fast_flat_np), one and two pairs of the reference's loop per trip: kernels of their own, the double-fast ones are untouched
+ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_flat_fast_kernel(ZhipEncodeArgs a) { ze_match_flat_body<1, true>(a); }
+ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_flat_fast2_kernel(ZhipEncodeArgs a) { ze_match_flat_body<2, true>(a); }
 static_assert(sizeof(ZeSrcLDS<ZF_BLOCK_MAX>) <= ZHIP_LDS_BYTES, "a workgroup's LDS must fit a CU");
 template <uint32_t BYTES, int NPROBE> __global__ __launch_bounds__(64) void zhip_encode_match_lds_kernel(ZhipEncodeArgs a)
 {
     __shared__ ZeSrcLDS<BYTES> L;
     ze_match_lds_body<NPROBE>(a, L.b, BYTES);
+}
+template <uint32_t BYTES, int NPAIR> __global__ __launch_bounds__(64) void zhip_encode_match_lds_fast_kernel(ZhipEncodeArgs a)      // the fast strategy's search on a source in LDS
+{
+    __shared__ ZeSrcLDS<BYTES> L;
+    ze_match_lds_body<NPAIR, true>(a, L.b, BYTES);
 }
 #ifndef ZE_E2_MINWAVES
 #define ZE_E2_MINWAVES 4
@@ -293,6 +301,9 @@ extern "C" void zhip_get_cparams(int level, uint64_t srcSizeHint, size_t dictSiz
 #ifndef ZHIP_E1LDS_PROBES
 #define ZHIP_E1LDS_PROBES 2       // probes per trip of the LDS-source match kernel (small batches: one source per CU)
 #endif
+#ifndef ZHIP_E1LDS_FAST_PAIRS
+#define ZHIP_E1LDS_FAST_PAIRS 2   // pairs per trip of the fast strategy's LDS-source match kernel: one source per CU is pure latency, and the second pair's loads ride in the same rounds
+#endif
 #ifndef ZHIP_TABLE_EPOCHS
 #define ZHIP_TABLE_EPOCHS 1      // launch numbers in the cells of the flat searches' tables; 0: the tables are zeroed every launch -- a memset, the dictionary search's own waves -- (A/B build)
 #endif
@@ -409,6 +420,10 @@ struct zhip_ctx {
         // probes per trip of the flat double-fast search by launch size: up to flat4Max sources four (bound by one source's serial chain: 21-25 % less time from
         // 1 024 to 32 768 sources, r04zd), up to flat3Max three, above two (with the placement picked, at 65 536: 421 / 415 / 425 ms for two / three / four, r05w)
         size_t flat4Max = 32768, flat3Max = 65536; bool flat3 = true;
+        // pairs per trip of the flat fast-strategy search (ze_fast_flat_np) by launch size: up to fast2Max sources two, above one. ZHIP_FAST_PAIRS=1 / 2 forces either (A/B, and the GPU test of both kernels)
+        // (fast2Max is NOT measured yet: it is the double-fast search's four-probe band -- two pairs are four positions a trip -- taken over; tests/tools/compress_levels_rate.py under
+        // ZHIP_FAST_PAIRS=1 and =2 at 16 384 and 65 536 sources is the measurement that sets it)
+        size_t fast2Max = 32768; int fastPairs = 0;
         bool e1fPick = true;                // ZHIP_E1F_PICK=0: take the flat tables where the first allocation put them (zhip_compress_batch_device)
         // host-buffer pipeline
         size_t hchunkE = 32768, hchunkE0 = 0;   // compress: items per chunk, items of the first chunk (0: like the others)
@@ -441,15 +456,16 @@ extern "C" zhip_ctx* zhip_ctx_create(void)
     if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) { g_lastError = "hipGetDeviceProperties failed"; delete c; return nullptr; }
     c->numCU = prop.multiProcessorCount;
     {   zhip_ctx::Knobs& k = c->knob;
-        // Run-time knobs (round 6: nine, each exercised by a GPU test or a resource policy; rounds 1-5's other twenty-two -- chunk shapes, probe counts, waves per CU,
+        // Run-time knobs (round 6: nine, ten with round 7's ZHIP_FAST_PAIRS, each exercised by a GPU test or a resource policy; rounds 1-5's other twenty-two -- chunk shapes, probe counts, waves per CU,
         // bring-up aids -- are the constants of this struct, and what lost its A/B is in DESIGN.md with its measurements): ZHIP_PROF (phase timers), ZHIP_K0_MIN, ZHIP_E1F_PICK,
-        // ZHIP_E1LDS_MAX, ZHIP_MBC_MIN here; ZHIP_DEVICES / ZHIP_DEVICE_MIN_BYTES (the in-call device fan-out), ZHIP_KEEP_GB, ZHIP_PIN_POOL_KEEP_MB (memory kept between
+        // ZHIP_E1LDS_MAX, ZHIP_MBC_MIN, ZHIP_FAST_PAIRS here; ZHIP_DEVICES / ZHIP_DEVICE_MIN_BYTES (the in-call device fan-out), ZHIP_KEEP_GB, ZHIP_PIN_POOL_KEEP_MB (memory kept between
         // calls) where they are used.
         k.prof = getenv("ZHIP_PROF") != nullptr;
         if (const char* e = getenv("ZHIP_K0_MIN")) k.k0Min = (size_t)atol(e);
         if (const char* e = getenv("ZHIP_MBC_MIN")) k.mbcMin = (size_t)atol(e);     // compress: batches of at least this many sources take the flat search for sources of several blocks
         if (const char* e = getenv("ZHIP_E1LDS_MAX")) { const long v = atol(e); if (v >= 0 && v <= 65536) k.e1LdsMax = v; }
         if (const char* e = getenv("ZHIP_E1F_PICK")) k.e1fPick = atol(e) != 0;    // 0: take the tables where the first allocation put them (A/B)
+        if (const char* e = getenv("ZHIP_FAST_PAIRS")) { const long v = atol(e); if (v >= 0 && v <= 2) k.fastPairs = (int)v; }      // pairs per trip of the flat fast-strategy search (0: by launch size)
     }
     zh_resolve_rows(&c->rows, 3, nullptr);
     int nb = 0;
@@ -967,11 +983,13 @@ extern "C" int zhip_decompress_batch_device(zhip_ctx* c, const void* d_src, cons
     if (c->timer[0].pending.size() > 1024) { HIP_TRY(hipStreamSynchronize(stream)); for (int i = 0; i < ZHIP_NTIMER; i++) drain_shared(c->timer[i]); for (int i = 0; i < ZHIP_NTIMER; i++) drain_timer(c->timer[i]); }
     return 0;
 }
-// the flat match kernel at `probes` per trip over `cnt` sources
-static void launch_flat(int probes, size_t cnt, hipStream_t stream, const ZhipEncodeArgs& a)
+// the flat match kernel at `probes` per trip over `cnt` sources (fastPairs != 0: the fast strategy's, at that many pairs per trip)
+static void launch_flat(int probes, size_t cnt, hipStream_t stream, const ZhipEncodeArgs& a, int fastPairs = 0)
 {
     const dim3 g((uint32_t)((cnt + ZE_FLAT_LANES - 1) / ZE_FLAT_LANES)), b(64);
-    if (probes == 4) hipLaunchKernelGGL(zhip_encode_match_flat4_kernel, g, b, 0, stream, a);
+    if (fastPairs == 2) hipLaunchKernelGGL(zhip_encode_match_flat_fast2_kernel, g, b, 0, stream, a);
+    else if (fastPairs) hipLaunchKernelGGL(zhip_encode_match_flat_fast_kernel, g, b, 0, stream, a);
+    else if (probes == 4) hipLaunchKernelGGL(zhip_encode_match_flat4_kernel, g, b, 0, stream, a);
     else if (probes == 3) hipLaunchKernelGGL(zhip_encode_match_flat3_kernel, g, b, 0, stream, a);
     else hipLaunchKernelGGL(zhip_encode_match_flat_kernel, g, b, 0, stream, a);
 }
@@ -1059,15 +1077,22 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
         }
         a.tableStride = stride;
         // double-fast without a dictionary: the flat match kernel (one lane per frame, the whole chunk in flight, tables zeroed by a
-        // memset) takes every double-fast frame; what it declines goes to the lane-serial kernel through a list. Fast strategy
-        // and dictionary batches use the lane-serial kernel for the whole chunk.
+        // memset) takes every double-fast frame; what it declines goes to the lane-serial kernel through a list. Dictionary batches of the
+        // fast strategy, and fast batches of several-block sources, use the lane-serial kernel for the whole chunk.
         // (r03: dictionary batches whose dictionary row is double-fast take the flat kernel too -- ze_dfast_dict_flat; its waves zero the tables)
         const bool flatDict = c->hasCDict && c->cdictStrat == 2;
-        const bool flat = (anyDfast && !c->hasCDict) || flatDict;
+        // (round 7) the fast strategy without a dictionary has a flat search too (ze_fast_flat_np): when BOTH one-block rows are fast the fast form of the kernel is
+        // launched, which takes the fast sources and leaves nothing but errors and tiny sources to the lane-serial kernel. A batch whose two one-block rows differ
+        // (explicit parameters cannot do that, the level tables do not) keeps the double-fast kernel, which hands its fast sources to the lane-serial search.
+        // Batches whose size hint says "sources of several blocks" stay where they were: the lane-serial kernel's chunk shapes (fastWide below), which only list such sources.
+        const bool flatFast = !c->hasCDict && a.rows.r[2][6] == 1 && a.rows.r[3][6] == 1 && sizeHint <= ZF_BLOCK_MAX;
+        const bool flat = (anyDfast && !c->hasCDict) || flatDict || flatFast;
         // (round 5) every row double-fast, no dictionary: the flat kernel takes every one-block source of 64 bytes and more and writes sequences only, and what
         // it declines -- sources below 64 bytes, parameter errors -- needs a literal area of its own size at most: the slot is the sequence area + 512 bytes
         // instead of + 128 KiB (21.4 GiB of arena per 65 536 sources instead of 30; it is what lets 262 144 sources be one launch, 88 + 96 GiB)
-        bool allDfast = anyDfast && !c->hasCDict; for (int t = 0; t < 4; t++) allDfast = allDfast && a.rows.r[t][6] == 2;
+        // (round 7: every row fast OR double-fast. Whichever form of the flat kernel runs, the one-block sources it declines for their strategy are fast ones,
+        // and the lane-serial fast search writes sequences only as well)
+        bool allDfast = (anyDfast || flatFast) && !c->hasCDict; for (int t = 0; t < 4; t++) allDfast = allDfast && (a.rows.r[t][6] == 2 || a.rows.r[t][6] == 1);
         if (flat && allDfast) a.arenaStride = (uint32_t)(ZE_ARENA_LIT + 512);
         // frames per launch of the flat match kernel: the search is a latency chain per frame, so its rate grows with the frames in flight -- 16 384: 204 ms,
         // 32 768: 270, 65 536: 417, 131 072: 760 (r04za: 9 % less per frame than two launches of 65 536, a second wave per SIMD) -- and what it costs
@@ -1089,7 +1114,7 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
                 flatMax = c->flatMaxCached;
             }
         }
-        // (the fast strategy -- levels 1, 2, negative -- runs in the lane-serial match kernel, whose time is ONE source's chain of dependent round trips: every source in flight at once
+        // (the fast strategy -- levels 1, 2, negative -- where it still runs in the lane-serial match kernel, i.e. under a size hint above one block: its time is ONE source's chain of dependent round trips: every source in flight at once
         // is one chain's time, two chunks of 32 768 are two. ZHIP_FAST_WIDE: 65 536 per chunk, sixteen sources per wave -- the kernel's 111 VGPRs hold 4 096 waves)
         const bool fastWide = ZHIP_FAST_WIDE && !flat && !c->hasCDict && n > 32768;
         size_t chunkMax = c->hasCDict ? 262144 : flat ? flatMax : fastWide ? 65536 : 32768;
@@ -1168,7 +1193,9 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
             if (es > 26) return 0;
             *zeroed = true;
             const uint32_t maxE = (1u << (32 - es)) - 1;
-            const uint64_t key = (flatDict ? c->cdictKey : 0x9E3779B97F4A7C15ull) ^ ((uint64_t)a.tableStride << 40);
+            // (the key tells table LAYOUTS apart: the dictionary, the slot size, and -- round 7 -- one table per slot (fast) or two (double-fast). The cells of both carry
+            // the launch number in the same six bits, so neither would read the other's as live inside one run of numbers; a change of layout zeroes and restarts anyway)
+            const uint64_t key = (flatDict ? c->cdictKey : 0x9E3779B97F4A7C15ull) ^ ((uint64_t)a.tableStride << 40) ^ (flatFast ? 0x00000000FA570000ull : 0ull);
             if (tables != c->encEpochPtr || gen != c->encEpochGen || es != c->encEpochShift || key != c->encEpochKey || c->encEpoch >= maxE || bytes > c->encEpochBytes) {
                 HIP_TRY(hipMemsetAsync(tables, 0, bytes, stream));
                 c->encEpoch = 0; c->encEpochPtr = tables; c->encEpochGen = gen; c->encEpochShift = es; c->encEpochKey = key; c->encEpochBytes = bytes;
@@ -1196,7 +1223,7 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
                         if (int rc = nextEpoch(pa, t, t == (uint8_t*)cand.p ? cand.gen : c->encFlatTables.gen, bytes, &z)) return rc;
                         if (!z && !flatDict) { HIP_TRY(hipMemsetAsync(t, 0, bytes, stream)); c->encEpochPtr = nullptr; } }
                     HIP_TRY(hipEventRecord(e0, stream));
-                    launch_flat(!flatDict && c->knob.flat3 && cnt0 <= c->knob.flat3Max ? 3 : 2, cnt0, stream, pa);
+                    launch_flat(!flatDict && c->knob.flat3 && cnt0 <= c->knob.flat3Max ? 3 : 2, cnt0, stream, pa, flatFast ? 1 : 0);
                     HIP_TRY(hipEventRecord(e1, stream));
                     HIP_TRY(hipEventSynchronize(e1));
                     HIP_TRY(hipEventElapsedTime(ms, e0, e1));
@@ -1292,14 +1319,22 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
                 const size_t rounds = shape == 3 ? ZHIP_E1LDS_PER_CU : c->knob.e1LdsRounds;
                 const size_t ldsMax = c->knob.e1LdsMax >= 0 ? (size_t)c->knob.e1LdsMax : (size_t)c->numCU * wavesPerCU[shape] * rounds;
                 if (mbc) hipLaunchKernelGGL(zhip_encode_split_kernel, dim3((uint32_t)(cnt < (size_t)c->numCU * 8 ? cnt : (size_t)c->numCU * 8)), dim3(64), 0, stream, a);
-                if (cnt <= ldsMax && !flatDict && !mbc) {
+                const int fastPairs = !flatFast ? 0 : c->knob.fastPairs ? c->knob.fastPairs : cnt <= c->knob.fast2Max ? 2 : 1;
+                if (cnt <= ldsMax && flatFast) {
+                    const dim3 g((uint32_t)cnt), b(64);
+                    if (shape == 0) hipLaunchKernelGGL((zhip_encode_match_lds_fast_kernel<4096, ZHIP_E1LDS_FAST_PAIRS>), g, b, 0, stream, a);
+                    else if (shape == 1) hipLaunchKernelGGL((zhip_encode_match_lds_fast_kernel<16384, ZHIP_E1LDS_FAST_PAIRS>), g, b, 0, stream, a);
+                    else if (shape == 2) hipLaunchKernelGGL((zhip_encode_match_lds_fast_kernel<65536, ZHIP_E1LDS_FAST_PAIRS>), g, b, 0, stream, a);
+                    else hipLaunchKernelGGL((zhip_encode_match_lds_fast_kernel<ZF_BLOCK_MAX, ZHIP_E1LDS_FAST_PAIRS>), g, b, 0, stream, a);
+                }
+                else if (cnt <= ldsMax && !flatDict && !mbc) {
                     const dim3 g((uint32_t)cnt), b(64);
                     if (shape == 0) hipLaunchKernelGGL((zhip_encode_match_lds_kernel<4096, ZHIP_E1LDS_PROBES>), g, b, 0, stream, a);
                     else if (shape == 1) hipLaunchKernelGGL((zhip_encode_match_lds_kernel<16384, ZHIP_E1LDS_PROBES>), g, b, 0, stream, a);
                     else if (shape == 2) hipLaunchKernelGGL((zhip_encode_match_lds_kernel<65536, ZHIP_E1LDS_PROBES>), g, b, 0, stream, a);
                     else hipLaunchKernelGGL((zhip_encode_match_lds_kernel<ZF_BLOCK_MAX, ZHIP_E1LDS_PROBES>), g, b, 0, stream, a);
                 }
-                else launch_flat(!flatDict && !mbc && cnt <= c->knob.flat4Max ? 4 : !flatDict && !mbc && c->knob.flat3 && cnt <= c->knob.flat3Max ? 3 : 2, cnt, stream, a);
+                else launch_flat(!flatDict && !mbc && cnt <= c->knob.flat4Max ? 4 : !flatDict && !mbc && c->knob.flat3 && cnt <= c->knob.flat3Max ? 3 : 2, cnt, stream, a, fastPairs);
                 if (mbc) hipLaunchKernelGGL(zhip_encode_match_flat_mb_kernel, dim3((uint32_t)((cnt + a.mbLanes - 1) / a.mbLanes)), dim3(64), 0, stream, a);
                 if (tm) HIP_TRY(hipEventRecord(ev[1], stream));
             }
