@@ -64,8 +64,11 @@ enum { ZHIP_DICT_AUTO = 0, ZHIP_DICT_RAWCONTENT = 1, ZHIP_DICT_FULLDICT = 2 };
 enum { ZHIP_FORMAT_ZSTD1 = 0, ZHIP_FORMAT_ZSTD1_MAGICLESS = 1 };
 /* explicit compression parameters == ZSTD_compressionParameters; the reference keeps them in the ZSTD_CCtx_params it applies to every
  * worker context (c-ext/compressor.c:20,203,1138; c-ext/compressionparams.c:13-120). 0 = "take it from the level" for each field,
- * exactly like ZSTD_CCtxParams_setParameter(…, 0). strategy: 1 = fast, 2 = dfast are the strategies this backend implements; a
- * combination that resolves to any other strategy fails loudly with ZHIP_ERR_UNSUPPORTED. */
+ * exactly like ZSTD_CCtxParams_setParameter(…, 0). strategy: 1 = fast and 2 = dfast are the strategies this backend implements for every
+ * source; 3 = greedy where libzstd runs it with its row match finder on 16-entry rows over one block -- sources of 16 385 ... 131 072 bytes
+ * (what level 5 resolves to there), a window of 2^15 or more that covers the whole source (an explicit windowLog of 15 or 16 on a larger
+ * source is refused, as for every strategy), searchLog <= 4, hashLog <= 17 after the windowLog + 1 cap, no dictionary. A combination that resolves to anything else fails
+ * loudly: ZHIP_ERR_UNSUPPORTED from zhip_ctx_set_cparams where no source could be served, else status 40 for the frame. */
 typedef struct { uint32_t windowLog, chainLog, hashLog, searchLog, minMatch, targetLength; int32_t strategy; } zhip_compression_parameters;
 
 /* compression parameters the hot path reads (the reference keeps them in ZSTD_CCtx_params,
@@ -198,7 +201,7 @@ int zhip_compact_device(const void* d_slots, const zhip_segment* d_slotSegs, con
 
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,
- * 4 K3, 5 / 6 the lane-serial match and the entropy kernels, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,
+ * 4 K3, 5 / 6 the lane-serial match kernel (the greedy strategy's zhip_encode_match_greedy_kernel where that runs in its place) and the entropy kernel, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,
  * 8 the flat match kernel -- the match stage of a chunk whichever of its forms ran: the double-fast search's and, since the fast strategy has a flat search of its own
  * (levels 1, 2 and negative levels without a dictionary, sources of one block), that one's; the LDS-source kernels of small batches too --, 9 "zhip_decode_pipeline_span": not a kernel, a chunk's decode pipeline from K1's start to K3's end (what the overlapping kernels cost together). */
 const char* zhip_kernel_name(int k);

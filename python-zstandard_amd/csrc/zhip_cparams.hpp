@@ -3,8 +3,9 @@
 // The level table is data of the format's reference implementation (ZSTD_defaultCParameters, zstd/zstd.c:30650-30755: 4 source-size
 // classes x levels 0..22, columns windowLog chainLog hashLog searchLog minMatch targetLength strategy); frames are only bit-identical
 // to libzstd's if the same numbers go in, so they are restated here as numbers (strategy: 1 fast 2 dfast 3 greedy 4 lazy 5 lazy2
-// 6 btlazy2 7 btopt 8 btultra 9 btultra2). The kernels implement strategies 1 and 2; rows that resolve to anything else are refused
-// per frame (ZE_PARAM_UNSUPPORTED), never approximated.
+// 6 btlazy2 7 btopt 8 btultra 9 btultra2). The kernels implement strategies 1 and 2, and 3 where libzstd runs it with the row match
+// finder on 16-entry rows over one block (ze_get_cparams); rows that resolve to anything else are refused per frame
+// (ZE_PARAM_UNSUPPORTED), never approximated.
 #pragma once
 #include <stdint.h>
 #include "../../include/zstd_hip.h"

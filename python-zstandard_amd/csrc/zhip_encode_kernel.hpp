@@ -50,7 +50,7 @@ struct ZeLDSMulti {
 };
 struct ZePrevHuf { const uint8_t* bits; const uint16_t* code; uint32_t maxSym, repeat; };   // a candidate table for the literals (dictionary or previous block)
 
-struct ZePar { int wlog, clog, hlog, mml, strat, tlen; };
+struct ZePar { int wlog, clog, hlog, mml, strat, tlen, slog; };      // (slog: the search log, read by the greedy search only)
 // optional per-phase cycle totals of the entropy kernel (ZHIP_PROF tuning aid; lives in registers, null when off)
 #ifdef ZE_PROF_STREAM       // diagnostic build: the sequence stream's rounds split into their four parts (eight bytes of accumulator each: not in the product's registers)
 enum { ZEP_GATHER = 0, ZEP_LITSTAT, ZEP_HUFBUILD, ZEP_HUFENC, ZEP_SEQSTAT, ZEP_SEQTAB, ZEP_SEQENC, ZEP_REST, ZEP_SQ_PRE, ZEP_SQ_CHAIN, ZEP_SQ_PACK, ZEP_SQ_FLUSH, ZEP_N };
@@ -1541,6 +1541,106 @@ ZH_DEV uint32_t ze_fast(uint64_t* seqs, uint8_t* lits, uint32_t* pLit, const uin
     return ze_fast_g(seqs, lits, pLit, src, src, srcSize, cp, table, rep);
 }
 
+// ------------------------------------------------------------------------------------------ greedy strategy, row match finder (level 5 above 16 KiB)
+// ZSTD_compressBlock_lazy_generic(search_rowHash, depth 0, ZSTD_noDict) (zstd.c:34217-34470) with ZSTD_RowFindBestMatch (:33842),
+// ZSTD_row_update_internal / _internalImpl (:33617 / :33586) and ZSTD_row_nextIndex (:33499), for a block that is the whole frame and
+// rows of 16 entries (searchLog <= 4). One lane. Positions are source-relative; cells hold position + 2 (0 = empty, below the lowest
+// valid index 2: a tag hit on a slot never written ends the scan as libzstd's `matchIndex < lowLimit` does -- every slot behind the
+// first empty one in scan order is empty too, so whatever tags such slots hold decides nothing). rowPos: 1 << hashLog cells, rowTag:
+// 1 << hashLog bytes, both zeroed: with zeroed tables libzstd's hash salt may be 0 -- it is XORed into the hash before the shift, which
+// permutes rows and tags one to one. libzstd's 8-entry hash cache only carries hash(position) from the prefetch to the use (every value
+// read from it is the hash of the position it is read for: it is refilled wherever the run of consecutive positions breaks -- the
+// 384-position skip, the end of lazy skipping), so hashes are computed where they are used and nothing is prefetched.
+// The candidates are measured as they are gathered instead of being buffered first: the reference's insertion of the searched position
+// between its two loops touches the tables only, the measuring reads the source only, and the gathering's exits (attempts used up, an
+// index below the low limit) do not depend on lengths -- the same candidates are measured in the same order. Sequences only: the
+// entropy kernel gathers the literals. Returns the sequence count.
+ZH_DEV void ze_row_put(uint32_t hash, uint32_t pos, uint32_t* rowPos, uint8_t* rowTag)      // position `pos`, whose hash this is, into its row
+{
+    const uint32_t rel = (hash >> 8) << 4;
+    uint8_t* const tagRow = rowTag + rel;
+    uint32_t next = ((uint32_t)tagRow[0] - 1u) & 15u;                 // ZSTD_row_nextIndex: the head moves backwards and skips slot 0 (the head byte itself)
+    next += next == 0 ? 15u : 0u;
+    tagRow[0] = (uint8_t)next;
+    tagRow[next] = (uint8_t)hash;
+    rowPos[rel + next] = pos + 2;
+}
+ZH_DEV void ze_row_insert(const uint8_t* src, uint32_t pos, int hbits, int mls, uint32_t* rowPos, uint8_t* rowTag) { ze_row_put(ze_hash(src + pos, hbits, mls), pos, rowPos, rowTag); }
+ZH_DEVFN uint32_t ze_greedy_row(uint64_t* seqs, const uint8_t* src, uint32_t srcSize, const ZePar& cp, uint32_t* rowPos, uint8_t* rowTag)
+{
+    const int mls = cp.mml <= 4 ? 4 : cp.mml >= 6 ? 6 : cp.mml;
+    const int hbits = cp.hlog - 4 + 8;                                // rowHashLog + ZSTD_ROW_HASH_TAG_BITS
+    const uint32_t maxAttempts = 1u << (cp.slog < 4 ? cp.slog : 4);
+    if (srcSize < 18) return 0;                                       // (ip = 1 is not below ilimit: no sequence)
+    const uint8_t* const iend = src + srcSize;
+    const uint32_t ilimit = srcSize - 8 - 8;                          // iend - 8 - ZSTD_ROW_HASH_CACHE_SIZE
+    // first block of a frame: ip starts one past the (empty) prefix, the repeat offsets {1, 4} above maxRep = 1 are zeroed (zstd.c:34252-34258)
+    uint32_t ip = 1, anchor = 0, off1 = 1, off2 = 0, nextToUpdate = 0, nseq = 0;
+    bool lazySkipping = false;
+    while (ip < ilimit) {
+        uint32_t mLength, offBase = 1, start = ip + 1;
+        if (off1 > 0 && zh_ld32(src + ip + 1 - off1) == zh_ld32(src + ip + 1)) {
+            mLength = ze_common_len(src + ip + 5, src + ip + 5 - off1, iend) + 4;      // depth 0: stored at once, nothing is searched or inserted here
+        } else {
+            if (!lazySkipping) {                                      // ZSTD_row_update_internal: every position up to ip, or the first 96 and the last 32 of a long stretch
+                uint32_t idx = nextToUpdate;
+                if (ip - idx > 384) {
+                    for (const uint32_t bound = idx + 96; idx < bound; idx++) ze_row_insert(src, idx, hbits, mls, rowPos, rowTag);
+                    idx = ip - 32;
+                }
+                for (; idx < ip; idx++) ze_row_insert(src, idx, hbits, mls, rowPos, rowTag);
+            }
+            nextToUpdate = ip;
+            const uint32_t hash = ze_hash(src + ip, hbits, mls), rel = (hash >> 8) << 4, tag = hash & 255u;
+            uint8_t* const tagRow = rowTag + rel;
+            uint32_t* const row = rowPos + rel;
+            // the row's 16 tags in one load; a bit per slot whose tag equals ours (exact zero-byte test on tag ^ splat), rotated so that bit 0 is the head: newest first
+            const zh_v16 tv = zh_ld128(tagRow);
+            const uint32_t head = (uint32_t)tv.lo & 15u;
+            const uint64_t splat = tag * 0x0101010101010101ull, x80 = 0x8080808080808080ull, x01 = 0x0101010101010101ull, pick = 0x0002040810204081ull;
+            const uint64_t xl = tv.lo ^ splat, xh = tv.hi ^ splat;
+            const uint32_t nz = (uint32_t)((((((xl | x80) - x01) | xl) & x80) * pick) >> 56) | ((uint32_t)((((((xh | x80) - x01) | xh) & x80) * pick) >> 56) << 8);
+            const uint32_t eq = ~nz & 0xFFFFu;
+            uint32_t matches = ((eq >> head) | (eq << (16u - head))) & 0xFFFFu;
+            uint32_t attempts = maxAttempts, ml = 3, found = 0;
+            for (; matches && attempts; matches &= matches - 1) {
+                const uint32_t slot = (head + (uint32_t)zh_ctz64(matches)) & 15u;
+                if (slot == 0) continue;
+                const uint32_t mi = row[slot];
+                if (mi < 2) break;
+                attempts--;
+                const uint8_t* const m = src + (mi - 2);
+                if (zh_ld32(m + ml - 3) != zh_ld32(src + ip + ml - 3)) continue;
+                const uint32_t cur = ze_common_len(src + ip, m, iend);
+                if (cur > ml) {
+                    ml = cur; found = ip + 2 - mi;
+                    if (ip + cur == srcSize) break;                   // best possible; (the reference gathered the rest already: nothing of it is used)
+                }
+            }
+            ze_row_put(hash, nextToUpdate++, rowPos, rowTag);         // the searched position goes in after the candidates were read
+            if (ml < 4) {
+                const uint32_t step = ((ip - anchor) >> 8) + 1;
+                ip += step;
+                lazySkipping = step > 8;
+                continue;
+            }
+            mLength = ml; start = ip; offBase = found + 3;
+            while (start > anchor && start > found && src[start - 1] == src[start - found - 1]) { start--; mLength++; }      // catch up, backwards
+            off2 = off1; off1 = found;
+        }
+        seqs[nseq++] = ZE_SEQ_PACK(offBase, start - anchor, mLength);
+        anchor = ip = start + mLength;
+        lazySkipping = false;
+        while (ip <= ilimit && off2 > 0 && zh_ld32(src + ip) == zh_ld32(src + ip - off2)) {
+            const uint32_t r = ze_common_len(src + ip + 4, src + ip + 4 - off2, iend) + 4;
+            const uint32_t t = off2; off2 = off1; off1 = t;
+            seqs[nseq++] = ZE_SEQ_PACK(1, 0, r);
+            ip += r; anchor = ip;
+        }
+    }
+    return nseq;
+}
+
 // ------------------------------------------------------------------------------------------ double-fast search against an attached dictionary
 // ZSTD_compressBlock_doubleFast_dictMatchState_generic (zstd.c:31262) for a frame of one block. One index space: dictionary
 // content byte k is index 2 + k, the source follows at CE = 2 + contentSize, so offsets are index differences. The frame's own
@@ -2645,6 +2745,9 @@ ZH_DEVFN uint32_t ze_compress_block(ZeLDS& L, uint8_t* out, uint32_t cap, const 
 // ------------------------------------------------------------------------------------------ frame
 // the row of the source's size class (level + explicit parameters, resolved on the host: ZSTD_getCParams_internal zstd.c:30848 +
 // ZSTD_overrideCParams :24578) adjusted to a known source size without dictionary (ZSTD_adjustCParams_internal :24427)
+// GREEDY = true (the greedy match kernel, and the entropy kernel that codes its sequences): a greedy row is accepted where ze_greedy_row serves it. Everywhere else the
+// function is what it was -- greedy refused -- so the other kernels' code does not change.
+template <bool GREEDY = false>
 ZH_DEV int ze_get_cparams(ZePar& out, const ZeRows& rows, uint32_t srcSize)
 {
     const uint32_t tableID = (srcSize <= 256u * 1024) + (srcSize <= 128u * 1024) + (srcSize <= 16u * 1024);
@@ -2656,6 +2759,13 @@ ZH_DEV int ze_get_cparams(ZePar& out, const ZeRows& rows, uint32_t srcSize)
     if (c > w) c = w;                                      // cycleLog == chainLog below btlazy2
     if (w < 10) w = 10;
     out.wlog = w; out.clog = c; out.hlog = h; out.mml = r[4]; out.strat = r[6]; out.tlen = r[5];
+    // greedy: the row match finder with 16-entry rows on a source of one block (ze_greedy_row) -- windowLog >= 15 (at 14 and below libzstd searches hash chains,
+    // ZSTD_resolveRowMatchFinderMode zstd.c:23192), searchLog <= 4 (5 and 6 are rows of 32 and 64). Everything else from greedy up is refused, never approximated
+    if constexpr (GREEDY) {
+        out.slog = r[3];
+        if (out.strat == 3) { if (w < 15 || r[3] > 4 || h > ZE_MAX_HLOG || srcSize > ZF_BLOCK_MAX) return ZE_PARAM_UNSUPPORTED; }      // (hashLog above 17: refused before the search, as the entropy kernel would after it)
+        else if (out.strat != 1 && out.strat != 2) return ZE_PARAM_UNSUPPORTED;
+    } else
     if (out.strat != 1 && out.strat != 2) return ZE_PARAM_UNSUPPORTED;     // greedy and above are not implemented: refused, never approximated
     // an explicit window smaller than the source AND smaller than a block makes the match window slide inside a block
     // (ZSTD_getLowestPrefixIndex, zstd.c:19470); the level tables never produce that and the kernels do not implement it: refused
@@ -2891,7 +3001,7 @@ ZH_DEVFN int ze_frame(const ZhipEncodeArgs& a, ZeLDS& L, uint32_t f, uint8_t* ws
     if (cap64 < ze_compress_bound(srcSize)) return ZE_DST_TOO_SMALL;
     const uint32_t cap = cap64 > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)cap64;
     ZePar cp;
-    const int e = ze_get_cparams(cp, a.rows, srcSize);
+    const int e = ze_get_cparams<!SEARCH>(cp, a.rows, srcSize);          // (the entropy kernel codes the greedy match kernel's sequences; this function's own search refuses greedy)
     if (e) return e;
     uint32_t dictID = 0;
     if (a.cdict) {
@@ -2903,7 +3013,8 @@ ZH_DEVFN int ze_frame(const ZhipEncodeArgs& a, ZeLDS& L, uint32_t f, uint8_t* ws
         } else ze_dict_cparams(cp, *a.cdict, srcSize);
         if (a.dictIDFlag) dictID = a.cdict->dictID;
     }
-    if ((cp.strat != 2 && cp.strat != 1) || cp.hlog > ZE_MAX_HLOG || cp.clog > ZE_MAX_HLOG) return ZE_PARAM_UNSUPPORTED;
+    // (greedy: sequences of the greedy match kernel only -- any dictionary stays fast / double-fast)
+    if ((cp.strat != 2 && cp.strat != 1 && !(!SEARCH && cp.strat == 3 && pre && !a.cdict)) || cp.hlog > ZE_MAX_HLOG || cp.clog > ZE_MAX_HLOG) return ZE_PARAM_UNSUPPORTED;
     const uint32_t dictCode = (dictID > 0) + (dictID >= 256) + (dictID >= 65536);
     uint32_t pos = 0;
     const uint32_t contentSize = a.contentSizeFlag != 0, checksum = a.checksumFlag != 0;
@@ -3115,6 +3226,9 @@ ZH_DEVFN void ze_kernel_body(const ZhipEncodeArgs& a, ZeLDS& L, ZeLDSMulti& M)
 // E1: double-fast search with one LANE per frame. The search is a chain of dependent global-memory probes (hash table,
 // candidate bytes), so the way to throughput is frames in flight: every lane of the wave runs the serial search of its own
 // frame against its own tables; nothing is shared between lanes and no cross-lane operation is needed.
+// GREEDY = true: the kernel for batches whose one-block row is greedy (ze_greedy_row: positions and tags of 16-entry rows in the lane's table slot). An instantiation of its
+// own, so that the fast / double-fast kernel's code and registers are what they were; the host launches it instead of that one (zhip_compress_batch_device).
+template <bool GREEDY = false>
 ZH_DEVFN void ze_match_body(const ZhipEncodeArgs& a)
 {
     const uint32_t lane = zh_lane();
@@ -3135,7 +3249,7 @@ ZH_DEVFN void ze_match_body(const ZhipEncodeArgs& a)
             continue;
         }
         const uint32_t srcSize = (uint32_t)srcSize64;
-        bool bad = ze_get_cparams(cp, a.rows, srcSize) != 0;
+        bool bad = ze_get_cparams<GREEDY>(cp, a.rows, srcSize) != 0;
         if (!bad && a.cdict) {
             if (a.cdict->status) bad = true;
             else if (a.cdict->contentSize && srcSize > ze_dict_slot_max(a)) {            // table-copy mode (needs tables of the dictionary's own size and a
@@ -3144,6 +3258,16 @@ ZH_DEVFN void ze_match_body(const ZhipEncodeArgs& a)
                 continue;
             }
             else ze_dict_cparams(cp, *a.cdict, srcSize);
+        }
+        if constexpr (GREEDY) {
+            if (!bad && !a.cdict && cp.strat == 3) {
+                if ((size_t)(5u << cp.hlog) > a.tableStride) { m.mode = 2; a.meta[i] = m; continue; }
+                { ZdPack16* z = (ZdPack16*)tables; const uint32_t nz = (5u << cp.hlog) / 16; ZdPack16 zero; zero.a = zero.b = zero.c = zero.d = 0; for (uint32_t k = 0; k < nz; k++) z[k] = zero; }
+                m.nbSeq = ze_greedy_row((uint64_t*)(a.arena + (size_t)i * a.arenaStride + ZE_ARENA_SEQ), src, srcSize, cp, (uint32_t*)tables, tables + (4u << cp.hlog));
+                m.mode = 4;                                                              // sequences only: the entropy kernel gathers the literals
+                a.meta[i] = m;
+                continue;
+            }
         }
         if (bad || (cp.strat != 2 && cp.strat != 1) ||
             (size_t)(4u << cp.hlog) + (cp.strat == 2 ? (4u << cp.clog) : 0u) > a.tableStride) { m.mode = 2; a.meta[i] = m; continue; }   // E2 reports the error

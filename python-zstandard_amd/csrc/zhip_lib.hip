@@ -107,6 +107,8 @@ ZH_GLOBAL __launch_bounds__(64, 3) void zhip_encode_frames_kernel(ZhipEncodeArgs
     ze_kernel_body(a, L, M);
 }
 ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_kernel(ZhipEncodeArgs a) { ze_match_body(a); }
+// the greedy strategy's search (ze_greedy_row: level 5 on sources of 16 385 ... 131 072 bytes), lane-serial like the kernel above and launched in its place: a kernel of its own, that one is untouched
+ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_greedy_kernel(ZhipEncodeArgs a) { ze_match_body<true>(a); }
 ZH_GLOBAL __launch_bounds__(64) void zhip_encode_split_kernel(ZhipEncodeArgs a)          // block layout of sources of several blocks for the flat match kernel
 {
     __shared__ ZeLDS L;
@@ -646,15 +648,16 @@ extern "C" int zhip_ctx_set_cparams(zhip_ctx* c, const zhip_cparams* p)
     if (!c || !p) return ZHIP_ERR_UNSUPPORTED;
     if (p->dictType != ZHIP_DICT_AUTO && p->dictType != ZHIP_DICT_RAWCONTENT && p->dictType != ZHIP_DICT_FULLDICT) { g_lastError = "invalid dictionary type"; return ZHIP_ERR_UNSUPPORTED; }
     if (p->format != ZHIP_FORMAT_ZSTD1 && p->format != ZHIP_FORMAT_ZSTD1_MAGICLESS) { g_lastError = "invalid frame format"; return ZHIP_ERR_UNSUPPORTED; }
-    // level + explicit parameters -> one row per source-size class; the kernels implement the fast and double-fast strategies
+    // level + explicit parameters -> one row per source-size class; the kernels implement the fast and double-fast strategies, and greedy where libzstd runs it with the
+    // row match finder on 16-entry rows over one block: the row of 16 385 ... 131 072-byte sources, windowLog >= 15, searchLog <= 4 (ze_get_cparams decides per source: the window must cover it, hashLog <= 17)
     ZeRows rows;
     zh_resolve_rows(&rows, p->level, &p->cp);
     bool any = false;
     for (int t = 0; t < 4; t++) {
         if (!zh_check_cparams(rows.r[t])) return -ZE_PARAM_OUTOFBOUND;        // what ZSTD_CCtx_setParametersUsingCCtxParams reports
-        any |= rows.r[t][6] == 1 || rows.r[t][6] == 2;
+        any |= rows.r[t][6] == 1 || rows.r[t][6] == 2 || (t == 2 && rows.r[t][6] == 3 && rows.r[t][0] >= 15 && rows.r[t][3] <= 4);
     }
-    if (!any) { g_lastError = "HIP backend compresses with the fast and double-fast strategies only (levels <= 3, negative levels; level 4 for inputs above 16 KiB; or explicit strategy / parameters that select them)"; return ZHIP_ERR_UNSUPPORTED; }
+    if (!any) { g_lastError = "HIP backend compresses with the fast and double-fast strategies, and with greedy on inputs of 16 385 ... 131 072 bytes at search_log <= 4 (levels <= 3, negative levels; levels 4 and 5 for inputs above 16 KiB up to 128 KiB; or explicit strategy / parameters that select them)"; return ZHIP_ERR_UNSUPPORTED; }
     // nothing of a dictionary shorter than 8 bytes is loaded (ZSTD_compress_insertDictionary, zstd.c:28167) -- unless a full dictionary
     // was demanded, which is then "Dictionary mismatch"; so is a blob without the magic. The ZSTD_CDict still exists and its
     // parameter row (chosen for a 513-byte source) is what the frames are compressed with, so such a blob is digested like any other
@@ -1025,13 +1028,15 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
         // wave per frame. Frames are processed in chunks so that the per-frame sequence/literal arena stays bounded.
         // table bytes of the largest one-block source of the two size classes these kernels serve (<= 128 KiB, <= 16 KiB), after the
         // per-source adjustment ze_get_cparams makes (windowLog <= 17 / 14, hashLog <= windowLog + 1, chainLog <= windowLog)
+        // (greedy: the row match finder's positions and tags, 5 << hashLog bytes -- 640 KiB at level 5; only the row of 16 385 ... 131 072-byte sources can be served, ze_get_cparams)
+        const bool greedy = !c->hasCDict && a.rows.r[2][6] == 3 && a.rows.r[2][0] >= 15 && a.rows.r[2][3] <= 4;
         bool anyDfast = false; uint32_t stride = 0;
         for (int t = 2; t < 4; t++) {
             const int32_t* r = a.rows.r[t];
-            if (r[6] != 1 && r[6] != 2) continue;
+            if (r[6] != 1 && r[6] != 2 && !(greedy && t == 2)) continue;
             const int w = r[0] < (t == 2 ? 17 : 14) ? r[0] : (t == 2 ? 17 : 14);
             const int h = r[2] > w + 1 ? w + 1 : r[2], cl = r[1] > w ? w : r[1];
-            const uint32_t bytes = (4u << h) + (r[6] == 2 ? (4u << cl) : 0u);
+            const uint32_t bytes = r[6] == 3 ? (5u << h) : (4u << h) + (r[6] == 2 ? (4u << cl) : 0u);
             if (bytes > stride) stride = bytes;
             anyDfast |= r[6] == 2;
         }
@@ -1134,6 +1139,7 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
         a.e1Lanes = (uint32_t)e1Lanes;
         size_t g1max = (size_t)c->numCU * (size_t)c->e1PerCU; if (g1max * e1Lanes > laneCap) g1max = laneCap / e1Lanes;
         if (flat && g1max > 256) g1max = 256;                                      // only the frames the flat kernel declines
+        if (greedy) { const size_t byMem = ((size_t)8 << 30) / (e1Lanes * (size_t)a.tableStride); if (g1max > byMem) g1max = byMem ? byMem : 1; }      // (row tables: 8 GiB of them at most, 1 638 waves at level 5)
         const size_t w1 = (chunk + e1Lanes - 1) / e1Lanes;
         const uint32_t g1 = (uint32_t)(w1 < g1max ? w1 : g1max);
         size_t g2max = (size_t)c->numCU * (size_t)c->e2PerCU;
@@ -1339,7 +1345,8 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
                 if (tm) HIP_TRY(hipEventRecord(ev[1], stream));
             }
             if (tm) HIP_TRY(hipEventRecord(ev[2], stream));
-            hipLaunchKernelGGL(zhip_encode_match_kernel, dim3(g1), dim3(64), 0, stream, a);
+            if (greedy) hipLaunchKernelGGL(zhip_encode_match_greedy_kernel, dim3(g1), dim3(64), 0, stream, a);      // (takes the chunk's fast / double-fast sources, tiny ones and errors as the kernel below does)
+            else hipLaunchKernelGGL(zhip_encode_match_kernel, dim3(g1), dim3(64), 0, stream, a);
             if (tm) { HIP_TRY(hipEventRecord(ev[3], stream)); HIP_TRY(hipEventRecord(ev[4], stream)); }
             a.xxLater = ZHIP_TRAILER_LATER && a.checksumFlag ? 1u : 0u;
             hipLaunchKernelGGL(zhip_encode_entropy_kernel, dim3(g2), dim3(64), 0, stream, a);
