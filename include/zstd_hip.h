@@ -199,6 +199,58 @@ int zhip_ctx_sync(zhip_ctx*, void* stream, const int32_t* d_status, size_t n, zh
 int zhip_compact_device(const void* d_slots, const zhip_segment* d_slotSegs, const uint64_t* d_outSizes, const int32_t* d_status,
                         const uint64_t* d_offsets, size_t n, void* d_dense, void* stream);
 
+/* ---- seekable streams: one large HBM buffer compressed as a batch, any byte range read back ----
+ * The zstd seekable format: independent frames back to back, then ONE skippable frame that holds a seek table. Every zstd decoder
+ * decompresses such a stream unchanged (it passes over the skippable frame); a reader that knows the table touches only the frames that cover
+ * the range it wants. All fields little-endian:
+ *
+ *   Skippable_Magic_Number 4  0x184D2A5E
+ *   Frame_Size             4  bytes that follow this field: n * E + 9
+ *   Seek_Table_Entries   n*E  E = 8, or 12 with checksums: Compressed_Size (4), Decompressed_Size (4), [Checksum (4)]
+ *   Number_Of_Frames       4  n <= 2^27
+ *   Seek_Table_Descriptor  1  bit 7 = Checksum_Flag; bits 6..2 reserved (written 0, rejected when set); bits 1..0 unused (ignored)
+ *   Seekable_Magic_Number  4  0x8F92EAB1
+ *
+ * Checksum = the low 32 bits of XXH64 (seed 0) of the frame's uncompressed bytes, the value of a frame's own content-checksum trailer. Frame i
+ * starts at the sum of Compressed_Size over the entries in front of it; an entry may describe a skippable or an empty frame (Decompressed_Size 0);
+ * Decompressed_Size <= 2^30. DESIGN.md section 9 has the decisions. */
+#define ZHIP_SEEKABLE_CHECKSUM 1
+uint64_t zhip_seekable_frame_count(uint64_t srcSize, uint32_t frameSize);              /* ceil(srcSize / frameSize); 0 for srcSize 0 */
+uint64_t zhip_seekable_bound(uint64_t srcSize, uint32_t frameSize, int flags);          /* worst-case stream bytes; 0 = invalid arguments */
+/* Cuts [d_src, d_src + srcSize) into chunks of frameSize bytes (a shorter last one), compresses them as ONE batch through zhip_compress_batch_device with the
+ * context's level, parameters, flags and dictionary (into zhip_compress_bound-sized slots of context scratch), lays the frames back to back into d_dst and
+ * writes the table behind them. frameSize: 1 ... 2^30, at most 2^27 frames, else ZHIP_ERR_UNSUPPORTED. With ZHIP_SEEKABLE_CHECKSUM the entries carry checksums
+ * (of the source chunks), whether or not the context's checksumFlag puts trailers into the frames. Asynchronous and stream-ordered under exactly the rules
+ * above for zhip_compress_batch_device: no host wait between its kernels except while scratch grows. The context's size hint is left as the caller set it.
+ * d_status[0] = 0 or the zstd error code of the lowest failing frame, d_status[1] = that frame's index -- zhip_ctx_sync(ctx, stream, d_status, 1, &err) works on
+ * it as it is. A failure sets *d_streamSize = 0 and writes nothing into d_dst: a chunk the context's level refuses (40), a stream that does not fit dstCapacity
+ * (70; the index is the first frame that ends beyond it, the last frame where only the table does not fit). Nothing at or beyond d_dst + dstCapacity is ever
+ * written. srcSize 0 gives the 17-byte stream of zero frames. */
+int zhip_seekable_compress_device(zhip_ctx*, const void* d_src, uint64_t srcSize, uint32_t frameSize, int flags,
+                                  void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status /* [2] */, void* stream);
+
+typedef struct zhip_seekable zhip_seekable;
+typedef struct { uint64_t streamSize, contentSize; uint32_t nFrames, maxFrameContent; int checksumFlag; } zhip_seekable_info;
+/* Reads the table of a stream in HBM (any writer's) and returns a handle for range reads; d_stream is borrowed and must stay as it is while the handle lives.
+ * This call MAY WAIT on the host: it reads the 9-byte footer, then the 8-byte skippable header, then a kernel checks every entry and builds the exclusive prefix
+ * sums of both size columns in device memory the handle owns. Checked: both magics (a wrong one: ZHIP_ERR_ZSTD with prefix_unknown, 10), and -- each
+ * ZHIP_ERR_ZSTD with corruption_detected, 20 -- Frame_Size == n * E + 9, the reserved bits, n <= 2^27, every Decompressed_Size <= 2^30, the sum of
+ * Compressed_Size == the table frame's offset (streamSize - 8 - Frame_Size). No handle is created for a stream that fails. After a successful open no
+ * offset derived from the table points outside [d_stream, d_stream + streamSize). The handle keeps on the host what the range call needs. */
+int  zhip_seekable_open_device(zhip_ctx*, const void* d_stream, uint64_t streamSize, void* stream,
+                               zhip_seekable** out, zhip_seekable_info* info, zhip_error* err);
+void zhip_seekable_close(zhip_seekable*);      /* waits for the device (it frees device memory) */
+/* Content bytes [offset, offset + length) into d_dst. Asynchronous and stream-ordered, no host wait (but where the handle's scratch grows). offset + length
+ * beyond contentSize: ZHIP_ERR_SIZE_MISMATCH, both numbers in zhip_last_error(), nothing written. length 0 launches nothing and sets the status to 0. Else the
+ * frames that cover the range are decoded as ONE batch through zhip_decompress_batch_device: frames wholly inside the range straight into their place in d_dst,
+ * a first and a last frame that the range cuts into the handle's scratch, from where a device copy moves the covered part; entries with Decompressed_Size 0
+ * are never handed to the decoder; maxFrameContent above 128 KiB selects the several-block mode for these launches only. A frame that comes out at another
+ * size than its entry's fails with 20, with Checksum_Flag a frame whose XXH64 low word differs from its entry's with 22 (checksum_wrong); a frame the decoder
+ * refuses keeps the decoder's code. d_status = {code, frame index} of the lowest failing frame, {0, 0} without one. Bytes of d_dst outside [0, length) are untouched.
+ * Range calls on one handle follow the context's rule: one host thread and one stream at a time. */
+int  zhip_seekable_decompress_device(zhip_ctx*, zhip_seekable*, uint64_t offset, uint64_t length,
+                                     void* d_dst /* length bytes */, int32_t* d_status /* [2] */, void* stream);
+
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,
  * 4 K3, 5 / 6 the lane-serial match kernel (the greedy strategy's zhip_encode_match_greedy_kernel where that runs in its place) and the entropy kernel, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,

@@ -41,12 +41,18 @@ class CParams(C.Structure):
                 ("cp", CompressionParameters)]
 
 
+class SeekableInfo(C.Structure):
+    _fields_ = [("streamSize", C.c_uint64), ("contentSize", C.c_uint64), ("nFrames", C.c_uint32), ("maxFrameContent", C.c_uint32),
+                ("checksumFlag", C.c_int)]
+
+
 class DParams(C.Structure):
     _fields_ = [("dict", C.c_void_p), ("dictSize", C.c_size_t), ("maxWindowSize", C.c_uint64), ("dictType", C.c_int),
                 ("format", C.c_int)]
 
 
 DICT_AUTO, DICT_RAWCONTENT, DICT_FULLDICT = 0, 1, 2
+SEEKABLE_CHECKSUM = 1
 FORMAT_ZSTD1, FORMAT_ZSTD1_MAGICLESS = 0, 1
 
 
@@ -104,6 +110,12 @@ def lib():
         "zhip_ctx_kernel_time": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64)]),
         "zhip_ctx_table_pick": (C.c_int, [vp, C.POINTER(C.c_float)]),
         "zhip_ctx_decode_fallbacks": (C.c_int, [vp, C.POINTER(u64)]),
+        "zhip_seekable_frame_count": (u64, [u64, C.c_uint32]),
+        "zhip_seekable_bound": (u64, [u64, C.c_uint32, C.c_int]),
+        "zhip_seekable_compress_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_int, vp, u64, vp, vp, vp]),
+        "zhip_seekable_open_device": (C.c_int, [vp, vp, u64, vp, C.POINTER(vp), C.POINTER(SeekableInfo), C.POINTER(Error)]),
+        "zhip_seekable_close": (None, [vp]),
+        "zhip_seekable_decompress_device": (C.c_int, [vp, vp, u64, u64, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         f = getattr(L, name)
@@ -122,6 +134,8 @@ EXPORTED_SYMBOLS = [
     "zhip_ctx_set_cparams", "zhip_decompress_batch_device", "zhip_compress_batch_device", "zhip_ctx_sync",
     "zhip_kernel_name", "zhip_ctx_kernel_time", "zhip_thread_memory_size", "zhip_compact_device", "zhip_ctx_set_size_hint",
     "zhip_ctx_table_pick", "zhip_ctx_decode_fallbacks", "zhip_partition_by_bytes", "zhip_batch_devices",
+    "zhip_seekable_frame_count", "zhip_seekable_bound", "zhip_seekable_compress_device", "zhip_seekable_open_device", "zhip_seekable_close",
+    "zhip_seekable_decompress_device",
 ]
 
 

@@ -11,12 +11,14 @@
 #include <time.h>
 #include <stdlib.h>
 #include <string.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include "../../include/zstd_hip.h"
 #include "zhip_decode_pipeline.hpp"
 #include "zhip_encode_kernel.hpp"
 #include "zhip_cparams.hpp"
+#include "zhip_seekable.hpp"
 
 #define ZHIP_LDS_BYTES (160u * 1024u)      // per CU on gfx950
 #ifndef ZHIP_E1LDS_PER_CU
@@ -401,6 +403,7 @@ struct zhip_ctx {
     int dformat = ZHIP_FORMAT_ZSTD1;
     // host-API staging
     DevBuf hSrc, hDst, hSegs, hStatus, hDense;
+    DevBuf skSlots, skMeta;            // seekable streams: the chunks' compressBound-sized slots; segments, sizes, statuses and the scan's cells
     void* pinned = nullptr; size_t pinnedCap = 0;
     bool hpReady = false; hipStream_t hpH2D = nullptr, hpCompute = nullptr, hpD2H = nullptr;     // host pipeline: copy-in, kernels, copy-out
     void* hpStage[2] = {nullptr, nullptr}; size_t hpStageCap[2] = {0, 0}; hipEvent_t hpStageFree[2] = {nullptr, nullptr}; int hpNextSlot = 0;
@@ -443,7 +446,7 @@ struct zhip_ctx {
     {
         const DevBuf* all[] = {&pipeMeta, &pipeLit, &pipeCounters, &pipeFallback, &pipeFse, &pipeOrder, &pipeHuf, &pipeOrderLit, &pipeItemFrame, &pipeItemReps, &pipeFrameRecs, &pipeBases, &pipePre, &encWorkspace, &encMeta, &encArena,
                                &encTables, &encBigList, &encBigWs, &encFlatTables, &encE1List, &encMbBlocks, &encMbCount, &encMbSeqs, &scratch, &counter, &cdictBlob, &cdictEntropy, &cdictDigest, &cdictTables,
-                               &dictBlob, &dictEntropy, &dictTables, &hSrc, &hDst, &hSegs, &hStatus, &hDense};
+                               &dictBlob, &dictEntropy, &dictTables, &hSrc, &hDst, &hSegs, &hStatus, &hDense, &skSlots, &skMeta};
         size_t n = 0;
         for (const DevBuf* b : all) n += b->cap;
         return n;
@@ -518,6 +521,7 @@ extern "C" void zhip_ctx_destroy(zhip_ctx* c)
     c->scratch.release(); c->counter.release(); c->encWorkspace.release(); c->encMeta.release(); c->encArena.release(); c->encTables.release(); c->encBigList.release(); c->encBigWs.release(); c->encFlatTables.release(); c->encE1List.release(); c->encMbBlocks.release(); c->encMbCount.release(); c->encMbSeqs.release(); c->dictBlob.release(); c->dictEntropy.release(); c->dictTables.release();
     c->cdictBlob.release(); c->cdictEntropy.release(); c->cdictDigest.release(); c->cdictTables.release();
     c->hSrc.release(); c->hDst.release(); c->hSegs.release(); c->hStatus.release(); c->hDense.release();
+    c->skSlots.release(); c->skMeta.release();
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->profDecode) (void)hipFree(c->profDecode);
     if (c->profPipe) (void)hipFree(c->profPipe);
@@ -2086,4 +2090,181 @@ extern "C" int zhip_decompress_batch(const zhip_dparams* params, const zhip_item
     std::vector<uint64_t> sizes(n);
     for (size_t i = 0; i < n; i++) sizes[i] = items[i].srcSize;
     return fan_out(d, sizes, n, [&](size_t lo, size_t hi, zhip_outbuf** o, size_t* no, zhip_error* e) { return decompress_batch_one(params, items + lo, hi - lo, requireSizes, o, no, e); }, out, nOut, err);
+}
+
+// ------------------------------------------------------------------------------------------ seekable streams (zhip_seekable.hpp)
+// One large buffer as the batch the kernels are fast at: chunks of frameSize bytes -> zhip_compress_batch_device -> frames back to back + the seek table;
+// a range read is zhip_decompress_batch_device over the frames that cover it. Everything between the batch calls is the small kernels of zhip_seekable.hpp,
+// queued on the caller's stream: no call here waits on the host except where scratch grows, and zhip_seekable_open_device, which reads the table's shape.
+static uint32_t zsk_lane_grid(const zhip_ctx* c, uint64_t lanes)
+{
+    const uint64_t w = (lanes + 63) / 64, gm = (uint64_t)(c->numCU > 0 ? c->numCU : 1) * 8;
+    return (uint32_t)(w < 1 ? 1 : w < gm ? w : gm);
+}
+static int zsk_launch_scan(ZskScanArgs a, hipStream_t stream)
+{
+    const uint32_t grid = zsk_scan_shape(a.n, &a.span);
+    hipLaunchKernelGGL(zhip_seekable_scan_reduce_kernel, dim3(grid), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(zhip_seekable_scan_write_kernel, dim3(grid), dim3(64), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+static size_t zsk_up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+extern "C" uint64_t zhip_seekable_frame_count(uint64_t srcSize, uint32_t frameSize) { return zsk_frame_count(srcSize, frameSize); }
+extern "C" uint64_t zhip_seekable_bound(uint64_t srcSize, uint32_t frameSize, int flags)
+{
+    if (flags & ~ZHIP_SEEKABLE_CHECKSUM) return 0;
+    return zsk_bound(srcSize, frameSize, flags & ZHIP_SEEKABLE_CHECKSUM);
+}
+
+extern "C" int zhip_seekable_compress_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, uint32_t frameSize, int flags,
+                                             void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+{
+    if (!c || !d_streamSize || !d_status || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) { g_lastError = "seekable compress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
+    if (!zsk_args_ok(srcSize, frameSize)) { g_lastError = "seekable compress: frameSize must be 1 ... 2^30 and the frame count at most 2^27"; return ZHIP_ERR_UNSUPPORTED; }
+    hipStream_t stream = (hipStream_t)streamv;
+    const size_t n = (size_t)zsk_frame_count(srcSize, frameSize);
+    // (growing either area frees the old one, which waits for the device: the wait the stream-order rules allow)
+    const size_t oSrcSegs = 0, oSlotSegs = oSrcSegs + zsk_up16(n * 16), oSizes = oSlotSegs + zsk_up16(n * 16), oOffs = oSizes + zsk_up16(n * 8),
+                 oPartSum = oOffs + zsk_up16((n + 1) * 8), oPartBad = oPartSum + ZSK_SCAN_GRID * 8, oGo = oPartBad + ZSK_SCAN_GRID * 8, oStatus = oGo + 16, metaBytes = oStatus + zsk_up16(n * 4);
+    if (c->skMeta.reserve(metaBytes)) return g_reserveRc;
+    if (n && c->skSlots.reserve((size_t)(n * zsk_slot_stride(frameSize)))) return g_reserveRc;
+    uint8_t* const m = (uint8_t*)c->skMeta.p;
+    ZskCompressArgs a; memset(&a, 0, sizeof a);
+    a.src = (const uint8_t*)d_src; a.srcSize = srcSize; a.frameSize = frameSize; a.n = (uint32_t)n; a.checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1u : 0u;
+    a.srcSegs = (uint64_t*)(m + oSrcSegs); a.slotSegs = (uint64_t*)(m + oSlotSegs); a.outSizes = (const uint64_t*)(m + oSizes); a.status = (int32_t*)(m + oStatus);
+    a.offs = (const uint64_t*)(m + oOffs); a.partBad = (const uint64_t*)(m + oPartBad);
+    a.dst = (uint8_t*)d_dst; a.dstCapacity = dstCapacity; a.streamSize = d_streamSize; a.outStatus = d_status; a.go = (uint32_t*)(m + oGo);
+    if (n) {
+        hipLaunchKernelGGL(zhip_seekable_chunk_segs_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, a);
+        HIP_TRY(hipGetLastError());
+        // the batch knows its largest source, as the host-buffer calls' batches do; the caller's own size hint is not touched
+        const size_t hintWas = c->srcMaxHint;
+        c->srcMaxHint = (size_t)(srcSize < frameSize ? srcSize : frameSize);
+        const int rc = zhip_compress_batch_device(c, d_src, (const zhip_segment*)a.srcSegs, n, c->skSlots.p, (const zhip_segment*)a.slotSegs, (uint64_t*)(m + oSizes), a.status, stream);
+        c->srcMaxHint = hintWas;
+        if (rc) return rc;
+    }
+    ZskScanArgs s; memset(&s, 0, sizeof s);
+    s.in = m + oSizes; s.status = a.status; s.mode = 0; s.n = (uint32_t)n; s.offs = (uint64_t*)(m + oOffs); s.partSum = (uint64_t*)(m + oPartSum); s.partBad = (uint64_t*)(m + oPartBad);
+    uint32_t span; a.nPart = zsk_scan_shape(s.n, &span);
+    if (int rc = zsk_launch_scan(s, stream)) return rc;
+    hipLaunchKernelGGL(zhip_seekable_verdict_kernel, dim3(1), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(zhip_seekable_table_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    if (n) {
+        const size_t gmax = (size_t)c->numCU * 16;
+        hipLaunchKernelGGL(zhip_compact_kernel, dim3((uint32_t)(n < gmax ? n : gmax)), dim3(64), 0, stream, (const uint8_t*)c->skSlots.p, (const zhip_segment*)a.slotSegs, a.outSizes,
+                           (const int32_t*)a.status, a.offs, (uint32_t)n, (uint8_t*)d_dst);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+struct zhip_seekable {
+    const uint8_t* stream = nullptr; uint64_t streamSize = 0;
+    ZskLayout lay = {0, 8, 0, 0};
+    uint64_t contentSize = 0; uint32_t maxFrameContent = 0;
+    DevBuf prefix;                       // the table's scans: compressed offsets, decompressed offsets, place among the frames with content -- [n + 1] each
+    DevBuf meta, edge;                   // a range call's segments / sizes / statuses, and where its partly covered frames are decoded
+    std::vector<uint64_t> dOff, place;   // the host's copies: which frames cover a range, and how many of them go to the decoder
+};
+
+extern "C" void zhip_seekable_close(zhip_seekable* h)
+{
+    if (!h) return;
+    h->prefix.release(); h->meta.release(); h->edge.release();
+    delete h;
+}
+
+extern "C" int zhip_seekable_open_device(zhip_ctx* c, const void* d_stream, uint64_t streamSize, void* streamv, zhip_seekable** out, zhip_seekable_info* info, zhip_error* err)
+{
+    if (err) memset(err, 0, sizeof *err);
+    if (out) *out = nullptr;
+    if (!c || !d_stream || !out) { g_lastError = "seekable open: bad arguments"; return set_err(err, ZHIP_ERR_UNSUPPORTED, 0, 0); }
+    hipStream_t stream = (hipStream_t)streamv;
+    const uint8_t* const base = (const uint8_t*)d_stream;
+    ZskLayout lay;
+    if (streamSize < ZSK_HEADER + ZSK_FOOTER) return set_err(err, ZHIP_ERR_ZSTD, 0, ZSK_ERR_CORRUPT);
+    uint8_t foot[ZSK_FOOTER], head[ZSK_HEADER];
+    if (hipMemcpyAsync(foot, base + streamSize - ZSK_FOOTER, ZSK_FOOTER, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { g_lastError = "seekable open: reading the footer failed"; return set_err(err, ZHIP_ERR_HIP, 0, 0); }
+    if (int e = zsk_parse_footer(foot, streamSize, &lay)) return set_err(err, ZHIP_ERR_ZSTD, 0, e);
+    if (hipMemcpyAsync(head, base + lay.tableOffset, ZSK_HEADER, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { g_lastError = "seekable open: reading the table's header failed"; return set_err(err, ZHIP_ERR_HIP, 0, 0); }
+    if (int e = zsk_check_header(head, &lay)) return set_err(err, ZHIP_ERR_ZSTD, 0, e);
+    // every entry now lies inside the stream; the kernels check what the entries SAY and build the offsets
+    zhip_seekable* h = new zhip_seekable();
+    auto fail = [&](int kind, int zerr) { zhip_seekable_close(h); return set_err(err, kind, 0, zerr); };
+    h->stream = base; h->streamSize = streamSize; h->lay = lay;
+    const size_t n = lay.n, col = zsk_up16((n + 1) * 8), part = ZSK_SCAN_GRID * 8;
+    if (h->prefix.reserve(3 * col) || h->meta.reserve(6 * part)) return fail(g_reserveRc, 0);
+    uint8_t* const pre = (uint8_t*)h->prefix.p; uint8_t* const pm = (uint8_t*)h->meta.p;
+    const uint8_t* const entries = base + lay.tableOffset + ZSK_HEADER;
+    for (int k = 0; k < 3; k++) {
+        ZskScanArgs s; memset(&s, 0, sizeof s);
+        s.in = entries + (k ? 4 : 0); s.stride = lay.entry; s.mode = k == 2 ? 2u : 1u; s.limit = k == 1 ? ZSK_MAX_CONTENT : 0xFFFFFFFFu; s.n = lay.n;
+        s.offs = (uint64_t*)(pre + k * col); s.partSum = (uint64_t*)(pm + 2 * k * part); s.partBad = (uint64_t*)(pm + (2 * k + 1) * part);
+        if (zsk_launch_scan(s, stream)) return fail(ZHIP_ERR_HIP, 0);
+    }
+    uint32_t span; const uint32_t grid = zsk_scan_shape(lay.n, &span);
+    std::vector<uint64_t> bad(grid);
+    uint64_t compressedTotal = 0;
+    h->dOff.resize(n + 1); h->place.resize(n + 1);
+    if (hipMemcpyAsync(h->dOff.data(), pre + col, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemcpyAsync(h->place.data(), pre + 2 * col, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipMemcpyAsync(bad.data(), pm + 3 * part, grid * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemcpyAsync(&compressedTotal, pre + n * 8, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+        hipStreamSynchronize(stream) != hipSuccess) { g_lastError = "seekable open: reading the table's scans failed"; return fail(ZHIP_ERR_HIP, 0); }
+    uint64_t lowestBad = ZSK_NONE;
+    for (uint64_t b : bad) if (b < lowestBad) lowestBad = b;
+    if (int e = zsk_table_verdict(lowestBad, compressedTotal, &lay)) { if (err) err->index = lowestBad != ZSK_NONE ? (size_t)lowestBad : 0; return fail(ZHIP_ERR_ZSTD, e) ; }
+    h->contentSize = h->dOff[n];
+    for (size_t i = 0; i < n; i++) { const uint64_t d = h->dOff[i + 1] - h->dOff[i]; if (d > h->maxFrameContent) h->maxFrameContent = (uint32_t)d; }
+    if (info) { info->streamSize = streamSize; info->contentSize = h->contentSize; info->nFrames = lay.n; info->maxFrameContent = h->maxFrameContent; info->checksumFlag = lay.checksum; }
+    *out = h;
+    return 0;
+}
+
+extern "C" int zhip_seekable_decompress_device(zhip_ctx* c, zhip_seekable* h, uint64_t offset, uint64_t length, void* d_dst, int32_t* d_status, void* streamv)
+{
+    if (!c || !h || !d_status) { g_lastError = "seekable decompress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
+    hipStream_t stream = (hipStream_t)streamv;
+    const uint64_t end = offset + length;
+    if (end < offset || end > h->contentSize) {
+        char buf[160]; snprintf(buf, sizeof buf, "seekable decompress: the range ends at %llu, the content at %llu", (unsigned long long)end, (unsigned long long)h->contentSize);
+        g_lastError = buf;
+        return ZHIP_ERR_SIZE_MISMATCH;
+    }
+    if (!length) { HIP_TRY(hipMemsetAsync(d_status, 0, 2 * sizeof(int32_t), stream)); return 0; }
+    if (!d_dst) { g_lastError = "seekable decompress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
+    // the frames that hold the range's first and last byte (both hold content: upper_bound steps over frames of none)
+    const std::vector<uint64_t>& D = h->dOff;
+    const uint32_t f0 = (uint32_t)(std::upper_bound(D.begin(), D.end(), offset) - D.begin() - 1), f1 = (uint32_t)(std::upper_bound(D.begin(), D.end(), end - 1) - D.begin() - 1);
+    const size_t count = (size_t)(h->place[f1 + 1] - h->place[f0]);
+    const bool cut0 = D[f0] < offset || D[f0 + 1] > end, cut1 = f1 != f0 && D[f1 + 1] > end;
+    const size_t edgeBytes = (size_t)((cut0 ? D[f0 + 1] - D[f0] : 0) + (cut1 ? D[f1 + 1] - D[f1] : 0));
+    const size_t oSrcSegs = 0, oDstSegs = oSrcSegs + zsk_up16(count * 16), oSizes = oDstSegs + zsk_up16(count * 16), oFrameOf = oSizes + zsk_up16(count * 8), oStatus = oFrameOf + zsk_up16(count * 4),
+                 oWorst = oStatus + zsk_up16(count * 4), metaBytes = oWorst + 16;
+    if (h->meta.reserve(metaBytes)) return g_reserveRc;
+    if (edgeBytes && h->edge.reserve(edgeBytes)) return g_reserveRc;
+    uint8_t* const m = (uint8_t*)h->meta.p; uint8_t* const pre = (uint8_t*)h->prefix.p;
+    const size_t col = zsk_up16(((size_t)h->lay.n + 1) * 8);
+    ZskRangeArgs a; memset(&a, 0, sizeof a);
+    a.cOff = (const uint64_t*)pre; a.dOff = (const uint64_t*)(pre + col); a.place = (const uint64_t*)(pre + 2 * col);
+    a.table = h->stream + h->lay.tableOffset + ZSK_HEADER; a.entry = h->lay.entry; a.checksum = (uint32_t)h->lay.checksum;
+    a.f0 = f0; a.f1 = f1; a.count = (uint32_t)count; a.offset = offset; a.length = length;
+    a.dst = (uint8_t*)d_dst; a.edge = edgeBytes ? (uint8_t*)h->edge.p : a.dst; a.dstBase = a.edge < a.dst ? a.edge : a.dst;
+    a.srcSegs = (uint64_t*)(m + oSrcSegs); a.dstSegs = (uint64_t*)(m + oDstSegs); a.frameOf = (uint32_t*)(m + oFrameOf);
+    a.outSizes = (const uint64_t*)(m + oSizes); a.status = (int32_t*)(m + oStatus); a.worst = (uint32_t*)(m + oWorst); a.outStatus = d_status;
+    HIP_TRY(hipMemsetAsync(a.worst, 0, 4, stream));
+    hipLaunchKernelGGL(zhip_seekable_range_segs_kernel, dim3(zsk_lane_grid(c, (uint64_t)f1 - f0 + 1)), dim3(64), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    // frames above one block: the several-block mode, for these launches only
+    const size_t hintWas = c->dstMaxHint;
+    if (h->maxFrameContent > ZF_BLOCK_MAX) c->dstMaxHint = h->maxFrameContent;
+    const int rc = zhip_decompress_batch_device(c, h->stream, (const zhip_segment*)a.srcSegs, count, a.dstBase, (const zhip_segment*)a.dstSegs, (uint64_t*)(m + oSizes), a.status, stream);
+    c->dstMaxHint = hintWas;
+    if (rc) return rc;
+    hipLaunchKernelGGL(zhip_seekable_range_verify_kernel, dim3(zsk_lane_grid(c, count)), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(zhip_seekable_range_finish_kernel, dim3(zsk_lane_grid(c, (uint64_t)edgeBytes / 16 + 1)), dim3(64), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }

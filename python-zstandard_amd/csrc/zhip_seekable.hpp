@@ -1,0 +1,305 @@
+// zhip_seekable.hpp -- the zstd seekable format on the device: independent frames back to back, then one skippable frame that holds a seek table
+//
+//     Skippable_Magic_Number 0x184D2A5E | Frame_Size = n * E + 9 | n entries of E = 8 (12 with checksums) bytes | Number_Of_Frames | Descriptor | 0x8F92EAB1
+//
+// (all little-endian; an entry is Compressed_Size, Decompressed_Size and, with bit 7 of the descriptor, the low 32 bits of XXH64 of the frame's content).
+// What is here: the format's arithmetic and checks (plain functions, host and device), and the kernels around the batch calls -- chunk segments, a
+// multi-workgroup exclusive scan of 64-bit sizes, the table writer, and the range pieces (segment builder, size / checksum verifier, edge copy).
+// Every kernel is one-wave workgroups written against zhip_device.hpp, so the same bodies run under the host wave emulator (tests/emu/emu_seekable.cpp).
+#pragma once
+#include "zhip_device.hpp"
+#include "zhip_xxh64.hpp"
+
+#ifndef ZHIP_EMU
+#define ZSK_HD __host__ __device__ static inline
+#else
+#define ZSK_HD static inline
+#endif
+
+#define ZSK_SKIP_MAGIC 0x184D2A5Eu
+#define ZSK_SEEK_MAGIC 0x8F92EAB1u
+#define ZSK_MAX_FRAMES 0x8000000u            // 2^27
+#define ZSK_MAX_CONTENT 0x40000000u          // 2^30: most bytes one frame may decompress to
+#define ZSK_FOOTER 9u                        // Number_Of_Frames, descriptor, magic
+#define ZSK_HEADER 8u                        // skippable magic, Frame_Size
+#define ZSK_ERR_PREFIX 10
+#define ZSK_ERR_CORRUPT 20
+#define ZSK_ERR_CHECKSUM 22
+#define ZSK_ERR_DSTSIZE 70
+#define ZSK_NONE (~(uint64_t)0)
+
+// the scan's tiles: a workgroup is one wave; a lane takes ZSK_SCAN_PER_LANE neighbouring items of a tile, a workgroup walks a contiguous span of whole tiles,
+// and a launch has at most ZSK_SCAN_GRID workgroups -- beyond ZSK_SCAN_GRID tiles (one full grid pass) the spans are several tiles long
+#define ZSK_SCAN_LANES 64u
+#define ZSK_SCAN_PER_LANE 4u
+#define ZSK_SCAN_TILE (ZSK_SCAN_LANES * ZSK_SCAN_PER_LANE)
+#define ZSK_SCAN_GRID 1024u
+
+ZSK_HD uint64_t zsk_compress_bound(uint64_t n) { return n + (n >> 8) + (n < (128u << 10) ? (((128u << 10) - n) >> 11) : 0); }      // == zhip_compress_bound
+ZSK_HD uint64_t zsk_frame_count(uint64_t srcSize, uint32_t frameSize) { return frameSize ? srcSize / frameSize + (srcSize % frameSize ? 1 : 0) : 0; }
+ZSK_HD uint32_t zsk_entry_size(int checksum) { return checksum ? 12u : 8u; }
+ZSK_HD uint64_t zsk_table_size(uint64_t n, int checksum) { return ZSK_HEADER + n * zsk_entry_size(checksum) + ZSK_FOOTER; }
+ZSK_HD bool zsk_args_ok(uint64_t srcSize, uint32_t frameSize) { return frameSize >= 1 && frameSize <= ZSK_MAX_CONTENT && zsk_frame_count(srcSize, frameSize) <= ZSK_MAX_FRAMES; }
+// distance between the compressBound-sized slots the chunks are compressed into (16-byte aligned: the compaction reads a slot 16 bytes at a time)
+ZSK_HD uint64_t zsk_slot_stride(uint32_t frameSize) { return (zsk_compress_bound(frameSize) + 15) & ~(uint64_t)15; }
+ZSK_HD uint64_t zsk_bound(uint64_t srcSize, uint32_t frameSize, int checksum)
+{
+    if (!zsk_args_ok(srcSize, frameSize)) return 0;
+    const uint64_t n = zsk_frame_count(srcSize, frameSize);
+    if (!n) return zsk_table_size(0, checksum);
+    return (n - 1) * zsk_compress_bound(frameSize) + zsk_compress_bound(srcSize - (n - 1) * frameSize) + zsk_table_size(n, checksum);
+}
+
+struct ZskLayout { uint32_t n, entry; int checksum; uint64_t tableOffset; };      // tableOffset: where the table frame starts == what the compressed sizes must sum to
+static inline uint32_t zsk_rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+// the last 9 bytes of a stream of streamSize bytes -> the table's shape. 0, or the zstd error code
+static inline int zsk_parse_footer(const uint8_t* footer, uint64_t streamSize, ZskLayout* l)
+{
+    if (streamSize < ZSK_HEADER + ZSK_FOOTER) return ZSK_ERR_CORRUPT;
+    if (zsk_rd32(footer + 5) != ZSK_SEEK_MAGIC) return ZSK_ERR_PREFIX;
+    const uint32_t desc = footer[4];
+    if (desc & 0x7Cu) return ZSK_ERR_CORRUPT;                                  // reserved bits 6..2 (bits 1..0 are unused: ignored)
+    l->checksum = (desc >> 7) & 1; l->entry = zsk_entry_size(l->checksum);
+    l->n = zsk_rd32(footer);
+    if (l->n > ZSK_MAX_FRAMES) return ZSK_ERR_CORRUPT;
+    const uint64_t table = zsk_table_size(l->n, l->checksum);
+    if (table > streamSize) return ZSK_ERR_CORRUPT;
+    l->tableOffset = streamSize - table;
+    return 0;
+}
+// the 8 bytes at l->tableOffset
+static inline int zsk_check_header(const uint8_t* header, const ZskLayout* l)
+{
+    if (zsk_rd32(header) != ZSK_SKIP_MAGIC) return ZSK_ERR_PREFIX;
+    if ((uint64_t)zsk_rd32(header + 4) != (uint64_t)l->n * l->entry + ZSK_FOOTER) return ZSK_ERR_CORRUPT;
+    return 0;
+}
+// what the kernels found: the lowest entry with a Decompressed_Size above the limit (ZSK_NONE: none) and the sum of the Compressed_Size column
+static inline int zsk_table_verdict(uint64_t lowestBad, uint64_t compressedTotal, const ZskLayout* l) { return lowestBad != ZSK_NONE || compressedTotal != l->tableOffset ? ZSK_ERR_CORRUPT : 0; }
+
+// ------------------------------------------------------------------------------------------------ wave helpers (64-bit values over the 32-bit shuffles)
+ZH_DEV uint64_t zsk_shfl64(uint64_t v, uint32_t srcLane) { const uint32_t lo = zh_shfl((uint32_t)v, srcLane), hi = zh_shfl((uint32_t)(v >> 32), srcLane); return ((uint64_t)hi << 32) | lo; }
+ZH_DEV uint64_t zsk_wave_sum64(uint64_t v) { for (uint32_t d = 32; d; d >>= 1) v += zsk_shfl64(v, zh_lane() ^ d); return v; }
+ZH_DEV uint64_t zsk_wave_min64(uint64_t v) { for (uint32_t d = 32; d; d >>= 1) { const uint64_t o = zsk_shfl64(v, zh_lane() ^ d); v = o < v ? o : v; } return v; }
+ZH_DEV uint64_t zsk_wave_scan64(uint64_t v)          // inclusive
+{
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t lo = zh_shfl_up((uint32_t)v, d), hi = zh_shfl_up((uint32_t)(v >> 32), d);
+        if (zh_lane() >= d) v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+
+// ------------------------------------------------------------------------------------------------ the scan
+// Exclusive prefix sums of n 64-bit sizes in two launches of the same grid: zsk_scan_reduce (a workgroup's span -> its sum and its lowest bad item) and
+// zsk_scan_write (the sums of the workgroups in front, then the span again tile by tile). No workgroup waits for another one.
+//   mode 0: in = uint64_t[n]; an item whose status is non-zero counts 0 and is "bad"
+//   mode 1: in = a 32-bit column of the seek table (any alignment), `stride` bytes from entry to entry; an item above `limit` is "bad"
+//   mode 2: the same column, an item counts 1 where it is non-zero (which place a frame has among those that hold content)
+struct ZskScanArgs {
+    const uint8_t* in; const int32_t* status; uint32_t stride, mode, limit, n;
+    uint32_t span;                    // items per workgroup: whole tiles (zsk_scan_shape)
+    uint64_t* offs;                   // [n + 1]: offs[n] = the total
+    uint64_t* partSum; uint64_t* partBad;      // [grid]
+};
+static inline uint32_t zsk_scan_shape(uint32_t n, uint32_t* span)
+{
+    const uint32_t tiles = n / ZSK_SCAN_TILE + (n % ZSK_SCAN_TILE ? 1 : 0);
+    const uint32_t grid = tiles < 1 ? 1 : tiles < ZSK_SCAN_GRID ? tiles : ZSK_SCAN_GRID;
+    *span = (tiles / grid + (tiles % grid ? 1 : 0)) * ZSK_SCAN_TILE;
+    return grid;
+}
+ZH_DEV uint64_t zsk_scan_item(const ZskScanArgs& a, uint32_t i, bool* bad)
+{
+    if (a.mode == 0) { const bool b = a.status[i] != 0; *bad = b; return b ? 0 : ((const uint64_t*)a.in)[i]; }
+    const uint32_t v = zh_ld32(a.in + (size_t)i * a.stride);
+    *bad = v > a.limit;
+    return a.mode == 1 ? (uint64_t)v : (uint64_t)(v != 0);
+}
+ZH_DEV void zsk_scan_reduce_body(const ZskScanArgs& a)
+{
+    const uint64_t lo64 = (uint64_t)zh_block() * a.span;
+    const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n, hi = a.n - lo < a.span ? a.n : lo + a.span;
+    uint64_t sum = 0, lowest = ZSK_NONE;
+    for (uint32_t i = lo + zh_lane(); i < hi; i += ZSK_SCAN_LANES) {
+        bool bad; sum += zsk_scan_item(a, i, &bad);
+        if (bad && lowest == ZSK_NONE) lowest = i;
+    }
+    sum = zsk_wave_sum64(sum); lowest = zsk_wave_min64(lowest);
+    if (zh_lane() == 0) { a.partSum[zh_block()] = sum; a.partBad[zh_block()] = lowest; }
+}
+ZH_DEV void zsk_scan_write_body(const ZskScanArgs& a)
+{
+    const uint32_t b = zh_block();
+    uint64_t base = 0, all = 0;
+    for (uint32_t j = zh_lane(); j < zh_nblocks(); j += ZSK_SCAN_LANES) { const uint64_t s = a.partSum[j]; all += s; if (j < b) base += s; }
+    base = zsk_wave_sum64(base);
+    if (b == 0) { all = zsk_wave_sum64(all); if (zh_lane() == 0) a.offs[a.n] = all; }
+    const uint64_t lo64 = (uint64_t)b * a.span;
+    const uint32_t lo = lo64 < a.n ? (uint32_t)lo64 : a.n, hi = a.n - lo < a.span ? a.n : lo + a.span;
+    for (uint32_t t = lo; t < hi; t += ZSK_SCAN_TILE) {                  // (t, hi are the same in every lane: the wave stays together through the shuffles)
+        const uint32_t first = t + zh_lane() * ZSK_SCAN_PER_LANE;
+        uint64_t v[ZSK_SCAN_PER_LANE], mine = 0;
+        for (uint32_t k = 0; k < ZSK_SCAN_PER_LANE; k++) { bool bad; v[k] = first + k < hi ? zsk_scan_item(a, first + k, &bad) : 0; mine += v[k]; }
+        const uint64_t incl = zsk_wave_scan64(mine);
+        uint64_t run = base + incl - mine;
+        for (uint32_t k = 0; k < ZSK_SCAN_PER_LANE; k++) if (first + k < hi) { a.offs[first + k] = run; run += v[k]; }
+        base += zsk_shfl64(incl, 63);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ compress: chunks, verdict, table
+struct ZskCompressArgs {
+    const uint8_t* src; uint64_t srcSize; uint32_t frameSize, n, checksum, nPart;
+    uint64_t* srcSegs; uint64_t* slotSegs;      // [n][2]: (offset, length) of chunk i in src, of its slot in the slot area
+    const uint64_t* outSizes; int32_t* status;  // [n]: what zhip_compress_batch_device wrote
+    const uint64_t* offs;                       // [n + 1]: the scan of outSizes
+    const uint64_t* partBad;                    // [nPart]: the scan's lowest failing frame per workgroup
+    uint8_t* dst; uint64_t dstCapacity;
+    uint64_t* streamSize; int32_t* outStatus;   // the caller's
+    uint32_t* go;                               // 1: the stream is written; 0: it failed, nothing is
+};
+ZH_DEV uint32_t zsk_chunk_len(const ZskCompressArgs& a, uint32_t i) { const uint64_t at = (uint64_t)i * a.frameSize, left = a.srcSize - at; return left < a.frameSize ? (uint32_t)left : a.frameSize; }
+// a lane per frame: where chunk i lies in the source, and the compressBound-sized slot it is compressed into
+ZH_DEV void zsk_chunk_segs_body(const ZskCompressArgs& a)
+{
+    const uint64_t stride = zsk_slot_stride(a.frameSize);
+    for (uint64_t i = (uint64_t)zh_block() * 64 + zh_lane(); i < a.n; i += (uint64_t)zh_nblocks() * 64) {
+        const uint32_t len = zsk_chunk_len(a, (uint32_t)i);
+        a.srcSegs[2 * i] = i * a.frameSize; a.srcSegs[2 * i + 1] = len;
+        a.slotSegs[2 * i] = i * stride; a.slotSegs[2 * i + 1] = zsk_compress_bound(len);
+    }
+}
+// one wave: the stream's status -- the lowest failing frame, else whether frames + table fit the capacity -- and its size
+ZH_DEV void zsk_verdict_body(const ZskCompressArgs& a)
+{
+    uint64_t bad = ZSK_NONE;
+    for (uint32_t j = zh_lane(); j < a.nPart; j += 64) { const uint64_t v = a.partBad[j]; bad = v < bad ? v : bad; }
+    bad = zsk_wave_min64(bad);
+    if (zh_lane() != 0) return;
+    const uint64_t frames = a.offs[a.n], need = frames + zsk_table_size(a.n, (int)a.checksum);
+    int32_t code = 0; uint32_t index = 0;
+    if (bad != ZSK_NONE) { code = a.status[bad]; index = (uint32_t)bad; }
+    else if (need > a.dstCapacity) {
+        // the first frame that ends beyond the capacity; the last frame where only the table does not fit (offs is non-decreasing: bisect)
+        uint32_t lo = 0, hi = a.n;
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (a.offs[mid + 1] > a.dstCapacity) hi = mid; else lo = mid + 1; }
+        code = ZSK_ERR_DSTSIZE; index = lo < a.n ? lo : a.n ? a.n - 1 : 0;
+    }
+    a.outStatus[0] = code; a.outStatus[1] = (int32_t)index;
+    *a.streamSize = code ? 0 : need;
+    *a.go = code ? 0u : 1u;
+}
+// a lane per frame: its entry (with the checksum of the SOURCE chunk where asked for); lane 0 of the grid: the table frame's header and footer.
+// A failed stream writes nothing: every frame's status is made non-zero instead, which is what keeps the compaction behind this kernel from copying.
+ZH_DEV void zsk_table_body(const ZskCompressArgs& a)
+{
+    const bool go = *a.go != 0;
+    const uint32_t entry = zsk_entry_size((int)a.checksum);
+    uint8_t* const table = a.dst + a.offs[a.n];
+    for (uint64_t i = (uint64_t)zh_block() * 64 + zh_lane(); i < a.n; i += (uint64_t)zh_nblocks() * 64) {
+        if (!go) { if (!a.status[i]) a.status[i] = ZSK_ERR_DSTSIZE; continue; }
+        const uint32_t len = zsk_chunk_len(a, (uint32_t)i);
+        uint8_t* const e = table + ZSK_HEADER + i * entry;
+        zh_st32(e, (uint32_t)a.outSizes[i]); zh_st32(e + 4, len);
+        if (a.checksum) zh_st32(e + 8, (uint32_t)ze_xxh64(a.src + i * a.frameSize, len));
+    }
+    if (go && zh_block() == 0 && zh_lane() == 0) {
+        uint8_t* const f = table + ZSK_HEADER + (uint64_t)a.n * entry;
+        zh_st32(table, ZSK_SKIP_MAGIC); zh_st32(table + 4, a.n * entry + ZSK_FOOTER);
+        zh_st32(f, a.n); f[4] = a.checksum ? 0x80 : 0; zh_st32(f + 5, ZSK_SEEK_MAGIC);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ ranges
+// The frames f0 .. f1 that cover a range are ONE decode batch of the `count` of them that hold content. A frame wholly inside the range decodes into its place
+// in the caller's buffer; f0 and f1 where the range cuts them decode into `edge` and the covered part is copied. The batch call takes one base address and
+// offsets from it: the base is the lower of the two buffers' addresses (dstBase), so every offset is a plain distance.
+struct ZskRangeArgs {
+    const uint64_t* cOff; const uint64_t* dOff; const uint64_t* place;     // [n + 1] each: the open call's scans (compressed / decompressed offsets, place among the frames with content)
+    const uint8_t* table; uint32_t entry, checksum;                        // the entries in the stream
+    uint32_t f0, f1, count;
+    uint64_t offset, length;                                               // the range, in content bytes
+    uint8_t* dst; uint8_t* edge; uint8_t* dstBase;
+    uint64_t* srcSegs; uint64_t* dstSegs; uint32_t* frameOf;               // [count]
+    const uint64_t* outSizes; int32_t* status;                             // [count]: what zhip_decompress_batch_device wrote
+    uint32_t* worst;                                                       // ~(lowest failing batch item), 0 = none (zeroed before the verifier)
+    int32_t* outStatus;
+};
+// where frame f's content is decoded to, and whether that is the edge buffer (f0's part first, f1's behind it)
+ZH_DEV uint8_t* zsk_frame_home(const ZskRangeArgs& a, uint32_t f, bool* partial)
+{
+    const uint64_t at = a.dOff[f], end = a.dOff[f + 1];
+    *partial = at < a.offset || end > a.offset + a.length;
+    if (!*partial) return a.dst + (at - a.offset);
+    if (f == a.f0) return a.edge;
+    const uint64_t d0 = a.dOff[a.f0], e0 = a.dOff[a.f0 + 1];
+    return a.edge + (d0 < a.offset || e0 > a.offset + a.length ? e0 - d0 : 0);
+}
+ZH_DEV void zsk_range_segs_body(const ZskRangeArgs& a)
+{
+    const uint64_t nf = (uint64_t)a.f1 - a.f0 + 1;
+    for (uint64_t j = (uint64_t)zh_block() * 64 + zh_lane(); j < nf; j += (uint64_t)zh_nblocks() * 64) {
+        const uint32_t f = a.f0 + (uint32_t)j;
+        const uint64_t size = a.dOff[f + 1] - a.dOff[f];
+        if (!size) continue;                                                // a skippable or an empty frame: never the decoder's
+        const uint64_t k = a.place[f] - a.place[a.f0];
+        bool partial; uint8_t* const home = zsk_frame_home(a, f, &partial);
+        a.srcSegs[2 * k] = a.cOff[f]; a.srcSegs[2 * k + 1] = a.cOff[f + 1] - a.cOff[f];
+        a.dstSegs[2 * k] = (uint64_t)(home - a.dstBase); a.dstSegs[2 * k + 1] = size;
+        a.frameOf[k] = f;
+    }
+}
+// a lane per decoded frame: the size it came out at against its entry's (20), its content's XXH64 against its entry's (22)
+ZH_DEV void zsk_range_verify_body(const ZskRangeArgs& a)
+{
+    for (uint64_t k = (uint64_t)zh_block() * 64 + zh_lane(); k < a.count; k += (uint64_t)zh_nblocks() * 64) {
+        int32_t code = a.status[k];
+        if (!code) {
+            const uint32_t f = a.frameOf[k];
+            const uint64_t size = a.dOff[f + 1] - a.dOff[f];
+            if (a.outSizes[k] != size) code = ZSK_ERR_CORRUPT;
+            else if (a.checksum) {
+                const uint32_t want = zh_ld32(a.table + (uint64_t)f * a.entry + 8);
+                if ((uint32_t)ze_xxh64(a.dstBase + a.dstSegs[2 * k], (uint32_t)size) != want) code = ZSK_ERR_CHECKSUM;
+            }
+            if (code) a.status[k] = code;
+        }
+        if (code) zh_atomic_max(a.worst, ~(uint32_t)k);
+    }
+}
+// the covered parts of the edge frames into the caller's buffer, 16 bytes per lane; lane 0 of the grid also writes the range's status
+ZH_DEV void zsk_range_finish_body(const ZskRangeArgs& a)
+{
+    if (zh_block() == 0 && zh_lane() == 0) {
+        const uint32_t w = *a.worst;
+        a.outStatus[0] = w ? a.status[~w] : 0; a.outStatus[1] = w ? (int32_t)a.frameOf[~w] : 0;
+    }
+    const uint64_t rangeEnd = a.offset + a.length;
+    for (int side = 0; side < 2; side++) {
+        const uint32_t f = side ? a.f1 : a.f0;
+        if (side && a.f1 == a.f0) break;
+        const uint64_t at = a.dOff[f], end = a.dOff[f + 1];
+        if (at == end) continue;
+        bool partial; const uint8_t* const home = zsk_frame_home(a, f, &partial);
+        if (!partial) continue;
+        const uint64_t from = at > a.offset ? at : a.offset, to = end < rangeEnd ? end : rangeEnd;       // the covered part, in content bytes
+        if (from >= to) continue;
+        const uint8_t* const s = home + (from - at); uint8_t* const d = a.dst + (from - a.offset);
+        const uint64_t len = to - from, whole = len & ~(uint64_t)15;
+        const uint64_t lane = (uint64_t)zh_block() * 64 + zh_lane(), lanes = (uint64_t)zh_nblocks() * 64;
+        for (uint64_t j = lane * 16; j < whole; j += lanes * 16) { const zh_v16 v = zh_ld128(s + j); zh_st64(d + j, v.lo); zh_st64(d + j + 8, v.hi); }
+        if (lane < len - whole) d[whole + lane] = s[whole + lane];
+    }
+}
+
+#ifndef ZHIP_EMU
+__global__ __launch_bounds__(64) void zhip_seekable_scan_reduce_kernel(ZskScanArgs a) { zsk_scan_reduce_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_scan_write_kernel(ZskScanArgs a) { zsk_scan_write_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_chunk_segs_kernel(ZskCompressArgs a) { zsk_chunk_segs_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_verdict_kernel(ZskCompressArgs a) { zsk_verdict_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_table_kernel(ZskCompressArgs a) { zsk_table_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_range_segs_kernel(ZskRangeArgs a) { zsk_range_segs_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_range_verify_kernel(ZskRangeArgs a) { zsk_range_verify_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_range_finish_kernel(ZskRangeArgs a) { zsk_range_finish_body(a); }
+#endif

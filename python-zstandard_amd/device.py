@@ -97,6 +97,34 @@ class DeviceBatchContext:
         if rc:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
 
+    def seekable_compress(self, src, frame_size=131072, checksum=False, stream=None):
+        """src (a uint8 CUDA tensor) as ONE zstd seekable stream: frames of frame_size bytes of it, compressed as a batch with this context's
+        parameters, back to back, then the seek table (checksum: with the low 32 bits of XXH64 of every frame's content). Returns a uint8 CUDA
+        tensor of exactly the stream's size -- a view of a zhip_seekable_bound-sized allocation. Waits for the size. Any zstd decoder decompresses
+        the stream whole; SeekableStream reads ranges of it."""
+        self._ensure_cparams()
+        self._check(src, torch.uint8)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        flags = _lib.SEEKABLE_CHECKSUM if checksum else 0
+        bound = self.L.zhip_seekable_bound(src.numel(), frame_size, flags)
+        if not bound:
+            raise ZstdError("seekable compress: frame_size must be 1 ... 2^30 and give at most 2^27 frames")
+        with torch.cuda.stream(s):
+            dst = torch.empty(bound, dtype=torch.uint8, device=src.device)
+            size = torch.zeros(1, dtype=torch.int64, device=src.device)
+            status = torch.zeros(2, dtype=torch.int32, device=src.device)
+        rc = self.L.zhip_seekable_compress_device(self.ctx, src.data_ptr(), src.numel(), frame_size, flags, dst.data_ptr(), bound, size.data_ptr(),
+                                                  status.data_ptr(), s.cuda_stream)
+        if rc:
+            raise ZstdError("seekable compress failed: %s" % _lib.last_error())
+        err = _lib.Error()
+        rc = self.L.zhip_ctx_sync(self.ctx, s.cuda_stream, status.data_ptr(), 1, C.byref(err))
+        if rc == _lib.ERR_ZSTD:
+            raise ZstdError("seekable compress: frame %d: %s" % (int(status[1]), _lib.error_name(err.zstdErr)))
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return dst[:int(size[0])]
+
     def kernel_time(self, direction):
         """(average ms per launch, launches) of the dominant kernel since the last call, from HIP events on the launch stream."""
         ms, n = C.c_double(0), C.c_uint64(0)
@@ -118,3 +146,69 @@ class DeviceBatchContext:
 
     def kernel_name(self, direction):
         return self.L.zhip_kernel_name(direction).decode()
+
+
+class SeekableStream:
+    """Range reads of a zstd seekable stream resident in HBM (any writer's): ``read(offset, length)`` decodes only the frames that cover the range.
+
+    ctx: the DeviceBatchContext that decodes (its dictionary, format and window limit apply); stream_tensor: the whole stream, a uint8 CUDA tensor,
+    kept alive and unchanged while this object is open. Opening reads and checks the seek table (it waits); a damaged table raises ZstdError."""
+
+    def __init__(self, ctx, stream_tensor, stream=None):
+        DeviceBatchContext._check(stream_tensor, torch.uint8)
+        self.ctx, self.tensor, self.handle = ctx, stream_tensor, None
+        s = stream if stream is not None else torch.cuda.current_stream()
+        h, info, err = C.c_void_p(), _lib.SeekableInfo(), _lib.Error()
+        rc = ctx.L.zhip_seekable_open_device(ctx.ctx, stream_tensor.data_ptr(), stream_tensor.numel(), s.cuda_stream, C.byref(h), C.byref(info), C.byref(err))
+        if rc == _lib.ERR_ZSTD:
+            raise ZstdError("not a seekable stream: %s" % _lib.error_name(err.zstdErr))
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        self.handle = h
+        self.content_size, self.n_frames, self.has_checksums = int(info.contentSize), int(info.nFrames), bool(info.checksumFlag)
+        self.max_frame_content = int(info.maxFrameContent)
+
+    def read(self, offset=0, length=None, out=None, stream=None):
+        """content bytes [offset, offset + length) (length None: to the end) as a uint8 CUDA tensor -- `out`, where given, else a new one. Waits for the
+        result's status; a frame that fails (corrupt, wrong size, wrong checksum) raises ZstdError with its index in the table."""
+        if self.handle is None:
+            raise ZstdError("the seekable stream is closed")
+        if length is None:
+            length = self.content_size - offset
+        if offset < 0 or length < 0 or offset + length > self.content_size:
+            raise ZstdError("range %d + %d is outside the content (%d bytes)" % (offset, length, self.content_size))
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            if out is None:
+                out = torch.empty(length, dtype=torch.uint8, device=self.tensor.device)
+            status = torch.zeros(2, dtype=torch.int32, device=self.tensor.device)
+        DeviceBatchContext._check(out, torch.uint8)
+        assert out.numel() >= length, "out is shorter than the range"
+        L = self.ctx.L
+        rc = L.zhip_seekable_decompress_device(self.ctx.ctx, self.handle, offset, length, out.data_ptr(), status.data_ptr(), s.cuda_stream)
+        if rc:
+            raise ZstdError("seekable read failed: %s" % _lib.last_error())
+        err = _lib.Error()
+        rc = L.zhip_ctx_sync(self.ctx.ctx, s.cuda_stream, status.data_ptr(), 1, C.byref(err))
+        if rc == _lib.ERR_ZSTD:
+            raise ZstdError("seekable read: frame %d: %s" % (int(status[1]), _lib.error_name(err.zstdErr)))
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return out[:length]
+
+    def close(self):
+        if self.handle is not None:
+            self.ctx.L.zhip_seekable_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

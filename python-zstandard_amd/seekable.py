@@ -1,0 +1,40 @@
+"""The zstd seekable format for host bytes: ``compress`` cuts the data into frames of ``frame_size`` bytes, compresses them as ONE batch on the GPU and
+appends the seek table; ``decompress`` reads any byte range of such a stream by decoding only the frames that cover it. The streams are ordinary zstd:
+``zstd -d`` and ``ZstdDecompressor`` decompress them whole (the table is a skippable frame). Built on ``device.DeviceBatchContext.seekable_compress`` and
+``device.SeekableStream``; the data crosses the link once each way."""
+import torch
+
+from .backend_hip import ZstdError
+from .device import DeviceBatchContext, SeekableStream
+
+
+def _to_device(data):
+    raw = bytes(data)
+    if not raw:
+        return torch.empty(0, dtype=torch.uint8, device="cuda")
+    return torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()
+
+
+def compress(data, level=3, frame_size=131072, checksum=False, **ctx_kw):
+    """data -> a seekable stream (bytes). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
+    ctx = DeviceBatchContext(level=level, **ctx_kw)
+    try:
+        return ctx.seekable_compress(_to_device(data), frame_size=frame_size, checksum=checksum).cpu().numpy().tobytes()
+    finally:
+        ctx.close()
+
+
+def decompress(data, offset=0, length=None, **ctx_kw):
+    """content bytes [offset, offset + length) of a seekable stream (length None: to the end). Raises ZstdError for a stream without a valid seek table,
+    a range outside the content, or a frame that fails."""
+    if len(data) == 0:
+        raise ZstdError("not a seekable stream: empty input")
+    ctx = DeviceBatchContext(**ctx_kw)
+    try:
+        st = SeekableStream(ctx, _to_device(data))
+        try:
+            return st.read(offset, length).cpu().numpy().tobytes()
+        finally:
+            st.close()
+    finally:
+        ctx.close()
