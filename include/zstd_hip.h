@@ -251,6 +251,29 @@ void zhip_seekable_close(zhip_seekable*);      /* waits for the device (it frees
 int  zhip_seekable_decompress_device(zhip_ctx*, zhip_seekable*, uint64_t offset, uint64_t length,
                                      void* d_dst /* length bytes */, int32_t* d_status /* [2] */, void* stream);
 
+/* Many ranges in ONE decode batch. ranges is a HOST array, read before the call returns: content bytes [offset, offset + length) go to d_dst + dstOffset.
+ * Asynchronous and stream-ordered under the rules of zhip_seekable_decompress_device: one host thread and one stream at a time per handle, no host wait (but
+ * where the handle's scratch grows). Checked on the host before anything is queued, and nothing -- d_status included -- is written where a check fails: a range
+ * that ends beyond contentSize or wraps, and a dstOffset + length beyond dstCapacity (ZHIP_ERR_SIZE_MISMATCH; zhip_last_error() holds the range's index and both
+ * numbers); two ranges of non-zero length whose destinations overlap, NULL arguments and nRanges > 2^27 (ZHIP_ERR_UNSUPPORTED). The overlap check sorts the
+ * ranges by dstOffset. Content ranges may overlap, repeat, share frames, come in any order and have length 0 (status {0, 0}, nothing written).
+ * Every frame with content that at least one range touches is handed to zhip_decompress_batch_device exactly ONCE per call (stats->items); entries of
+ * Decompressed_Size 0 never are. A frame wholly inside exactly one range and touched by no other decodes straight into its place (inPlace); every other frame
+ * decodes into the handle's scratch, slots in ascending frame order (scratchBytes: their sizes' sum), and device copies of contiguous spans (copyJobs) move
+ * the covered parts to every range that needs them. Where scratchBytes exceeds the handle's scratch limit the item list is cut at frame boundaries into
+ * `passes`, each a decode batch of its own queued back to back with no host wait; the scratch never grows beyond max(limit, largest scratch frame).
+ * d_status[0 .. 1] = {code, range index} of the lowest-index range that failed ({0, 0}: none; zhip_ctx_sync(ctx, stream, d_status, 1, &err) works on it);
+ * d_status[2 + 2r .. 3 + 2r] = {code, frame index} of the lowest failing frame among those range r needs -- what the single-range call reports for it. A failing
+ * frame fails only the ranges that need it. No byte of d_dst outside the union of the ranges' destinations is ever written. nRanges 0 sets d_status[0 .. 1]
+ * and launches nothing else. The plan's tables travel through pinned memory the handle owns, so the caller's array is free when the call returns. A
+ * device-resident range array is not offered: the host must know the batch's item count without a wait. */
+typedef struct { uint64_t offset, length, dstOffset; } zhip_seekable_range;
+typedef struct { uint64_t items, inPlace, scratchBytes, copyJobs, passes; } zhip_seekable_gather_stats;
+int  zhip_seekable_decompress_ranges_device(zhip_ctx*, zhip_seekable*, const zhip_seekable_range* ranges, size_t nRanges,
+                                            void* d_dst, uint64_t dstCapacity, int32_t* d_status /* [2 + 2 * nRanges] */,
+                                            zhip_seekable_gather_stats* stats /* host, may be NULL; filled before the call returns */, void* stream);
+void zhip_seekable_set_scratch_limit(zhip_seekable*, uint64_t bytes);      /* of the many-ranges call; 0 = the default, 1 GiB */
+
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,
  * 4 K3, 5 / 6 the lane-serial match kernel (the greedy strategy's zhip_encode_match_greedy_kernel where that runs in its place) and the entropy kernel, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,

@@ -46,6 +46,14 @@ class SeekableInfo(C.Structure):
                 ("checksumFlag", C.c_int)]
 
 
+class SeekableRange(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint64), ("dstOffset", C.c_uint64)]
+
+
+class SeekableGatherStats(C.Structure):
+    _fields_ = [("items", C.c_uint64), ("inPlace", C.c_uint64), ("scratchBytes", C.c_uint64), ("copyJobs", C.c_uint64), ("passes", C.c_uint64)]
+
+
 class DParams(C.Structure):
     _fields_ = [("dict", C.c_void_p), ("dictSize", C.c_size_t), ("maxWindowSize", C.c_uint64), ("dictType", C.c_int),
                 ("format", C.c_int)]
@@ -116,6 +124,8 @@ def lib():
         "zhip_seekable_open_device": (C.c_int, [vp, vp, u64, vp, C.POINTER(vp), C.POINTER(SeekableInfo), C.POINTER(Error)]),
         "zhip_seekable_close": (None, [vp]),
         "zhip_seekable_decompress_device": (C.c_int, [vp, vp, u64, u64, vp, vp, vp]),
+        "zhip_seekable_decompress_ranges_device": (C.c_int, [vp, vp, vp, sz, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
+        "zhip_seekable_set_scratch_limit": (None, [vp, u64]),
     }
     for name, (res, args) in protos.items():
         f = getattr(L, name)
@@ -135,7 +145,7 @@ EXPORTED_SYMBOLS = [
     "zhip_kernel_name", "zhip_ctx_kernel_time", "zhip_thread_memory_size", "zhip_compact_device", "zhip_ctx_set_size_hint",
     "zhip_ctx_table_pick", "zhip_ctx_decode_fallbacks", "zhip_partition_by_bytes", "zhip_batch_devices",
     "zhip_seekable_frame_count", "zhip_seekable_bound", "zhip_seekable_compress_device", "zhip_seekable_open_device", "zhip_seekable_close",
-    "zhip_seekable_decompress_device",
+    "zhip_seekable_decompress_device", "zhip_seekable_decompress_ranges_device", "zhip_seekable_set_scratch_limit",
 ]
 
 

@@ -2169,12 +2169,20 @@ struct zhip_seekable {
     DevBuf prefix;                       // the table's scans: compressed offsets, decompressed offsets, place among the frames with content -- [n + 1] each
     DevBuf meta, edge;                   // a range call's segments / sizes / statuses, and where its partly covered frames are decoded
     std::vector<uint64_t> dOff, place;   // the host's copies: which frames cover a range, and how many of them go to the decoder
+    // the many-ranges call: its plan's tables on the device, its item arrays and per-range words, its scratch frames; the pinned slots the tables are
+    // uploaded from (a slot is written again only after the event behind its upload has completed)
+    DevBuf gTables, gMeta, gScratch;
+    uint64_t scratchLimit = 0;           // 0 = ZSK_SCRATCH_DEFAULT
+    struct Slot { void* p; size_t cap; hipEvent_t done; };
+    std::vector<Slot> slots;
 };
 
 extern "C" void zhip_seekable_close(zhip_seekable* h)
 {
     if (!h) return;
     h->prefix.release(); h->meta.release(); h->edge.release();
+    h->gTables.release(); h->gMeta.release(); h->gScratch.release();      // (hipFree waits for the device: no upload from a slot is in flight behind it)
+    for (zhip_seekable::Slot& s : h->slots) { if (s.p) (void)hipHostFree(s.p); (void)hipEventDestroy(s.done); }
     delete h;
 }
 
@@ -2267,4 +2275,112 @@ extern "C" int zhip_seekable_decompress_device(zhip_ctx* c, zhip_seekable* h, ui
     hipLaunchKernelGGL(zhip_seekable_range_finish_kernel, dim3(zsk_lane_grid(c, (uint64_t)edgeBytes / 16 + 1)), dim3(64), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
+}
+
+extern "C" void zhip_seekable_set_scratch_limit(zhip_seekable* h, uint64_t bytes) { if (h) h->scratchLimit = bytes; }
+
+// a pinned slot of at least `bytes` that no upload still reads: one whose event has completed (grown where too small), else a new one
+static int zsk_take_slot(zhip_seekable* h, size_t bytes, zhip_seekable::Slot** out)
+{
+    zhip_seekable::Slot* s = nullptr;
+    for (zhip_seekable::Slot& x : h->slots) if (hipEventQuery(x.done) == hipSuccess) { s = &x; break; }
+    (void)hipGetLastError();                                               // (hipErrorNotReady of a slot still in flight is no failure)
+    if (!s) {
+        zhip_seekable::Slot x = {nullptr, 0, nullptr};
+        HIP_TRY(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
+        h->slots.push_back(x); s = &h->slots.back();
+    }
+    if (s->cap < bytes) {
+        if (s->p) { (void)hipHostFree(s->p); s->p = nullptr; s->cap = 0; }
+        const size_t want = bytes + (bytes >> 2) + 4096;
+        const hipError_t e = hipHostMalloc(&s->p, want, hipHostMallocDefault);
+        if (e != hipSuccess) { s->p = nullptr; (void)hipGetLastError(); g_lastError = "seekable ranges: no pinned memory for the plan's tables"; return ZHIP_ERR_NO_MEMORY; }
+        s->cap = want;
+    }
+    *out = s;
+    return 0;
+}
+
+extern "C" int zhip_seekable_decompress_ranges_device(zhip_ctx* c, zhip_seekable* h, const zhip_seekable_range* ranges, size_t nRanges, void* d_dst, uint64_t dstCapacity,
+                                                      int32_t* d_status, zhip_seekable_gather_stats* stats, void* streamv)
+{
+    static_assert(sizeof(zhip_seekable_range) == 24, "the plan reads the ranges as [R][3]");
+    if (!c || !h || !d_status || (nRanges && !ranges) || nRanges > ZSK_MAX_RANGES) { g_lastError = "seekable ranges: bad arguments (NULL, or more than 2^27 ranges)"; return ZHIP_ERR_UNSUPPORTED; }
+    hipStream_t stream = (hipStream_t)streamv;
+    const uint64_t* const rg = (const uint64_t*)ranges;
+    size_t bad = 0, other = 0;
+    if (const int why = zsk_gather_check(rg, nRanges, h->contentSize, dstCapacity, &bad, &other)) {
+        char buf[224];
+        if (why == 1) snprintf(buf, sizeof buf, "seekable ranges: range %zu ends at %llu + %llu, the content at %llu", bad, (unsigned long long)ranges[bad].offset, (unsigned long long)ranges[bad].length, (unsigned long long)h->contentSize);
+        else if (why == 2) snprintf(buf, sizeof buf, "seekable ranges: range %zu goes to %llu + %llu, the capacity is %llu", bad, (unsigned long long)ranges[bad].dstOffset, (unsigned long long)ranges[bad].length, (unsigned long long)dstCapacity);
+        else snprintf(buf, sizeof buf, "seekable ranges: the destinations of ranges %zu and %zu overlap", other, bad);
+        g_lastError = buf;
+        return why == 3 ? ZHIP_ERR_UNSUPPORTED : ZHIP_ERR_SIZE_MISMATCH;
+    }
+    bool any = false;
+    for (size_t r = 0; r < nRanges; r++) any = any || ranges[r].length;
+    if (any && !d_dst) { g_lastError = "seekable ranges: bad arguments (no destination)"; return ZHIP_ERR_UNSUPPORTED; }
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!any) { HIP_TRY(hipMemsetAsync(d_status, 0, (2 + 2 * nRanges) * sizeof(int32_t), stream)); return 0; }
+
+    ZskGatherPlan plan;
+    zsk_gather_plan(h->dOff.data(), h->place.data(), h->lay.n, rg, nRanges, h->scratchLimit, &plan);
+    if (stats) { stats->items = plan.items; stats->inPlace = plan.inPlace; stats->scratchBytes = plan.scratchBytes; stats->copyJobs = plan.jobs.size(); stats->passes = plan.passes.size(); }
+    const size_t R = nRanges, S = plan.segs.size(), J = plan.jobs.size(), count = (size_t)plan.items;
+    // the tables: ranges, segments, jobs (32 bytes an entry each)
+    const size_t oRanges = 0, oSegs = oRanges + R * sizeof(ZskGatherRange), oJobs = oSegs + S * sizeof(ZskGatherSeg), tableBytes = oJobs + J * sizeof(ZskGatherJob);
+    const size_t oSrcSegs = 0, oDstSegs = oSrcSegs + zsk_up16(count * 16), oSizes = oDstSegs + zsk_up16(count * 16), oFrameOf = oSizes + zsk_up16(count * 8), oStatus = oFrameOf + zsk_up16(count * 4),
+                 oWorst = oStatus + zsk_up16(count * 4), metaBytes = oWorst + zsk_up16(R * 4);
+    // (growing an area frees the old one, which waits for the device: the wait the stream-order rules allow. The scratch is allocated at exactly what the
+    // largest pass needs: it never exceeds max(limit, largest scratch frame))
+    if (h->gTables.reserve(tableBytes) || h->gMeta.reserve(metaBytes)) return g_reserveRc;
+    if (plan.scratchMax > h->gScratch.cap) {
+        h->gScratch.release();
+        const hipError_t e = hipMalloc(&h->gScratch.p, (size_t)plan.scratchMax);
+        if (e != hipSuccess) { h->gScratch.p = nullptr; (void)hipGetLastError(); g_lastError = "out of device memory"; return ZHIP_ERR_NO_MEMORY; }
+        h->gScratch.cap = (size_t)plan.scratchMax;
+    }
+    zhip_seekable::Slot* slot = nullptr;
+    if (int rc = zsk_take_slot(h, tableBytes, &slot)) return rc;
+    uint8_t* const pin = (uint8_t*)slot->p;
+    memcpy(pin + oRanges, plan.ranges.data(), R * sizeof(ZskGatherRange));
+    if (S) memcpy(pin + oSegs, plan.segs.data(), S * sizeof(ZskGatherSeg));
+    if (J) memcpy(pin + oJobs, plan.jobs.data(), J * sizeof(ZskGatherJob));
+    uint8_t* const t = (uint8_t*)h->gTables.p; uint8_t* const m = (uint8_t*)h->gMeta.p; uint8_t* const pre = (uint8_t*)h->prefix.p;
+    HIP_TRY(hipMemcpyAsync(t, pin, tableBytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(slot->done, stream));
+    HIP_TRY(hipMemsetAsync(m + oWorst, 0, R * 4, stream));
+
+    const size_t col = zsk_up16(((size_t)h->lay.n + 1) * 8);
+    ZskGatherArgs a; memset(&a, 0, sizeof a);
+    a.cOff = (const uint64_t*)pre; a.dOff = (const uint64_t*)(pre + col); a.place = (const uint64_t*)(pre + 2 * col);
+    a.table = h->stream + h->lay.tableOffset + ZSK_HEADER; a.entry = h->lay.entry; a.checksum = (uint32_t)h->lay.checksum;
+    a.ranges = (const ZskGatherRange*)(t + oRanges); a.nRanges = (uint32_t)R;
+    a.dst = (uint8_t*)d_dst; a.scratch = plan.scratchMax ? (uint8_t*)h->gScratch.p : a.dst; a.dstBase = a.scratch < a.dst ? a.scratch : a.dst;
+    a.srcSegs = (uint64_t*)(m + oSrcSegs); a.dstSegs = (uint64_t*)(m + oDstSegs); a.frameOf = (uint32_t*)(m + oFrameOf);
+    a.outSizes = (const uint64_t*)(m + oSizes); a.status = (int32_t*)(m + oStatus); a.worst = (uint32_t*)(m + oWorst); a.outStatus = d_status;
+    // frames above one block: the several-block mode, for these launches only
+    const size_t hintWas = c->dstMaxHint;
+    if (h->maxFrameContent > ZF_BLOCK_MAX) c->dstMaxHint = h->maxFrameContent;
+    int rc = 0;
+    for (size_t p = 0; p < plan.passes.size() && !rc; p++) {
+        const ZskGatherPass& ps = plan.passes[p];
+        a.segs = (const ZskGatherSeg*)(t + oSegs) + ps.seg0; a.nSegs = ps.seg1 - ps.seg0; a.frames = ps.frames;
+        a.jobs = (const ZskGatherJob*)(t + oJobs) + ps.job0; a.nJobs = ps.job1 - ps.job0; a.tiles = ps.tiles;
+        a.item0 = ps.item0; a.count = ps.item1 - ps.item0; a.last = p + 1 == plan.passes.size() ? 1u : 0u;
+        hipLaunchKernelGGL(zhip_seekable_gather_segs_kernel, dim3(zsk_lane_grid(c, ps.frames)), dim3(64), 0, stream, a);
+        if (a.count) {
+            rc = zhip_decompress_batch_device(c, h->stream, (const zhip_segment*)a.srcSegs + a.item0, a.count, a.dstBase, (const zhip_segment*)a.dstSegs + a.item0,
+                                              (uint64_t*)(m + oSizes) + a.item0, a.status + a.item0, stream);
+            if (rc) break;
+            hipLaunchKernelGGL(zhip_seekable_gather_verify_kernel, dim3(zsk_lane_grid(c, a.count)), dim3(64), 0, stream, a);
+        }
+        if (a.tiles || a.last) {
+            const uint64_t lanes = a.tiles * 64 > (a.last ? R : 0) ? a.tiles * 64 : R;
+            hipLaunchKernelGGL(zhip_seekable_gather_finish_kernel, dim3(zsk_lane_grid(c, lanes)), dim3(64), 0, stream, a);
+        }
+        if (hipGetLastError() != hipSuccess) { g_lastError = "seekable ranges: a launch failed"; rc = ZHIP_ERR_HIP; }
+    }
+    c->dstMaxHint = hintWas;
+    return rc;
 }

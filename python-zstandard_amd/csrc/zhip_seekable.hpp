@@ -9,6 +9,9 @@
 #pragma once
 #include "zhip_device.hpp"
 #include "zhip_xxh64.hpp"
+#include <string.h>
+#include <algorithm>
+#include <vector>
 
 #ifndef ZHIP_EMU
 #define ZSK_HD __host__ __device__ static inline
@@ -293,6 +296,218 @@ ZH_DEV void zsk_range_finish_body(const ZskRangeArgs& a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ many ranges in one decode batch
+// R ranges -> every frame with content that at least one of them touches is ONE item of the decode batch. A frame that lies wholly inside exactly one range
+// and is touched by no other decodes into its place in the caller's buffer; every other frame (cut by a range's edge, or needed by two or more ranges) decodes
+// into the handle's scratch, slots in ascending frame order, and contiguous copies ("jobs") move the covered parts to the ranges that need them. Where the
+// scratch frames exceed the handle's limit the item list is cut at frame boundaries into passes -- each a batch of its own that reuses the scratch from 0.
+// The plan is a host function over the open call's dOff / place columns: O(R log R) + segments + jobs, never O(frames of the stream).
+#define ZSK_MAX_RANGES 0x8000000u            // 2^27
+#define ZSK_SCRATCH_DEFAULT 0x40000000ull    // 1 GiB: holds the largest frame the format allows
+#define ZSK_COPY_TILE 4096u                  // bytes one workgroup copies per step: 4 x 16 bytes per lane
+struct ZskGatherRange { uint64_t offset, length, dstOffset; uint32_t f0, f1; };      // f0 .. f1: the frames of the first and last byte (length 0: f0 = 1, f1 = 0)
+// frames first .. first + frames - 1 share a home: content byte dOff[first] lies at `home` from d_dst (inPlace) or from the scratch; framePrefix counts the
+// pass's frames in front (a lane of the segment builder bisects it), item is the batch item of the segment's first frame with content, counted over the call
+struct ZskGatherSeg { uint32_t first, frames, framePrefix, item; uint64_t home; uint32_t inPlace, pass; };
+struct ZskGatherJob { uint64_t src, dst, bytes, tilePrefix; };                       // scratch + src -> d_dst + dst; tilePrefix: the pass's copy tiles in front
+struct ZskGatherPass { uint32_t seg0, seg1, item0, item1, job0, job1, frames; uint64_t scratch, tiles; };
+
+struct ZskGatherPlan {
+    std::vector<ZskGatherRange> ranges; std::vector<ZskGatherSeg> segs; std::vector<ZskGatherJob> jobs; std::vector<ZskGatherPass> passes;
+    uint64_t items = 0, inPlace = 0, scratchBytes = 0, scratchMax = 0;               // scratchMax: the largest pass's scratch == what the handle must hold
+};
+// the checks in front of the plan; rg = [R][3] (offset, length, dstOffset). 0, or 1: range *bad ends beyond the content (or wraps), 2: its destination ends
+// beyond the capacity (or wraps), 3: its destination overlaps that of range *other. The overlap check is a sort by dstOffset.
+static inline int zsk_gather_check(const uint64_t* rg, size_t R, uint64_t contentSize, uint64_t dstCapacity, size_t* bad, size_t* other)
+{
+    for (size_t r = 0; r < R; r++) {
+        const uint64_t off = rg[3 * r], len = rg[3 * r + 1], at = rg[3 * r + 2];
+        *bad = r; *other = r;
+        if (off + len < off || off + len > contentSize) return 1;
+        if (at + len < at || at + len > dstCapacity) return 2;
+    }
+    std::vector<size_t> order;
+    for (size_t r = 0; r < R; r++) if (rg[3 * r + 1]) order.push_back(r);
+    std::sort(order.begin(), order.end(), [&](size_t x, size_t y) { return rg[3 * x + 2] != rg[3 * y + 2] ? rg[3 * x + 2] < rg[3 * y + 2] : x < y; });
+    for (size_t i = 1; i < order.size(); i++) {
+        const size_t p = order[i - 1], q = order[i];
+        if (rg[3 * p + 2] + rg[3 * p + 1] > rg[3 * q + 2]) { *bad = p < q ? q : p; *other = p < q ? p : q; return 3; }
+    }
+    return 0;
+}
+// D = dOff, P = place: [n + 1] each. The ranges have passed zsk_gather_check. limit 0 = ZSK_SCRATCH_DEFAULT.
+static inline void zsk_gather_plan(const uint64_t* D, const uint64_t* P, uint32_t n, const uint64_t* rg, size_t R, uint64_t limit, ZskGatherPlan* out)
+{
+    if (!limit) limit = ZSK_SCRATCH_DEFAULT;
+    *out = ZskGatherPlan();
+    out->ranges.resize(R);
+    // 1. every range's first and last frame (both hold content: upper_bound steps over frames of none), and its intervals: the frames it covers whole,
+    //    and each frame it cuts as an interval of its own
+    struct Ev { uint32_t pos; int32_t d, partial; uint64_t r; };
+    std::vector<Ev> ev;
+    for (size_t r = 0; r < R; r++) {
+        ZskGatherRange& g = out->ranges[r];
+        g.offset = rg[3 * r]; g.length = rg[3 * r + 1]; g.dstOffset = rg[3 * r + 2]; g.f0 = 1; g.f1 = 0;
+        if (!g.length) continue;
+        const uint64_t end = g.offset + g.length;
+        g.f0 = (uint32_t)(std::upper_bound(D, D + n + 1, g.offset) - D - 1); g.f1 = (uint32_t)(std::upper_bound(D, D + n + 1, end - 1) - D - 1);
+        const uint32_t cut0 = D[g.f0] < g.offset || D[g.f0 + 1] > end ? 1u : 0u, cut1 = g.f1 != g.f0 && D[g.f1 + 1] > end ? 1u : 0u;
+        if (cut0) { ev.push_back({g.f0, 1, 1, r}); ev.push_back({g.f0 + 1, -1, 1, r}); }
+        if (cut1) { ev.push_back({g.f1, 1, 1, r}); ev.push_back({g.f1 + 1, -1, 1, r}); }
+        if (g.f0 + cut0 < g.f1 + 1 - cut1) { ev.push_back({g.f0 + cut0, 1, 0, r}); ev.push_back({g.f1 + 1 - cut1, -1, 0, r}); }
+    }
+    std::sort(ev.begin(), ev.end(), [](const Ev& x, const Ev& y) { return x.pos < y.pos; });
+    // 2. the sweep: runs of frames under one state -- in place (one interval over them, and that one whole: `sum` is then its range) or scratch. Neighbouring
+    //    runs of the same state are one run (scratch slots ascend with frames, so neighbouring scratch runs are contiguous there too)
+    struct Run { uint32_t a, b; uint32_t inPlace; uint64_t owner; };
+    std::vector<Run> runs;
+    {
+        int64_t cnt = 0, part = 0; uint64_t sum = 0; uint32_t prev = 0;
+        for (size_t i = 0; i < ev.size();) {
+            const uint32_t pos = ev[i].pos;
+            if (cnt > 0 && pos > prev) {
+                const uint32_t inPlace = cnt == 1 && part == 0 ? 1u : 0u;
+                if (!runs.empty() && runs.back().b == prev && runs.back().inPlace == inPlace && (!inPlace || runs.back().owner == sum)) runs.back().b = pos;
+                else runs.push_back({prev, pos, inPlace, sum});
+            }
+            for (; i < ev.size() && ev[i].pos == pos; i++) { cnt += ev[i].d; part += ev[i].d * ev[i].partial; sum += (uint64_t)(int64_t)ev[i].d * ev[i].r; }
+            prev = pos;
+        }
+    }
+    // 3. passes: the runs in frame order, a scratch run cut where the pass's scratch would exceed the limit (a frame above the limit alone in its pass's scratch)
+    ZskGatherPass cur; memset(&cur, 0, sizeof cur);
+    uint64_t used = 0; uint32_t items = 0;
+    auto closePass = [&]() {
+        cur.seg1 = (uint32_t)out->segs.size(); cur.item1 = items; cur.scratch = used;
+        if (cur.seg1 > cur.seg0) { out->passes.push_back(cur); if (used > out->scratchMax) out->scratchMax = used; }
+        memset(&cur, 0, sizeof cur); cur.seg0 = (uint32_t)out->segs.size(); cur.item0 = items; used = 0;
+    };
+    auto pushSeg = [&](uint32_t a, uint32_t b, uint64_t home, uint32_t inPlace) {
+        out->segs.push_back({a, b - a, cur.frames, items, home, inPlace, (uint32_t)out->passes.size()});
+        cur.frames += b - a; items += (uint32_t)(P[b] - P[a]);
+    };
+    for (const Run& run : runs) {
+        if (run.inPlace) {
+            const ZskGatherRange& g = out->ranges[run.owner];
+            pushSeg(run.a, run.b, g.dstOffset + (D[run.a] - g.offset), 1);
+            out->inPlace += P[run.b] - P[run.a];
+            continue;
+        }
+        for (uint32_t a = run.a; a < run.b;) {
+            const uint64_t room = used < limit ? limit - used : 0;
+            uint32_t e = (uint32_t)(std::upper_bound(D + a + 1, D + run.b + 1, D[a] + room) - D - 1);          // the last e in [a, b] with D[e] - D[a] <= room
+            if (e == a) { if (used) { closePass(); continue; } e = a + 1; }
+            pushSeg(a, e, used, 0);
+            used += D[e] - D[a]; out->scratchBytes += D[e] - D[a];
+            a = e;
+        }
+    }
+    closePass();
+    out->items = items;
+    // 4. copy jobs: per range and scratch segment it touches (a maximal run of consecutive scratch frames of one pass), clipped to the range
+    std::vector<ZskGatherJob> jobs; std::vector<uint32_t> passOf;
+    for (size_t r = 0; r < R; r++) {
+        const ZskGatherRange& g = out->ranges[r];
+        if (!g.length) continue;
+        const uint64_t end = g.offset + g.length;
+        size_t s = (size_t)(std::upper_bound(out->segs.begin(), out->segs.end(), g.f0, [](uint32_t f, const ZskGatherSeg& x) { return f < x.first; }) - out->segs.begin()) - 1;
+        for (; s < out->segs.size() && out->segs[s].first <= g.f1; s++) {
+            const ZskGatherSeg& x = out->segs[s];
+            if (x.inPlace) continue;
+            const uint64_t at = D[x.first], to0 = D[x.first + x.frames];
+            const uint64_t from = at > g.offset ? at : g.offset, to = to0 < end ? to0 : end;
+            if (from >= to) continue;
+            jobs.push_back({x.home + (from - at), g.dstOffset + (from - g.offset), to - from, 0}); passOf.push_back(x.pass);
+        }
+    }
+    std::vector<uint32_t> at(out->passes.size() + 1, 0);
+    for (uint32_t p : passOf) at[p + 1]++;
+    for (size_t p = 0; p < out->passes.size(); p++) { at[p + 1] += at[p]; out->passes[p].job0 = at[p]; out->passes[p].job1 = at[p + 1]; }
+    out->jobs.resize(jobs.size());
+    for (size_t j = 0; j < jobs.size(); j++) out->jobs[at[passOf[j]]++] = jobs[j];
+    for (ZskGatherPass& p : out->passes) {
+        uint64_t tiles = 0;
+        for (uint32_t j = p.job0; j < p.job1; j++) { out->jobs[j].tilePrefix = tiles; tiles += (out->jobs[j].bytes + ZSK_COPY_TILE - 1) / ZSK_COPY_TILE; }
+        p.tiles = tiles;
+    }
+}
+
+// one pass's launches read this; the item arrays and `worst` are the whole call's (items are counted over the call, so a range's lowest failing item is its
+// lowest failing frame whatever pass decoded it)
+struct ZskGatherArgs {
+    const uint64_t* cOff; const uint64_t* dOff; const uint64_t* place;
+    const uint8_t* table; uint32_t entry, checksum;
+    const ZskGatherRange* ranges; uint32_t nRanges;
+    const ZskGatherSeg* segs; uint32_t nSegs, frames;                      // the pass's
+    const ZskGatherJob* jobs; uint32_t nJobs; uint64_t tiles;              // the pass's
+    uint32_t item0, count;                                                 // the pass's items
+    uint8_t* dst; uint8_t* scratch; uint8_t* dstBase;
+    uint64_t* srcSegs; uint64_t* dstSegs; uint32_t* frameOf; const uint64_t* outSizes; int32_t* status;
+    uint32_t* worst;                                                       // [nRanges]: ~(lowest failing item among the frames the range needs), 0 = none
+    int32_t* outStatus; uint32_t last;                                     // last: this pass's finish also writes the status pairs
+};
+// a lane per frame of the pass's segments: its batch item
+ZH_DEV void zsk_gather_segs_body(const ZskGatherArgs& a)
+{
+    for (uint64_t j = (uint64_t)zh_block() * 64 + zh_lane(); j < a.frames; j += (uint64_t)zh_nblocks() * 64) {
+        uint32_t lo = 0, hi = a.nSegs;                                      // the last segment whose framePrefix <= j
+        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.segs[mid].framePrefix <= j) lo = mid; else hi = mid; }
+        const ZskGatherSeg s = a.segs[lo];
+        const uint32_t f = s.first + ((uint32_t)j - s.framePrefix);
+        const uint64_t size = a.dOff[f + 1] - a.dOff[f];
+        if (!size) continue;                                                // a skippable or an empty frame: never the decoder's
+        const uint64_t k = s.item + (a.place[f] - a.place[s.first]);
+        uint8_t* const home = (s.inPlace ? a.dst : a.scratch) + s.home + (a.dOff[f] - a.dOff[s.first]);
+        a.srcSegs[2 * k] = a.cOff[f]; a.srcSegs[2 * k + 1] = a.cOff[f + 1] - a.cOff[f];
+        a.dstSegs[2 * k] = (uint64_t)(home - a.dstBase); a.dstSegs[2 * k + 1] = size;
+        a.frameOf[k] = f;
+    }
+}
+// a lane per item of the pass, as zsk_range_verify_body; a failing item is folded into every range that needs its frame (the rare path: the lane walks them)
+ZH_DEV void zsk_gather_verify_body(const ZskGatherArgs& a)
+{
+    for (uint64_t i = (uint64_t)zh_block() * 64 + zh_lane(); i < a.count; i += (uint64_t)zh_nblocks() * 64) {
+        const uint64_t k = a.item0 + i;
+        int32_t code = a.status[k];
+        const uint32_t f = a.frameOf[k];
+        if (!code) {
+            const uint64_t size = a.dOff[f + 1] - a.dOff[f];
+            if (a.outSizes[k] != size) code = ZSK_ERR_CORRUPT;
+            else if (a.checksum) {
+                const uint32_t want = zh_ld32(a.table + (uint64_t)f * a.entry + 8);
+                if ((uint32_t)ze_xxh64(a.dstBase + a.dstSegs[2 * k], (uint32_t)size) != want) code = ZSK_ERR_CHECKSUM;
+            }
+            if (code) a.status[k] = code;
+        }
+        if (code) for (uint32_t r = 0; r < a.nRanges; r++) if (a.ranges[r].f0 <= f && f <= a.ranges[r].f1) zh_atomic_max(a.worst + r, ~(uint32_t)k);
+    }
+}
+// the pass's copy jobs, a workgroup per ZSK_COPY_TILE bytes (it bisects the jobs' tile prefix), 16 bytes per lane; behind the last pass a lane per range
+// writes the range's pair and workgroup 0 the overall one: the lowest range that failed
+ZH_DEV void zsk_gather_finish_body(const ZskGatherArgs& a)
+{
+    for (uint64_t t = zh_block(); t < a.tiles; t += zh_nblocks()) {
+        uint32_t lo = 0, hi = a.nJobs;
+        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.jobs[mid].tilePrefix <= t) lo = mid; else hi = mid; }
+        const ZskGatherJob job = a.jobs[lo];
+        const uint64_t off = (t - job.tilePrefix) * ZSK_COPY_TILE, left = job.bytes - off;
+        const uint32_t bytes = left < ZSK_COPY_TILE ? (uint32_t)left : ZSK_COPY_TILE, whole = bytes & ~15u;
+        const uint8_t* const s = a.scratch + job.src + off; uint8_t* const d = a.dst + job.dst + off;
+        for (uint32_t j = zh_lane() * 16; j < whole; j += 64 * 16) { const zh_v16 v = zh_ld128(s + j); zh_st64(d + j, v.lo); zh_st64(d + j + 8, v.hi); }
+        if (zh_lane() < bytes - whole) d[whole + zh_lane()] = s[whole + zh_lane()];
+    }
+    if (!a.last) return;
+    for (uint64_t r = (uint64_t)zh_block() * 64 + zh_lane(); r < a.nRanges; r += (uint64_t)zh_nblocks() * 64) {
+        const uint32_t w = a.worst[r];
+        a.outStatus[2 + 2 * r] = w ? a.status[~w] : 0; a.outStatus[3 + 2 * r] = w ? (int32_t)a.frameOf[~w] : 0;
+    }
+    if (zh_block() != 0) return;
+    uint64_t first = ZSK_NONE;
+    for (uint32_t r = zh_lane(); r < a.nRanges; r += 64) if (a.worst[r] && first == ZSK_NONE) first = r;
+    first = zsk_wave_min64(first);
+    if (zh_lane() == 0) { a.outStatus[0] = first != ZSK_NONE ? a.status[~a.worst[first]] : 0; a.outStatus[1] = first != ZSK_NONE ? (int32_t)first : 0; }
+}
+
 #ifndef ZHIP_EMU
 __global__ __launch_bounds__(64) void zhip_seekable_scan_reduce_kernel(ZskScanArgs a) { zsk_scan_reduce_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_scan_write_kernel(ZskScanArgs a) { zsk_scan_write_body(a); }
@@ -302,4 +517,7 @@ __global__ __launch_bounds__(64) void zhip_seekable_table_kernel(ZskCompressArgs
 __global__ __launch_bounds__(64) void zhip_seekable_range_segs_kernel(ZskRangeArgs a) { zsk_range_segs_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_range_verify_kernel(ZskRangeArgs a) { zsk_range_verify_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_range_finish_kernel(ZskRangeArgs a) { zsk_range_finish_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_gather_segs_kernel(ZskGatherArgs a) { zsk_gather_segs_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_gather_verify_kernel(ZskGatherArgs a) { zsk_gather_verify_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_gather_finish_kernel(ZskGatherArgs a) { zsk_gather_finish_body(a); }
 #endif

@@ -149,12 +149,14 @@ class DeviceBatchContext:
 
 
 class SeekableStream:
-    """Range reads of a zstd seekable stream resident in HBM (any writer's): ``read(offset, length)`` decodes only the frames that cover the range.
+    """Range reads of a zstd seekable stream resident in HBM (any writer's): ``read(offset, length)`` decodes only the frames that cover the range,
+    ``read_ranges`` many ranges as one decode batch.
 
     ctx: the DeviceBatchContext that decodes (its dictionary, format and window limit apply); stream_tensor: the whole stream, a uint8 CUDA tensor,
     kept alive and unchanged while this object is open. Opening reads and checks the seek table (it waits); a damaged table raises ZstdError."""
 
-    def __init__(self, ctx, stream_tensor, stream=None):
+    def __init__(self, ctx, stream_tensor, stream=None, scratch_limit=None):
+        """scratch_limit: see set_scratch_limit"""
         DeviceBatchContext._check(stream_tensor, torch.uint8)
         self.ctx, self.tensor, self.handle = ctx, stream_tensor, None
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -167,6 +169,18 @@ class SeekableStream:
         self.handle = h
         self.content_size, self.n_frames, self.has_checksums = int(info.contentSize), int(info.nFrames), bool(info.checksumFlag)
         self.max_frame_content = int(info.maxFrameContent)
+        self.last_gather_stats = None
+        if scratch_limit is not None:
+            self.set_scratch_limit(scratch_limit)
+
+    def set_scratch_limit(self, nbytes):
+        """most device memory read_ranges may hold frames in that do not decode straight into their place (0: the default, 1 GiB). A call that needs more
+        runs in several passes; one frame larger than the limit is still held whole."""
+        if self.handle is None:
+            raise ZstdError("the seekable stream is closed")
+        if nbytes < 0:
+            raise ZstdError("scratch_limit must not be negative")
+        self.ctx.L.zhip_seekable_set_scratch_limit(self.handle, int(nbytes))
 
     def read(self, offset=0, length=None, out=None, stream=None):
         """content bytes [offset, offset + length) (length None: to the end) as a uint8 CUDA tensor -- `out`, where given, else a new one. Waits for the
@@ -195,6 +209,62 @@ class SeekableStream:
         if rc:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return out[:length]
+
+    def read_ranges(self, ranges, out=None, out_offsets=None, stream=None):
+        """Many ranges as ONE decode batch: every frame a range touches is decoded once, whatever the ranges share. ranges: a sequence of (offset, length) or
+        an integer array of shape (R, 2). Without `out` a new uint8 CUDA tensor holds the ranges back to back in call order; with `out`, range r goes to
+        out[out_offsets[r]:] (out_offsets None: back to back) -- the destinations must not overlap. Returns a list of views, one per range. Waits for the
+        status; a frame that fails raises ZstdError naming the lowest range that needs it, the frame and the error. last_gather_stats holds the call's
+        counts (items, inPlace, scratchBytes, copyJobs, passes)."""
+        if self.handle is None:
+            raise ZstdError("the seekable stream is closed")
+        import numpy as np
+        try:
+            r = np.asarray(ranges if len(ranges) else np.zeros((0, 2), dtype=np.int64))
+        except Exception:
+            raise ZstdError("ranges must be a sequence of (offset, length)")
+        if r.ndim != 2 or r.shape[1] != 2 or r.dtype.kind not in "iu":
+            raise ZstdError("ranges must be a sequence of (offset, length) or an integer array of shape (R, 2)")
+        n = r.shape[0]
+        if n and (r.astype(object) < 0).any():
+            raise ZstdError("ranges must not be negative")
+        table = np.zeros((max(n, 1), 3), dtype=np.uint64)
+        table[:n, :2] = r
+        lengths = [int(x) for x in table[:n, 1]]
+        if out_offsets is None:
+            at = 0
+            for k, ln in enumerate(lengths):
+                table[k, 2] = at; at += ln
+            need = at
+        else:
+            if out is None:
+                raise ZstdError("out_offsets needs out")
+            offs = [int(x) for x in out_offsets]
+            if len(offs) != n or any(x < 0 for x in offs):
+                raise ZstdError("out_offsets must hold one non-negative offset per range")
+            table[:n, 2] = np.array(offs, dtype=np.uint64) if n else 0
+            need = max([o + ln for o, ln in zip(offs, lengths)] + [0])
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            if out is None:
+                out = torch.empty(need, dtype=torch.uint8, device=self.tensor.device)
+            status = torch.zeros(2 + 2 * n, dtype=torch.int32, device=self.tensor.device)
+        DeviceBatchContext._check(out, torch.uint8)
+        L = self.ctx.L
+        stats = _lib.SeekableGatherStats()
+        rc = L.zhip_seekable_decompress_ranges_device(self.ctx.ctx, self.handle, table.ctypes.data, n, out.data_ptr(), out.numel(), status.data_ptr(),
+                                                      C.byref(stats), s.cuda_stream)
+        if rc:
+            raise ZstdError("seekable read failed: %s" % _lib.last_error())
+        self.last_gather_stats = {k: int(getattr(stats, k)) for k, _ in stats._fields_}
+        err = _lib.Error()
+        rc = L.zhip_ctx_sync(self.ctx.ctx, s.cuda_stream, status.data_ptr(), 1, C.byref(err))
+        if rc == _lib.ERR_ZSTD:
+            bad = int(status[1])
+            raise ZstdError("seekable read: range %d: frame %d: %s" % (bad, int(status[3 + 2 * bad]), _lib.error_name(err.zstdErr)))
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return [out[int(table[k, 2]):int(table[k, 2]) + lengths[k]] for k in range(n)]
 
     def close(self):
         if self.handle is not None:

@@ -1,5 +1,5 @@
 """The zstd seekable format for host bytes: ``compress`` cuts the data into frames of ``frame_size`` bytes, compresses them as ONE batch on the GPU and
-appends the seek table; ``decompress`` reads any byte range of such a stream by decoding only the frames that cover it. The streams are ordinary zstd:
+appends the seek table; ``decompress`` reads any byte range of such a stream by decoding only the frames that cover it, ``decompress_ranges`` many ranges as one batch. The streams are ordinary zstd:
 ``zstd -d`` and ``ZstdDecompressor`` decompress them whole (the table is a skippable frame). Built on ``device.DeviceBatchContext.seekable_compress`` and
 ``device.SeekableStream``; the data crosses the link once each way."""
 import torch
@@ -34,6 +34,29 @@ def decompress(data, offset=0, length=None, **ctx_kw):
         st = SeekableStream(ctx, _to_device(data))
         try:
             return st.read(offset, length).cpu().numpy().tobytes()
+        finally:
+            st.close()
+    finally:
+        ctx.close()
+
+
+def decompress_ranges(data, ranges, **ctx_kw):
+    """the content bytes of every (offset, length) of `ranges` as a list of bytes: ONE decode batch over the frames the ranges touch, each decoded once.
+    Raises ZstdError as ``decompress`` does; a failing frame's error names the lowest range that needs it."""
+    if len(data) == 0:
+        raise ZstdError("not a seekable stream: empty input")
+    ctx = DeviceBatchContext(**ctx_kw)
+    try:
+        st = SeekableStream(ctx, _to_device(data))
+        try:
+            views = st.read_ranges(ranges)
+            if not views:
+                return []
+            host = torch.cat(views).cpu().numpy().tobytes()                 # (the views lie back to back in call order: one copy over the link)
+            out, at = [], 0
+            for v in views:
+                out.append(host[at:at + v.numel()]); at += v.numel()
+            return out
         finally:
             st.close()
     finally:
