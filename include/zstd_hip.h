@@ -229,6 +229,26 @@ uint64_t zhip_seekable_bound(uint64_t srcSize, uint32_t frameSize, int flags);  
 int zhip_seekable_compress_device(zhip_ctx*, const void* d_src, uint64_t srcSize, uint32_t frameSize, int flags,
                                   void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status /* [2] */, void* stream);
 
+/* One frame per RECORD: d_records[i] = (offset, length) of record i in d_src, a table in DEVICE memory that a kernel queued on `stream` just before the call may
+ * have written. The stream holds nRecords frames in index order -- its content is the records concatenated in that order -- and the table behind them; records
+ * may lie anywhere in d_src, in any order, with gaps, two may name the same bytes, length 0 is allowed (zhip_compress_batch_device's rule for its segments).
+ * Everything else is zhip_seekable_compress_device's: the context's level, parameters, flags and dictionary, ZHIP_SEEKABLE_CHECKSUM (of the source records),
+ * one stream-ordered sequence with no host wait except while scratch grows, the context's size hint left as the caller set it.
+ * What the host says without waiting: nRecords <= 2^27; maxContentBytes, an upper bound on the sum of the lengths (with nRecords it sizes the slots the records
+ * are compressed into: maxContentBytes + (maxContentBytes >> 8) + 80 * nRecords bytes of context scratch, never more than for nRecords records of
+ * maxRecordBytes); maxRecordBytes <= 2^30, an upper bound on every length -- the batch's size hint for this call, so a value above 128 KiB selects the
+ * several-block paths. Else ZHIP_ERR_UNSUPPORTED. The device checks what the host assumed BEFORE anything is compressed: a length above maxRecordBytes, an
+ * offset + length beyond srcSize or one that wraps: 72 (srcSize_wrong) at the lowest such record; none of these, but the lengths sum to more than maxContentBytes:
+ * 72 at the lowest record whose running end exceeds it. Behind the batch: the lowest failing frame keeps the compressor's code (40 for a record the level
+ * refuses), then the capacity (70; the first frame that ends beyond dstCapacity, the last frame where only the table does not fit). d_status = {code, record
+ * index}; every failure sets *d_streamSize = 0 and writes nothing into d_dst; nothing at or beyond d_dst + dstCapacity is ever written. nRecords 0 gives the
+ * 17-byte stream of zero frames. */
+uint64_t zhip_seekable_records_bound(uint64_t maxContentBytes, uint64_t nRecords, int flags);   /* worst-case stream bytes for nRecords records whose lengths sum to at most maxContentBytes; 0 = invalid arguments */
+int zhip_seekable_compress_records_device(zhip_ctx*, const void* d_src, uint64_t srcSize,
+                                          const zhip_segment* d_records /* DEVICE: (offset, length) of record i in d_src */, size_t nRecords,
+                                          uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
+                                          void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status /* [2] */, void* stream);
+
 typedef struct zhip_seekable zhip_seekable;
 typedef struct { uint64_t streamSize, contentSize; uint32_t nFrames, maxFrameContent; int checksumFlag; } zhip_seekable_info;
 /* Reads the table of a stream in HBM (any writer's) and returns a handle for range reads; d_stream is borrowed and must stay as it is while the handle lives.
@@ -273,6 +293,18 @@ int  zhip_seekable_decompress_ranges_device(zhip_ctx*, zhip_seekable*, const zhi
                                             void* d_dst, uint64_t dstCapacity, int32_t* d_status /* [2 + 2 * nRanges] */,
                                             zhip_seekable_gather_stats* stats /* host, may be NULL; filled before the call returns */, void* stream);
 void zhip_seekable_set_scratch_limit(zhip_seekable*, uint64_t bytes);      /* of the many-ranges call; 0 = the default, 1 GiB */
+/* The table the handle opened: out[0 .. count] = the decompressed offsets of frames first .. first + count (count + 1 values; frame f is content bytes
+ * [out[f - first], out[f - first + 1])), from the handle's host copy: no device work, no wait. first + count beyond nFrames: ZHIP_ERR_SIZE_MISMATCH. */
+int  zhip_seekable_frame_offsets(const zhip_seekable*, uint32_t first, uint32_t count, uint64_t* out);
+/* Whole frames by index -- records of a stream written by zhip_seekable_compress_records_device, frames of any writer's: frame frames[k]'s content goes to
+ * d_dst + dstOffsets[k] or, with dstOffsets NULL, back to back in call order. frames and dstOffsets are HOST arrays, read before the call returns. Every index
+ * becomes the range of its frame's content and the call is zhip_seekable_decompress_ranges_device's from there: its checks (destinations beyond dstCapacity,
+ * overlapping destinations), its stream order, its d_status layout with positions for ranges, its guards, its stats. Every distinct frame is decoded once; a
+ * frame named once decodes straight into its place (inPlace == items where the indices are distinct), a frame named more than once goes through the handle's
+ * scratch; an empty frame yields {0, 0} and no item. An index >= nFrames: ZHIP_ERR_SIZE_MISMATCH with the position in zhip_last_error(), nothing queued. */
+int  zhip_seekable_decompress_frames_device(zhip_ctx*, zhip_seekable*, const uint32_t* frames, size_t nFrames,
+                                            const uint64_t* dstOffsets /* host, may be NULL */, void* d_dst, uint64_t dstCapacity,
+                                            int32_t* d_status /* [2 + 2 * nFrames] */, zhip_seekable_gather_stats* stats, void* stream);
 
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,

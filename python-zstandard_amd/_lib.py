@@ -126,6 +126,10 @@ def lib():
         "zhip_seekable_decompress_device": (C.c_int, [vp, vp, u64, u64, vp, vp, vp]),
         "zhip_seekable_decompress_ranges_device": (C.c_int, [vp, vp, vp, sz, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
         "zhip_seekable_set_scratch_limit": (None, [vp, u64]),
+        "zhip_seekable_records_bound": (u64, [u64, u64, C.c_int]),
+        "zhip_seekable_compress_records_device": (C.c_int, [vp, vp, u64, vp, sz, u64, u64, C.c_int, vp, u64, vp, vp, vp]),
+        "zhip_seekable_frame_offsets": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
+        "zhip_seekable_decompress_frames_device": (C.c_int, [vp, vp, vp, sz, vp, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
     }
     for name, (res, args) in protos.items():
         f = getattr(L, name)
@@ -146,6 +150,7 @@ EXPORTED_SYMBOLS = [
     "zhip_ctx_table_pick", "zhip_ctx_decode_fallbacks", "zhip_partition_by_bytes", "zhip_batch_devices",
     "zhip_seekable_frame_count", "zhip_seekable_bound", "zhip_seekable_compress_device", "zhip_seekable_open_device", "zhip_seekable_close",
     "zhip_seekable_decompress_device", "zhip_seekable_decompress_ranges_device", "zhip_seekable_set_scratch_limit",
+    "zhip_seekable_records_bound", "zhip_seekable_compress_records_device", "zhip_seekable_frame_offsets", "zhip_seekable_decompress_frames_device",
 ]
 
 

@@ -2162,6 +2162,74 @@ extern "C" int zhip_seekable_compress_device(zhip_ctx* c, const void* d_src, uin
     return 0;
 }
 
+extern "C" uint64_t zhip_seekable_records_bound(uint64_t maxContentBytes, uint64_t nRecords, int flags)
+{
+    if (flags & ~ZHIP_SEEKABLE_CHECKSUM) return 0;
+    return zsk_records_bound(maxContentBytes, nRecords, flags & ZHIP_SEEKABLE_CHECKSUM);
+}
+
+// zhip_seekable_compress_device with the caller's record table in the place of the fixed cut: the pre-check (two scans, a verdict), the segments, the batch,
+// then the fixed-size call's tail -- the scan of the sizes, its verdict, the (records) table writer, the compaction
+extern "C" int zhip_seekable_compress_records_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, const zhip_segment* d_records, size_t nRecords,
+                                                     uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
+                                                     void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+{
+    if (!c || !d_streamSize || !d_status || (nRecords && !d_records) || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) { g_lastError = "seekable compress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
+    if (nRecords > ZSK_MAX_FRAMES || maxRecordBytes > ZSK_MAX_CONTENT) { g_lastError = "seekable compress: at most 2^27 records of at most 2^30 bytes"; return ZHIP_ERR_UNSUPPORTED; }
+    hipStream_t stream = (hipStream_t)streamv;
+    const size_t n = nRecords;
+    maxContentBytes = zsk_records_content_cap(maxContentBytes, n, maxRecordBytes);
+    // (growing either area frees the old one, which waits for the device: the wait the stream-order rules allow)
+    const size_t oSrcSegs = 0, oSlotSegs = oSrcSegs + zsk_up16(n * 16), oSizes = oSlotSegs + zsk_up16(n * 16), oOffs = oSizes + zsk_up16(n * 8),
+                 oLenOffs = oOffs + zsk_up16((n + 1) * 8), oSlotOffs = oLenOffs + zsk_up16((n + 1) * 8), oPartSum = oSlotOffs + zsk_up16((n + 1) * 8),
+                 oPartBad = oPartSum + ZSK_SCAN_GRID * 8, oPreBad = oPartBad + ZSK_SCAN_GRID * 8, oGo = oPreBad + ZSK_SCAN_GRID * 8, oStatus = oGo + 16, metaBytes = oStatus + zsk_up16(n * 4);
+    if (c->skMeta.reserve(metaBytes)) return g_reserveRc;
+    if (n && c->skSlots.reserve((size_t)zsk_records_slot_bytes(maxContentBytes, n))) return g_reserveRc;
+    uint8_t* const m = (uint8_t*)c->skMeta.p;
+    uint32_t* const words = (uint32_t*)(m + oGo);                          // go, pre, the pre-check's status pair
+    ZskRecordsArgs r; memset(&r, 0, sizeof r);
+    r.src = (const uint8_t*)d_src; r.srcSize = srcSize; r.records = (const uint64_t*)d_records; r.n = (uint32_t)n; r.checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1u : 0u;
+    r.maxContent = maxContentBytes; r.lenOffs = (const uint64_t*)(m + oLenOffs); r.slotOffs = (const uint64_t*)(m + oSlotOffs); r.partBad = (const uint64_t*)(m + oPreBad);
+    r.srcSegs = (uint64_t*)(m + oSrcSegs); r.slotSegs = (uint64_t*)(m + oSlotSegs); r.pre = words + 1; r.preStatus = (int32_t*)(words + 2);
+    r.outSizes = (const uint64_t*)(m + oSizes); r.status = (int32_t*)(m + oStatus); r.offs = (const uint64_t*)(m + oOffs); r.go = words;
+    r.dst = (uint8_t*)d_dst; r.streamSize = d_streamSize; r.outStatus = d_status;
+    ZskScanArgs s; memset(&s, 0, sizeof s);
+    s.in = (const uint8_t*)d_records + 8; s.stride = 16; s.mode = 3; s.n = (uint32_t)n; s.limit64 = maxRecordBytes; s.srcSize = srcSize;
+    s.offs = (uint64_t*)(m + oLenOffs); s.partSum = (uint64_t*)(m + oPartSum); s.partBad = (uint64_t*)(m + oPreBad);
+    uint32_t span; r.nPart = zsk_scan_shape(s.n, &span);
+    if (int rc = zsk_launch_scan(s, stream)) return rc;
+    s.mode = 4; s.offs = (uint64_t*)(m + oSlotOffs); s.partBad = (uint64_t*)(m + oPartBad);
+    if (int rc = zsk_launch_scan(s, stream)) return rc;
+    hipLaunchKernelGGL(zhip_seekable_records_verdict_kernel, dim3(1), dim3(64), 0, stream, r);
+    HIP_TRY(hipGetLastError());
+    if (n) {
+        hipLaunchKernelGGL(zhip_seekable_records_segs_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, r);
+        HIP_TRY(hipGetLastError());
+        // the batch's largest source is what the caller says it is; the caller's own size hint is not touched
+        const size_t hintWas = c->srcMaxHint;
+        c->srcMaxHint = (size_t)maxRecordBytes;
+        const int rc = zhip_compress_batch_device(c, d_src, (const zhip_segment*)r.srcSegs, n, c->skSlots.p, (const zhip_segment*)r.slotSegs, (uint64_t*)(m + oSizes), r.status, stream);
+        c->srcMaxHint = hintWas;
+        if (rc) return rc;
+    }
+    ZskCompressArgs a; memset(&a, 0, sizeof a);
+    a.n = (uint32_t)n; a.checksum = r.checksum; a.nPart = r.nPart; a.outSizes = r.outSizes; a.status = r.status; a.offs = r.offs; a.partBad = (const uint64_t*)(m + oPartBad);
+    a.dst = (uint8_t*)d_dst; a.dstCapacity = dstCapacity; a.streamSize = d_streamSize; a.outStatus = d_status; a.go = words;
+    memset(&s, 0, sizeof s);
+    s.in = m + oSizes; s.status = r.status; s.mode = 0; s.n = (uint32_t)n; s.offs = (uint64_t*)(m + oOffs); s.partSum = (uint64_t*)(m + oPartSum); s.partBad = (uint64_t*)(m + oPartBad);
+    if (int rc = zsk_launch_scan(s, stream)) return rc;
+    hipLaunchKernelGGL(zhip_seekable_verdict_kernel, dim3(1), dim3(64), 0, stream, a);
+    hipLaunchKernelGGL(zhip_seekable_records_table_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, r);
+    HIP_TRY(hipGetLastError());
+    if (n) {
+        const size_t gmax = (size_t)c->numCU * 16;
+        hipLaunchKernelGGL(zhip_compact_kernel, dim3((uint32_t)(n < gmax ? n : gmax)), dim3(64), 0, stream, (const uint8_t*)c->skSlots.p, (const zhip_segment*)r.slotSegs, r.outSizes,
+                           (const int32_t*)r.status, r.offs, (uint32_t)n, (uint8_t*)d_dst);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
 struct zhip_seekable {
     const uint8_t* stream = nullptr; uint64_t streamSize = 0;
     ZskLayout lay = {0, 8, 0, 0};
@@ -2383,4 +2451,30 @@ extern "C" int zhip_seekable_decompress_ranges_device(zhip_ctx* c, zhip_seekable
     }
     c->dstMaxHint = hintWas;
     return rc;
+}
+
+extern "C" int zhip_seekable_frame_offsets(const zhip_seekable* h, uint32_t first, uint32_t count, uint64_t* out)
+{
+    if (!h || !out) { g_lastError = "seekable frame offsets: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
+    if (!zsk_frame_offsets(h->dOff.data(), h->lay.n, first, count, out)) {
+        char buf[160]; snprintf(buf, sizeof buf, "seekable frame offsets: frames %u + %u, the table has %u", first, count, h->lay.n);
+        g_lastError = buf;
+        return ZHIP_ERR_SIZE_MISMATCH;
+    }
+    return 0;
+}
+
+// whole frames by index: every index becomes the range of its frame's content, and the many-ranges call does the rest
+extern "C" int zhip_seekable_decompress_frames_device(zhip_ctx* c, zhip_seekable* h, const uint32_t* frames, size_t nFrames, const uint64_t* dstOffsets, void* d_dst, uint64_t dstCapacity,
+                                                      int32_t* d_status, zhip_seekable_gather_stats* stats, void* streamv)
+{
+    if (!c || !h || !d_status || (nFrames && !frames) || nFrames > ZSK_MAX_RANGES) { g_lastError = "seekable frames: bad arguments (NULL, or more than 2^27 indices)"; return ZHIP_ERR_UNSUPPORTED; }
+    std::vector<zhip_seekable_range> rg(nFrames ? nFrames : 1);
+    const size_t bad = zsk_frames_to_ranges(h->dOff.data(), h->lay.n, frames, nFrames, dstOffsets, (uint64_t*)rg.data());
+    if (bad != nFrames) {
+        char buf[160]; snprintf(buf, sizeof buf, "seekable frames: position %zu names frame %u, the table has %u", bad, frames[bad], h->lay.n);
+        g_lastError = buf;
+        return ZHIP_ERR_SIZE_MISMATCH;
+    }
+    return zhip_seekable_decompress_ranges_device(c, h, rg.data(), nFrames, d_dst, dstCapacity, d_status, stats, streamv);
 }

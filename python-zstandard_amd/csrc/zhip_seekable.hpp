@@ -4,7 +4,8 @@
 //
 // (all little-endian; an entry is Compressed_Size, Decompressed_Size and, with bit 7 of the descriptor, the low 32 bits of XXH64 of the frame's content).
 // What is here: the format's arithmetic and checks (plain functions, host and device), and the kernels around the batch calls -- chunk segments, a
-// multi-workgroup exclusive scan of 64-bit sizes, the table writer, and the range pieces (segment builder, size / checksum verifier, edge copy).
+// multi-workgroup exclusive scan of 64-bit sizes, the table writer, their twins for a caller's record table (one frame per record), and the range pieces
+// (segment builder, size / checksum verifier, edge copy).
 // Every kernel is one-wave workgroups written against zhip_device.hpp, so the same bodies run under the host wave emulator (tests/emu/emu_seekable.cpp).
 #pragma once
 #include "zhip_device.hpp"
@@ -99,11 +100,15 @@ ZH_DEV uint64_t zsk_wave_scan64(uint64_t v)          // inclusive
 //   mode 0: in = uint64_t[n]; an item whose status is non-zero counts 0 and is "bad"
 //   mode 1: in = a 32-bit column of the seek table (any alignment), `stride` bytes from entry to entry; an item above `limit` is "bad"
 //   mode 2: the same column, an item counts 1 where it is non-zero (which place a frame has among those that hold content)
+//   mode 3: in = the 64-bit length column of a record table (record i's length at in + i * stride, its offset 8 bytes in front; 8-byte aligned); an item counts
+//           its length and is "bad" where the length is above limit64, or offset + length ends beyond srcSize or wraps
+//   mode 4: the same column, an item counts (zsk_compress_bound(length) + 15) & ~15 -- the distance to the next record's slot; no item is bad
 struct ZskScanArgs {
     const uint8_t* in; const int32_t* status; uint32_t stride, mode, limit, n;
     uint32_t span;                    // items per workgroup: whole tiles (zsk_scan_shape)
     uint64_t* offs;                   // [n + 1]: offs[n] = the total
     uint64_t* partSum; uint64_t* partBad;      // [grid]
+    uint64_t limit64, srcSize;        // modes 3 and 4 (0 in the other modes)
 };
 static inline uint32_t zsk_scan_shape(uint32_t n, uint32_t* span)
 {
@@ -115,6 +120,14 @@ static inline uint32_t zsk_scan_shape(uint32_t n, uint32_t* span)
 ZH_DEV uint64_t zsk_scan_item(const ZskScanArgs& a, uint32_t i, bool* bad)
 {
     if (a.mode == 0) { const bool b = a.status[i] != 0; *bad = b; return b ? 0 : ((const uint64_t*)a.in)[i]; }
+    if (a.mode >= 3) {
+        const uint64_t* const rec = (const uint64_t*)(a.in + (size_t)i * a.stride);
+        const uint64_t len = rec[0];
+        if (a.mode == 4) { *bad = false; return (zsk_compress_bound(len) + 15) & ~(uint64_t)15; }
+        const uint64_t off = rec[-1];
+        *bad = len > a.limit64 || off + len < off || off + len > a.srcSize;
+        return len;
+    }
     const uint32_t v = zh_ld32(a.in + (size_t)i * a.stride);
     *bad = v > a.limit;
     return a.mode == 1 ? (uint64_t)v : (uint64_t)(v != 0);
@@ -212,6 +225,115 @@ ZH_DEV void zsk_table_body(const ZskCompressArgs& a)
         zh_st32(table, ZSK_SKIP_MAGIC); zh_st32(table + 4, a.n * entry + ZSK_FOOTER);
         zh_st32(f, a.n); f[4] = a.checksum ? 0x80 : 0; zh_st32(f + 5, ZSK_SEEK_MAGIC);
     }
+}
+
+// ------------------------------------------------------------------------------------------------ compress: records
+// One frame per record: the caller's table of (offset, length) in device memory takes the place of the fixed cut. The host knows bounds only -- what the
+// lengths sum to at most (it sizes the slot area), what a length is at most (the batch's size hint) --, so the device checks them before anything is
+// compressed: two scans of the length column (mode 3: the lengths, with the per-record checks; mode 4: the slot strides), one wave's verdict, and a lane per
+// record that hands the batch either the records and their slots or, after a failed check, n empty sources with 64-byte slots (zsk_compress_bound(0)) at 64 * i.
+//
+// The slot area. Record i's slot starts at the sum of the strides in front, a stride being zsk_compress_bound(len) rounded up to 16. zsk_compress_bound(len)
+// = len + (len >> 8) + (len < 128 KiB ? (128 KiB - len) >> 11 : 0) <= len + (len >> 8) + 64, so a stride is at most len + (len >> 8) + 64 + 15, and
+// sum(len >> 8) <= (sum len) >> 8: n records whose lengths sum to at most C need at most C + (C >> 8) + 79 * n bytes. The host reserves
+// zsk_records_slot_bytes = C + (C >> 8) + 80 * n, which also holds the 64 * n bytes of the harmless form.
+#define ZSK_ERR_SRCSIZE 72
+ZSK_HD uint64_t zsk_records_slot_bytes(uint64_t maxContent, uint64_t n) { return maxContent + (maxContent >> 8) + 80 * n; }
+// (no record is above maxRecord, so the lengths cannot sum to more than n of them: a generous maxContent does not size the slots)
+ZSK_HD uint64_t zsk_records_content_cap(uint64_t maxContent, uint64_t n, uint64_t maxRecord) { return maxContent > n * maxRecord ? n * maxRecord : maxContent; }
+ZSK_HD bool zsk_records_args_ok(uint64_t maxContent, uint64_t n) { return n <= ZSK_MAX_FRAMES && maxContent <= (uint64_t)ZSK_MAX_FRAMES * ZSK_MAX_CONTENT; }
+// worst-case stream bytes: every frame at its zsk_compress_bound (the derivation above without the rounding), and the table
+ZSK_HD uint64_t zsk_records_bound(uint64_t maxContent, uint64_t n, int checksum)
+{
+    if (!zsk_records_args_ok(maxContent, n)) return 0;
+    return maxContent + (maxContent >> 8) + 64 * n + zsk_table_size(n, checksum);
+}
+struct ZskRecordsArgs {
+    const uint8_t* src; uint64_t srcSize;
+    const uint64_t* records;                    // [n][2]: the caller's (offset, length) of record i in src -- device memory
+    uint32_t n, checksum, nPart;
+    uint64_t maxContent;                        // what the lengths may sum to
+    const uint64_t* lenOffs;                    // [n + 1]: the scan of the lengths (mode 3)
+    const uint64_t* slotOffs;                   // [n + 1]: the scan of the slot strides (mode 4)
+    const uint64_t* partBad;                    // [nPart]: the length scan's lowest bad record per workgroup
+    uint64_t* srcSegs; uint64_t* slotSegs;      // [n][2]: what the batch call is handed
+    uint32_t* pre; int32_t* preStatus;          // the pre-check's go word (1: passed) and its {code, index}
+    const uint64_t* outSizes; int32_t* status;  // [n]: what zhip_compress_batch_device wrote
+    const uint64_t* offs;                       // [n + 1]: the scan of outSizes
+    const uint32_t* go;                         // zsk_verdict_body's word
+    uint8_t* dst; uint64_t* streamSize; int32_t* outStatus;      // the caller's
+};
+// one wave: the pre-check's verdict -- the lowest record a lane of the scan refused, else the lowest record whose running end exceeds maxContent
+ZH_DEV void zsk_records_verdict_body(const ZskRecordsArgs& a)
+{
+    uint64_t bad = ZSK_NONE;
+    for (uint32_t j = zh_lane(); j < a.nPart; j += 64) { const uint64_t v = a.partBad[j]; bad = v < bad ? v : bad; }
+    bad = zsk_wave_min64(bad);
+    if (zh_lane() != 0) return;
+    int32_t code = 0; uint32_t index = 0;
+    if (bad != ZSK_NONE) { code = ZSK_ERR_SRCSIZE; index = (uint32_t)bad; }
+    else if (a.lenOffs[a.n] > a.maxContent) {
+        // (every length passed its check: at most 2^27 of at most 2^30, the sums did not wrap and do not decrease: bisect)
+        uint32_t lo = 0, hi = a.n;
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (a.lenOffs[mid + 1] > a.maxContent) hi = mid; else lo = mid + 1; }
+        code = ZSK_ERR_SRCSIZE; index = lo;
+    }
+    a.preStatus[0] = code; a.preStatus[1] = (int32_t)index;
+    *a.pre = code ? 0u : 1u;
+}
+// a lane per record: its source segment and its slot. After a failed pre-check the batch still runs (the host cannot know the verdict): it is handed empty
+// sources and 64-byte slots, all inside the source and the slot area whatever the records say
+ZH_DEV void zsk_records_segs_body(const ZskRecordsArgs& a)
+{
+    const bool ok = *a.pre != 0;
+    for (uint64_t i = (uint64_t)zh_block() * 64 + zh_lane(); i < a.n; i += (uint64_t)zh_nblocks() * 64) {
+        const uint64_t len = ok ? a.records[2 * i + 1] : 0;
+        a.srcSegs[2 * i] = ok ? a.records[2 * i] : 0; a.srcSegs[2 * i + 1] = len;
+        a.slotSegs[2 * i] = ok ? a.slotOffs[i] : 64 * i; a.slotSegs[2 * i + 1] = zsk_compress_bound(len);
+    }
+}
+// zsk_table_body's twin: a record's length and checksum come from the caller's table. Where the pre-check failed, lane 0 of the grid puts its status over
+// what zsk_verdict_body made of the harmless batch and sets the stream size to 0; every frame's status is made non-zero as for any failed stream
+ZH_DEV void zsk_records_table_body(const ZskRecordsArgs& a)
+{
+    const bool pre = *a.pre != 0, go = pre && *a.go != 0;
+    const uint32_t entry = zsk_entry_size((int)a.checksum);
+    uint8_t* const table = a.dst + a.offs[a.n];
+    for (uint64_t i = (uint64_t)zh_block() * 64 + zh_lane(); i < a.n; i += (uint64_t)zh_nblocks() * 64) {
+        if (!go) { if (!a.status[i]) a.status[i] = ZSK_ERR_DSTSIZE; continue; }
+        const uint64_t at = a.records[2 * i]; const uint32_t len = (uint32_t)a.records[2 * i + 1];
+        uint8_t* const e = table + ZSK_HEADER + i * entry;
+        zh_st32(e, (uint32_t)a.outSizes[i]); zh_st32(e + 4, len);
+        if (a.checksum) zh_st32(e + 8, (uint32_t)ze_xxh64(a.src + at, len));
+    }
+    if (zh_block() != 0 || zh_lane() != 0) return;
+    if (go) {
+        uint8_t* const f = table + ZSK_HEADER + (uint64_t)a.n * entry;
+        zh_st32(table, ZSK_SKIP_MAGIC); zh_st32(table + 4, a.n * entry + ZSK_FOOTER);
+        zh_st32(f, a.n); f[4] = a.checksum ? 0x80 : 0; zh_st32(f + 5, ZSK_SEEK_MAGIC);
+    } else if (!pre) { a.outStatus[0] = a.preStatus[0]; a.outStatus[1] = a.preStatus[1]; *a.streamSize = 0; }
+}
+
+// reads by frame index: which content bytes a frame is (zhip_seekable_frame_offsets), and the range list zhip_seekable_decompress_frames_device hands the
+// many-ranges plan -- rg [count][3] = {dOff[f], dOff[f + 1] - dOff[f], dstOffsets[k] or, without them, the sizes in front}. Returns count, or the position of
+// the first index that is not a frame of the table
+static inline bool zsk_frame_offsets(const uint64_t* D, uint32_t n, uint32_t first, uint32_t count, uint64_t* out)
+{
+    if (first > n || count > n - first) return false;
+    for (uint64_t k = 0; k <= count; k++) out[k] = D[first + k];
+    return true;
+}
+static inline size_t zsk_frames_to_ranges(const uint64_t* D, uint32_t n, const uint32_t* frames, size_t count, const uint64_t* dstOffsets, uint64_t* rg)
+{
+    uint64_t at = 0;
+    for (size_t k = 0; k < count; k++) {
+        const uint32_t f = frames[k];
+        if (f >= n) return k;
+        const uint64_t len = D[f + 1] - D[f];
+        rg[3 * k] = D[f]; rg[3 * k + 1] = len; rg[3 * k + 2] = dstOffsets ? dstOffsets[k] : at;
+        at += len;
+    }
+    return count;
 }
 
 // ------------------------------------------------------------------------------------------------ ranges
@@ -514,6 +636,9 @@ __global__ __launch_bounds__(64) void zhip_seekable_scan_write_kernel(ZskScanArg
 __global__ __launch_bounds__(64) void zhip_seekable_chunk_segs_kernel(ZskCompressArgs a) { zsk_chunk_segs_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_verdict_kernel(ZskCompressArgs a) { zsk_verdict_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_table_kernel(ZskCompressArgs a) { zsk_table_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_records_verdict_kernel(ZskRecordsArgs a) { zsk_records_verdict_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_records_segs_kernel(ZskRecordsArgs a) { zsk_records_segs_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_records_table_kernel(ZskRecordsArgs a) { zsk_records_table_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_range_segs_kernel(ZskRangeArgs a) { zsk_range_segs_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_range_verify_kernel(ZskRangeArgs a) { zsk_range_verify_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_range_finish_kernel(ZskRangeArgs a) { zsk_range_finish_body(a); }

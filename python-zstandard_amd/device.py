@@ -125,6 +125,64 @@ class DeviceBatchContext:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return dst[:int(size[0])]
 
+    def seekable_compress_records(self, src, records, max_content_bytes=None, max_record_bytes=None, checksum=False, stream=None):
+        """One frame per record: records[i] = (offset, length) of record i in src (a uint8 CUDA tensor), anywhere in it, in any order, with gaps or sharing
+        bytes, length 0 allowed; the stream's content is the records concatenated in index order. records: an (n, 2) int64 CUDA tensor -- it may have been
+        written by work queued on `stream`, nothing is waited for; max_content_bytes (an upper bound on the lengths' sum) and max_record_bytes (on every
+        length, at most 2^30) are then required, and the device checks them -- or a host sequence / array of (offset, length), which is uploaded and gives both
+        bounds itself. Returns a uint8 CUDA tensor of exactly the stream's size, as seekable_compress does. Waits for the size. A record outside src or above
+        a bound raises ZstdError (srcSize_wrong) with its index. SeekableStream.read_records reads records back by index."""
+        import numpy as np
+        self._ensure_cparams()
+        self._check(src, torch.uint8)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if isinstance(records, torch.Tensor) and records.is_cuda:
+            if max_content_bytes is None or max_record_bytes is None:
+                raise ZstdError("seekable compress: a device-resident record table needs max_content_bytes and max_record_bytes")
+            self._check(records, torch.int64)
+            if records.dim() != 2 or records.shape[1] != 2:
+                raise ZstdError("seekable compress: records must have the shape (n, 2)")
+            table = records
+        else:
+            try:
+                r = np.asarray(records.cpu() if isinstance(records, torch.Tensor) else records if len(records) else np.zeros((0, 2), dtype=np.int64))
+            except Exception:
+                raise ZstdError("seekable compress: records must be a sequence of (offset, length)")
+            if r.ndim != 2 or r.shape[1] != 2 or r.dtype.kind not in "iu":
+                raise ZstdError("seekable compress: records must be a sequence of (offset, length) or an integer array of shape (n, 2)")
+            if r.shape[0] and ((r.astype(object) < 0).any() or (r.astype(object) >= 1 << 63).any()):
+                raise ZstdError("seekable compress: records must not be negative")
+            r = np.ascontiguousarray(r.astype(np.int64))
+            if max_content_bytes is None:
+                max_content_bytes = int(r[:, 1].sum()) if r.shape[0] else 0
+            if max_record_bytes is None:
+                max_record_bytes = int(r[:, 1].max()) if r.shape[0] else 0
+            with torch.cuda.stream(s):
+                table = torch.from_numpy(r).to(src.device) if r.shape[0] else torch.zeros((0, 2), dtype=torch.int64, device=src.device)
+        n = int(table.shape[0])
+        max_content_bytes, max_record_bytes = int(max_content_bytes), int(max_record_bytes)
+        if max_content_bytes < 0 or not 0 <= max_record_bytes <= 1 << 30 or n > 1 << 27:
+            raise ZstdError("seekable compress: at most 2^27 records of at most 2^30 bytes")
+        flags = _lib.SEEKABLE_CHECKSUM if checksum else 0
+        bound = self.L.zhip_seekable_records_bound(min(max_content_bytes, n * max_record_bytes), n, flags)
+        if not bound:
+            raise ZstdError("seekable compress: at most 2^27 records of at most 2^30 bytes")
+        with torch.cuda.stream(s):
+            dst = torch.empty(bound, dtype=torch.uint8, device=src.device)
+            size = torch.zeros(1, dtype=torch.int64, device=src.device)
+            status = torch.zeros(2, dtype=torch.int32, device=src.device)
+        rc = self.L.zhip_seekable_compress_records_device(self.ctx, src.data_ptr(), src.numel(), table.data_ptr() if n else None, n, max_content_bytes, max_record_bytes,
+                                                          flags, dst.data_ptr(), bound, size.data_ptr(), status.data_ptr(), s.cuda_stream)
+        if rc:
+            raise ZstdError("seekable compress failed: %s" % _lib.last_error())
+        err = _lib.Error()
+        rc = self.L.zhip_ctx_sync(self.ctx, s.cuda_stream, status.data_ptr(), 1, C.byref(err))
+        if rc == _lib.ERR_ZSTD:
+            raise ZstdError("seekable compress: record %d: %s" % (int(status[1]), _lib.error_name(err.zstdErr)))
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return dst[:int(size[0])]
+
     def kernel_time(self, direction):
         """(average ms per launch, launches) of the dominant kernel since the last call, from HIP events on the launch stream."""
         ms, n = C.c_double(0), C.c_uint64(0)
@@ -150,7 +208,7 @@ class DeviceBatchContext:
 
 class SeekableStream:
     """Range reads of a zstd seekable stream resident in HBM (any writer's): ``read(offset, length)`` decodes only the frames that cover the range,
-    ``read_ranges`` many ranges as one decode batch.
+    ``read_ranges`` many ranges as one decode batch, ``read_records`` whole frames by index; ``frame_offsets`` is the table it opened.
 
     ctx: the DeviceBatchContext that decodes (its dictionary, format and window limit apply); stream_tensor: the whole stream, a uint8 CUDA tensor,
     kept alive and unchanged while this object is open. Opening reads and checks the seek table (it waits); a damaged table raises ZstdError."""
@@ -170,6 +228,7 @@ class SeekableStream:
         self.content_size, self.n_frames, self.has_checksums = int(info.contentSize), int(info.nFrames), bool(info.checksumFlag)
         self.max_frame_content = int(info.maxFrameContent)
         self.last_gather_stats = None
+        self._frame_offsets = None
         if scratch_limit is not None:
             self.set_scratch_limit(scratch_limit)
 
@@ -265,6 +324,77 @@ class SeekableStream:
         if rc:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return [out[int(table[k, 2]):int(table[k, 2]) + lengths[k]] for k in range(n)]
+
+    def frame_offsets(self):
+        """the table this object opened: a numpy uint64 array of n_frames + 1 decompressed offsets -- frame (record) f is content bytes [a[f], a[f + 1])"""
+        if self.handle is None:
+            raise ZstdError("the seekable stream is closed")
+        import numpy as np
+        if self._frame_offsets is None:
+            a = np.zeros(self.n_frames + 1, dtype=np.uint64)
+            if self.ctx.L.zhip_seekable_frame_offsets(self.handle, 0, self.n_frames, a.ctypes.data):
+                raise ZstdError("seekable read failed: %s" % _lib.last_error())
+            self._frame_offsets = a
+        return self._frame_offsets.copy()
+
+    def read_records(self, indices, out=None, out_offsets=None, stream=None):
+        """Whole frames by index -- the records of a stream written by seekable_compress_records -- as ONE decode batch: every distinct frame is decoded once,
+        a frame named once straight into its place. indices: a sequence of frame indices, in any order, repeats allowed. Without `out` a new uint8 CUDA tensor
+        holds the records back to back in call order; with `out`, record k goes to out[out_offsets[k]:] (out_offsets None: back to back) -- the destinations
+        must not overlap. Returns a list of views, one per index. Waits for the status; a frame that fails raises ZstdError naming the lowest position that
+        names it, the frame and the error. last_gather_stats holds the call's counts, as after read_ranges."""
+        if self.handle is None:
+            raise ZstdError("the seekable stream is closed")
+        import numpy as np
+        try:
+            idx = np.asarray(indices if len(indices) else np.zeros(0, dtype=np.int64))
+        except Exception:
+            raise ZstdError("indices must be a sequence of frame indices")
+        if idx.ndim != 1 or idx.dtype.kind not in "iu":
+            raise ZstdError("indices must be a sequence of frame indices")
+        n = idx.shape[0]
+        wrong = np.nonzero((idx < 0) | (idx >= self.n_frames))[0]
+        if len(wrong):
+            raise ZstdError("seekable read: position %d names frame %d, the table has %d" % (int(wrong[0]), int(idx[wrong[0]]), self.n_frames))
+        idx32 = np.ascontiguousarray(idx.astype(np.uint32)) if n else np.zeros(1, dtype=np.uint32)
+        if self._frame_offsets is None:
+            self.frame_offsets()
+        d = self._frame_offsets
+        lengths = (d[idx32[:n].astype(np.int64) + 1] - d[idx32[:n].astype(np.int64)]).tolist()
+        if out_offsets is None:
+            offs, at = [], 0
+            for ln in lengths:
+                offs.append(at); at += ln
+            need = at
+        else:
+            if out is None:
+                raise ZstdError("out_offsets needs out")
+            offs = [int(x) for x in out_offsets]
+            if len(offs) != n or any(x < 0 for x in offs):
+                raise ZstdError("out_offsets must hold one non-negative offset per index")
+            need = max([o + ln for o, ln in zip(offs, lengths)] + [0])
+        offs64 = np.array(offs, dtype=np.uint64) if n else np.zeros(1, dtype=np.uint64)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            if out is None:
+                out = torch.empty(need, dtype=torch.uint8, device=self.tensor.device)
+            status = torch.zeros(2 + 2 * n, dtype=torch.int32, device=self.tensor.device)
+        DeviceBatchContext._check(out, torch.uint8)
+        L = self.ctx.L
+        stats = _lib.SeekableGatherStats()
+        rc = L.zhip_seekable_decompress_frames_device(self.ctx.ctx, self.handle, idx32.ctypes.data, n, offs64.ctypes.data, out.data_ptr(), out.numel(), status.data_ptr(),
+                                                      C.byref(stats), s.cuda_stream)
+        if rc:
+            raise ZstdError("seekable read failed: %s" % _lib.last_error())
+        self.last_gather_stats = {k: int(getattr(stats, k)) for k, _ in stats._fields_}
+        err = _lib.Error()
+        rc = L.zhip_ctx_sync(self.ctx.ctx, s.cuda_stream, status.data_ptr(), 1, C.byref(err))
+        if rc == _lib.ERR_ZSTD:
+            bad = int(status[1])
+            raise ZstdError("seekable read: position %d: frame %d: %s" % (bad, int(status[3 + 2 * bad]), _lib.error_name(err.zstdErr)))
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return [out[offs[k]:offs[k] + lengths[k]] for k in range(n)]
 
     def close(self):
         if self.handle is not None:

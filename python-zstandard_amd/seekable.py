@@ -1,7 +1,8 @@
 """The zstd seekable format for host bytes: ``compress`` cuts the data into frames of ``frame_size`` bytes, compresses them as ONE batch on the GPU and
 appends the seek table; ``decompress`` reads any byte range of such a stream by decoding only the frames that cover it, ``decompress_ranges`` many ranges as one batch. The streams are ordinary zstd:
 ``zstd -d`` and ``ZstdDecompressor`` decompress them whole (the table is a skippable frame). Built on ``device.DeviceBatchContext.seekable_compress`` and
-``device.SeekableStream``; the data crosses the link once each way."""
+``device.SeekableStream``; the data crosses the link once each way. ``compress_records`` / ``decompress_records`` do the same for a list of records of any
+sizes: one frame per record, read back by index."""
 import torch
 
 from .backend_hip import ZstdError
@@ -50,6 +51,43 @@ def decompress_ranges(data, ranges, **ctx_kw):
         st = SeekableStream(ctx, _to_device(data))
         try:
             views = st.read_ranges(ranges)
+            if not views:
+                return []
+            host = torch.cat(views).cpu().numpy().tobytes()                 # (the views lie back to back in call order: one copy over the link)
+            out, at = [], 0
+            for v in views:
+                out.append(host[at:at + v.numel()]); at += v.numel()
+            return out
+        finally:
+            st.close()
+    finally:
+        ctx.close()
+
+
+def compress_records(records, level=3, checksum=False, **ctx_kw):
+    """a list of bytes -> a seekable stream (bytes) with ONE frame per record, compressed as one batch; ``decompress_records`` reads records back by index.
+    ctx_kw: what DeviceBatchContext takes. Raises ZstdError."""
+    raws = [bytes(r) for r in records]
+    table, at = [], 0
+    for r in raws:
+        table.append((at, len(r))); at += len(r)
+    ctx = DeviceBatchContext(level=level, **ctx_kw)
+    try:
+        return ctx.seekable_compress_records(_to_device(b"".join(raws)), table, checksum=checksum).cpu().numpy().tobytes()
+    finally:
+        ctx.close()
+
+
+def decompress_records(data, indices, **ctx_kw):
+    """the records (frames) of a seekable stream named by `indices`, in that order, as a list of bytes: ONE decode batch, each distinct frame decoded once.
+    Raises ZstdError as ``decompress`` does, and for an index that is not a frame of the table."""
+    if len(data) == 0:
+        raise ZstdError("not a seekable stream: empty input")
+    ctx = DeviceBatchContext(**ctx_kw)
+    try:
+        st = SeekableStream(ctx, _to_device(data))
+        try:
+            views = st.read_records(indices)
             if not views:
                 return []
             host = torch.cat(views).cpu().numpy().tobytes()                 # (the views lie back to back in call order: one copy over the link)
