@@ -191,6 +191,29 @@ int zhip_decompress_batch_device(zhip_ctx*, const void* d_src, const zhip_segmen
 int zhip_compress_batch_device(zhip_ctx*, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
                                void* d_dst, const zhip_segment* d_dstSegs,
                                uint64_t* d_outSizes, int32_t* d_status, void* stream);
+/* Compression from sequences the CALLER supplies: the match search of zhip_compress_batch_device is skipped, everything behind it -- entropy coding, block and
+ * frame assembly, checksums -- is that call's, with the context's zhip_ctx_set_cparams state (level, parameters, frame flags, format, dictionary) and under the
+ * same stream-order and one-call-sequence-per-context rules. For an external match finder (the frames are what ZSTD_compressSequences writes with explicit block
+ * delimiters for the same list), and for tests that hand the entropy stage exact sequence lists. Sources of ONE block: at most 131 072 bytes (with a dictionary:
+ * at most what the batch call's match kernels take); a larger source gets d_status 40 (Unsupported parameter).
+ * d_seqs: packed sequences of the whole batch, 8 bytes each, little-endian fields
+ *     bits  0..27  offBase      1, 2, 3 = repeat offset 1, 2, 3 (with litLength 0: 2, 3, and "repeat offset 1 minus one"); offset + 3 otherwise
+ *     bits 28..45  litLength    literals copied in front of the match
+ *     bits 46..63  matchLength  the match's full length, 3 or more
+ * in source order; what the sequences of a source do not cover is its last literal run. d_seqSegs[i] = (first, count): source i's list is
+ * d_seqs[first .. first + count). count 0 is a source without matches.
+ * Checked per source, because the entropy stage relies on it: count <= the sequence capacity of a slot (43 704; fewer in a dictionary batch), every matchLength
+ * >= 3, every offBase != 0, litLength + matchLength over the list sum to at most the source's size. A list that fails gets d_status 107 (External sequences are
+ * not valid), size 0, nothing written to its destination; the other sources of the batch are unaffected. Offsets are NOT validated (as in libzstd with
+ * ZSTD_c_validateSequences off): a list whose offsets do not reproduce the source yields a well-formed frame of other content. Whether a raw offset that equals a
+ * repeat offset is coded as the repeat code is the caller's choice; libzstd writes the same bytes for the same codes.
+ * flags: bit 0 clear = the entropy kernel gathers the literals from the source through the sequences (what the flat match kernels leave it); set = the loader
+ * copies them to the context's literal area first (what the lane-serial match kernel leaves). The frames are the same. Other bits: ZHIP_ERR_UNSUPPORTED. */
+int zhip_compress_sequences_device(zhip_ctx*, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
+                                   const uint64_t* d_seqs, const zhip_segment* d_seqSegs,
+                                   void* d_dst, const zhip_segment* d_dstSegs,
+                                   uint64_t* d_outSizes, int32_t* d_status, void* stream, uint32_t flags);
+size_t zhip_ctx_entropy_grid(zhip_ctx*);    /* waves of the entropy kernel resident on the context's device: a batch above it gives every wave several frames (for tests) */
 int zhip_ctx_sync(zhip_ctx*, void* stream, const int32_t* d_status, size_t n, zhip_error* err);
 /* The compress direction writes every frame into a zhip_compress_bound-sized slot; what is handed on (a BufferWithSegments, a payload
  * all-gatherv across GPUs) is the frames back to back. d_offsets[i] = where frame i goes inside d_dense (the caller's exclusive prefix

@@ -3505,3 +3505,52 @@ ZH_DEVFN void ze_trailer_body(const ZhipEncodeArgs& a)
         zh_st32(a.dst + a.dstSegs[2 * (size_t)f] + n - 4, (uint32_t)ze_xxh64(src, (uint32_t)srcSize));
     }
 }
+
+// ------------------------------------------------------------------------------------------ caller-supplied sequences (a LANE per source, in place of a match kernel)
+// zhip_compress_sequences_device: the caller found the matches (an external match finder, a test that aims at the entropy kernel's decisions). Every lane checks its
+// source's list for what the entropy kernel RELIES on -- the list fits the slot, every match length is 3 or more (its code table starts there), every offBase is non-zero
+// (its code is the highest set bit), literal and match lengths sum to at most the source (the literal gather and the last literal run read inside it) -- and copies it
+// to the source's arena slot. Offsets are not looked at beyond that: nothing dereferences them (libzstd does not either with ZSTD_c_validateSequences off).
+// A refused source gets its status HERE and mode 3, which the entropy and trailer kernels pass over: externalSequences_invalid (107) for a bad list, 40 for a source above
+// one block or above the slot. Sources below 7 bytes are stored raw, as after a match kernel (mode 1); parameter errors are the entropy kernel's to report (ze_frame).
+ZH_DEVFN void ze_load_sequences_body(const ZhipEncodeArgs& a, const ZeSeqLoad& in)
+{
+    const uint32_t i = zh_block() * 64 + zh_lane();
+    if (i >= a.count) return;
+    const uint32_t f = a.first + i;
+    ZeMeta m; m.nbSeq = 0; m.litSize = 0; m.mode = 3; m.pad = 0;
+    const uint64_t srcSize64 = a.srcSegs[2 * (size_t)f + 1];
+    const uint64_t first = in.table[2 * (size_t)f], count = in.table[2 * (size_t)f + 1];
+    const uint32_t seqCap = a.arenaLit / 8 - 8, litCap = a.arenaStride - a.arenaLit - 256;
+    const uint64_t* const sq = in.seqs + first;
+    int32_t refuse = 0;
+    if (srcSize64 > ZF_BLOCK_MAX || srcSize64 > litCap) refuse = ZE_PARAM_UNSUPPORTED;
+    else if (count > seqCap) refuse = ZE_SEQ_INVALID;
+    else {
+        uint64_t sum = 0; bool bad = false;
+        for (uint32_t k = 0; k < (uint32_t)count; k++) {
+            const uint64_t q = sq[k];
+            bad |= ZE_SEQ_ML(q) < 3 || ZE_SEQ_OFF(q) == 0;
+            sum += (uint64_t)ZE_SEQ_LL(q) + ZE_SEQ_ML(q);
+        }
+        if (bad || sum > srcSize64) refuse = ZE_SEQ_INVALID;
+    }
+    if (refuse) { a.meta[i] = m; a.status[f] = refuse; a.outSizes[f] = 0; return; }
+    const uint32_t srcSize = (uint32_t)srcSize64;
+    if (srcSize < 7) { m.mode = 1; a.meta[i] = m; return; }
+    uint8_t* const fr = a.arena + (size_t)i * a.arenaStride;
+    uint64_t* const dq = (uint64_t*)(fr + ZE_ARENA_SEQ);
+    const uint8_t* const src = a.src + a.srcSegs[2 * (size_t)f];
+    uint8_t* lp = fr + a.arenaLit;
+    uint32_t pos = 0;
+    for (uint32_t k = 0; k < (uint32_t)count; k++) {
+        const uint64_t q = sq[k];
+        dq[k] = q;
+        const uint32_t ll = ZE_SEQ_LL(q);
+        if (in.copyLits) { for (uint32_t b = 0; b < ll; b++) lp[b] = src[pos + b]; lp += ll; }
+        pos += ll + ZE_SEQ_ML(q);
+    }
+    if (in.copyLits) { for (uint32_t b = pos; b < srcSize; b++) *lp++ = src[b]; m.litSize = (uint32_t)(lp - (fr + a.arenaLit)); }
+    m.nbSeq = (uint32_t)count; m.mode = in.copyLits ? 0u : 4u;
+    a.meta[i] = m;
+}

@@ -7,7 +7,7 @@ enum {
     ZE_OK = 0, ZE_GENERIC = 1, ZE_PREFIX_UNKNOWN = 10, ZE_FRAMEPARAM_UNSUPPORTED = 14, ZE_WINDOW_TOO_LARGE = 16,
     ZE_CORRUPTION = 20, ZE_CHECKSUM_WRONG = 22, ZE_LITERALS_HEADER_WRONG = 24, ZE_DICT_CORRUPTED = 30,
     ZE_DICT_WRONG = 32, ZE_PARAM_UNSUPPORTED = 40, ZE_PARAM_OUTOFBOUND = 42, ZE_TABLELOG_TOO_LARGE = 44, ZE_MAXSYMBOL_TOO_LARGE = 46,
-    ZE_MAXSYMBOL_TOO_SMALL = 48, ZE_MEMORY = 64, ZE_DST_TOO_SMALL = 70, ZE_SRC_SIZE_WRONG = 72
+    ZE_MAXSYMBOL_TOO_SMALL = 48, ZE_MEMORY = 64, ZE_DST_TOO_SMALL = 70, ZE_SRC_SIZE_WRONG = 72, ZE_SEQ_INVALID = 107
 };
 
 #define ZF_MAGIC 0xFD2FB528u
@@ -169,6 +169,17 @@ struct ZeMbBlock { uint32_t end, seqStart, nbSeq, rep0, rep1, pad[3]; };
 #define ZE_E1_LANES_DICT 32             // small uniform sources, one dependent-probe chain each: frames in flight beat divergence (r02i: 8 -> 14.2, 16 -> 17.8, 32 -> 20.5, 64 -> 20.0 GB/s)
 #endif
 #define ZE_E2_STRIDE ((size_t)ZF_BLOCK_MAX + 256)              // E2 needs one block's literals per resident wave (gathered from the sequences)
+// Sequences the CALLER supplies (zhip_compress_sequences_device): the loader kernel (ze_load_sequences_body, a lane per source) stands where the match kernels
+// stand and leaves what they leave -- packed sequences in the source's arena slot and its ZeMeta -- so the entropy and trailer kernels run unchanged behind it.
+// seqs: packed sequences of the whole batch; table: n x (first, count) into seqs; copyLits: 0 = sequences only (mode 4: the entropy kernel gathers the literals),
+// 1 = the literals are copied to the slot's literal area too (mode 0: what the lane-serial match kernel leaves)
+// the arena slot of a dictionary batch whose sources are at most `lim` bytes (host side: zhip_lib.hip's enc_dict_slots, and the emulator harnesses that mirror it)
+static inline void ze_dict_slot_shape(uint32_t lim, uint32_t* arenaLit, uint32_t* arenaStride)
+{
+    *arenaLit = (8u * (lim / 3 + 16) + 15) & ~15u;
+    *arenaStride = (*arenaLit + lim + 256 + 15) & ~15u;
+}
+struct ZeSeqLoad { const uint64_t* seqs; const uint64_t* table; uint32_t copyLits; };
 
 // FSE encoding table: per symbol, its cells in table order
 struct ZeCTab {

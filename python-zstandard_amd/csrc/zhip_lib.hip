@@ -117,6 +117,7 @@ ZH_GLOBAL __launch_bounds__(64) void zhip_encode_split_kernel(ZhipEncodeArgs a) 
     ze_split_body(a, L);
 }
 ZH_GLOBAL __launch_bounds__(64) void zhip_encode_trailer_kernel(ZhipEncodeArgs a) { ze_trailer_body(a); }      // EX: checksum trailers, a lane per frame, after E2
+ZH_GLOBAL __launch_bounds__(64) void zhip_encode_load_sequences_kernel(ZhipEncodeArgs a, ZeSeqLoad in) { ze_load_sequences_body(a, in); }      // zhip_compress_sequences_device: in place of the match kernels
 ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_flat_kernel(ZhipEncodeArgs a) { ze_match_flat_body<2>(a); }
 // four probes per trip: chunks small enough to be bound by a source's serial chain rather than by the memory system (ze_dfast_flat_np)
 ZH_GLOBAL __launch_bounds__(64) void zhip_encode_match_flat4_kernel(ZhipEncodeArgs a) { ze_match_flat_body<4>(a); }
@@ -211,6 +212,7 @@ extern "C" const char* zhip_error_name(int code)
     case ZE_MEMORY: return "Allocation error : not enough memory";
     case ZE_DST_TOO_SMALL: return "Destination buffer is too small";
     case ZE_SRC_SIZE_WRONG: return "Src size is incorrect";
+    case ZE_SEQ_INVALID: return "External sequences are not valid";
     default: return "Unspecified error code";
     }
 }
@@ -1000,20 +1002,12 @@ static void launch_flat(int probes, size_t cnt, hipStream_t stream, const ZhipEn
     else if (probes == 3) hipLaunchKernelGGL(zhip_encode_match_flat3_kernel, g, b, 0, stream, a);
     else hipLaunchKernelGGL(zhip_encode_match_flat_kernel, g, b, 0, stream, a);
 }
-extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
-                                          void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
-                                          int32_t* d_status, void* streamv)
+// ---- what zhip_compress_batch_device and zhip_compress_sequences_device share: the launch arguments every encode kernel reads from the context's zhip_ctx_set_cparams
+// state, the slot shape of dictionary batches, and the entropy + trailer launches behind whatever left the sequences
+static void enc_args_init(zhip_ctx* c, ZhipEncodeArgs& a, const void* d_src, const zhip_segment* d_srcSegs, size_t n, void* d_dst, const zhip_segment* d_dstSegs,
+                          uint64_t* d_outSizes, int32_t* d_status, uint8_t* cbase)
 {
-    if (!c) return ZHIP_ERR_UNSUPPORTED;
-    if (n == 0) return 0;
-    if (n > 0x7FFFFFFFu) { g_lastError = "too many frames in one launch"; return ZHIP_ERR_UNSUPPORTED; }
-    hipStream_t stream = (hipStream_t)streamv;
-    size_t maxBlocks = (size_t)c->numCU * (size_t)c->encBlocksPerCU;
-    uint32_t grid = (uint32_t)(n < maxBlocks ? n : maxBlocks);
-    if (c->counter.reserve(64 * 8)) return g_reserveRc;
-    uint8_t* const cbase = (uint8_t*)c->counter.p;
-    HIP_TRY(hipMemsetAsync(cbase + 8, 0, 4, stream));
-    ZhipEncodeArgs a; memset(&a, 0, sizeof a);
+    memset(&a, 0, sizeof a);
     a.src = (const uint8_t*)d_src; a.srcSegs = (const uint64_t*)d_srcSegs; a.dst = (uint8_t*)d_dst;
     a.dstSegs = (const uint64_t*)d_dstSegs; a.outSizes = d_outSizes; a.status = d_status;
     a.workspace = (uint8_t*)c->encWorkspace.p; a.counter = (uint32_t*)(cbase + 8); a.n = (uint32_t)n;
@@ -1027,6 +1021,48 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
         a.cdictHashLong = (const uint32_t*)c->cdictTables.p;
         a.cdictHashSmall = (const uint32_t*)c->cdictTables.p + cells;
     }
+}
+// dictionary batches: every source is below the attach cutoff, so the per-lane tables are the dictionary row's shrunk to that
+// size (ze_dict_cparams) and a frame's sequences + literals fit a slot of the cutoff's size -- a tenth of the 128 KiB shapes,
+// which is what lets a whole 262 144-document batch be one chunk
+// (round 4: where the caller says how large its sources are -- the host API knows, a device-API caller can tell with
+// zhip_ctx_set_size_hint -- the slots are sized for THAT: 4 KiB documents need 48 KiB of tables, not the cutoff's 192, and 262 144 of
+// them are one launch instead of two. A source above the hint is the generic kernel's: correct, slower)
+// Sets a.slotSrcMax, a.arenaLit and a.arenaStride; returns the table bytes per source.
+static uint32_t enc_dict_slots(const zhip_ctx* c, size_t sizeHint, ZhipEncodeArgs& a)
+{
+    size_t lim = c->cdictAttachMax;
+    if (sizeHint && sizeHint < lim) { lim = 1024; while (lim < sizeHint) lim <<= 1; }
+    if (lim < c->cdictAttachMax) a.slotSrcMax = (uint32_t)lim; else lim = c->cdictAttachMax;
+    int w = 10; while (((size_t)1 << w) < lim) w++;
+    const int h = c->cdictHlog > w + 1 ? w + 1 : c->cdictHlog, cl = c->cdictClog > w ? w : c->cdictClog;
+    uint32_t stride = (4u << h) + (c->cdictStrat == 2 ? (4u << cl) : 0u);
+    if (stride < (4u << 10)) stride = 4u << 10;
+    ze_dict_slot_shape((uint32_t)lim, &a.arenaLit, &a.arenaStride);
+    return stride;
+}
+// E2 over the chunk, g2 waves, and EX behind it for checksummed frames (timed with E2)
+static void launch_entropy(const zhip_ctx* c, ZhipEncodeArgs& a, uint32_t g2, size_t cnt, hipStream_t stream)
+{
+    a.xxLater = ZHIP_TRAILER_LATER && a.checksumFlag ? 1u : 0u;
+    hipLaunchKernelGGL(zhip_encode_entropy_kernel, dim3(g2), dim3(64), 0, stream, a);
+    if (a.xxLater) { const size_t w = (cnt + 63) / 64, gm = (size_t)c->numCU * 8; hipLaunchKernelGGL(zhip_encode_trailer_kernel, dim3((uint32_t)(w < gm ? w : gm)), dim3(64), 0, stream, a); }      // EX
+    a.xxLater = 0;
+}
+extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
+                                          void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
+                                          int32_t* d_status, void* streamv)
+{
+    if (!c) return ZHIP_ERR_UNSUPPORTED;
+    if (n == 0) return 0;
+    if (n > 0x7FFFFFFFu) { g_lastError = "too many frames in one launch"; return ZHIP_ERR_UNSUPPORTED; }
+    hipStream_t stream = (hipStream_t)streamv;
+    size_t maxBlocks = (size_t)c->numCU * (size_t)c->encBlocksPerCU;
+    uint32_t grid = (uint32_t)(n < maxBlocks ? n : maxBlocks);
+    if (c->counter.reserve(64 * 8)) return g_reserveRc;
+    uint8_t* const cbase = (uint8_t*)c->counter.p;
+    HIP_TRY(hipMemsetAsync(cbase + 8, 0, 4, stream));
+    ZhipEncodeArgs a; enc_args_init(c, a, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, cbase);
     {
         // two kernels: E1 searches with one LANE per frame (frames in flight hide the probe latency), E2 entropy-codes with one
         // wave per frame. Frames are processed in chunks so that the per-frame sequence/literal arena stays bounded.
@@ -1068,21 +1104,7 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
         if (stride > (12u << 17)) stride = 12u << 17;                  // larger tables: the frame is refused loudly by the match kernels
         a.arenaStride = (uint32_t)ZE_ARENA_STRIDE; a.arenaLit = ZE_ARENA_LIT;
         if (c->hasCDict) {
-            // dictionary batches: every source is below the attach cutoff, so the per-lane tables are the dictionary row's shrunk to that
-            // size (ze_dict_cparams) and a frame's sequences + literals fit a slot of the cutoff's size -- a tenth of the 128 KiB shapes,
-            // which is what lets a whole 262 144-document batch be one chunk
-            // (round 4: where the caller says how large its sources are -- the host API knows, a device-API caller can tell with
-            // zhip_ctx_set_size_hint -- the slots are sized for THAT: 4 KiB documents need 48 KiB of tables, not the cutoff's 192, and 262 144 of
-            // them are one launch instead of two. A source above the hint is the generic kernel's: correct, slower)
-            size_t lim = c->cdictAttachMax;
-            if (sizeHint && sizeHint < lim) { lim = 1024; while (lim < sizeHint) lim <<= 1; }
-            if (lim < c->cdictAttachMax) a.slotSrcMax = (uint32_t)lim; else lim = c->cdictAttachMax;
-            int w = 10; while (((size_t)1 << w) < lim) w++;
-            const int h = c->cdictHlog > w + 1 ? w + 1 : c->cdictHlog, cl = c->cdictClog > w ? w : c->cdictClog;
-            stride = (4u << h) + (c->cdictStrat == 2 ? (4u << cl) : 0u);
-            if (stride < (4u << 10)) stride = 4u << 10;
-            a.arenaLit = (8u * ((uint32_t)lim / 3 + 16) + 15) & ~15u;
-            a.arenaStride = (a.arenaLit + (uint32_t)lim + 256 + 15) & ~15u;
+            stride = enc_dict_slots(c, sizeHint, a);
         }
         a.tableStride = stride;
         // double-fast without a dictionary: the flat match kernel (one lane per frame, the whole chunk in flight, tables zeroed by a
@@ -1352,10 +1374,7 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
             if (greedy) hipLaunchKernelGGL(zhip_encode_match_greedy_kernel, dim3(g1), dim3(64), 0, stream, a);      // (takes the chunk's fast / double-fast sources, tiny ones and errors as the kernel below does)
             else hipLaunchKernelGGL(zhip_encode_match_kernel, dim3(g1), dim3(64), 0, stream, a);
             if (tm) { HIP_TRY(hipEventRecord(ev[3], stream)); HIP_TRY(hipEventRecord(ev[4], stream)); }
-            a.xxLater = ZHIP_TRAILER_LATER && a.checksumFlag ? 1u : 0u;
-            hipLaunchKernelGGL(zhip_encode_entropy_kernel, dim3(g2), dim3(64), 0, stream, a);
-            if (a.xxLater) { const size_t w = (cnt + 63) / 64, gm = (size_t)c->numCU * 8; hipLaunchKernelGGL(zhip_encode_trailer_kernel, dim3((uint32_t)(w < gm ? w : gm)), dim3(64), 0, stream, a); }      // EX (timed with E2)
-            a.xxLater = 0;
+            launch_entropy(c, a, g2, cnt, stream);
             if (tm) HIP_TRY(hipEventRecord(ev[5], stream));
             if (mbc) {      // this chunk's sources of several blocks: the generic kernel over the list the flat kernel just made (it reads the chunk's arenas)
                 ZhipEncodeArgs b = a;
@@ -1403,6 +1422,50 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
     if (c->timer[1].pending.size() > 4096) { HIP_TRY(hipStreamSynchronize(stream)); drain_timer(c->timer[1]); }
     return 0;
 }
+
+// Compression from the CALLER's sequences: zhip_compress_batch_device with the match search replaced by a loader (ze_load_sequences_body, a lane per source: checks the
+// list, fills the source's arena slot and ZeMeta as a match kernel would) -- the entropy kernel and the trailer kernel behind it are the batch call's, launched the same way.
+// Sources of one block only; the arena slots are the full one-block shape (dictionary batches: the dictionary shape, enc_dict_slots), whatever the level's strategy.
+extern "C" int zhip_compress_sequences_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
+                                              const uint64_t* d_seqs, const zhip_segment* d_seqSegs,
+                                              void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
+                                              int32_t* d_status, void* streamv, uint32_t flags)
+{
+    if (!c) return ZHIP_ERR_UNSUPPORTED;
+    if (flags & ~1u) { g_lastError = "zhip_compress_sequences_device: unknown flags"; return ZHIP_ERR_UNSUPPORTED; }
+    if (n == 0) return 0;
+    if (n > 0x7FFFFFFFu) { g_lastError = "too many frames in one launch"; return ZHIP_ERR_UNSUPPORTED; }
+    hipStream_t stream = (hipStream_t)streamv;
+    if (c->counter.reserve(64 * 8)) return g_reserveRc;
+    uint8_t* const cbase = (uint8_t*)c->counter.p;
+    ZhipEncodeArgs a; enc_args_init(c, a, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, cbase);
+    a.arenaStride = (uint32_t)ZE_ARENA_STRIDE; a.arenaLit = ZE_ARENA_LIT;
+    if (c->hasCDict) (void)enc_dict_slots(c, c->srcMaxHint ? c->srcMaxHint : c->itemHint, a);
+    const size_t chunkMax = c->hasCDict ? 262144 : 16384;                    // (7.4 GiB of one-block slots)
+    size_t chunk = n < chunkMax ? n : chunkMax;
+    const size_t g2max = (size_t)c->numCU * (size_t)c->e2PerCU;
+    // no room for the arena of a whole chunk: half as many sources per launch, down to 64, before the call fails (the slots are full one-block slots whatever the sources' sizes)
+    while (c->encArena.reserve(chunk * (size_t)a.arenaStride)) {
+        if (g_reserveRc != ZHIP_ERR_NO_MEMORY || chunk <= 64) return g_reserveRc;
+        chunk = (chunk + 1) / 2;
+    }
+    const uint32_t g2 = (uint32_t)(chunk < g2max ? chunk : g2max);
+    if (c->encMeta.reserve(chunk * sizeof(ZeMeta)) || c->encWorkspace.reserve((size_t)g2 * ZE_E2_STRIDE + ZHIP_ENC_STRIDE)) return g_reserveRc;
+    a.workspace = (uint8_t*)c->encWorkspace.p; a.meta = (ZeMeta*)c->encMeta.p; a.arena = (uint8_t*)c->encArena.p;
+    a.idle = cbase + 256;
+    ZeSeqLoad in; in.seqs = d_seqs; in.table = (const uint64_t*)d_seqSegs; in.copyLits = flags & 1u;
+    for (size_t first = 0; first < n; first += chunk) {
+        const size_t cnt = n - first < chunk ? n - first : chunk;
+        a.first = (uint32_t)first; a.count = (uint32_t)cnt;
+        HIP_TRY(hipMemsetAsync(cbase + 8, 0, 8, stream));
+        hipLaunchKernelGGL(zhip_encode_load_sequences_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, stream, a, in);
+        launch_entropy(c, a, g2, cnt, stream);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+// waves the entropy kernel holds resident on this device (the occupancy query of zhip_ctx_create): batches above it take several frames per wave
+extern "C" size_t zhip_ctx_entropy_grid(zhip_ctx* c) { return c ? (size_t)c->numCU * (size_t)c->e2PerCU : 0; }
 
 extern "C" int zhip_ctx_sync(zhip_ctx* c, void* streamv, const int32_t* d_status, size_t n, zhip_error* err)
 {

@@ -97,6 +97,25 @@ class DeviceBatchContext:
         if rc:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
 
+    def compress_sequences(self, src, src_segs, seqs, seq_segs, dst, dst_segs, out_sizes, status, copy_literals=False, stream=None):
+        """compress() from the caller's sequences instead of a match search (an external match finder; tests of the entropy stage). seqs: int64 CUDA tensor of
+        packed sequences -- offBase | litLength << 28 | matchLength << 46 --, seq_segs: int64 [n,2] (first, count) per source. Sources of one block. A list the
+        loader refuses gets status 107. copy_literals: the loader copies the literals out (the lane-serial match kernel's hand-over) instead of leaving
+        the gather to the entropy kernel; the frames are the same."""
+        self._ensure_cparams()
+        self._check(src, torch.uint8); self._check(dst, torch.uint8); self._check(seqs, torch.int64); self._check(seq_segs, torch.int64)
+        n = src_segs.shape[0]
+        assert seq_segs.shape[0] == n
+        s = stream if stream is not None else torch.cuda.current_stream()
+        rc = self.L.zhip_compress_sequences_device(self.ctx, src.data_ptr(), src_segs.data_ptr(), n, seqs.data_ptr(), seq_segs.data_ptr(), dst.data_ptr(),
+                                                   dst_segs.data_ptr(), out_sizes.data_ptr(), status.data_ptr(), s.cuda_stream, 1 if copy_literals else 0)
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+
+    def entropy_grid(self):
+        """waves of the entropy kernel resident on this device"""
+        return int(self.L.zhip_ctx_entropy_grid(self.ctx))
+
     def seekable_compress(self, src, frame_size=131072, checksum=False, stream=None):
         """src (a uint8 CUDA tensor) as ONE zstd seekable stream: frames of frame_size bytes of it, compressed as a batch with this context's
         parameters, back to back, then the seek table (checksum: with the low 32 bits of XXH64 of every frame's content). Returns a uint8 CUDA

@@ -3,3 +3,5 @@
 set -e
 cd "$(dirname "$0")"
 g++ -O1 -g -fPIC -shared -std=c++17 -I. -Wall -Wno-unused-function -Wno-unused-variable -o libzhip_emu.so zhemu.cpp emu_kernels.cpp
+# tests/emu/libzhip_emu_entropy_sequences.so : the loader, the entropy kernel and the trailer kernel driven by explicit sequences (a library of its own: the kernel headers define their functions)
+g++ -O1 -g -fPIC -shared -std=c++17 -I. -Wall -Wno-unused-function -Wno-unused-variable -o libzhip_emu_entropy_sequences.so zhemu.cpp emu_entropy_sequences.cpp

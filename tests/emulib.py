@@ -204,3 +204,70 @@ def _emu_set_check_later(self, v):
 
 
 Emu.set_check_later = _emu_set_check_later
+
+
+# ---- the entropy kernel driven by explicit sequences (tests/emu/emu_entropy_sequences.cpp: a library of its own beside libzhip_emu.so, built by the same build.sh)
+SEQ_SO = os.path.join(_DIR, "libzhip_emu_entropy_sequences.so")
+_PARAM_ORDER = ("window_log", "chain_log", "hash_log", "search_log", "min_match", "target_length", "strategy")
+
+
+def _seq_lib(self):
+    lib = getattr(self, "_seqlib", None)
+    if lib is None:
+        if not os.path.exists(SEQ_SO):
+            build()
+        lib = self._seqlib = C.CDLL(SEQ_SO)
+        lib.emu_seq_set_cdict.restype = C.c_int
+        lib.emu_seq_set_cdict.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int]
+        lib.emu_seq_dict_rep.restype = C.c_uint32; lib.emu_seq_dict_rep.argtypes = [C.c_int]
+        lib.emu_seq_capacity.restype = C.c_uint32
+        lib.emu_entropy_sequences.restype = C.c_int
+        lib.emu_entropy_sequences.argtypes = [C.c_void_p] * 9 + [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+    return lib
+
+
+def _emu_seq_set_dict(self, dict_data, level=3, params=None, raw_dict=False):
+    """digests the compression dictionary of the following entropy_sequences calls (None: no dictionary) with the product's kernels under emulation; returns
+    the repeat offsets frames then start from (1, 4, 8 without a dictionary or with a raw-content one)"""
+    lib = _seq_lib(self)
+    ov = np.array([(params or {}).get(k, 0) for k in _PARAM_ORDER], dtype=np.int32)
+    if dict_data:
+        d = np.frombuffer(dict_data, dtype=np.uint8).copy()
+        st = lib.emu_seq_set_cdict(d.ctypes.data, len(d), level, ov.ctypes.data, 1 if raw_dict else 0)
+        if st:
+            raise RuntimeError("cdict error %d" % st)
+    else:
+        lib.emu_seq_set_cdict(None, 0, level, ov.ctypes.data, 0)
+    return tuple(int(lib.emu_seq_dict_rep(i)) for i in range(3))
+
+
+def _emu_entropy_sequences(self, sources, packed, level=3, flags=5, load_flags=0, params=None, dict_data=None, raw_dict=False, magicless=False, n_blocks=3, chunk=0):
+    """the loader, the entropy kernel and the trailer kernel under emulation, as zhip_compress_sequences_device launches them. sources: bytes per item; packed:
+    a uint64 array of packed sequences per item; flags: 1 content size, 2 checksum, 4 dictionary ID; load_flags bit 0: the loader copies the literals.
+    Returns (frames, statuses). Destination slots are zhip_compress_bound-sized, back to back."""
+    lib = _seq_lib(self)
+    ov = np.array([(params or {}).get(k, 0) for k in _PARAM_ORDER], dtype=np.int32)
+    _emu_seq_set_dict(self, dict_data, level, params, raw_dict)
+    n = len(sources)
+    lens = np.array([len(r) for r in sources], dtype=np.uint64)
+    caps = lens + (lens >> np.uint64(8)) + np.where(lens < (128 << 10), (np.uint64(128 << 10) - np.minimum(lens, np.uint64(128 << 10))) >> np.uint64(11), 0).astype(np.uint64)
+    ssegs = np.zeros((n, 2), dtype=np.uint64); ssegs[:, 1] = lens; ssegs[1:, 0] = np.cumsum(lens)[:-1]
+    dsegs = np.zeros((n, 2), dtype=np.uint64); dsegs[:, 1] = caps; dsegs[1:, 0] = np.cumsum(caps)[:-1]
+    counts = np.array([len(q) for q in packed], dtype=np.uint64)
+    qsegs = np.zeros((n, 2), dtype=np.uint64); qsegs[:, 1] = counts; qsegs[1:, 0] = np.cumsum(counts)[:-1]
+    src = np.frombuffer(b"".join(sources), dtype=np.uint8).copy() if lens.sum() else np.zeros(1, dtype=np.uint8)
+    seqs = np.concatenate([np.asarray(q, dtype=np.uint64) for q in packed] + [np.zeros(1, dtype=np.uint64)])
+    dst = np.zeros(int(caps.sum()) + 1, dtype=np.uint8)
+    sizes = np.zeros(n, dtype=np.uint64); st = np.full(n, -1, dtype=np.int32)
+    lib.emu_entropy_sequences(src.ctypes.data, ssegs.ctypes.data, n, seqs.ctypes.data, qsegs.ctypes.data, dst.ctypes.data, dsegs.ctypes.data, sizes.ctypes.data, st.ctypes.data,
+                              level, ov.ctypes.data, flags | (8 if magicless else 0), load_flags, n_blocks, chunk)
+    return [dst[int(dsegs[i, 0]): int(dsegs[i, 0] + sizes[i])].tobytes() for i in range(n)], st.tolist()
+
+
+def _emu_seq_capacity(self):
+    return int(_seq_lib(self).emu_seq_capacity())
+
+
+Emu.entropy_sequences = _emu_entropy_sequences
+Emu.seq_set_dict = _emu_seq_set_dict
+Emu.seq_capacity = _emu_seq_capacity

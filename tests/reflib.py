@@ -35,6 +35,13 @@ class _CMem(C.Structure):         # ZSTD_customMem: all NULL = the default alloc
     _fields_ = [("customAlloc", C.c_void_p), ("customFree", C.c_void_p), ("opaque", C.c_void_p)]
 
 
+class _Sequence(C.Structure):   # ZSTD_Sequence (zstd.h)
+    _fields_ = [("offset", C.c_uint), ("litLength", C.c_uint), ("matchLength", C.c_uint), ("rep", C.c_uint)]
+
+
+# ZSTD_c_blockDelimiters, ZSTD_c_validateSequences, ZSTD_c_searchForExternalRepcodes (experimental parameters 11, 12 and 19 of zstd.h)
+_P_BLOCKDELIM, _P_VALIDATESEQ, _P_EXTREPSEARCH = 1008, 1009, 1016
+
 REF_KIND = None     # which libzstd 1.5.7 the checker is: "reference build" (oracle/_ref, compiled from /root/reference/zstd/zstd.c) or "image copy"
 
 
@@ -105,6 +112,11 @@ class RefZstd:
         ]:
             f = getattr(L, name)
             f.restype, f.argtypes = res, args
+        # (bound apart and on first use: a checker library without it must not take the other suites down -- compress_sequences raises)
+        self._compress_sequences = getattr(L, "ZSTD_compressSequences", None)
+        if self._compress_sequences is not None:
+            self._compress_sequences.restype = C.c_size_t
+            self._compress_sequences.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(_Sequence), C.c_size_t, C.c_char_p, C.c_size_t]
         assert L.ZSTD_versionNumber() == 10507, "oracle/_ref must be libzstd 1.5.7"
         self._tls = threading.local()
 
@@ -143,6 +155,41 @@ class RefZstd:
                 raise RuntimeError(L.ZSTD_getErrorName(r).decode())
             assert r == 0
             return dst.raw[: out.pos]
+        finally:
+            L.ZSTD_freeCCtx(ctx)
+
+    def compress_sequences(self, data, seqs, tail, level=3, flags=DEFAULT_FLAGS, dict_data=None, rep_search=True, dict_type=0, **params):
+        """one frame of ONE block from explicit sequences -- ZSTD_compressSequences with explicit block delimiters, ZSTD_c_validateSequences off --:
+        seqs = [(litLength, matchLength, rawOffset)], tail = the last literals' count. rep_search: ZSTD_c_searchForExternalRepcodes enabled (every raw
+        offset that equals a repeat offset becomes that repeat code) or disabled (every offset is coded as offset + 3). Raises RuntimeError with
+        libzstd's message where it refuses the list. A checker library without the entry point is an error."""
+        L = self.lib
+        if self._compress_sequences is None:
+            raise RuntimeError("the checker library does not export ZSTD_compressSequences")
+        data = bytes(data)
+        ctx = L.ZSTD_createCCtx()
+        try:
+            for pid, v in [(_P_LEVEL, level), (_P_CONTENTSIZE, 1 if flags & F_CONTENTSIZE else 0), (_P_CHECKSUM, 1 if flags & F_CHECKSUM else 0),
+                           (_P_DICTID, 1 if flags & F_DICTID else 0)] + [(self.PARAM_IDS[k], v) for k, v in params.items()] + [
+                          (_P_BLOCKDELIM, 1), (_P_VALIDATESEQ, 0), (_P_EXTREPSEARCH, 1 if rep_search else 2)]:
+                r = L.ZSTD_CCtx_setParameter(ctx, pid, v)          # (returns the value it set for some parameters: ZSTD_isError is the test)
+                if L.ZSTD_isError(r):
+                    raise RuntimeError("parameter %d: %s" % (pid, L.ZSTD_getErrorName(r).decode()))
+            if dict_data:
+                r = L.ZSTD_CCtx_loadDictionary_advanced(ctx, dict_data, len(dict_data), 1, dict_type)     # ZSTD_dlm_byRef
+                if L.ZSTD_isError(r):
+                    raise RuntimeError(L.ZSTD_getErrorName(r).decode())
+            n = len(seqs)
+            arr = (_Sequence * (n + 1))()
+            for i, (ll, ml, off) in enumerate(seqs):
+                arr[i].offset, arr[i].litLength, arr[i].matchLength = off, ll, ml
+            arr[n].litLength = tail                                # the block delimiter: offset 0, matchLength 0, the last literals
+            cap = L.ZSTD_compressBound(len(data))
+            dst = C.create_string_buffer(max(cap, 1))
+            r = self._compress_sequences(ctx, dst, cap, arr, n + 1, data, len(data))
+            if L.ZSTD_isError(r):
+                raise RuntimeError(L.ZSTD_getErrorName(r).decode())
+            return dst.raw[:r]
         finally:
             L.ZSTD_freeCCtx(ctx)
 

@@ -107,6 +107,31 @@ def resolved(blocks, start_reps=(1, 4, 8)):
     return res
 
 
+def canonical(blocks, start_reps=(1, 4, 8)):
+    """`blocks` with every offset value rewritten to the form libzstd's ZSTD_c_searchForExternalRepcodes leaves: walking the repeat-offset history (it starts
+    at the format's 1, 4, 8, or at the dictionary's), an offset that IS one of the three history entries is written as that entry's repeat code -- with
+    literals in front, codes 1, 2, 3 name entries one, two, three; with NO literals the codes shift, 1 and 2 name entries two and three, and 3 names "entry
+    one minus one" --, the first that applies in the order entry one (only with literals), two, three, one-minus-one (only without); any other offset is
+    offset + 3. The sequences resolve to the same offsets before and after (resolved())."""
+    reps, out = tuple(start_reps), []
+    for b, res in zip(blocks, resolved(blocks, start_reps)):
+        if res is None: out.append(b); continue
+        q = []
+        for ll, ml, off in res:
+            names = ([(1, reps[0])] if ll else []) + [(2 if ll else 1, reps[1]), (3 if ll else 2, reps[2])] + ([] if ll else [(3, reps[0] - 1)])
+            code = next((c for c, v in names if v == off), off + 3)
+            back, reps = next_reps(reps, ll, code)
+            assert back == off
+            q.append((ll, ml, code))
+        out.append(("seq", b[1], q) + tuple(b[3:]))
+    return out
+
+
+def plain(blocks, start_reps=(1, 4, 8)):
+    """`blocks` with every offset written as offset + 3, none as a repeat code (libzstd with ZSTD_c_searchForExternalRepcodes disabled)"""
+    return [b if res is None else ("seq", b[1], [(ll, ml, off + 3) for ll, ml, off in res]) + tuple(b[3:]) for b, res in zip(blocks, resolved(blocks, start_reps))]
+
+
 def census(blocks, k=K3, dict_size=0, start_reps=(1, 4, 8)):
     """the set of named events the VALID frame `blocks` reaches in zp_exec_block, block by block (each compressed block starts with an empty
     history, at its own output position)"""
