@@ -213,6 +213,26 @@ int zhip_compress_sequences_device(zhip_ctx*, const void* d_src, const zhip_segm
                                    const uint64_t* d_seqs, const zhip_segment* d_seqSegs,
                                    void* d_dst, const zhip_segment* d_dstSegs,
                                    uint64_t* d_outSizes, int32_t* d_status, void* stream, uint32_t flags);
+/* Which match finder zhip_compress_batch_device runs -- and with it zhip_seekable_compress_device and zhip_seekable_compress_records_device, which call it. Host state
+ * only, never waits; the default is ZHIP_FINDER_LIBZSTD. Not read by zhip_compress_sequences_device or by the host-buffer API (zhip_compress_batch), whose contract is
+ * libzstd's bytes.
+ *   ZHIP_FINDER_LIBZSTD  the searches that keep libzstd's table contents: frames byte for byte libzstd's.
+ *   ZHIP_FINDER_WAVE     one wave per source, a hash table of positions in LDS, 64 positions probed per trip (zhip_encode_wave.hpp), launched once per chunk in place of
+ *                        every other match kernel. The frames are valid zstd that every zstd decoder reads; they are NOT libzstd's bytes: a different parse from a
+ *                        4 096-cell table, measured 7-8 % larger than libzstd's at level 1 and 17-19 % larger at level 3 on 128 KiB sources, -1 % and +10 % on 4 KiB documents
+ *                        (what it buys is time: 1.5-1.9 x at 16 384 x 128 KiB, 10 x and more on batches of a thousand sources and fewer).
+ *                        They are deterministic: a pure function of the source and the context's parameters, the same on every run and device. (The ZHIP_WAVE_HLOG
+ *                        environment variable, a measurement aid of tests/tools/wave_finder_rate.py, changes the table size and with it the bytes: a process that sets
+ *                        it has given that up.)
+ *                        The level still governs everything behind the search (table modes, raw literals at negative levels, frame flags, format, checksum).
+ *                        Scope: sources of one block (<= 131 072 bytes), no dictionary, a level or parameters whose row for 16 385 ... 131 072-byte sources is fast or
+ *                        double-fast (levels <= 4, negative levels, explicit strategy 1 / 2). A context with a dictionary, or outside those levels, makes the compress
+ *                        call return ZHIP_ERR_UNSUPPORTED with a zhip_last_error() text that names the finder. A source of several blocks gets d_status 40 at its own
+ *                        index and its neighbours compress; so does a source the row of its own size class does not serve (level 4 at 16 384 bytes and below, a window
+ *                        that does not cover the source). Slot rules (zhip_compress_bound, d_status 70) are unchanged.
+ * An unknown value: ZHIP_ERR_UNSUPPORTED, the finder stays what it was. */
+enum { ZHIP_FINDER_LIBZSTD = 0, ZHIP_FINDER_WAVE = 1 };
+int zhip_ctx_set_match_finder(zhip_ctx*, int finder);
 size_t zhip_ctx_entropy_grid(zhip_ctx*);    /* waves of the entropy kernel resident on the context's device: a batch above it gives every wave several frames (for tests) */
 int zhip_ctx_sync(zhip_ctx*, void* stream, const int32_t* d_status, size_t n, zhip_error* err);
 /* The compress direction writes every frame into a zhip_compress_bound-sized slot; what is handed on (a BufferWithSegments, a payload
@@ -333,7 +353,8 @@ int  zhip_seekable_decompress_frames_device(zhip_ctx*, zhip_seekable*, const uin
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,
  * 4 K3, 5 / 6 the lane-serial match kernel (the greedy strategy's zhip_encode_match_greedy_kernel where that runs in its place) and the entropy kernel, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,
  * 8 the flat match kernel -- the match stage of a chunk whichever of its forms ran: the double-fast search's and, since the fast strategy has a flat search of its own
- * (levels 1, 2 and negative levels without a dictionary, sources of one block), that one's; the LDS-source kernels of small batches too --, 9 "zhip_decode_pipeline_span": not a kernel, a chunk's decode pipeline from K1's start to K3's end (what the overlapping kernels cost together). */
+ * (levels 1, 2 and negative levels without a dictionary, sources of one block), that one's; the LDS-source kernels of small batches too --, 9 "zhip_decode_pipeline_span": not a kernel, a chunk's decode pipeline from K1's start to K3's end (what the overlapping kernels cost together),
+ * 10 the wave match kernel (ZHIP_FINDER_WAVE: once per chunk, with 5 and 8 at zero launches). */
 const char* zhip_kernel_name(int k);
 int         zhip_ctx_kernel_time(zhip_ctx*, int direction, double* avgMs, uint64_t* launches);
 /* how many frames of the context's last zhip_decompress_batch_device call the phase-split kernels (K1 -> K2 -> K3) handed to the generic kernel: frames of several

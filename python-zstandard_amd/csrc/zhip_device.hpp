@@ -56,6 +56,7 @@ ZH_DEV void zh_atomic_or(uint32_t* p, uint32_t v) { atomicOr(p, v); }
 ZH_DEV void zh_lds_atomic_or(uint32_t* p, uint32_t v) { atomicOr(p, v); }
 ZH_DEV void zh_lds_atomic_inc(uint32_t* p) { atomicAdd(p, 1u); }
 ZH_DEV uint32_t zh_lds_atomic_add(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
+ZH_DEV void zh_lds_atomic_max(uint32_t* p, uint32_t v) { atomicMax(p, v); }      // (the wave match finder's table cells, zhip_encode_wave.hpp; the emulator's form is in tests/emu/zhip_device_emu_wave.hpp)
 ZH_DEV uint32_t zh_wave_max(uint32_t v) { for (int d = 32; d; d >>= 1) { uint32_t o = (uint32_t)__shfl_xor((int)v, d, 64); v = o > v ? o : v; } return v; }
 ZH_DEV void ze_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 // hides a value's provenance from the optimizer (used so `lane == 0` is not provably loop-invariant)

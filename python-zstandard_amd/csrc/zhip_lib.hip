@@ -17,6 +17,7 @@
 #include "../../include/zstd_hip.h"
 #include "zhip_decode_pipeline.hpp"
 #include "zhip_encode_kernel.hpp"
+#include "zhip_encode_wave.hpp"
 #include "zhip_cparams.hpp"
 #include "zhip_seekable.hpp"
 
@@ -137,6 +138,17 @@ template <uint32_t BYTES, int NPAIR> __global__ __launch_bounds__(64) void zhip_
     __shared__ ZeSrcLDS<BYTES> L;
     ze_match_lds_body<NPAIR, true>(a, L.b, BYTES);
 }
+// the wave-parallel match finder (ZHIP_FINDER_WAVE, zhip_encode_wave.hpp): one wave per source, 1 << H table cells in LDS -- 16 / 32 / 64 KiB a workgroup
+template <int H> __global__ __launch_bounds__(64) void zhip_encode_match_wave_kernel(ZhipEncodeArgs a)
+{
+    __shared__ uint32_t table[1u << H];
+    ze_match_wave_body<H>(a, table);
+}
+#ifndef ZHIP_WAVE_HLOG
+#define ZHIP_WAVE_HLOG 12                  // table cells of the wave match finder, log2: 12 by the rate measurement (profiles/r11_wave_finder_rate.txt, DESIGN.md 4.2 -- the kernel's rate is its resident
+                                           // waves, which LDS bounds: 16 384 x 128 KiB 77 / 140 / 174 ms at 12 / 13 / 14). ZHIP_WAVE_HLOG in the environment overrides it FOR THAT MEASUREMENT ONLY
+                                           // (tests/tools/wave_finder_rate.py): the frames differ with the table size, so a process that sets it gives up "the same bytes everywhere"
+#endif
 #ifndef ZE_E2_MINWAVES
 #define ZE_E2_MINWAVES 4
 #endif
@@ -362,7 +374,7 @@ struct DevBuf {
         p = nullptr; cap = 0;
     }
 };
-#define ZHIP_NTIMER 10
+#define ZHIP_NTIMER 11
 struct KTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // owned: destroyed after reading
     std::vector<std::pair<hipEvent_t, hipEvent_t>> shared;    // borrowed: another timer owns the events
@@ -380,6 +392,8 @@ struct zhip_ctx {
     hipStream_t sideStream[ZHIP_NSLOT] = {};
     DevBuf encWorkspace, encMeta, encArena, encTables, encBigList, encBigWs, encFlatTables, encE1List, encMbBlocks, encMbCount, encMbSeqs;
     int e1PerCU = 0, e2PerCU = 0;
+    int matchFinder = ZHIP_FINDER_LIBZSTD;     // zhip_ctx_set_match_finder
+    int wavePerCU[3] = {0, 0, 0};      // resident workgroups per CU of the wave match kernel at H = 12, 13, 14
     size_t srcMaxHint = 0;             // largest source of the batch being launched when the caller knows it (host-buffer API), else 0
     size_t dstMaxHint = 0;             // the same for the decode direction: largest announced content size of the batch (host-buffer API), else 0
     bool hostPipe = false;             // the host-buffer pipeline is the caller (decompress_batch_one): its chunks' kernels are far from its bound -- the copies over the link -- and it
@@ -431,6 +445,7 @@ struct zhip_ctx {
         // (fast2Max is NOT measured yet: it is the double-fast search's four-probe band -- two pairs are four positions a trip -- taken over; tests/tools/compress_levels_rate.py under
         // ZHIP_FAST_PAIRS=1 and =2 at 16 384 and 65 536 sources is the measurement that sets it)
         size_t fast2Max = 32768; int fastPairs = 0;
+        int waveH = ZHIP_WAVE_HLOG;         // ZHIP_WAVE_HLOG: table cells of the wave match finder, log2 (12, 13, 14)
         bool e1fPick = true;                // ZHIP_E1F_PICK=0: take the flat tables where the first allocation put them (zhip_compress_batch_device)
         // host-buffer pipeline
         size_t hchunkE = 32768, hchunkE0 = 0;   // compress: items per chunk, items of the first chunk (0: like the others)
@@ -443,7 +458,7 @@ struct zhip_ctx {
     unsigned long long* profDecode = nullptr;    // ZHIP_PROF phase-timer accumulators, owned by the context (one context == one caller)
     unsigned long long* profPipe = nullptr;
     unsigned long long* profEncode = nullptr;
-    KTimer timer[ZHIP_NTIMER];   // 0 fused decode, 1 fused encode, 2 K1 literals, 3 K2 sequences, 4 K3 execution, 5 E1 match, 6 E2 entropy, 7 K1b Huffman streams, 8 the flat match kernel, 9 the decode pipeline of a chunk from K1's start to K3's end (K1b runs beside K2)
+    KTimer timer[ZHIP_NTIMER];   // (10: the wave match kernel) 0 fused decode, 1 fused encode, 2 K1 literals, 3 K2 sequences, 4 K3 execution, 5 E1 match, 6 E2 entropy, 7 K1b Huffman streams, 8 the flat match kernel, 9 the decode pipeline of a chunk from K1's start to K3's end (K1b runs beside K2)
     size_t device_bytes() const
     {
         const DevBuf* all[] = {&pipeMeta, &pipeLit, &pipeCounters, &pipeFallback, &pipeFse, &pipeOrder, &pipeHuf, &pipeOrderLit, &pipeItemFrame, &pipeItemReps, &pipeFrameRecs, &pipeBases, &pipePre, &encWorkspace, &encMeta, &encArena,
@@ -473,6 +488,7 @@ extern "C" zhip_ctx* zhip_ctx_create(void)
         if (const char* e = getenv("ZHIP_E1LDS_MAX")) { const long v = atol(e); if (v >= 0 && v <= 65536) k.e1LdsMax = v; }
         if (const char* e = getenv("ZHIP_E1F_PICK")) k.e1fPick = atol(e) != 0;    // 0: take the tables where the first allocation put them (A/B)
         if (const char* e = getenv("ZHIP_FAST_PAIRS")) { const long v = atol(e); if (v >= 0 && v <= 2) k.fastPairs = (int)v; }      // pairs per trip of the flat fast-strategy search (0: by launch size)
+        if (const char* e = getenv("ZHIP_WAVE_HLOG")) { const long v = atol(e); if (v >= 12 && v <= 14) k.waveH = (int)v; }      // MEASUREMENT ONLY (tests/tools/wave_finder_rate.py): table size of the wave match finder -- the frames differ with it
     }
     zh_resolve_rows(&c->rows, 3, nullptr);
     int nb = 0;
@@ -491,6 +507,12 @@ extern "C" zhip_ctx* zhip_ctx_create(void)
     c->e1PerCU = nb;
     nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_encode_entropy_kernel, 64, 0) != hipSuccess || nb < 1) nb = 4;
     c->e2PerCU = nb;
+    nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_encode_match_wave_kernel<12>, 64, 0) != hipSuccess || nb < 1) nb = 8;
+    c->wavePerCU[0] = nb;
+    nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_encode_match_wave_kernel<13>, 64, 0) != hipSuccess || nb < 1) nb = 4;
+    c->wavePerCU[1] = nb;
+    nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_encode_match_wave_kernel<14>, 64, 0) != hipSuccess || nb < 1) nb = 2;
+    c->wavePerCU[2] = nb;
     return c;
 }
 static void drain_shared(KTimer& t)
@@ -538,7 +560,8 @@ extern "C" const char* zhip_kernel_name(int k)
 {
     static const char* names[ZHIP_NTIMER] = {"zhip_decode_frames_kernel", "zhip_encode_frames_kernel", "zhip_decode_lit_kernel",
                                    "zhip_decode_seq_kernel", "zhip_decode_exec_kernel", "zhip_encode_match_kernel",
-                                   "zhip_encode_entropy_kernel", "zhip_decode_huf_kernel", "zhip_encode_match_flat_kernel", "zhip_decode_pipeline_span"};
+                                   "zhip_encode_entropy_kernel", "zhip_decode_huf_kernel", "zhip_encode_match_flat_kernel", "zhip_decode_pipeline_span",
+                                   "zhip_encode_match_wave_kernel"};
     return k >= 0 && k < ZHIP_NTIMER ? names[k] : "";
 }
 extern "C" int zhip_ctx_kernel_time(zhip_ctx* c, int direction, double* avgMs, uint64_t* launches)
@@ -1049,6 +1072,52 @@ static void launch_entropy(const zhip_ctx* c, ZhipEncodeArgs& a, uint32_t g2, si
     if (a.xxLater) { const size_t w = (cnt + 63) / 64, gm = (size_t)c->numCU * 8; hipLaunchKernelGGL(zhip_encode_trailer_kernel, dim3((uint32_t)(w < gm ? w : gm)), dim3(64), 0, stream, a); }      // EX
     a.xxLater = 0;
 }
+extern "C" int zhip_ctx_set_match_finder(zhip_ctx* c, int finder)
+{
+    if (!c || (finder != ZHIP_FINDER_LIBZSTD && finder != ZHIP_FINDER_WAVE)) { g_lastError = "zhip_ctx_set_match_finder: unknown match finder"; return ZHIP_ERR_UNSUPPORTED; }
+    c->matchFinder = finder;
+    return 0;
+}
+// zhip_compress_batch_device under ZHIP_FINDER_WAVE: per chunk the wave match kernel in place of every other match kernel, then the entropy and trailer kernels as ever.
+// No flat tables, no table-placement pick, no generic kernel: a source of several blocks is refused at its own index (status 40, by the entropy kernel's ze_frame).
+static int compress_batch_wave(zhip_ctx* c, ZhipEncodeArgs& a, uint8_t* cbase, size_t n, hipStream_t stream)
+{
+    // the one-block row (sources of 16 385 ... 131 072 bytes) must be fast or double-fast -- the entropy side codes those; where only the row of smaller sources is
+    // something else (level 4), those sources are refused one by one
+    if (c->hasCDict) { g_lastError = "the wave match finder (ZHIP_FINDER_WAVE) does not take a dictionary"; return ZHIP_ERR_UNSUPPORTED; }
+    if (a.rows.r[2][6] != 1 && a.rows.r[2][6] != 2) { g_lastError = "the wave match finder (ZHIP_FINDER_WAVE) serves the levels whose one-block row is fast or double-fast (levels <= 4, negative levels, explicit strategy 1 / 2)"; return ZHIP_ERR_UNSUPPORTED; }
+    a.arenaStride = (uint32_t)(ZE_ARENA_LIT + 512); a.arenaLit = ZE_ARENA_LIT;      // sequences only (mode 4): the slot needs no literal area
+    size_t chunk = n < 65536 ? n : 65536;
+    if (c->knob.echunk && c->knob.echunk < chunk) chunk = c->knob.echunk;
+    while (c->encArena.reserve(chunk * (size_t)a.arenaStride)) {                      // no room for a whole chunk's slots: half as many sources per launch
+        if (g_reserveRc != ZHIP_ERR_NO_MEMORY || chunk <= 64) return g_reserveRc;
+        chunk = (chunk + 1) / 2;
+    }
+    const size_t g2max = (size_t)c->numCU * (size_t)c->e2PerCU, gwmax = (size_t)c->numCU * (size_t)c->wavePerCU[c->knob.waveH - 12];
+    const uint32_t g2 = (uint32_t)(chunk < g2max ? chunk : g2max);
+    if (c->encMeta.reserve(chunk * sizeof(ZeMeta)) || c->encWorkspace.reserve((size_t)g2 * ZE_E2_STRIDE + ZHIP_ENC_STRIDE)) return g_reserveRc;
+    a.workspace = (uint8_t*)c->encWorkspace.p; a.meta = (ZeMeta*)c->encMeta.p; a.arena = (uint8_t*)c->encArena.p;
+    a.idle = cbase + 256;
+    for (size_t first = 0; first < n; first += chunk) {
+        const size_t cnt = n - first < chunk ? n - first : chunk;
+        a.first = (uint32_t)first; a.count = (uint32_t)cnt;
+        HIP_TRY(hipMemsetAsync(cbase + 8, 0, 8, stream));
+        const bool tm = c->timing;
+        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // wave kernel: ev[0] .. ev[1], entropy + trailer: ev[2] .. ev[3] (a timer owns both events of its pairs, so the two stages share none)
+        // (an event call that fails gives back the chunk's events before the error is returned)
+        auto dropEvents = [&](hipError_t e) { if (e != hipSuccess) for (hipEvent_t& x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } return e; };
+        if (tm) { for (int i = 0; i < 4; i++) HIP_TRY(dropEvents(hipEventCreate(&ev[i]))); HIP_TRY(dropEvents(hipEventRecord(ev[0], stream))); }
+        const dim3 g((uint32_t)(cnt < gwmax ? cnt : gwmax)), b(64);
+        if (c->knob.waveH == 12) hipLaunchKernelGGL(zhip_encode_match_wave_kernel<12>, g, b, 0, stream, a);
+        else if (c->knob.waveH == 14) hipLaunchKernelGGL(zhip_encode_match_wave_kernel<14>, g, b, 0, stream, a);
+        else hipLaunchKernelGGL(zhip_encode_match_wave_kernel<13>, g, b, 0, stream, a);
+        if (tm) { HIP_TRY(dropEvents(hipEventRecord(ev[1], stream))); HIP_TRY(dropEvents(hipEventRecord(ev[2], stream))); }
+        launch_entropy(c, a, g2, cnt, stream);
+        if (tm) { HIP_TRY(dropEvents(hipEventRecord(ev[3], stream))); c->timer[10].pending.emplace_back(ev[0], ev[1]); c->timer[6].pending.emplace_back(ev[2], ev[3]); }
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
 extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
                                           void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
                                           int32_t* d_status, void* streamv)
@@ -1063,6 +1132,7 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
     uint8_t* const cbase = (uint8_t*)c->counter.p;
     HIP_TRY(hipMemsetAsync(cbase + 8, 0, 4, stream));
     ZhipEncodeArgs a; enc_args_init(c, a, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, cbase);
+    if (c->matchFinder == ZHIP_FINDER_WAVE) return compress_batch_wave(c, a, cbase, n, stream);
     {
         // two kernels: E1 searches with one LANE per frame (frames in flight hide the probe latency), E2 entropy-codes with one
         // wave per frame. Frames are processed in chunks so that the per-frame sequence/literal arena stays bounded.

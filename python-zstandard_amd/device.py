@@ -16,13 +16,18 @@ class DeviceBatchContext:
     """Owns the native context (scratch, dictionary tables, kernel timers) for one GPU / one stream."""
 
     def __init__(self, dict_data=None, level=3, write_checksum=False, write_content_size=True, write_dict_id=True, dict_type=0,
-                 format=0, max_window_size=0, **cparams):
+                 format=0, max_window_size=0, match_finder="libzstd", **cparams):
         """dict_data: a ZstdCompressionDict (or bytes) used by both directions; level / write_* / cparams (window_log, hash_log,
-        chain_log, min_match, target_length, strategy): what ZstdCompressor takes; format / max_window_size: what ZstdDecompressor takes."""
+        chain_log, min_match, target_length, strategy): what ZstdCompressor takes; format / max_window_size: what ZstdDecompressor takes.
+        match_finder: "libzstd" (the default: frames byte for byte libzstd's) or "wave" -- see set_match_finder."""
+        self.ctx = None
+        if match_finder not in self.MATCH_FINDERS:                      # (before anything native exists)
+            raise ZstdError("match_finder must be one of %s" % ", ".join(repr(k) for k in self.MATCH_FINDERS))
         self.L = _lib.lib()
         self.ctx = self.L.zhip_ctx_create()
         if not self.ctx:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        self.set_match_finder(match_finder)
         raw = None if dict_data is None else (dict_data.as_bytes() if hasattr(dict_data, "as_bytes") else bytes(dict_data))
         self._dict_buf = C.create_string_buffer(raw, len(raw)) if raw else None          # kept alive: the library fingerprints it per call
         rc = self.L.zhip_ctx_set_dformat(self.ctx, format, max_window_size)
@@ -58,8 +63,21 @@ class DeviceBatchContext:
         kernel; untold, such items are served one wave each by a token grid of the generic kernels (correct, slow)"""
         self.L.zhip_ctx_set_size_hint(self.ctx, int(max_item_bytes))
 
+    MATCH_FINDERS = {"libzstd": 0, "wave": 1}
+
+    def set_match_finder(self, match_finder):
+        """the match finder of the coming compress / seekable_compress / seekable_compress_records calls (compress_sequences has none). "libzstd": the searches
+        that keep libzstd's table contents, frames byte for byte libzstd's. "wave": one wave per source with its hash table in LDS -- valid zstd frames that every
+        decoder reads, deterministic, NOT libzstd's bytes; sources of one block, no dictionary, levels whose one-block row is fast or double-fast (<= 4, negative),
+        anything else raises ZstdError from the compress call or gets status 40 at its own index. Host state only."""
+        if match_finder not in self.MATCH_FINDERS:
+            raise ZstdError("match_finder must be one of %s" % ", ".join(repr(k) for k in self.MATCH_FINDERS))
+        if self.L.zhip_ctx_set_match_finder(self.ctx, self.MATCH_FINDERS[match_finder]):
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        self.match_finder = match_finder
+
     def close(self):
-        if self.ctx:
+        if getattr(self, "ctx", None):
             self.L.zhip_ctx_destroy(self.ctx)
             self.ctx = None
 

@@ -16,9 +16,10 @@ def _to_device(data):
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()
 
 
-def compress(data, level=3, frame_size=131072, checksum=False, **ctx_kw):
-    """data -> a seekable stream (bytes). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
-    ctx = DeviceBatchContext(level=level, **ctx_kw)
+def compress(data, level=3, frame_size=131072, checksum=False, match_finder="libzstd", **ctx_kw):
+    """data -> a seekable stream (bytes). match_finder: "libzstd" (frames byte for byte libzstd's) or "wave" (DeviceBatchContext.set_match_finder: valid zstd,
+    not libzstd's bytes; frame_size at most 131 072). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
+    ctx = DeviceBatchContext(level=level, match_finder=match_finder, **ctx_kw)
     try:
         return ctx.seekable_compress(_to_device(data), frame_size=frame_size, checksum=checksum).cpu().numpy().tobytes()
     finally:
@@ -64,14 +65,14 @@ def decompress_ranges(data, ranges, **ctx_kw):
         ctx.close()
 
 
-def compress_records(records, level=3, checksum=False, **ctx_kw):
+def compress_records(records, level=3, checksum=False, match_finder="libzstd", **ctx_kw):
     """a list of bytes -> a seekable stream (bytes) with ONE frame per record, compressed as one batch; ``decompress_records`` reads records back by index.
-    ctx_kw: what DeviceBatchContext takes. Raises ZstdError."""
+    match_finder: as in ``compress`` (records of at most 131 072 bytes under "wave"). ctx_kw: what DeviceBatchContext takes. Raises ZstdError."""
     raws = [bytes(r) for r in records]
     table, at = [], 0
     for r in raws:
         table.append((at, len(r))); at += len(r)
-    ctx = DeviceBatchContext(level=level, **ctx_kw)
+    ctx = DeviceBatchContext(level=level, match_finder=match_finder, **ctx_kw)
     try:
         return ctx.seekable_compress_records(_to_device(b"".join(raws)), table, checksum=checksum).cpu().numpy().tobytes()
     finally:

@@ -1,0 +1,40 @@
+// tests/emu/wave_bounds_main.cpp -- bounds check of the wave-parallel match finder as a stand-alone PROGRAM (its own main; nothing is loaded into python, no LD_PRELOAD).
+// Built by tests/emu/build_wave_bounds.sh with -fsanitize=address,undefined together with zhemu.cpp and emu_wave_finder.cpp. Every argument is a file holding one source:
+// it is read into a heap block of EXACTLY its size, so a load of the match kernel, the literal gather or the trailer kernel past (or before) the source is reported, and
+// compressed alone at levels 3, 1 (with min_match 4) and -3, and at level 3 at each table size, into a slot of exactly zhip_compress_bound's size. Exit status 0 and "ok" when every status is 0.
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+extern "C" int emu_wave_frames(const uint8_t* src, const uint64_t* srcSegs, uint32_t n, uint8_t* dst, const uint64_t* dstSegs, uint64_t* outSizes, int32_t* status,
+                               int level, const int32_t* ov, uint32_t flags, uint32_t nBlocks, int finder, int H, uint64_t* seqOut, uint32_t seqStride, uint32_t* metaOut);
+
+int main(int argc, char** argv)
+{
+    int bad = 0; long runs = 0;
+    const bool quick = argc > 1 && !strcmp(argv[1], "-q");            // -q (the test suite's run): the product's table size only, level 3 and level 1 with min_match 4
+    for (int k = quick ? 2 : 1; k < argc; k++) {
+        FILE* f = fopen(argv[k], "rb");
+        if (!f) { fprintf(stderr, "cannot open %s\n", argv[k]); return 2; }
+        fseek(f, 0, SEEK_END); const long n = ftell(f); fseek(f, 0, SEEK_SET);
+        uint8_t* src = (uint8_t*)malloc((size_t)n);                  // exactly the source (a zero-byte block for the empty one)
+        if (n && fread(src, 1, (size_t)n, f) != (size_t)n) { fprintf(stderr, "cannot read %s\n", argv[k]); return 2; }
+        fclose(f);
+        const uint64_t cap = (uint64_t)n + ((uint64_t)n >> 8) + 64 + 32;
+        static const int levels[3] = {3, 1, -3};
+        for (int l = 0; l < 3; l++) for (int H = 12; H <= 14; H++) {
+            if (H != 12 && l) continue;
+            if (quick && (H != 12 || l == 2)) continue;
+            uint8_t* dst = (uint8_t*)malloc(cap);
+            const uint64_t ssegs[2] = {0, (uint64_t)n}, dsegs[2] = {0, cap};
+            uint64_t size = 0; int32_t st = -1; int32_t ov[7] = {0, 0, 0, 0, l == 1 ? 4 : 0, 0, 0};      // (level 1 with min_match 4: the shortest matches)
+            const int rc = emu_wave_frames(src, ssegs, 1, dst, dsegs, &size, &st, levels[l], ov, 1 | 2, 1, 1, H, nullptr, 0, nullptr);
+            if (rc || st || size > cap) { fprintf(stderr, "%s: level %d H %d: rc %d status %d size %llu\n", argv[k], levels[l], H, rc, st, (unsigned long long)size); bad++; }
+            free(dst); runs++;
+        }
+        free(src);
+    }
+    printf("%s: %d sources, %ld runs, %d failed\n", bad ? "FAILED" : "ok", argc - (quick ? 2 : 1), runs, bad);
+    return bad ? 1 : 0;
+}
