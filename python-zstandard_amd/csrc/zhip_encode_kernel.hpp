@@ -1127,11 +1127,14 @@ ZH_DEV uint32_t ze_dfast_flat_np(uint64_t* seqs, const uint8_t* src, uint32_t bs
         for (int k = 1; k < NP; k++) if (R == (uint32_t)k && pos[k + 1] <= ilimit) R = (uint32_t)k + 1;
         ZE_STAT(10);
         // round 0: the probes' own bytes (positions beyond the last real one read the last valid position: ignored)
-        uint64_t w[NP + 1]; uint32_t rp[NP], pL[NP + 1], hl[NP + 1], hs[NP];
+        // pc[k] = the position probe k reads at. It is also the position its cells would carry: a probe past ilimit (never real) holds ilimit's bytes, and through the forwarding
+        // selects below a later probe of the trip may take its cell for a candidate's and read 8 bytes there in round 2 -- at ilimit that stays inside the source, at pos[k] it
+        // lay up to (NP - 1) * step bytes behind its end. Real probes have pc == pos, so no decision and no table write changes.
+        uint64_t w[NP + 1]; uint32_t pc[NP + 1], rp[NP], pL[NP + 1], hl[NP + 1], hs[NP];
 #pragma unroll
-        for (int k = 0; k <= NP; k++) { const uint32_t q = pos[k] <= ilimit ? pos[k] : ilimit; w[k] = zh_ld64(src + q); }
+        for (int k = 0; k <= NP; k++) { pc[k] = pos[k] <= ilimit ? pos[k] : ilimit; w[k] = zh_ld64(src + pc[k]); }
 #pragma unroll
-        for (int k = 0; k < NP; k++) { const uint32_t q = pos[k] <= ilimit ? pos[k] : ilimit; rp[k] = zh_ld32(src + q + 1 - off1); }
+        for (int k = 0; k < NP; k++) rp[k] = zh_ld32(src + pc[k] + 1 - off1);
 #pragma unroll
         for (int k = 0; k <= NP; k++) { pL[k] = ZE_PL(w[k]); hl[k] = pL[k] >> shL; }
 #pragma unroll
@@ -1146,9 +1149,9 @@ ZH_DEV uint32_t ze_dfast_flat_np(uint64_t* seqs, const uint8_t* src, uint32_t bs
         if (fresh) cellL0 = tA;
         cL[0] = cellL0;
 #pragma unroll
-        for (int k = 0; k <= NP; k++) newL[k] = (pos[k] + 2) | ZE_TL(pL[k]);
+        for (int k = 0; k <= NP; k++) newL[k] = (pc[k] + 2) | ZE_TL(pL[k]);
 #pragma unroll
-        for (int k = 0; k < NP; k++) newS[k] = (pos[k] + 2) | ZE_TS(w[k]);
+        for (int k = 0; k < NP; k++) newS[k] = (pc[k] + 2) | ZE_TS(w[k]);
         // what the reference's later reads see after its earlier writes of this trip (zstd.c:31121 then :31163): the latest earlier probe with the same cell wins
 #pragma unroll
         for (int k = 1; k <= NP; k++) {

@@ -8,3 +8,6 @@ g++ -O1 -g -fPIC -shared -std=c++17 -I. -fsanitize=address -fno-omit-frame-point
 # the same for the entropy kernel driven by explicit sequences, as a stand-alone PROGRAM (its own main; nothing is loaded into python, no LD_PRELOAD):
 #   /tmp/emu_entropy_sequences_asan tests/golden/entropy_sequences.bin
 g++ -O1 -g -std=c++17 -I. -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wno-unused-function -Wno-unused-variable -DEMU_ENTROPY_SEQUENCES_MAIN -o ${2:-/tmp/emu_entropy_sequences_asan} zhemu.cpp emu_entropy_sequences.cpp
+# and for the double-fast searches over the aimed sources (tests/dfast_sources.py, python -m tests.dfast_sources --write-fixture), again a stand-alone program:
+#   /tmp/emu_dfast_asan tests/golden/dfast_sources.bin
+g++ -O1 -g -std=c++17 -I. -fsanitize=address,undefined -fno-sanitize-recover=undefined -static-libasan -static-libubsan -fno-omit-frame-pointer -Wno-unused-function -Wno-unused-variable -DEMU_DFAST_MAIN -o ${3:-/tmp/emu_dfast_asan} zhemu.cpp emu_dfast.cpp
