@@ -173,7 +173,7 @@ struct ZeMbBlock { uint32_t end, seqStart, nbSeq, rep0, rep1, pad[3]; };
 // stand and leaves what they leave -- packed sequences in the source's arena slot and its ZeMeta -- so the entropy and trailer kernels run unchanged behind it.
 // seqs: packed sequences of the whole batch; table: n x (first, count) into seqs; copyLits: 0 = sequences only (mode 4: the entropy kernel gathers the literals),
 // 1 = the literals are copied to the slot's literal area too (mode 0: what the lane-serial match kernel leaves)
-// the arena slot of a dictionary batch whose sources are at most `lim` bytes (host side: zhip_lib.hip's enc_dict_slots, and the emulator harnesses that mirror it)
+// the arena slot of a dictionary batch whose sources are at most `lim` bytes (host side: ze_dict_slots, zhip_encode_plan.hpp)
 static inline void ze_dict_slot_shape(uint32_t lim, uint32_t* arenaLit, uint32_t* arenaStride)
 {
     *arenaLit = (8u * (lim / 3 + 16) + 15) & ~15u;

@@ -19,12 +19,10 @@
 #include "zhip_encode_kernel.hpp"
 #include "zhip_encode_wave.hpp"
 #include "zhip_cparams.hpp"
+#include "zhip_encode_plan.hpp"
 #include "zhip_seekable.hpp"
 
 #define ZHIP_LDS_BYTES (160u * 1024u)      // per CU on gfx950
-#ifndef ZHIP_E1LDS_PER_CU
-#define ZHIP_E1LDS_PER_CU 4                // batches up to this many frames per CU take the LDS-source match kernel (ZHIP_E1LDS_MAX overrides the frame count); r02zq: 1 024 frames 147 ms against 159-163 with the flat kernel, 512: 89 against 146
-#endif
 static_assert(sizeof(ZpSeqQLDS) <= ZHIP_LDS_BYTES && sizeof(ZpHufKernelLDS) <= ZHIP_LDS_BYTES, "a workgroup's LDS must fit a CU");
 
 // ------------------------------------------------------------------------------------------ kernels
@@ -322,12 +320,6 @@ extern "C" void zhip_get_cparams(int level, uint64_t srcSizeHint, size_t dictSiz
 #ifndef ZHIP_E1LDS_FAST_PAIRS
 #define ZHIP_E1LDS_FAST_PAIRS 2   // pairs per trip of the fast strategy's LDS-source match kernel: one source per CU is pure latency, and the second pair's loads ride in the same rounds
 #endif
-#ifndef ZHIP_TABLE_EPOCHS
-#define ZHIP_TABLE_EPOCHS 1      // launch numbers in the cells of the flat searches' tables; 0: the tables are zeroed every launch -- a memset, the dictionary search's own waves -- (A/B build)
-#endif
-#ifndef ZHIP_FAST_WIDE
-#define ZHIP_FAST_WIDE 1          // fast-strategy batches above 32 768 sources: 65 536 per chunk at sixteen sources per wave; 0: chunks of 32 768 at eight (A/B build)
-#endif
 #ifndef ZHIP_TRAILER_LATER
 #define ZHIP_TRAILER_LATER 1     // compress: checksum trailers by EX after the entropy kernel; 0: by the entropy kernel on one lane per frame (A/B build)
 #endif
@@ -424,7 +416,7 @@ struct zhip_ctx {
     bool hpReady = false; hipStream_t hpH2D = nullptr, hpCompute = nullptr, hpD2H = nullptr;     // host pipeline: copy-in, kernels, copy-out
     void* hpStage[2] = {nullptr, nullptr}; size_t hpStageCap[2] = {0, 0}; hipEvent_t hpStageFree[2] = {nullptr, nullptr}; int hpNextSlot = 0;
     // bring-up / tuning knobs, read from the environment ONCE when the context is created (never in a launch path)
-    struct Knobs {
+    struct Knobs : ZeEncodeKnobs {      // (the encode knobs the launch plan reads: ZeEncodeKnobs, zhip_encode_plan.hpp)
         // bring-up aids
         bool prof = false;                  // ZHIP_PROF: the kernels' phase timers (a separate instantiation of K3; printed to stderr)
         size_t k0Min = 6144;                // ZHIP_K0_MIN: frames per chunk from which K0 runs in front of K1 (a GPU test sets 0: K0 on every batch)
@@ -432,19 +424,7 @@ struct zhip_ctx {
         size_t dchunk = ZHIP_DCHUNK;        // frames (several-block mode: block slots) per chunk
         int nslot = 2; bool nslotSet = false;   // chunk slots on their own streams (small frames get a third unless ZHIP_NSLOT says otherwise)
         int k1PerCU = 0, k3PerCU = 0;       // waves per CU of K1 / K3 (0: what the occupancy query says)
-        // encode
-        size_t echunk = 0;                  // ZHIP_ECHUNK: sources per chunk, upper bound (0: none)
-        size_t echunkMax = 0;               // ZHIP_ECHUNK_MAX: frames per launch of the flat match kernel (0 = 65 536, and 131 072 for larger batches where memory allows)
-        long e1LdsMax = -1; size_t e1LdsRounds = 2;     // the LDS-source match kernel of small batches: most sources it takes (-1: by the CU count), rounds per CU
-        size_t mbcMin = 4096;               // sources per 256 KiB of size hint from which sources of several blocks take the flat search (8 192 until r06zzi)
-        unsigned mbcLanes = 32;             // sources per wave of that search (64 / 32 / 16 / 8 within 10-30 % of each other, r03z)
-        // probes per trip of the flat double-fast search by launch size: up to flat4Max sources four (bound by one source's serial chain: 21-25 % less time from
-        // 1 024 to 32 768 sources, r04zd), up to flat3Max three, above two (with the placement picked, at 65 536: 421 / 415 / 425 ms for two / three / four, r05w)
-        size_t flat4Max = 32768, flat3Max = 65536; bool flat3 = true;
-        // pairs per trip of the flat fast-strategy search (ze_fast_flat_np) by launch size: up to fast2Max sources two, above one. ZHIP_FAST_PAIRS=1 / 2 forces either (A/B, and the GPU test of both kernels)
-        // (fast2Max is NOT measured yet: it is the double-fast search's four-probe band -- two pairs are four positions a trip -- taken over; tests/tools/compress_levels_rate.py under
-        // ZHIP_FAST_PAIRS=1 and =2 at 16 384 and 65 536 sources is the measurement that sets it)
-        size_t fast2Max = 32768; int fastPairs = 0;
+        // encode (the rest: ZeEncodeKnobs)
         int waveH = ZHIP_WAVE_HLOG;         // ZHIP_WAVE_HLOG: table cells of the wave match finder, log2 (12, 13, 14)
         bool e1fPick = true;                // ZHIP_E1F_PICK=0: take the flat tables where the first allocation put them (zhip_compress_batch_device)
         // host-buffer pipeline
@@ -1015,25 +995,51 @@ extern "C" int zhip_decompress_batch_device(zhip_ctx* c, const void* d_src, cons
     if (c->timer[0].pending.size() > 1024) { HIP_TRY(hipStreamSynchronize(stream)); for (int i = 0; i < ZHIP_NTIMER; i++) drain_shared(c->timer[i]); for (int i = 0; i < ZHIP_NTIMER; i++) drain_timer(c->timer[i]); }
     return 0;
 }
-// the flat match kernel at `probes` per trip over `cnt` sources (fastPairs != 0: the fast strategy's, at that many pairs per trip)
-static void launch_flat(int probes, size_t cnt, hipStream_t stream, const ZhipEncodeArgs& a, int fastPairs = 0)
+// the LDS-source match kernel at one source size per CU slot -- the fast strategy's (FAST) or the double-fast one's -- of the four sizes the one the plan's shape names
+template <uint32_t BYTES, bool FAST> static void launch_lds_at(dim3 g, hipStream_t stream, const ZhipEncodeArgs& a)
 {
-    const dim3 g((uint32_t)((cnt + ZE_FLAT_LANES - 1) / ZE_FLAT_LANES)), b(64);
-    if (fastPairs == 2) hipLaunchKernelGGL(zhip_encode_match_flat_fast2_kernel, g, b, 0, stream, a);
-    else if (fastPairs) hipLaunchKernelGGL(zhip_encode_match_flat_fast_kernel, g, b, 0, stream, a);
-    else if (probes == 4) hipLaunchKernelGGL(zhip_encode_match_flat4_kernel, g, b, 0, stream, a);
-    else if (probes == 3) hipLaunchKernelGGL(zhip_encode_match_flat3_kernel, g, b, 0, stream, a);
+    if constexpr (FAST) hipLaunchKernelGGL((zhip_encode_match_lds_fast_kernel<BYTES, ZHIP_E1LDS_FAST_PAIRS>), g, dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((zhip_encode_match_lds_kernel<BYTES, ZHIP_E1LDS_PROBES>), g, dim3(64), 0, stream, a);
+}
+template <bool FAST> static void launch_lds(int shape, dim3 g, hipStream_t stream, const ZhipEncodeArgs& a)
+{
+    if (shape == 0) launch_lds_at<4096, FAST>(g, stream, a);
+    else if (shape == 1) launch_lds_at<16384, FAST>(g, stream, a);
+    else if (shape == 2) launch_lds_at<65536, FAST>(g, stream, a);
+    else launch_lds_at<ZF_BLOCK_MAX, FAST>(g, stream, a);
+}
+// the match kernel a chunk's plan names (ze_encode_chunk_plan), on its grid
+static void launch_match(const ZeChunkPlan& k, hipStream_t stream, const ZhipEncodeArgs& a)
+{
+    const dim3 g(k.grid), b(64);
+    if (k.kernel == ZE_MATCH_LDS_FAST) launch_lds<true>(k.shape, g, stream, a);
+    else if (k.kernel == ZE_MATCH_LDS) launch_lds<false>(k.shape, g, stream, a);
+    else if (k.fastPairs == 2) hipLaunchKernelGGL(zhip_encode_match_flat_fast2_kernel, g, b, 0, stream, a);
+    else if (k.fastPairs) hipLaunchKernelGGL(zhip_encode_match_flat_fast_kernel, g, b, 0, stream, a);
+    else if (k.probes == 4) hipLaunchKernelGGL(zhip_encode_match_flat4_kernel, g, b, 0, stream, a);
+    else if (k.probes == 3) hipLaunchKernelGGL(zhip_encode_match_flat3_kernel, g, b, 0, stream, a);
     else hipLaunchKernelGGL(zhip_encode_match_flat_kernel, g, b, 0, stream, a);
 }
-// ---- what zhip_compress_batch_device and zhip_compress_sequences_device share: the launch arguments every encode kernel reads from the context's zhip_ctx_set_cparams
-// state, the slot shape of dictionary batches, and the entropy + trailer launches behind whatever left the sequences
+// ---- what the compress calls share: the counter block's cells, the launch arguments every encode kernel reads from the context's zhip_ctx_set_cparams
+// state, the launch plan's inputs, a chunk's timing events, and the entropy + trailer launches behind whatever left the sequences
+// the cells of the context's counter block (zhip_ctx::counter) the encode paths use, as byte offsets
+enum : size_t {
+    ZC_E1_WORK = 8,        // the E1 work counter: the match kernels' sources taken so far (ZhipEncodeArgs.counter)
+    ZC_E2_WORK = 12,       // the E2 work counter: the entropy kernel's, which it finds at ZhipEncodeArgs.counter + 1
+    ZC_BIG_COUNT = 24,     // bigCount: length of the list of sources left to the generic kernel
+    ZC_BIG_WORK = 28,      // the generic kernel's work counter over that list
+    ZC_E1_COUNT = 32,      // e1Count: length of the list the flat match kernel leaves to the lane-serial one
+    ZC_IDLE = 256,         // the idle pad: 16 readable bytes for the flat searches' lanes without a candidate (ZhipEncodeArgs.idle)
+};
+static_assert(ZC_E2_WORK == ZC_E1_WORK + 4 && ZC_BIG_WORK == ZC_BIG_COUNT + 4 && ZC_E1_COUNT == ZC_BIG_WORK + 4, "one memset clears neighbouring cells: E1 + E2, bigCount + the generic kernel's (+ e1Count)");
 static void enc_args_init(zhip_ctx* c, ZhipEncodeArgs& a, const void* d_src, const zhip_segment* d_srcSegs, size_t n, void* d_dst, const zhip_segment* d_dstSegs,
                           uint64_t* d_outSizes, int32_t* d_status, uint8_t* cbase)
 {
     memset(&a, 0, sizeof a);
     a.src = (const uint8_t*)d_src; a.srcSegs = (const uint64_t*)d_srcSegs; a.dst = (uint8_t*)d_dst;
     a.dstSegs = (const uint64_t*)d_dstSegs; a.outSizes = d_outSizes; a.status = d_status;
-    a.workspace = (uint8_t*)c->encWorkspace.p; a.counter = (uint32_t*)(cbase + 8); a.n = (uint32_t)n;
+    a.workspace = (uint8_t*)c->encWorkspace.p; a.counter = (uint32_t*)(cbase + ZC_E1_WORK); a.n = (uint32_t)n;
+    a.idle = cbase + ZC_IDLE;                                                   // (the context's own counter block: ADVICE r04 -- the caller's arena base need not be readable)
     a.level = c->cparams.level == 0 ? 3 : c->cparams.level;
     a.rows = c->rows; a.magicless = c->cparams.format == ZHIP_FORMAT_ZSTD1_MAGICLESS;
     a.contentSizeFlag = c->cparams.contentSizeFlag != 0; a.checksumFlag = c->cparams.checksumFlag != 0; a.dictIDFlag = c->cparams.dictIDFlag != 0;
@@ -1045,25 +1051,25 @@ static void enc_args_init(zhip_ctx* c, ZhipEncodeArgs& a, const void* d_src, con
         a.cdictHashSmall = (const uint32_t*)c->cdictTables.p + cells;
     }
 }
-// dictionary batches: every source is below the attach cutoff, so the per-lane tables are the dictionary row's shrunk to that
-// size (ze_dict_cparams) and a frame's sequences + literals fit a slot of the cutoff's size -- a tenth of the 128 KiB shapes,
-// which is what lets a whole 262 144-document batch be one chunk
-// (round 4: where the caller says how large its sources are -- the host API knows, a device-API caller can tell with
-// zhip_ctx_set_size_hint -- the slots are sized for THAT: 4 KiB documents need 48 KiB of tables, not the cutoff's 192, and 262 144 of
-// them are one launch instead of two. A source above the hint is the generic kernel's: correct, slower)
-// Sets a.slotSrcMax, a.arenaLit and a.arenaStride; returns the table bytes per source.
-static uint32_t enc_dict_slots(const zhip_ctx* c, size_t sizeHint, ZhipEncodeArgs& a)
+// the launch plan's inputs (zhip_encode_plan.hpp) as this context has them
+static ZePlanIn plan_inputs(const zhip_ctx* c, size_t n)
 {
-    size_t lim = c->cdictAttachMax;
-    if (sizeHint && sizeHint < lim) { lim = 1024; while (lim < sizeHint) lim <<= 1; }
-    if (lim < c->cdictAttachMax) a.slotSrcMax = (uint32_t)lim; else lim = c->cdictAttachMax;
-    int w = 10; while (((size_t)1 << w) < lim) w++;
-    const int h = c->cdictHlog > w + 1 ? w + 1 : c->cdictHlog, cl = c->cdictClog > w ? w : c->cdictClog;
-    uint32_t stride = (4u << h) + (c->cdictStrat == 2 ? (4u << cl) : 0u);
-    if (stride < (4u << 10)) stride = 4u << 10;
-    ze_dict_slot_shape((uint32_t)lim, &a.arenaLit, &a.arenaStride);
-    return stride;
+    ZePlanIn in;
+    in.rows = c->rows; in.n = n; in.sizeHint = c->srcMaxHint ? c->srcMaxHint : c->itemHint; in.srcMaxHint = c->srcMaxHint;
+    in.dict = ZePlanDict{c->hasCDict, c->cdictHlog, c->cdictClog, c->cdictStrat, c->cdictAttachMax, c->cdictContentSize};
+    in.dev = ZePlanDevice{c->numCU, c->encBlocksPerCU, c->e1PerCU, c->e2PerCU};
+    in.knob = c->knob;
+    return in;
 }
+// a chunk's timing events. Nothing is created while the context's timers are off, and every call is then a no-op; an event is destroyed with the owner unless a KTimer took it
+// (a timer owns both events of its pairs, so two stages share none) -- a HIP call that fails in the middle of a chunk leaks none
+struct ChunkEvents {
+    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~ChunkEvents() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+    hipError_t create(int count) { for (int i = 0; i < count; i++) { const hipError_t e = hipEventCreate(&ev[i]); if (e != hipSuccess) return e; } return hipSuccess; }
+    hipError_t record(int i, hipStream_t stream) { return ev[i] ? hipEventRecord(ev[i], stream) : hipSuccess; }
+    void give(KTimer& t, int i, int j) { if (ev[i] && ev[j]) { t.pending.emplace_back(ev[i], ev[j]); ev[i] = ev[j] = nullptr; } }
+};
 // E2 over the chunk, g2 waves, and EX behind it for checksummed frames (timed with E2)
 static void launch_entropy(const zhip_ctx* c, ZhipEncodeArgs& a, uint32_t g2, size_t cnt, hipStream_t stream)
 {
@@ -1071,6 +1077,19 @@ static void launch_entropy(const zhip_ctx* c, ZhipEncodeArgs& a, uint32_t g2, si
     hipLaunchKernelGGL(zhip_encode_entropy_kernel, dim3(g2), dim3(64), 0, stream, a);
     if (a.xxLater) { const size_t w = (cnt + 63) / 64, gm = (size_t)c->numCU * 8; hipLaunchKernelGGL(zhip_encode_trailer_kernel, dim3((uint32_t)(w < gm ? w : gm)), dim3(64), 0, stream, a); }      // EX
     a.xxLater = 0;
+}
+// the arena of the calls that run no match search of the library's (ZeSlotPlan): no room for a whole chunk's slots: half as many sources per launch, down to 64, before the call fails
+static int reserve_slots(zhip_ctx* c, const ZePlanDevice& dev, ZeSlotPlan& s, ZhipEncodeArgs& a, uint32_t* g2)
+{
+    a.arenaStride = s.arenaStride; a.arenaLit = s.arenaLit; a.slotSrcMax = s.slotSrcMax;
+    while (c->encArena.reserve(s.chunk * (size_t)s.arenaStride)) {
+        if (g_reserveRc != ZHIP_ERR_NO_MEMORY || s.chunk <= 64) return g_reserveRc;
+        s.chunk = (s.chunk + 1) / 2;
+    }
+    *g2 = ze_entropy_grid(dev, s.chunk);
+    if (c->encMeta.reserve(s.chunk * sizeof(ZeMeta)) || c->encWorkspace.reserve((size_t)*g2 * ZE_E2_STRIDE + ZHIP_ENC_STRIDE)) return g_reserveRc;
+    a.workspace = (uint8_t*)c->encWorkspace.p; a.meta = (ZeMeta*)c->encMeta.p; a.arena = (uint8_t*)c->encArena.p;
+    return 0;
 }
 extern "C" int zhip_ctx_set_match_finder(zhip_ctx* c, int finder)
 {
@@ -1086,37 +1105,181 @@ static int compress_batch_wave(zhip_ctx* c, ZhipEncodeArgs& a, uint8_t* cbase, s
     // something else (level 4), those sources are refused one by one
     if (c->hasCDict) { g_lastError = "the wave match finder (ZHIP_FINDER_WAVE) does not take a dictionary"; return ZHIP_ERR_UNSUPPORTED; }
     if (a.rows.r[2][6] != 1 && a.rows.r[2][6] != 2) { g_lastError = "the wave match finder (ZHIP_FINDER_WAVE) serves the levels whose one-block row is fast or double-fast (levels <= 4, negative levels, explicit strategy 1 / 2)"; return ZHIP_ERR_UNSUPPORTED; }
-    a.arenaStride = (uint32_t)(ZE_ARENA_LIT + 512); a.arenaLit = ZE_ARENA_LIT;      // sequences only (mode 4): the slot needs no literal area
-    size_t chunk = n < 65536 ? n : 65536;
-    if (c->knob.echunk && c->knob.echunk < chunk) chunk = c->knob.echunk;
-    while (c->encArena.reserve(chunk * (size_t)a.arenaStride)) {                      // no room for a whole chunk's slots: half as many sources per launch
-        if (g_reserveRc != ZHIP_ERR_NO_MEMORY || chunk <= 64) return g_reserveRc;
-        chunk = (chunk + 1) / 2;
-    }
-    const size_t g2max = (size_t)c->numCU * (size_t)c->e2PerCU, gwmax = (size_t)c->numCU * (size_t)c->wavePerCU[c->knob.waveH - 12];
-    const uint32_t g2 = (uint32_t)(chunk < g2max ? chunk : g2max);
-    if (c->encMeta.reserve(chunk * sizeof(ZeMeta)) || c->encWorkspace.reserve((size_t)g2 * ZE_E2_STRIDE + ZHIP_ENC_STRIDE)) return g_reserveRc;
-    a.workspace = (uint8_t*)c->encWorkspace.p; a.meta = (ZeMeta*)c->encMeta.p; a.arena = (uint8_t*)c->encArena.p;
-    a.idle = cbase + 256;
+    const ZePlanIn in = plan_inputs(c, n);
+    ZeSlotPlan s = ze_wave_plan(in);
+    uint32_t g2 = 0;
+    if (int rc = reserve_slots(c, in.dev, s, a, &g2)) return rc;
+    const size_t chunk = s.chunk, gwmax = (size_t)c->numCU * (size_t)c->wavePerCU[c->knob.waveH - 12];
     for (size_t first = 0; first < n; first += chunk) {
         const size_t cnt = n - first < chunk ? n - first : chunk;
         a.first = (uint32_t)first; a.count = (uint32_t)cnt;
-        HIP_TRY(hipMemsetAsync(cbase + 8, 0, 8, stream));
-        const bool tm = c->timing;
-        hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // wave kernel: ev[0] .. ev[1], entropy + trailer: ev[2] .. ev[3] (a timer owns both events of its pairs, so the two stages share none)
-        // (an event call that fails gives back the chunk's events before the error is returned)
-        auto dropEvents = [&](hipError_t e) { if (e != hipSuccess) for (hipEvent_t& x : ev) if (x) { (void)hipEventDestroy(x); x = nullptr; } return e; };
-        if (tm) { for (int i = 0; i < 4; i++) HIP_TRY(dropEvents(hipEventCreate(&ev[i]))); HIP_TRY(dropEvents(hipEventRecord(ev[0], stream))); }
+        HIP_TRY(hipMemsetAsync(cbase + ZC_E1_WORK, 0, 8, stream));
+        ChunkEvents ev;      // wave kernel: 0 .. 1, entropy + trailer: 2 .. 3
+        if (c->timing) HIP_TRY(ev.create(4));
+        HIP_TRY(ev.record(0, stream));
         const dim3 g((uint32_t)(cnt < gwmax ? cnt : gwmax)), b(64);
         if (c->knob.waveH == 12) hipLaunchKernelGGL(zhip_encode_match_wave_kernel<12>, g, b, 0, stream, a);
         else if (c->knob.waveH == 14) hipLaunchKernelGGL(zhip_encode_match_wave_kernel<14>, g, b, 0, stream, a);
         else hipLaunchKernelGGL(zhip_encode_match_wave_kernel<13>, g, b, 0, stream, a);
-        if (tm) { HIP_TRY(dropEvents(hipEventRecord(ev[1], stream))); HIP_TRY(dropEvents(hipEventRecord(ev[2], stream))); }
+        HIP_TRY(ev.record(1, stream)); HIP_TRY(ev.record(2, stream));
         launch_entropy(c, a, g2, cnt, stream);
-        if (tm) { HIP_TRY(dropEvents(hipEventRecord(ev[3], stream))); c->timer[10].pending.emplace_back(ev[0], ev[1]); c->timer[6].pending.emplace_back(ev[2], ev[3]); }
+        HIP_TRY(ev.record(3, stream));
+        ev.give(c->timer[10], 0, 1); ev.give(c->timer[6], 2, 3);
         HIP_TRY(hipGetLastError());
     }
     return 0;
+}
+// frames per launch of the flat match kernel for a batch above 65 536 (ZePlan::flatMaxOpen): 131 072 where the device has `need` bytes free, asked once per context
+// (hipMemGetInfo is not a launch-path call)
+static size_t flat_max_decided(zhip_ctx* c, size_t need)
+{
+    if (!c->flatMaxCached) {
+        size_t freeB = 0, totalB = 0;
+        c->flatMaxCached = 65536;
+        if (hipMemGetInfo(&freeB, &totalB) == hipSuccess && freeB + c->encFlatTables.cap + c->encArena.cap >= need) c->flatMaxCached = 131072;
+    }
+    return c->flatMaxCached;
+}
+// A launch of a flat search on `tables`: the next launch number for its cells (ZhipEncodeArgs.tabEpoch), the tables zeroed where the numbers start again. `zeroed` comes
+// back false when the plan's tables carry no launch numbers (ZePlan::epochShift) and the caller zeroes them as before. Changes the context's encEpoch* fields and `args` only.
+static int next_epoch(zhip_ctx* c, const ZePlan& p, ZhipEncodeArgs& args, uint8_t* tables, uint64_t gen, size_t bytes, hipStream_t stream, bool* zeroed)
+{
+    args.tabEpoch = 0; args.tabEpochShift = 31; *zeroed = false;
+    if (!p.epochShift) return 0;
+    *zeroed = true;
+    const uint32_t es = p.epochShift, maxE = (1u << (32 - es)) - 1;
+    const uint64_t key = (p.flatDict ? c->cdictKey : 0x9E3779B97F4A7C15ull) ^ p.epochKeyLayout;
+    if (tables != c->encEpochPtr || gen != c->encEpochGen || es != c->encEpochShift || key != c->encEpochKey || c->encEpoch >= maxE || bytes > c->encEpochBytes) {
+        HIP_TRY(hipMemsetAsync(tables, 0, bytes, stream));
+        c->encEpoch = 0; c->encEpochPtr = tables; c->encEpochGen = gen; c->encEpochShift = es; c->encEpochKey = key; c->encEpochBytes = bytes;
+    }
+    args.tabEpoch = ++c->encEpoch; args.tabEpochShift = es;
+    return 0;
+}
+// Picking the tables' placement (round 5). The flat match kernel's time for one and the same launch differs by ~14 % with WHERE the driver put
+// this 25 GiB allocation (397-415 ms or 455-488 per 65 536 frames; sticky for the life of the allocation, not controllable
+// through the allocator) -- and two allocations held at the same time are different memory. So the first large launch of a context times the
+// real kernel on its tables, reserves a second set beside them, times that, and keeps the faster (tests/tools/e1f_pick_best.py, r05g: in every
+// trial at least one of three candidates was the fast kind, and the best stayed the best). Costs two extra launches of the kernel and a transient
+// second table allocation, once per context; skipped where the second set does not fit. ZHIP_E1F_PICK=0 turns it off.
+// Leaves the kept tables in c->encFlatTables and a.flatTables.
+static int pick_table_placement(zhip_ctx* c, const ZePlan& p, ZhipEncodeArgs& a, hipStream_t stream)
+{
+    if (!p.flat || p.mbc || !c->knob.e1fPick || p.chunk < ZHIP_PICK_MIN || (c->e1fPicked && c->e1fPickedPtr == c->encFlatTables.p)) return 0;      // (again when a larger batch made the context reallocate its tables)
+    c->e1fPicked = true; c->e1fPickKept = 0; c->e1fPickMs[1] = c->e1fPickMs[2] = 0;
+    uint8_t* const cbase = (uint8_t*)c->counter.p;
+    uint8_t* const flatTables = a.flatTables;
+    const size_t cnt0 = p.chunk, bytes = p.flatTablesBytes;
+    DevBuf cand;
+    struct PickGuard { DevBuf& b; ~PickGuard() { b.release(); } } pickGuard{cand};
+    ChunkEvents ev;
+    if (ev.create(2) == hipSuccess) {
+        const hipEvent_t e0 = ev.ev[0], e1 = ev.ev[1];
+        ZhipEncodeArgs pa = a; pa.first = 0; pa.count = (uint32_t)cnt0;
+        // (round 6, last session: a probe searches the first 8 KiB of every source only. What makes an allocation the slow kind shows in any stretch of the launch -- eight
+        // candidates in each of six processes, whole launch / first 8 KiB: 405-412 ms / 30.1-30.5 or 468-485 / 35.7-36.4, never out of order (profiles/r06zzr_pick_study.txt) --
+        // so a candidate costs ~35 ms instead of ~450, the first large launch of a context 0.1-0.2 s instead of 1.3, and three slow candidates in a row (one time in eleven
+        // at this box's 4 in 9) get three more tries by the rule below instead of a slow context)
+        pa.probeCap = p.flatDict ? 0u : 8192u;
+        auto timeOn = [&](uint8_t* t, float* ms) -> int {
+            pa.flatTables = t;
+            HIP_TRY(hipMemsetAsync(cbase + ZC_E1_WORK, 0, 8, stream)); HIP_TRY(hipMemsetAsync(cbase + ZC_BIG_COUNT, 0, 12, stream));
+            {   bool z = false;                                                    // (launch numbers in the cells: a candidate allocation is zeroed once, by next_epoch)
+                if (int rc = next_epoch(c, p, pa, t, t == (uint8_t*)cand.p ? cand.gen : c->encFlatTables.gen, bytes, stream, &z)) return rc;
+                if (!z && !p.flatDict) { HIP_TRY(hipMemsetAsync(t, 0, bytes, stream)); c->encEpochPtr = nullptr; } }
+            HIP_TRY(hipEventRecord(e0, stream));
+            launch_match(p.pick, stream, pa);
+            HIP_TRY(hipEventRecord(e1, stream));
+            HIP_TRY(hipEventSynchronize(e1));
+            HIP_TRY(hipEventElapsedTime(ms, e0, e1));
+            return 0;
+        };
+        // three candidates: the context's own tables, then two further sets, each reserved beside the best so far (r05g / r05h: 397-415 or 455-488 ms per
+        // 65 536 frames; 746-764, 805, 855, 928 per 131 072); the fastest is kept
+#if ZHIP_PICK_STUDY
+        // DIAGNOSTIC build: eight candidate allocations, each timed whole and over the sources' first 8 KiB; the probe's waves leave their durations (wall clock, 10 ns units), printed
+        // as the mean of each sixteenth of the allocation -- is a slow allocation slow everywhere?
+        {   const uint32_t cap0 = pa.probeCap;
+            const size_t nw = (cnt0 + 63) / 64;
+            unsigned long long* dClock = nullptr; HIP_TRY(hipMalloc((void**)&dClock, nw * 8));
+            std::vector<unsigned long long> hClock(nw);
+            for (int k = 0; k < (ZHIP_PICK_STUDY > 1 ? ZHIP_PICK_STUDY : 8); k++) {            // (-DZHIP_PICK_STUDY=n, n > 1: n candidates, whole launches for the first eight only)
+                uint8_t* t = flatTables;
+                if (k) { if (cand.reserve(bytes)) { (void)hipGetLastError(); break; } t = (uint8_t*)cand.p; }
+                float whole = 0, probe = 0;
+                pa.probeCap = 0; if (k < 8) if (int rc = timeOn(t, &whole)) return rc;
+                HIP_TRY(hipMemsetAsync(dClock, 0, nw * 8, stream));
+                pa.probeCap = 8192; pa.waveClock = dClock; if (int rc = timeOn(t, &probe)) return rc;
+                pa.waveClock = nullptr; pa.probeCap = cap0;
+                HIP_TRY(hipMemcpy(hClock.data(), dClock, nw * 8, hipMemcpyDeviceToHost));
+                char line[512]; int o = 0; unsigned long long mn = ~0ull, mx = 0;
+                for (int q = 0; q < 16; q++) { double sum = 0; size_t lo = nw * q / 16, hi = nw * (q + 1) / 16; for (size_t w = lo; w < hi; w++) { sum += (double)hClock[w]; if (hClock[w] < mn) mn = hClock[w]; if (hClock[w] > mx) mx = hClock[w]; }
+                                               o += snprintf(line + o, sizeof line - o, " %.2f", sum / (double)(hi - lo ? hi - lo : 1) / 1e5); }
+                fprintf(stderr, "[zhip-pick-study] candidate %d %p whole %.1f ms, first 8 KiB %.1f; waves' ms by sixteenth of the allocation:%s (min %.2f max %.2f)\n", k, (void*)t, whole, probe, line, mn / 1e5, mx / 1e5);
+                if (k) cand.release();
+            }
+            (void)hipFree(dClock);
+        }
+#endif
+        float best = 0;
+        if (int rc = timeOn(flatTables, &best)) return rc;
+        c->e1fPickMs[0] = best;
+        // (round 6: where a probe is cheap -- dictionary batches: ~40 ms and 12 GiB a candidate -- and the first three came out ALIKE, which says they are one kind but not
+        // which, up to three more are tried until one is clearly faster: a dictionary batch's candidates are the fast kind one time in three, 35.4 ms against 41-42
+        // (r06u: [35.6, 42.1, 42.1], [42.3, 35.3, 42.1]; r06z: [41.1, 40.9, 41.2] -- all slow, 23.2 GB/s instead of 26.5), so three of them are all slow three runs in ten)
+        // (round 6, last session: EIGHT candidates, always. With probes at ~35 ms there is no reason to stop at the first fast one, and there is a third kind: the wave-clock study
+        // (profiles/r06zzv_wave_clocks.txt) found allocations at 388-392 ms per 65 536 sources beside the 406-417 and 467-473 ones -- one candidate in eight, the eighth in each of
+        // three processes; an allocation's kind is the same over all of its sixteenths, so there is nothing to pick INSIDE one)
+        // (a released candidate's memory does not come back at once: the EIGHTH 28 GiB reservation of a 65 536-source context, with ~70 GiB of the process's own in use, waited
+        // 4.7 s for the driver to reclaim what the earlier candidates had left -- profiles/r06zzz6_pick_candidates_cost.txt -- where every other one took 0.3 ms. So the candidates'
+        // reservations together stay inside what was free when the pick began, less one more set and 8 GiB: seven candidates there, two at 131 072 sources per launch)
+        float worst = best;
+        size_t free0 = 0, total0 = 0;
+        if (hipMemGetInfo(&free0, &total0) != hipSuccess) { (void)hipGetLastError(); free0 = 0; }
+        const size_t want = bytes + (bytes >> 3) + 4096;
+        for (int k = 1; k < ZHIP_PICK_CANDIDATES; k++) {
+            if ((size_t)k * want + want + ((size_t)8 << 30) > free0) break;
+            const auto tc0 = std::chrono::steady_clock::now();
+            if (cand.reserve(bytes)) { (void)hipGetLastError(); break; }                 // no room for another set: keep what we have
+            const auto tc1 = std::chrono::steady_clock::now();
+            float ms = 0;
+            if (int rc = timeOn((uint8_t*)cand.p, &ms)) return rc;
+            if (c->knob.prof) fprintf(stderr, "[zhip-prof] pick candidate %d: reserve %.1f ms, zero + probe %.1f ms (the probe launch %.1f)\n", k,
+                                      std::chrono::duration<double, std::milli>(tc1 - tc0).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc1).count(), ms);
+            if (k < 3) c->e1fPickMs[k] = ms;
+            if (ms > worst) worst = ms;
+            if (ms < 0.97f * best) { std::swap(c->encFlatTables.p, cand.p); std::swap(c->encFlatTables.cap, cand.cap); std::swap(c->encFlatTables.gen, cand.gen); best = ms; c->e1fPickKept = k; }
+            cand.release();
+            // (no early stop among the first three: at 131 072 frames per launch the kinds are not two but a spread -- 750, 805, 855, 928 ms, r05n / r05u -- so all three are timed)
+        }
+        a.flatTables = (uint8_t*)c->encFlatTables.p;
+    } else (void)hipGetLastError();
+    c->e1fPickedPtr = c->encFlatTables.p;
+    return 0;
+}
+// a chunk's flat match stage: fresh tables, then what the chunk's plan names -- with the split kernel in front and the several-block search behind it where the plan has
+// sources of several blocks in the flat kernel. Events 0 .. 1 of the chunk around the kernels.
+static int launch_flat_stage(zhip_ctx* c, const ZePlan& p, const ZeChunkPlan& k, ZhipEncodeArgs& a, size_t cnt, ChunkEvents& ev, hipStream_t stream)
+{
+    // every launch its own number in the tables' cells (the tables serve other sources now), or -- where the cells carry none -- zeroed tables
+    bool z = false;
+    if (int rc = next_epoch(c, p, a, a.flatTables, c->encFlatTables.gen, p.flatTablesBytes, stream, &z)) return rc;
+    if (!z && !p.flatDict) { HIP_TRY(hipMemsetAsync(a.flatTables, 0, cnt * (size_t)a.tableStride, stream)); c->encEpochPtr = nullptr; }      // (cells without numbers in the tables now: the next numbered launch starts from zeroed tables)
+    HIP_TRY(ev.record(0, stream));
+    a.mbProbes = k.mbProbes;
+    if (p.mbc) hipLaunchKernelGGL(zhip_encode_split_kernel, dim3((uint32_t)(cnt < (size_t)c->numCU * 8 ? cnt : (size_t)c->numCU * 8)), dim3(64), 0, stream, a);
+    launch_match(k, stream, a);
+    if (p.mbc) hipLaunchKernelGGL(zhip_encode_match_flat_mb_kernel, dim3((uint32_t)((cnt + a.mbLanes - 1) / a.mbLanes)), dim3(64), 0, stream, a);
+    HIP_TRY(ev.record(1, stream));
+    return 0;
+}
+// the generic one-wave-per-frame kernel over the list the match kernels made, on a workspace and a work counter of its own
+static void launch_big_list(const zhip_ctx* c, const ZePlan& p, const ZhipEncodeArgs& a, hipStream_t stream)
+{
+    ZhipEncodeArgs b = a;
+    b.workspace = (uint8_t*)c->encBigWs.p; b.counter = (uint32_t*)((uint8_t*)c->counter.p + ZC_BIG_WORK);
+    b.frameList = a.bigList; b.listCount = a.bigCount;
+    hipLaunchKernelGGL(zhip_encode_frames_kernel, dim3(p.gBig), dim3(64), 0, stream, b);
 }
 extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
                                           void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
@@ -1126,376 +1289,84 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
     if (n == 0) return 0;
     if (n > 0x7FFFFFFFu) { g_lastError = "too many frames in one launch"; return ZHIP_ERR_UNSUPPORTED; }
     hipStream_t stream = (hipStream_t)streamv;
-    size_t maxBlocks = (size_t)c->numCU * (size_t)c->encBlocksPerCU;
-    uint32_t grid = (uint32_t)(n < maxBlocks ? n : maxBlocks);
     if (c->counter.reserve(64 * 8)) return g_reserveRc;
     uint8_t* const cbase = (uint8_t*)c->counter.p;
-    HIP_TRY(hipMemsetAsync(cbase + 8, 0, 4, stream));
+    HIP_TRY(hipMemsetAsync(cbase + ZC_E1_WORK, 0, 4, stream));
     ZhipEncodeArgs a; enc_args_init(c, a, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, cbase);
     if (c->matchFinder == ZHIP_FINDER_WAVE) return compress_batch_wave(c, a, cbase, n, stream);
-    {
-        // two kernels: E1 searches with one LANE per frame (frames in flight hide the probe latency), E2 entropy-codes with one
-        // wave per frame. Frames are processed in chunks so that the per-frame sequence/literal arena stays bounded.
-        // table bytes of the largest one-block source of the two size classes these kernels serve (<= 128 KiB, <= 16 KiB), after the
-        // per-source adjustment ze_get_cparams makes (windowLog <= 17 / 14, hashLog <= windowLog + 1, chainLog <= windowLog)
-        // (greedy: the row match finder's positions and tags, 5 << hashLog bytes -- 640 KiB at level 5; only the row of 16 385 ... 131 072-byte sources can be served, ze_get_cparams)
-        const bool greedy = !c->hasCDict && a.rows.r[2][6] == 3 && a.rows.r[2][0] >= 15 && a.rows.r[2][3] <= 4;
-        bool anyDfast = false; uint32_t stride = 0;
-        for (int t = 2; t < 4; t++) {
-            const int32_t* r = a.rows.r[t];
-            if (r[6] != 1 && r[6] != 2 && !(greedy && t == 2)) continue;
-            const int w = r[0] < (t == 2 ? 17 : 14) ? r[0] : (t == 2 ? 17 : 14);
-            const int h = r[2] > w + 1 ? w + 1 : r[2], cl = r[1] > w ? w : r[1];
-            const uint32_t bytes = r[6] == 3 ? (5u << h) : (4u << h) + (r[6] == 2 ? (4u << cl) : 0u);
-            if (bytes > stride) stride = bytes;
-            anyDfast |= r[6] == 2;
-        }
-        // (sources of several blocks in the flat kernel -- `mbc` below: the rows of the larger size classes count too, at the hint's size)
-        const size_t sizeHint = c->srcMaxHint ? c->srcMaxHint : c->itemHint;
-        // (worth it from ~8 000 sources on. Either kernel's time is a source's serial chain of probes -- ~0.2 s per 128 KiB of source at these
-        // batch sizes -- times the ROUNDS it needs: the generic kernel holds ~4 096 searches at a time (one per wave), the flat one a whole chunk
-        // (64 per wave, whose every trip waits for the slowest of 64 requests and runs every lane's branch: ~10 % slower per round at 256 KiB,
-        // 50 % at 512 KiB+). r03u / r03v, flat against generic: 2 048 x 1 MiB 2.5 s / 1.04 s, 4 096 x 512 KiB 1.31 / 0.85, 4 096 x 256 KiB
-        // 0.44 / 0.42, 8 192 x 256 KiB 0.47 / 0.68, 16 384 x 256 KiB 0.51 / 1.24, 8 192 x 1 MiB 3.3 / ~2.1: the longer the sources the more
-        // rounds of the generic kernel it takes to lose, hence the threshold grows with the size hint -- ZHIP_MBC_MIN sources per 256 KiB of it.
-        // Round 6's kernels, flat / generic (r06zzi): 3 072 x 256 KiB 340 / 325 ms, 4 096 x 256 KiB 351 / 420, 6 144 x 384 KiB 810 / 846, 4 096 x 512 KiB 1 075 / 860,
-        // 8 192 x 512 KiB 1 191 / 1 417, 12 288 x 512 KiB 1 639 / 1 965, 2 048 x 1 MiB 1 950 / 1 034: the flat search wins from 4 096 per 256 KiB on, was 8 192)
-        const bool mbcWanted = anyDfast && !c->hasCDict && n >= c->knob.mbcMin * ((sizeHint + (256u << 10) - 1) / (256u << 10)) && sizeHint > ZF_BLOCK_MAX && sizeHint < ((size_t)1 << ZE_MB_POS_BITS) - 8;
-        if (mbcWanted) for (int t = 0; t < 2; t++) {
-            const int32_t* r = a.rows.r[t];
-            if (r[6] != 2) continue;
-            int w = 17; while (((size_t)1 << w) < sizeHint) w++;
-            if (w > r[0]) w = r[0];
-            const int h = r[2] > w + 1 ? w + 1 : r[2], cl = r[1] > w ? w : r[1];
-            const uint32_t bytes = (4u << h) + (4u << cl);
-            if (bytes > stride && bytes <= (12u << 17)) stride = bytes;
-        }
-        if (stride < (4u << 10)) stride = 4u << 10;
-        if (stride > (12u << 17)) stride = 12u << 17;                  // larger tables: the frame is refused loudly by the match kernels
-        a.arenaStride = (uint32_t)ZE_ARENA_STRIDE; a.arenaLit = ZE_ARENA_LIT;
-        if (c->hasCDict) {
-            stride = enc_dict_slots(c, sizeHint, a);
-        }
-        a.tableStride = stride;
-        // double-fast without a dictionary: the flat match kernel (one lane per frame, the whole chunk in flight, tables zeroed by a
-        // memset) takes every double-fast frame; what it declines goes to the lane-serial kernel through a list. Dictionary batches of the
-        // fast strategy, and fast batches of several-block sources, use the lane-serial kernel for the whole chunk.
-        // (r03: dictionary batches whose dictionary row is double-fast take the flat kernel too -- ze_dfast_dict_flat; its waves zero the tables)
-        const bool flatDict = c->hasCDict && c->cdictStrat == 2;
-        // (round 7) the fast strategy without a dictionary has a flat search too (ze_fast_flat_np): when BOTH one-block rows are fast the fast form of the kernel is
-        // launched, which takes the fast sources and leaves nothing but errors and tiny sources to the lane-serial kernel. A batch whose two one-block rows differ
-        // (explicit parameters cannot do that, the level tables do not) keeps the double-fast kernel, which hands its fast sources to the lane-serial search.
-        // Batches whose size hint says "sources of several blocks" stay where they were: the lane-serial kernel's chunk shapes (fastWide below), which only list such sources.
-        const bool flatFast = !c->hasCDict && a.rows.r[2][6] == 1 && a.rows.r[3][6] == 1 && sizeHint <= ZF_BLOCK_MAX;
-        const bool flat = (anyDfast && !c->hasCDict) || flatDict || flatFast;
-        // (round 5) every row double-fast, no dictionary: the flat kernel takes every one-block source of 64 bytes and more and writes sequences only, and what
-        // it declines -- sources below 64 bytes, parameter errors -- needs a literal area of its own size at most: the slot is the sequence area + 512 bytes
-        // instead of + 128 KiB (21.4 GiB of arena per 65 536 sources instead of 30; it is what lets 262 144 sources be one launch, 88 + 96 GiB)
-        // (round 7: every row fast OR double-fast. Whichever form of the flat kernel runs, the one-block sources it declines for their strategy are fast ones,
-        // and the lane-serial fast search writes sequences only as well)
-        bool allDfast = (anyDfast || flatFast) && !c->hasCDict; for (int t = 0; t < 4; t++) allDfast = allDfast && (a.rows.r[t][6] == 2 || a.rows.r[t][6] == 1);
-        if (flat && allDfast) a.arenaStride = (uint32_t)(ZE_ARENA_LIT + 512);
-        // frames per launch of the flat match kernel: the search is a latency chain per frame, so its rate grows with the frames in flight -- 16 384: 204 ms,
-        // 32 768: 270, 65 536: 417, 131 072: 760 (r04za: 9 % less per frame than two launches of 65 536, a second wave per SIMD) -- and what it costs
-        // is memory, 384 KiB of tables + 196 KiB of arena per frame. Batches above 65 536 take 131 072 per launch where the device has that free.
-        // (the decision is taken once per context -- hipMemGetInfo is not a launch-path call -- and a reservation that fails at 131 072
-        // after all, because another context took the memory in between, falls back to 65 536 below instead of failing the call)
-        size_t flatMax = c->knob.echunkMax;
-        if (!flatMax) {
-            flatMax = 65536;
-            if (flat && !c->hasCDict && n > 65536) {
-                if (!c->flatMaxCached) {
-                    size_t freeB = 0, totalB = 0;
-                    c->flatMaxCached = 65536;
-                    if (hipMemGetInfo(&freeB, &totalB) == hipSuccess) {
-                        const size_t need = (size_t)131072 * ((size_t)a.tableStride + (size_t)a.arenaStride) / 8 * 9 + ((size_t)4 << 30);
-                        if (freeB + c->encFlatTables.cap + c->encArena.cap >= need) c->flatMaxCached = 131072;
-                    }
-                }
-                flatMax = c->flatMaxCached;
-            }
-        }
-        // (the fast strategy -- levels 1, 2, negative -- where it still runs in the lane-serial match kernel, i.e. under a size hint above one block: its time is ONE source's chain of dependent round trips: every source in flight at once
-        // is one chain's time, two chunks of 32 768 are two. ZHIP_FAST_WIDE: 65 536 per chunk, sixteen sources per wave -- the kernel's 111 VGPRs hold 4 096 waves)
-        const bool fastWide = ZHIP_FAST_WIDE && !flat && !c->hasCDict && n > 32768;
-        size_t chunkMax = c->hasCDict ? 262144 : flat ? flatMax : fastWide ? 65536 : 32768;
-        if (flat) { const size_t byMem = ((size_t)(flatMax > 65536 ? 96 : 32) << 30) / a.tableStride; if (chunkMax > byMem) chunkMax = byMem; }
-        if (c->knob.echunk && c->knob.echunk < chunkMax) chunkMax = c->knob.echunk;
-        // Sources of several blocks (the caller's size hint says so) in a double-fast batch without dictionary: the flat kernel searches them
-        // too, a lane per frame over all its blocks (ZeMbBlock, zhip_format.hpp); the generic kernel then only does their entropy coding and
-        // runs once per chunk. Per frame: block records and room for its sequences (a sequence covers four bytes or more).
-        const bool mbc = flat && !flatDict && mbcWanted;
-        const size_t mbMaxBlocks = mbc ? 2 * ((sizeHint + ZF_BLOCK_MAX - 1) / ZF_BLOCK_MAX) + 2 : 0;
-        const size_t mbSeqCap = mbc ? sizeHint / 4 + mbMaxBlocks + 64 : 0;          // (double-fast matches are four bytes or more: zstd.c:31167 / :31150)
-        if (mbc) { const size_t byMem = ((size_t)32 << 30) / (mbSeqCap * 8); if (chunkMax > byMem) chunkMax = byMem ? byMem : 1; }
-        const size_t chunk = n < chunkMax ? n : chunkMax;
-        const size_t cap = chunk;                                              // items the arenas are sized for
-        const size_t laneCap = c->hasCDict ? 262144 : fastWide ? 65536 : 32768;          // lanes of the lane-serial match kernel in flight (each owns tableStride bytes of tables)
-        const size_t e1Lanes = c->hasCDict ? ZE_E1_LANES_DICT : fastWide ? 16 : ZE_E1_LANES;
-        a.e1Lanes = (uint32_t)e1Lanes;
-        size_t g1max = (size_t)c->numCU * (size_t)c->e1PerCU; if (g1max * e1Lanes > laneCap) g1max = laneCap / e1Lanes;
-        if (flat && g1max > 256) g1max = 256;                                      // only the frames the flat kernel declines
-        if (greedy) { const size_t byMem = ((size_t)8 << 30) / (e1Lanes * (size_t)a.tableStride); if (g1max > byMem) g1max = byMem ? byMem : 1; }      // (row tables: 8 GiB of them at most, 1 638 waves at level 5)
-        const size_t w1 = (chunk + e1Lanes - 1) / e1Lanes;
-        const uint32_t g1 = (uint32_t)(w1 < g1max ? w1 : g1max);
-        size_t g2max = (size_t)c->numCU * (size_t)c->e2PerCU;
-        const uint32_t g2 = (uint32_t)(chunk < g2max ? chunk : g2max);
-        const size_t w1cap = (cap + e1Lanes - 1) / e1Lanes, g1cap = w1cap < g1max ? w1cap : g1max, g2cap = cap < g2max ? cap : g2max;
-        // waves for what the generic kernel takes: inputs above one block, and -- with a dictionary -- inputs above the attach cutoff
-        // (with a dictionary: inputs above the attach cutoff too. Every wave of this kernel carries 544 bytes of scratch per lane: a full-chip
-        // grid that finds an empty list still took 2.3 ms of every dictionary batch -- r02zi kernel trace; half a wave per CU is 0.4)
-        // (r03: when the caller says its sources exceed one block -- the host API knows, a device-API caller can tell with zhip_ctx_set_size_hint --
-        // the list is the whole batch and gets the whole chip: 2 048 x 1 MiB took 10.6 s on 64 waves, profiles/r03_multiblock_rate.txt)
-        const size_t gBigMax = sizeHint > ZF_BLOCK_MAX ? (size_t)c->numCU * (size_t)c->encBlocksPerCU : c->hasCDict ? (size_t)c->numCU / 2 : 64;
-        const uint32_t gBig = (uint32_t)(n < gBigMax ? n : gBigMax);
-        const size_t tabPer = g1cap * e1Lanes * a.tableStride, wsPer = g2cap * ZE_E2_STRIDE + ZHIP_ENC_STRIDE, bigListPer = n * sizeof(uint32_t) + 16,
-                     e1ListPer = cap * sizeof(uint32_t) + 16, bigWsPer = (size_t)gBig * ZHIP_ENC_STRIDE;
-        if (c->encMeta.reserve(cap * sizeof(ZeMeta)) || c->encArena.reserve(cap * (size_t)a.arenaStride) ||
-            c->encTables.reserve(tabPer) || c->encWorkspace.reserve(wsPer) ||
-            c->encBigList.reserve(bigListPer) || c->encE1List.reserve(e1ListPer) ||
-            (flat && c->encFlatTables.reserve(cap * (size_t)a.tableStride))) {
-            if (g_reserveRc == ZHIP_ERR_NO_MEMORY && !c->knob.echunkMax && c->flatMaxCached > 65536) {      // no room for 131 072 per launch after all: 65 536
-                c->flatMaxCached = 65536; c->encArena.release(); c->encFlatTables.release();
-                return zhip_compress_batch_device(c, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, streamv);
-            }
-            return g_reserveRc;
-        }
-        if (mbc) {
-            if (c->encMbBlocks.reserve(chunk * mbMaxBlocks * sizeof(ZeMbBlock)) || c->encMbCount.reserve(chunk * sizeof(uint32_t) + 16) ||
-                c->encMbSeqs.reserve(chunk * mbSeqCap * 8)) return g_reserveRc;
-            a.mbBlocks = (ZeMbBlock*)c->encMbBlocks.p; a.mbCount = (uint32_t*)c->encMbCount.p; a.mbSeqs = (uint64_t*)c->encMbSeqs.p;
-            a.mbMaxBlocks = (uint32_t)mbMaxBlocks; a.mbSeqCap = (uint32_t)mbSeqCap; a.mbLanes = c->knob.mbcLanes; a.mbProbes = chunk * ((sizeHint + ZF_BLOCK_MAX - 1) / ZF_BLOCK_MAX) <= c->knob.flat4Max ? 4u : 2u;        // (the traffic in flight is sources x blocks each: 16 384 x 256 KiB 7.9 -> 8.9 GB/s with four probes, 32 768 x 256 KiB 12.0 -> 11.8, r04zj)
-            if (c->encBigWs.reserve((size_t)gBig * ZHIP_ENC_STRIDE)) return g_reserveRc;
-        }
-        a.workspace = (uint8_t*)c->encWorkspace.p;
-        a.meta = (ZeMeta*)c->encMeta.p; a.arena = (uint8_t*)c->encArena.p; a.laneTables = (uint8_t*)c->encTables.p;
-        uint8_t* flatTables = flat ? (uint8_t*)c->encFlatTables.p : nullptr;
-        a.flatTables = flatTables; a.e1List = (uint32_t*)c->encE1List.p; a.e1Count = (uint32_t*)(cbase + 32);
-        a.idle = cbase + 256;                                                       // (the context's own counter block: ADVICE r04 -- the caller's arena base need not be readable)
-        a.useE1List = flat ? 1u : 0u;
-        a.bigList = (uint32_t*)c->encBigList.p; a.bigCount = (uint32_t*)(cbase + 24);
-        // Picking the tables' placement (round 5). The flat match kernel's time for one and the same launch differs by ~14 % with WHERE the driver put
-        // this 25 GiB allocation (397-415 ms or 455-488 per 65 536 frames; sticky for the life of the allocation, not controllable
-        // through the allocator) -- and two allocations held at the same time are different memory. So the first large launch of a context times the
-        // real kernel on its tables, reserves a second set beside them, times that, and keeps the faster (tests/tools/e1f_pick_best.py, r05g: in every
-        // trial at least one of three candidates was the fast kind, and the best stayed the best). Costs two extra launches of the kernel and a transient
-        // second table allocation, once per context; skipped where the second set does not fit. ZHIP_E1F_PICK=0 turns it off.
-        // The dictionary search's tables are not zeroed per launch: a cell carries its launch's number above the index and reads as empty under any other number.
-        // The index space is 2 + the dictionary's content + a source (+ slack): what is left of 32 bits counts launches, at least 6 bits or the kernel zeroes as before.
-        // (the dictionary-less flat search of one-block sources does the same with six fixed bits: its cells are position 18 | tag 8 | launch number 6, ze_dfast_flat_np. `zeroed`
-        // comes back false when the tables carry no launch numbers -- the several-block search, an index space too wide -- and the caller zeroes them as before.)
-        auto nextEpoch = [&](ZhipEncodeArgs& args, uint8_t* tables, uint64_t gen, size_t bytes, bool* zeroed) -> int {
-            args.tabEpoch = 0; args.tabEpochShift = 31; *zeroed = false;
-            if (!ZHIP_TABLE_EPOCHS || !flat || mbc) return 0;
-            uint32_t es = 26;
-            if (flatDict) {
-                const uint64_t span = 2ull + c->cdictContentSize + (a.slotSrcMax ? a.slotSrcMax : c->cdictAttachMax) + 64;
-                es = 1; while ((1ull << es) < span) es++;
-            }
-            if (es > 26) return 0;
-            *zeroed = true;
-            const uint32_t maxE = (1u << (32 - es)) - 1;
-            // (the key tells table LAYOUTS apart: the dictionary, the slot size, and -- round 7 -- one table per slot (fast) or two (double-fast). The cells of both carry
-            // the launch number in the same six bits, so neither would read the other's as live inside one run of numbers; a change of layout zeroes and restarts anyway)
-            const uint64_t key = (flatDict ? c->cdictKey : 0x9E3779B97F4A7C15ull) ^ ((uint64_t)a.tableStride << 40) ^ (flatFast ? 0x00000000FA570000ull : 0ull);
-            if (tables != c->encEpochPtr || gen != c->encEpochGen || es != c->encEpochShift || key != c->encEpochKey || c->encEpoch >= maxE || bytes > c->encEpochBytes) {
-                HIP_TRY(hipMemsetAsync(tables, 0, bytes, stream));
-                c->encEpoch = 0; c->encEpochPtr = tables; c->encEpochGen = gen; c->encEpochShift = es; c->encEpochKey = key; c->encEpochBytes = bytes;
-            }
-            args.tabEpoch = ++c->encEpoch; args.tabEpochShift = es;
-            return 0;
-        };
-        if (flat && !mbc && c->knob.e1fPick && chunk >= ZHIP_PICK_MIN && (!c->e1fPicked || c->e1fPickedPtr != c->encFlatTables.p)) {      // (again when a larger batch made the context reallocate its tables)
-            c->e1fPicked = true; c->e1fPickKept = 0; c->e1fPickMs[1] = c->e1fPickMs[2] = 0;
-            const size_t cnt0 = chunk, bytes = cnt0 * (size_t)a.tableStride;
-            DevBuf cand;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            struct PickGuard { DevBuf& b; hipEvent_t& x; hipEvent_t& y; ~PickGuard() { b.release(); if (x) (void)hipEventDestroy(x); if (y) (void)hipEventDestroy(y); } } pickGuard{cand, e0, e1};
-            if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) {
-                ZhipEncodeArgs pa = a; pa.first = 0; pa.count = (uint32_t)cnt0;
-                // (round 6, last session: a probe searches the first 8 KiB of every source only. What makes an allocation the slow kind shows in any stretch of the launch -- eight
-                // candidates in each of six processes, whole launch / first 8 KiB: 405-412 ms / 30.1-30.5 or 468-485 / 35.7-36.4, never out of order (profiles/r06zzr_pick_study.txt) --
-                // so a candidate costs ~35 ms instead of ~450, the first large launch of a context 0.1-0.2 s instead of 1.3, and three slow candidates in a row (one time in eleven
-                // at this box's 4 in 9) get three more tries by the rule below instead of a slow context)
-                pa.probeCap = flatDict ? 0u : 8192u;
-                auto timeOn = [&](uint8_t* t, float* ms) -> int {
-                    pa.flatTables = t;
-                    HIP_TRY(hipMemsetAsync(cbase + 8, 0, 8, stream)); HIP_TRY(hipMemsetAsync(cbase + 24, 0, 12, stream));
-                    {   bool z = false;                                                    // (launch numbers in the cells: a candidate allocation is zeroed once, by nextEpoch)
-                        if (int rc = nextEpoch(pa, t, t == (uint8_t*)cand.p ? cand.gen : c->encFlatTables.gen, bytes, &z)) return rc;
-                        if (!z && !flatDict) { HIP_TRY(hipMemsetAsync(t, 0, bytes, stream)); c->encEpochPtr = nullptr; } }
-                    HIP_TRY(hipEventRecord(e0, stream));
-                    launch_flat(!flatDict && c->knob.flat3 && cnt0 <= c->knob.flat3Max ? 3 : 2, cnt0, stream, pa, flatFast ? 1 : 0);
-                    HIP_TRY(hipEventRecord(e1, stream));
-                    HIP_TRY(hipEventSynchronize(e1));
-                    HIP_TRY(hipEventElapsedTime(ms, e0, e1));
-                    return 0;
-                };
-                // three candidates: the context's own tables, then two further sets, each reserved beside the best so far (r05g / r05h: 397-415 or 455-488 ms per
-                // 65 536 frames; 746-764, 805, 855, 928 per 131 072); the fastest is kept
-#if ZHIP_PICK_STUDY
-                // DIAGNOSTIC build: eight candidate allocations, each timed whole and over the sources' first 8 KiB; the probe's waves leave their durations (wall clock, 10 ns units), printed
-                // as the mean of each sixteenth of the allocation -- is a slow allocation slow everywhere?
-                {   const uint32_t cap0 = pa.probeCap;
-                    const size_t nw = (cnt0 + 63) / 64;
-                    unsigned long long* dClock = nullptr; HIP_TRY(hipMalloc((void**)&dClock, nw * 8));
-                    std::vector<unsigned long long> hClock(nw);
-                    for (int k = 0; k < (ZHIP_PICK_STUDY > 1 ? ZHIP_PICK_STUDY : 8); k++) {            // (-DZHIP_PICK_STUDY=n, n > 1: n candidates, whole launches for the first eight only)
-                        uint8_t* t = flatTables;
-                        if (k) { if (cand.reserve(bytes)) { (void)hipGetLastError(); break; } t = (uint8_t*)cand.p; }
-                        float whole = 0, probe = 0;
-                        pa.probeCap = 0; if (k < 8) if (int rc = timeOn(t, &whole)) return rc;
-                        HIP_TRY(hipMemsetAsync(dClock, 0, nw * 8, stream));
-                        pa.probeCap = 8192; pa.waveClock = dClock; if (int rc = timeOn(t, &probe)) return rc;
-                        pa.waveClock = nullptr; pa.probeCap = cap0;
-                        HIP_TRY(hipMemcpy(hClock.data(), dClock, nw * 8, hipMemcpyDeviceToHost));
-                        char line[512]; int o = 0; unsigned long long mn = ~0ull, mx = 0;
-                        for (int q = 0; q < 16; q++) { double sum = 0; size_t lo = nw * q / 16, hi = nw * (q + 1) / 16; for (size_t w = lo; w < hi; w++) { sum += (double)hClock[w]; if (hClock[w] < mn) mn = hClock[w]; if (hClock[w] > mx) mx = hClock[w]; }
-                                                       o += snprintf(line + o, sizeof line - o, " %.2f", sum / (double)(hi - lo ? hi - lo : 1) / 1e5); }
-                        fprintf(stderr, "[zhip-pick-study] candidate %d %p whole %.1f ms, first 8 KiB %.1f; waves' ms by sixteenth of the allocation:%s (min %.2f max %.2f)\n", k, (void*)t, whole, probe, line, mn / 1e5, mx / 1e5);
-                        if (k) cand.release();
-                    }
-                    (void)hipFree(dClock);
-                }
-#endif
-                float best = 0;
-                if (int rc = timeOn(flatTables, &best)) return rc;
-                c->e1fPickMs[0] = best;
-                // (round 6: where a probe is cheap -- dictionary batches: ~40 ms and 12 GiB a candidate -- and the first three came out ALIKE, which says they are one kind but not
-                // which, up to three more are tried until one is clearly faster: a dictionary batch's candidates are the fast kind one time in three, 35.4 ms against 41-42
-                // (r06u: [35.6, 42.1, 42.1], [42.3, 35.3, 42.1]; r06z: [41.1, 40.9, 41.2] -- all slow, 23.2 GB/s instead of 26.5), so three of them are all slow three runs in ten)
-                // (round 6, last session: EIGHT candidates, always. With probes at ~35 ms there is no reason to stop at the first fast one, and there is a third kind: the wave-clock study
-                // (profiles/r06zzv_wave_clocks.txt) found allocations at 388-392 ms per 65 536 sources beside the 406-417 and 467-473 ones -- one candidate in eight, the eighth in each of
-                // three processes; an allocation's kind is the same over all of its sixteenths, so there is nothing to pick INSIDE one)
-                // (a released candidate's memory does not come back at once: the EIGHTH 28 GiB reservation of a 65 536-source context, with ~70 GiB of the process's own in use, waited
-                // 4.7 s for the driver to reclaim what the earlier candidates had left -- profiles/r06zzz6_pick_candidates_cost.txt -- where every other one took 0.3 ms. So the candidates'
-                // reservations together stay inside what was free when the pick began, less one more set and 8 GiB: seven candidates there, two at 131 072 sources per launch)
-                float worst = best;
-                size_t free0 = 0, total0 = 0;
-                if (hipMemGetInfo(&free0, &total0) != hipSuccess) { (void)hipGetLastError(); free0 = 0; }
-                const size_t want = bytes + (bytes >> 3) + 4096;
-                for (int k = 1; k < ZHIP_PICK_CANDIDATES; k++) {
-                    if ((size_t)k * want + want + ((size_t)8 << 30) > free0) break;
-                    const auto tc0 = std::chrono::steady_clock::now();
-                    if (cand.reserve(bytes)) { (void)hipGetLastError(); break; }                 // no room for another set: keep what we have
-                    const auto tc1 = std::chrono::steady_clock::now();
-                    float ms = 0;
-                    if (int rc = timeOn((uint8_t*)cand.p, &ms)) return rc;
-                    if (c->knob.prof) fprintf(stderr, "[zhip-prof] pick candidate %d: reserve %.1f ms, zero + probe %.1f ms (the probe launch %.1f)\n", k,
-                                              std::chrono::duration<double, std::milli>(tc1 - tc0).count(), std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tc1).count(), ms);
-                    if (k < 3) c->e1fPickMs[k] = ms;
-                    if (ms > worst) worst = ms;
-                    if (ms < 0.97f * best) { std::swap(c->encFlatTables.p, cand.p); std::swap(c->encFlatTables.cap, cand.cap); std::swap(c->encFlatTables.gen, cand.gen); best = ms; c->e1fPickKept = k; }
-                    cand.release();
-                    // (no early stop among the first three: at 131 072 frames per launch the kinds are not two but a spread -- 750, 805, 855, 928 ms, r05n / r05u -- so all three are timed)
-                }
-                flatTables = (uint8_t*)c->encFlatTables.p; a.flatTables = flatTables;
-            } else (void)hipGetLastError();
-            c->e1fPickedPtr = c->encFlatTables.p;
-        }
-        HIP_TRY(hipMemsetAsync(cbase + 24, 0, 8, stream));
-        if (c->knob.prof) {                                                         // tuning aid: per-phase cycle totals of the entropy kernel
-            if (!c->profEncode) HIP_TRY(hipMalloc((void**)&c->profEncode, 16 * 8));
-            HIP_TRY(hipMemsetAsync(c->profEncode, 0, 16 * 8, stream));
-            a.prof = c->profEncode;
-        }
-        for (size_t first = 0; first < n; first += chunk) {
-            const size_t cnt = n - first < chunk ? n - first : chunk;
-            a.first = (uint32_t)first; a.count = (uint32_t)cnt;
-            HIP_TRY(hipMemsetAsync(cbase + 8, 0, 8, stream));
-            HIP_TRY(hipMemsetAsync(cbase + 32, 0, 4, stream));
-            const bool tm = c->timing;
-            hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-            if (tm) for (int i = 0; i < 6; i++) HIP_TRY(hipEventCreate(&ev[i]));
-            if (flat) {
-                // every launch its own number in the tables' cells (the tables serve other sources now), or -- where the cells carry none -- zeroed tables
-                bool z = false;
-                if (int rc = nextEpoch(a, flatTables, c->encFlatTables.gen, cap * (size_t)a.tableStride, &z)) return rc;
-                if (!z && !flatDict) { HIP_TRY(hipMemsetAsync(flatTables, 0, cnt * (size_t)a.tableStride, stream)); c->encEpochPtr = nullptr; }      // (cells without numbers in the tables now: the next numbered launch starts from zeroed tables)
-                if (tm) HIP_TRY(hipEventRecord(ev[0], stream));
-                // a few frames: nothing hides the search's round trips, so each frame gets a CU and its source goes to LDS (ze_match_lds_body)
-                // (the LDS area follows the batch's largest source where the caller told us -- the host-buffer API does: more frames per CU)
-                const size_t hint = c->srcMaxHint ? c->srcMaxHint : (size_t)ZF_BLOCK_MAX;
-                const int shape = hint <= 4096 ? 0 : hint <= 16384 ? 1 : hint <= 65536 ? 2 : 3;
-                static const unsigned wavesPerCU[4] = { 32, 9, 2, 1 };          // by LDS (160 KiB per CU) and the 32-wave limit
-                const size_t rounds = shape == 3 ? ZHIP_E1LDS_PER_CU : c->knob.e1LdsRounds;
-                const size_t ldsMax = c->knob.e1LdsMax >= 0 ? (size_t)c->knob.e1LdsMax : (size_t)c->numCU * wavesPerCU[shape] * rounds;
-                if (mbc) hipLaunchKernelGGL(zhip_encode_split_kernel, dim3((uint32_t)(cnt < (size_t)c->numCU * 8 ? cnt : (size_t)c->numCU * 8)), dim3(64), 0, stream, a);
-                const int fastPairs = !flatFast ? 0 : c->knob.fastPairs ? c->knob.fastPairs : cnt <= c->knob.fast2Max ? 2 : 1;
-                if (cnt <= ldsMax && flatFast) {
-                    const dim3 g((uint32_t)cnt), b(64);
-                    if (shape == 0) hipLaunchKernelGGL((zhip_encode_match_lds_fast_kernel<4096, ZHIP_E1LDS_FAST_PAIRS>), g, b, 0, stream, a);
-                    else if (shape == 1) hipLaunchKernelGGL((zhip_encode_match_lds_fast_kernel<16384, ZHIP_E1LDS_FAST_PAIRS>), g, b, 0, stream, a);
-                    else if (shape == 2) hipLaunchKernelGGL((zhip_encode_match_lds_fast_kernel<65536, ZHIP_E1LDS_FAST_PAIRS>), g, b, 0, stream, a);
-                    else hipLaunchKernelGGL((zhip_encode_match_lds_fast_kernel<ZF_BLOCK_MAX, ZHIP_E1LDS_FAST_PAIRS>), g, b, 0, stream, a);
-                }
-                else if (cnt <= ldsMax && !flatDict && !mbc) {
-                    const dim3 g((uint32_t)cnt), b(64);
-                    if (shape == 0) hipLaunchKernelGGL((zhip_encode_match_lds_kernel<4096, ZHIP_E1LDS_PROBES>), g, b, 0, stream, a);
-                    else if (shape == 1) hipLaunchKernelGGL((zhip_encode_match_lds_kernel<16384, ZHIP_E1LDS_PROBES>), g, b, 0, stream, a);
-                    else if (shape == 2) hipLaunchKernelGGL((zhip_encode_match_lds_kernel<65536, ZHIP_E1LDS_PROBES>), g, b, 0, stream, a);
-                    else hipLaunchKernelGGL((zhip_encode_match_lds_kernel<ZF_BLOCK_MAX, ZHIP_E1LDS_PROBES>), g, b, 0, stream, a);
-                }
-                else launch_flat(!flatDict && !mbc && cnt <= c->knob.flat4Max ? 4 : !flatDict && !mbc && c->knob.flat3 && cnt <= c->knob.flat3Max ? 3 : 2, cnt, stream, a, fastPairs);
-                if (mbc) hipLaunchKernelGGL(zhip_encode_match_flat_mb_kernel, dim3((uint32_t)((cnt + a.mbLanes - 1) / a.mbLanes)), dim3(64), 0, stream, a);
-                if (tm) HIP_TRY(hipEventRecord(ev[1], stream));
-            }
-            if (tm) HIP_TRY(hipEventRecord(ev[2], stream));
-            if (greedy) hipLaunchKernelGGL(zhip_encode_match_greedy_kernel, dim3(g1), dim3(64), 0, stream, a);      // (takes the chunk's fast / double-fast sources, tiny ones and errors as the kernel below does)
-            else hipLaunchKernelGGL(zhip_encode_match_kernel, dim3(g1), dim3(64), 0, stream, a);
-            if (tm) { HIP_TRY(hipEventRecord(ev[3], stream)); HIP_TRY(hipEventRecord(ev[4], stream)); }
-            launch_entropy(c, a, g2, cnt, stream);
-            if (tm) HIP_TRY(hipEventRecord(ev[5], stream));
-            if (mbc) {      // this chunk's sources of several blocks: the generic kernel over the list the flat kernel just made (it reads the chunk's arenas)
-                ZhipEncodeArgs b = a;
-                b.workspace = (uint8_t*)c->encBigWs.p; b.counter = (uint32_t*)(cbase + 28);
-                b.frameList = a.bigList; b.listCount = a.bigCount;
-                hipLaunchKernelGGL(zhip_encode_frames_kernel, dim3(gBig), dim3(64), 0, stream, b);
-                HIP_TRY(hipMemsetAsync(cbase + 24, 0, 8, stream));          // list length and the kernel's work counter: fresh for the next chunk
-            }
-            HIP_TRY(hipGetLastError());
-            if (tm) {
-                if (flat) c->timer[8].pending.emplace_back(ev[0], ev[1]);
-                else { (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); }
-                c->timer[5].pending.emplace_back(ev[2], ev[3]);
-                c->timer[6].pending.emplace_back(ev[4], ev[5]);
-            }
-        }
-        if (a.prof) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            unsigned long long h[16];
-            HIP_TRY(hipMemcpy(h, a.prof, sizeof h, hipMemcpyDeviceToHost));
-            static const char* nm[12] = {"gather literals", "literal stats+decide", "huffman build+table", "huffman encode", "sequence stats", "sequence tables", "sequence stream", "frame assembly",
-                                          "  stream: constants", "  stream: state chains", "  stream: pack + OR", "  stream: flush"};      // (the last four: -DZE_PROF_STREAM builds only)
-            unsigned long long tot = 0; for (int q = 0; q <= ZEP_REST; q++) tot += h[q];
-            fprintf(stderr, "[zhip-prof] E2: %.0f wave-cycles per frame\n", (double)tot / (double)n);
-            for (int q = 0; q < ZEP_N; q++) fprintf(stderr, "[zhip-prof]    %-22s %6.2f%% %10.0f cyc/frame\n", nm[q], 100.0 * h[q] / (tot ? tot : 1), (double)h[q] / (double)n);
-            a.prof = nullptr;
-        }
-        if (!mbc) {   // inputs above 128 KiB (multi-block frames): the generic one-wave-per-frame kernel over the list E1 made (usually empty)
-            if (c->encBigWs.reserve(bigWsPer)) return g_reserveRc;
-            ZhipEncodeArgs b = a;
-            b.workspace = (uint8_t*)c->encBigWs.p; b.counter = (uint32_t*)(cbase + 28);
-            b.frameList = a.bigList; b.listCount = a.bigCount;
-            hipLaunchKernelGGL(zhip_encode_frames_kernel, dim3(gBig), dim3(64), 0, stream, b);
-            HIP_TRY(hipGetLastError());
-        }
-        return 0;
+    // the plan: which kernels, how many sources per launch, how much memory (zhip_encode_plan.hpp)
+    ZePlanIn in = plan_inputs(c, n);
+    ZePlan p = ze_encode_plan(in);
+    // the reservations. One that fails at 131 072 sources per launch after all, because another context took the memory in between, is planned again at 65 536
+    for (int pass = 0; ; pass++) {
+        if (p.flatMaxOpen) { in.flatMax = flat_max_decided(c, p.flatMaxNeed); p = ze_encode_plan(in); }
+        if (!(c->encMeta.reserve(p.metaBytes) || c->encArena.reserve(p.arenaBytes) || c->encTables.reserve(p.tablesBytes) || c->encWorkspace.reserve(p.workspaceBytes) ||
+              c->encBigList.reserve(p.bigListBytes) || c->encE1List.reserve(p.e1ListBytes) || (p.flat && c->encFlatTables.reserve(p.flatTablesBytes)))) break;
+        if (pass || g_reserveRc != ZHIP_ERR_NO_MEMORY || c->knob.echunkMax || c->flatMaxCached <= 65536) return g_reserveRc;
+        c->flatMaxCached = 65536; c->encArena.release(); c->encFlatTables.release();      // no room for 131 072 per launch after all: 65 536
     }
-    if (c->encWorkspace.reserve((size_t)grid * ZHIP_ENC_STRIDE)) return g_reserveRc;
+    if (p.mbc) {
+        if (c->encMbBlocks.reserve(p.mbBlocksBytes) || c->encMbCount.reserve(p.mbCountBytes) || c->encMbSeqs.reserve(p.mbSeqsBytes) || c->encBigWs.reserve(p.bigWsBytes)) return g_reserveRc;
+        a.mbBlocks = (ZeMbBlock*)c->encMbBlocks.p; a.mbCount = (uint32_t*)c->encMbCount.p; a.mbSeqs = (uint64_t*)c->encMbSeqs.p;
+        a.mbMaxBlocks = p.mbMaxBlocks; a.mbSeqCap = p.mbSeqCap; a.mbLanes = p.mbLanes;
+    }
+    a.tableStride = p.tableStride; a.arenaStride = p.arenaStride; a.arenaLit = p.arenaLit; a.slotSrcMax = p.slotSrcMax; a.e1Lanes = p.e1Lanes;
     a.workspace = (uint8_t*)c->encWorkspace.p;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
-    hipLaunchKernelGGL(zhip_encode_frames_kernel, dim3(grid), dim3(64), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    if (c->timing) { HIP_TRY(hipEventRecord(e1, stream)); c->timer[1].pending.emplace_back(e0, e1); }
-    if (c->timer[1].pending.size() > 4096) { HIP_TRY(hipStreamSynchronize(stream)); drain_timer(c->timer[1]); }
+    a.meta = (ZeMeta*)c->encMeta.p; a.arena = (uint8_t*)c->encArena.p; a.laneTables = (uint8_t*)c->encTables.p;
+    a.flatTables = p.flat ? (uint8_t*)c->encFlatTables.p : nullptr; a.useE1List = p.flat ? 1u : 0u;
+    a.e1List = (uint32_t*)c->encE1List.p; a.e1Count = (uint32_t*)(cbase + ZC_E1_COUNT);
+    a.bigList = (uint32_t*)c->encBigList.p; a.bigCount = (uint32_t*)(cbase + ZC_BIG_COUNT);
+    if (int rc = pick_table_placement(c, p, a, stream)) return rc;
+    HIP_TRY(hipMemsetAsync(cbase + ZC_BIG_COUNT, 0, 8, stream));
+    if (c->knob.prof) {                                                         // tuning aid: per-phase cycle totals of the entropy kernel
+        if (!c->profEncode) HIP_TRY(hipMalloc((void**)&c->profEncode, 16 * 8));
+        HIP_TRY(hipMemsetAsync(c->profEncode, 0, 16 * 8, stream));
+        a.prof = c->profEncode;
+    }
+    for (size_t first = 0; first < n; first += p.chunk) {
+        const size_t cnt = n - first < p.chunk ? n - first : p.chunk;
+        a.first = (uint32_t)first; a.count = (uint32_t)cnt;
+        HIP_TRY(hipMemsetAsync(cbase + ZC_E1_WORK, 0, 8, stream));
+        HIP_TRY(hipMemsetAsync(cbase + ZC_E1_COUNT, 0, 4, stream));
+        ChunkEvents ev;      // the flat match stage: 0 .. 1, the lane-serial match kernel: 2 .. 3, entropy + trailer: 4 .. 5
+        if (c->timing) HIP_TRY(ev.create(6));
+        if (p.flat) if (int rc = launch_flat_stage(c, p, ze_encode_chunk_plan(in, p, cnt), a, cnt, ev, stream)) return rc;
+        HIP_TRY(ev.record(2, stream));
+        if (p.greedy) hipLaunchKernelGGL(zhip_encode_match_greedy_kernel, dim3(p.g1), dim3(64), 0, stream, a);      // (takes the chunk's fast / double-fast sources, tiny ones and errors as the kernel below does)
+        else hipLaunchKernelGGL(zhip_encode_match_kernel, dim3(p.g1), dim3(64), 0, stream, a);
+        HIP_TRY(ev.record(3, stream)); HIP_TRY(ev.record(4, stream));
+        launch_entropy(c, a, p.g2, cnt, stream);
+        HIP_TRY(ev.record(5, stream));
+        if (p.mbc) {      // this chunk's sources of several blocks: the generic kernel over the list the flat kernel just made (it reads the chunk's arenas)
+            launch_big_list(c, p, a, stream);
+            HIP_TRY(hipMemsetAsync(cbase + ZC_BIG_COUNT, 0, 8, stream));          // list length and the kernel's work counter: fresh for the next chunk
+        }
+        HIP_TRY(hipGetLastError());
+        if (p.flat) ev.give(c->timer[8], 0, 1);
+        ev.give(c->timer[5], 2, 3); ev.give(c->timer[6], 4, 5);
+    }
+    if (a.prof) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        unsigned long long h[16];
+        HIP_TRY(hipMemcpy(h, a.prof, sizeof h, hipMemcpyDeviceToHost));
+        static const char* nm[12] = {"gather literals", "literal stats+decide", "huffman build+table", "huffman encode", "sequence stats", "sequence tables", "sequence stream", "frame assembly",
+                                      "  stream: constants", "  stream: state chains", "  stream: pack + OR", "  stream: flush"};      // (the last four: -DZE_PROF_STREAM builds only)
+        unsigned long long tot = 0; for (int q = 0; q <= ZEP_REST; q++) tot += h[q];
+        fprintf(stderr, "[zhip-prof] E2: %.0f wave-cycles per frame\n", (double)tot / (double)n);
+        for (int q = 0; q < ZEP_N; q++) fprintf(stderr, "[zhip-prof]    %-22s %6.2f%% %10.0f cyc/frame\n", nm[q], 100.0 * h[q] / (tot ? tot : 1), (double)h[q] / (double)n);
+        a.prof = nullptr;
+    }
+    if (!p.mbc) {   // inputs above 128 KiB (multi-block frames): the generic one-wave-per-frame kernel over the list E1 made (usually empty)
+        if (c->encBigWs.reserve(p.bigWsBytes)) return g_reserveRc;
+        launch_big_list(c, p, a, stream);
+        HIP_TRY(hipGetLastError());
+    }
     return 0;
 }
 
 // Compression from the CALLER's sequences: zhip_compress_batch_device with the match search replaced by a loader (ze_load_sequences_body, a lane per source: checks the
 // list, fills the source's arena slot and ZeMeta as a match kernel would) -- the entropy kernel and the trailer kernel behind it are the batch call's, launched the same way.
-// Sources of one block only; the arena slots are the full one-block shape (dictionary batches: the dictionary shape, enc_dict_slots), whatever the level's strategy.
+// Sources of one block only; the arena slots are the full one-block shape (dictionary batches: the dictionary shape, ze_dict_slots), whatever the level's strategy.
 extern "C" int zhip_compress_sequences_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
                                               const uint64_t* d_seqs, const zhip_segment* d_seqSegs,
                                               void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
@@ -1509,25 +1380,16 @@ extern "C" int zhip_compress_sequences_device(zhip_ctx* c, const void* d_src, co
     if (c->counter.reserve(64 * 8)) return g_reserveRc;
     uint8_t* const cbase = (uint8_t*)c->counter.p;
     ZhipEncodeArgs a; enc_args_init(c, a, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, cbase);
-    a.arenaStride = (uint32_t)ZE_ARENA_STRIDE; a.arenaLit = ZE_ARENA_LIT;
-    if (c->hasCDict) (void)enc_dict_slots(c, c->srcMaxHint ? c->srcMaxHint : c->itemHint, a);
-    const size_t chunkMax = c->hasCDict ? 262144 : 16384;                    // (7.4 GiB of one-block slots)
-    size_t chunk = n < chunkMax ? n : chunkMax;
-    const size_t g2max = (size_t)c->numCU * (size_t)c->e2PerCU;
-    // no room for the arena of a whole chunk: half as many sources per launch, down to 64, before the call fails (the slots are full one-block slots whatever the sources' sizes)
-    while (c->encArena.reserve(chunk * (size_t)a.arenaStride)) {
-        if (g_reserveRc != ZHIP_ERR_NO_MEMORY || chunk <= 64) return g_reserveRc;
-        chunk = (chunk + 1) / 2;
-    }
-    const uint32_t g2 = (uint32_t)(chunk < g2max ? chunk : g2max);
-    if (c->encMeta.reserve(chunk * sizeof(ZeMeta)) || c->encWorkspace.reserve((size_t)g2 * ZE_E2_STRIDE + ZHIP_ENC_STRIDE)) return g_reserveRc;
-    a.workspace = (uint8_t*)c->encWorkspace.p; a.meta = (ZeMeta*)c->encMeta.p; a.arena = (uint8_t*)c->encArena.p;
-    a.idle = cbase + 256;
+    const ZePlanIn pin = plan_inputs(c, n);
+    ZeSlotPlan s = ze_sequences_plan(pin);
+    uint32_t g2 = 0;
+    if (int rc = reserve_slots(c, pin.dev, s, a, &g2)) return rc;
+    const size_t chunk = s.chunk;
     ZeSeqLoad in; in.seqs = d_seqs; in.table = (const uint64_t*)d_seqSegs; in.copyLits = flags & 1u;
     for (size_t first = 0; first < n; first += chunk) {
         const size_t cnt = n - first < chunk ? n - first : chunk;
         a.first = (uint32_t)first; a.count = (uint32_t)cnt;
-        HIP_TRY(hipMemsetAsync(cbase + 8, 0, 8, stream));
+        HIP_TRY(hipMemsetAsync(cbase + ZC_E1_WORK, 0, 8, stream));
         hipLaunchKernelGGL(zhip_encode_load_sequences_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, stream, a, in);
         launch_entropy(c, a, g2, cnt, stream);
         HIP_TRY(hipGetLastError());

@@ -4,7 +4,7 @@
 #       ZHIP_EMU_SO=/tmp/libzhip_emu_asan.so python tests/stress_emu_encode.py 1 p 3
 set -e
 cd "$(dirname "$0")"
-g++ -O1 -g -fPIC -shared -std=c++17 -I. -fsanitize=address -fno-omit-frame-pointer -Wno-unused-function -Wno-unused-variable -o ${1:-/tmp/libzhip_emu_asan.so} zhemu.cpp emu_kernels.cpp
+g++ -O1 -g -fPIC -shared -std=c++17 -I. -fsanitize=address -fno-omit-frame-pointer -Wno-unused-function -Wno-unused-variable -o ${1:-/tmp/libzhip_emu_asan.so} zhemu.cpp emu_kernels.cpp emu_encode_plan.cpp
 # the same for the entropy kernel driven by explicit sequences, as a stand-alone PROGRAM (its own main; nothing is loaded into python, no LD_PRELOAD):
 #   /tmp/emu_entropy_sequences_asan tests/golden/entropy_sequences.bin
 g++ -O1 -g -std=c++17 -I. -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -Wno-unused-function -Wno-unused-variable -DEMU_ENTROPY_SEQUENCES_MAIN -o ${2:-/tmp/emu_entropy_sequences_asan} zhemu.cpp emu_entropy_sequences.cpp

@@ -9,6 +9,7 @@ extern "C" { long zd_trace_pos = -1; long zd_cur_frame = -1; long zd_stat[16]; }
 #include "../../python-zstandard_amd/csrc/zhip_decode_pipeline.hpp"      // (zd_clock and friends: the encoder header relies on them, as in emu_kernels.cpp)
 #include "../../python-zstandard_amd/csrc/zhip_encode_kernel.hpp"
 #include "../../python-zstandard_amd/csrc/zhip_cparams.hpp"
+#include "../../python-zstandard_amd/csrc/zhip_encode_plan.hpp"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -71,13 +72,17 @@ extern "C" int emu_entropy_sequences(const uint8_t* src, const uint64_t* srcSegs
     a.src = src; a.srcSegs = srcSegs; a.dst = dst; a.dstSegs = dstSegs; a.outSizes = outSizes; a.status = status;
     a.counter = counters; a.n = n; a.level = level; zh_resolve_rows(&a.rows, level, &o);
     a.contentSizeFlag = flags & 1; a.checksumFlag = (flags >> 1) & 1; a.dictIDFlag = (flags >> 2) & 1; a.magicless = (flags >> 3) & 1;
-    a.arenaStride = (uint32_t)ZE_ARENA_STRIDE; a.arenaLit = ZE_ARENA_LIT;
     if (g_hasCD) {
         a.cdict = &g_cd;
         a.cdictContent = g_cdBlob.data() + (g_cdEntropy.hufCount ? g_cdEntropy.contentOffset : 0u);
         a.cdictHashLong = g_cdTables.data(); a.cdictHashSmall = g_cdTables.data() + ((size_t)1 << ZE_CDICT_MAX_HLOG);
-        const uint32_t lim = g_cd.strat == 1 ? ZE_DICT_ATTACH_MAX_FAST : ZE_DICT_ATTACH_MAX;          // (enc_dict_slots without a size hint)
-        ze_dict_slot_shape(lim, &a.arenaLit, &a.arenaStride);
+    }
+    {   // the slots of the product's plan for this call, without a size hint
+        ZePlanIn in; in.rows = a.rows; in.n = n;
+        if (g_hasCD) { in.dict.present = true; in.dict.hlog = g_cd.hlog; in.dict.clog = g_cd.clog; in.dict.strat = g_cd.strat; in.dict.contentSize = g_cd.contentSize;
+                       in.dict.attachMax = g_cd.strat == 1 ? ZE_DICT_ATTACH_MAX_FAST : ZE_DICT_ATTACH_MAX; }
+        const ZeSlotPlan s = ze_sequences_plan(in);
+        a.arenaStride = s.arenaStride; a.arenaLit = s.arenaLit; a.slotSrcMax = s.slotSrcMax;
     }
     a.workspace = (uint8_t*)malloc((size_t)nBlocks * ZE_E2_STRIDE + ZHIP_ENC_STRIDE);
     a.meta = (ZeMeta*)malloc((size_t)chunk * sizeof(ZeMeta)); memset(a.meta, 0xA5, (size_t)chunk * sizeof(ZeMeta));

@@ -24,6 +24,7 @@ extern "C" int64_t emu_greedy_row(const uint8_t* src, uint32_t n, int wlog, int 
 
 // ---- the greedy match kernel and the entropy kernel under emulation: whole frames (zhip_compress_batch_device's lane-serial form for a batch whose one-block row is greedy)
 #include "../../python-zstandard_amd/csrc/zhip_cparams.hpp"
+#include "../../python-zstandard_amd/csrc/zhip_encode_plan.hpp"
 #include <stdlib.h>
 static ZeLDS g_elds;
 static void e1g_lane(void* p) { ze_match_body<true>(*(const ZhipEncodeArgs*)p); }
@@ -41,8 +42,7 @@ extern "C" int emu_greedy_frames(const uint8_t* src, const uint64_t* srcSegs, ui
     a.counter = counters; a.n = n; a.level = level; zh_resolve_rows(&a.rows, level, &o);
     a.contentSizeFlag = flags & 1; a.checksumFlag = (flags >> 1) & 1; a.dictIDFlag = 1;
     a.workspace = (uint8_t*)malloc((size_t)nBlocks * ZE_E2_STRIDE + ZHIP_ENC_STRIDE);
-    {   const int32_t* r = a.rows.r[2]; const int w = r[0] < 17 ? r[0] : 17, h = r[2] > w + 1 ? w + 1 : r[2]; a.tableStride = 5u << h; }
-    a.e1Lanes = ZE_E1_LANES;
+    {   ZePlanIn in; in.rows = a.rows; in.n = n; const ZePlan p = ze_encode_plan(in); a.tableStride = p.tableStride; a.e1Lanes = p.e1Lanes; }      // the product's plan: the row tables' bytes per lane
     a.laneTables = (uint8_t*)malloc((size_t)nBlocks * a.e1Lanes * a.tableStride); memset(a.laneTables, 0xA5, (size_t)nBlocks * a.e1Lanes * a.tableStride);
     a.meta = (ZeMeta*)calloc(n ? n : 1, sizeof(ZeMeta));
     a.arena = (uint8_t*)malloc((size_t)(n ? n : 1) * ZE_ARENA_STRIDE); a.arenaStride = (uint32_t)ZE_ARENA_STRIDE; a.arenaLit = ZE_ARENA_LIT;

@@ -6,6 +6,7 @@ extern "C" { long zd_trace_pos = -1; long zd_cur_frame = -1; long zd_stat[16]; }
 #include "../../python-zstandard_amd/csrc/zhip_decode_pipeline.hpp"
 #include "../../python-zstandard_amd/csrc/zhip_encode_kernel.hpp"
 #include "../../python-zstandard_amd/csrc/zhip_cparams.hpp"
+#include "../../python-zstandard_amd/csrc/zhip_encode_plan.hpp"
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -54,21 +55,6 @@ extern "C" void emu_set_cparams(uint32_t w, uint32_t c, uint32_t h, uint32_t s, 
 {
     g_ov.windowLog = w; g_ov.chainLog = c; g_ov.hashLog = h; g_ov.searchLog = s; g_ov.minMatch = mm; g_ov.targetLength = tl; g_ov.strategy = strat;
     g_magicless = magicless;
-}
-static uint32_t emu_table_stride(const ZeRows& rows)            // mirrors zhip_compress_batch_device
-{
-    uint32_t stride = 0;
-    for (int t = 2; t < 4; t++) {
-        const int32_t* r = rows.r[t];
-        if (r[6] != 1 && r[6] != 2) continue;
-        const int w = r[0] < (t == 2 ? 17 : 14) ? r[0] : (t == 2 ? 17 : 14);
-        const int h = r[2] > w + 1 ? w + 1 : r[2], cl = r[1] > w ? w : r[1];
-        const uint32_t bytes = (4u << h) + (r[6] == 2 ? (4u << cl) : 0u);
-        if (bytes > stride) stride = bytes;
-    }
-    if (stride < (4u << 10)) stride = 4u << 10;
-    if (stride > (12u << 17)) stride = 12u << 17;
-    return stride;
 }
 struct CDLaunch { ZeRows rows; };
 static void cdict_lane(void* p)
@@ -268,7 +254,7 @@ static ZeSrcLDS<ZF_BLOCK_MAX> g_srclds;
 static uint32_t g_e1LdsBytes = ZF_BLOCK_MAX;       // the LDS shape under emulation (the product picks it from the batch's largest source)
 static void e1l_lane(void* p) { if (g_probes == 4) ze_match_lds_body<4>(*(const ZhipEncodeArgs*)p, g_srclds.b, g_e1LdsBytes); else ze_match_lds_body<2>(*(const ZhipEncodeArgs*)p, g_srclds.b, g_e1LdsBytes); }
 extern "C" void emu_set_e1lds_bytes(uint32_t v) { g_e1LdsBytes = v; }
-static uint32_t g_e1LdsMax = 0;                 // chunks of up to this many frames take the LDS-source match kernel (mirrors zhip_compress_batch_device's choice)
+static uint32_t g_e1LdsMax = 0;                 // chunks of up to this many frames take the LDS-source match kernel (the plan's ldsMax, which the product derives from the CU count)
 extern "C" void emu_set_e1lds_max(uint32_t v) { g_e1LdsMax = v; }
 extern "C" int emu_compress_pipeline(const uint8_t* src, const uint64_t* srcSegs, uint32_t n, uint8_t* dst, const uint64_t* dstSegs,
                                      uint64_t* outSizes, int32_t* status, int level, uint32_t flags, uint32_t nBlocks, uint32_t chunk)
@@ -281,49 +267,39 @@ extern "C" int emu_compress_pipeline(const uint8_t* src, const uint64_t* srcSegs
     a.counter = counters; a.n = n; a.level = level; zh_resolve_rows(&a.rows, level, &g_ov); a.magicless = g_magicless;
     a.contentSizeFlag = flags & 1; a.checksumFlag = (flags >> 1) & 1; a.dictIDFlag = (flags >> 2) & 1;
     free(a.workspace); a.workspace = (uint8_t*)malloc((size_t)nBlocks * ZE_E2_STRIDE + ZHIP_ENC_STRIDE);
-    a.tableStride = emu_table_stride(a.rows);
+    // the product's launch plan (zhip_encode_plan.hpp) under the harness's hooks: the size hint is g_dictSlotMax for dictionary batches, else g_mbHint, else the batch's largest
+    // source; g_mbCompress decides alone whether sources of several blocks take the flat search; g_e1LdsMax is the LDS kernel's bound; launch numbers in the cells by g_dictEpochs
     uint64_t maxSrc = 0; for (uint32_t i = 0; i < n; i++) if (srcSegs[2 * (size_t)i + 1] > maxSrc) maxSrc = srcSegs[2 * (size_t)i + 1];
-    if (!g_hasCD && g_mbCompress && maxSrc > ZF_BLOCK_MAX && maxSrc < (1ull << ZE_MB_POS_BITS) - 8)          // mirrors zhip_compress_batch_device (mbcWanted)
-        for (int t = 0; t < 2; t++) {
-            const int32_t* r = a.rows.r[t];
-            if (r[6] != 2) continue;
-            int w = 17; while ((1ull << w) < maxSrc) w++;
-            if (w > r[0]) w = r[0];
-            const int h = r[2] > w + 1 ? w + 1 : r[2], cl = r[1] > w ? w : r[1];
-            const uint32_t bytes = (4u << h) + (4u << cl);
-            if (bytes > a.tableStride && bytes <= (12u << 17)) a.tableStride = bytes;
-        }
-    a.e1Lanes = g_hasCD ? ZE_E1_LANES_DICT : ZE_E1_LANES;
-    a.slotSrcMax = g_hasCD ? g_dictSlotMax : 0u;
+    ZePlanIn in;
+    in.rows = a.rows; in.n = n; in.knob.echunk = chunk; in.sizeHint = g_hasCD ? g_dictSlotMax : g_mbHint ? g_mbHint : maxSrc;
+    if (g_hasCD) { in.dict.present = true; in.dict.hlog = g_cd.hlog; in.dict.clog = g_cd.clog; in.dict.strat = g_cd.strat; in.dict.contentSize = g_cd.contentSize;
+                   in.dict.attachMax = g_cd.strat == 1 ? ZE_DICT_ATTACH_MAX_FAST : ZE_DICT_ATTACH_MAX; }
+    in.dev.numCU = in.dev.encBlocksPerCU = in.dev.e1PerCU = in.dev.e2PerCU = 1;      // (grids are the caller's nBlocks here)
+    in.knob.mbcMin = g_mbCompress ? 0 : ~(size_t)0 >> 16; in.knob.e1LdsMax = g_e1LdsMax; in.tableEpochs = g_dictEpochs != 0;
+    const ZePlan p = ze_encode_plan(in);
+    // (on purpose not the product's: this harness never launches the fast form of the flat kernel -- a batch whose one-block rows are both fast is the lane-serial kernel's --
+    // and runs the several-block search at 16 lanes per wave and g_probes probes per trip)
+    const bool flat = p.flat && !p.flatFast, flatDict = p.flatDict, mbc = p.mbc, epochs = flat && p.epochShift != 0;
+    a.tableStride = p.tableStride; a.e1Lanes = p.e1Lanes; a.slotSrcMax = p.slotSrcMax; a.arenaStride = p.arenaStride; a.arenaLit = p.arenaLit;
     a.laneTables = (uint8_t*)malloc((size_t)nBlocks * a.e1Lanes * a.tableStride);
     a.meta = (ZeMeta*)calloc(chunk, sizeof(ZeMeta));
-    a.arena = (uint8_t*)malloc((size_t)chunk * ZE_ARENA_STRIDE); a.arenaStride = (uint32_t)ZE_ARENA_STRIDE; a.arenaLit = ZE_ARENA_LIT;
+    a.arena = (uint8_t*)malloc((size_t)chunk * a.arenaStride);
     uint32_t bigCount = 0; a.bigList = (uint32_t*)calloc(n ? n : 1, 4); a.bigCount = &bigCount;
     attach_cdict(a);
     memset(&g_elds, 0xA5, sizeof g_elds);
-    bool anyDfast = false; for (int t = 2; t < 4; t++) anyDfast |= a.rows.r[t][6] == 2;
-    const bool flatDict = g_hasCD && a.cdict && a.cdict->strat == 2;      // mirrors zhip_compress_batch_device
-    const bool flat = (anyDfast && !g_hasCD) || flatDict;
     uint32_t e1Count = 0; a.e1List = (uint32_t*)calloc(chunk, 4); a.e1Count = &e1Count; a.useE1List = flat ? 1u : 0u;
-    // launch numbers in the dictionary search's cells (ZhipEncodeArgs.tabEpoch; mirrors zhip_compress_batch_device): the tables persist from call to call, zeroed when they are
+    // launch numbers in the flat searches' cells (ZhipEncodeArgs.tabEpoch): the tables persist from call to call, zeroed when they are
     // (re)made, and every launch on them takes the next number -- earlier launches' cells must read as empty
-    const bool mbcWanted = flat && !flatDict && g_mbCompress && maxSrc > ZF_BLOCK_MAX && maxSrc < (1ull << ZE_MB_POS_BITS) - 8;
-    const bool epochs = flat && !mbcWanted && g_dictEpochs;
     if (epochs) {
-        const size_t need = (size_t)chunk * a.tableStride;
-        uint32_t es = 26;                                      // (the dictionary-less search: six fixed bits, ze_dfast_flat_np)
-        if (flatDict) { const uint64_t span = 2ull + a.cdict->contentSize + (a.slotSrcMax ? a.slotSrcMax : (uint32_t)ZE_DICT_ATTACH_MAX) + 64; es = 1; while ((1ull << es) < span) es++; }
+        const size_t need = p.flatTablesBytes; const uint32_t es = p.epochShift;
         if (need > g_epochCap || es != g_epochShift || g_epoch + 8 >= (1u << (32 - es))) { free(g_epochTables); g_epochTables = (uint8_t*)calloc(need, 1); g_epochCap = need; g_epochShift = es; g_epoch = 0; }
         a.flatTables = g_epochTables; a.tabEpochShift = es;
     } else
-    a.flatTables = flat ? (uint8_t*)malloc((size_t)chunk * a.tableStride) : nullptr;
+    a.flatTables = flat ? (uint8_t*)malloc(p.flatTablesBytes) : nullptr;
     static uint8_t idlePad[64]; a.idle = idlePad;                  // (the product points it at the context's counter block)
-    // sources of several blocks in the flat kernel (mirrors zhip_compress_batch_device: the size hint is the batch's largest source)
-    const bool mbc = flat && !flatDict && g_mbCompress && maxSrc > ZF_BLOCK_MAX && maxSrc < (1ull << ZE_MB_POS_BITS) - 8;
     if (getenv("ZHIP_EMU_DEBUG")) fprintf(stderr, "[emu] mbc %d flat %d maxSrc %llu\n", (int)mbc, (int)flat, (unsigned long long)maxSrc);
     if (mbc) {
-        const uint64_t hint = g_mbHint ? g_mbHint : maxSrc;
-        a.mbMaxBlocks = g_mbCompress > 1 ? g_mbCompress : (uint32_t)(2 * ((hint + ZF_BLOCK_MAX - 1) / ZF_BLOCK_MAX) + 2); a.mbSeqCap = (uint32_t)(hint / 4 + a.mbMaxBlocks + 64);
+        a.mbMaxBlocks = g_mbCompress > 1 ? g_mbCompress : p.mbMaxBlocks; a.mbSeqCap = g_mbCompress > 1 ? (uint32_t)(in.sizeHint / 4 + a.mbMaxBlocks + 64) : p.mbSeqCap;
         a.mbBlocks = (ZeMbBlock*)malloc((size_t)chunk * a.mbMaxBlocks * sizeof(ZeMbBlock)); a.mbCount = (uint32_t*)malloc((size_t)chunk * 4); a.mbSeqs = (uint64_t*)malloc((size_t)chunk * a.mbSeqCap * 8);
         memset(a.mbBlocks, 0xA5, (size_t)chunk * a.mbMaxBlocks * sizeof(ZeMbBlock)); memset(a.mbCount, 0xA5, (size_t)chunk * 4);
     }
@@ -334,8 +310,9 @@ extern "C" int emu_compress_pipeline(const uint8_t* src, const uint64_t* srcSegs
             if (epochs) a.tabEpoch = ++g_epoch;
             else memset(a.flatTables, flatDict ? 0xA5 : 0, (size_t)a.count * a.tableStride);      // (dictionary batches: the kernel's waves zero what they use)
             if (mbc) { memset(&g_elds, 0xA5, sizeof g_elds); zhemu::run_grid(a.count < 3 ? a.count : 3, split_lane, &a); if (getenv("ZHIP_EMU_DEBUG")) fprintf(stderr, "[emu] split: count[0] = %u stride %u\n", a.mbCount[0], a.tableStride); }
-            if (a.count <= g_e1LdsMax && !flatDict && !mbc) { memset(&g_srclds, 0xA5, sizeof g_srclds); zhemu::run_grid(a.count, e1l_lane, &a); }
-            else zhemu::run_grid((a.count + ZE_FLAT_LANES - 1) / ZE_FLAT_LANES, e1f_lane, &a);
+            const ZeChunkPlan k = ze_encode_chunk_plan(in, p, a.count);                 // (which kernel and its grid; the probes per trip are g_probes, the LDS shape g_e1LdsBytes)
+            if (k.kernel == ZE_MATCH_LDS) { memset(&g_srclds, 0xA5, sizeof g_srclds); zhemu::run_grid(k.grid, e1l_lane, &a); }
+            else zhemu::run_grid(k.grid, e1f_lane, &a);
             if (mbc) { a.mbLanes = 16; a.mbProbes = g_probes; zhemu::run_grid((a.count + a.mbLanes - 1) / a.mbLanes, e1fmb_lane, &a); }
         }
         zhemu::run_grid(nBlocks, e1_lane, &a);
@@ -353,7 +330,7 @@ extern "C" int emu_compress_pipeline(const uint8_t* src, const uint64_t* srcSegs
         }
     }
     free(a.e1List); if (!epochs) free(a.flatTables); free(a.mbBlocks); free(a.mbCount); free(a.mbSeqs);
-    if (bigCount) {                              // inputs above one block: generic kernel over the list (mirrors zhip_compress_batch_device)
+    if (bigCount) {                              // inputs above one block: generic kernel over the list
         ZhipEncodeArgs b = a; uint32_t bc = 0;
         b.workspace = (uint8_t*)malloc((size_t)nBlocks * ZHIP_ENC_STRIDE); b.counter = &bc; b.frameList = a.bigList; b.listCount = &bigCount;
         EncLaunch l = { &b };

@@ -9,6 +9,7 @@ extern "C" { long zd_trace_pos = -1; long zd_cur_frame = -1; long zd_stat[16]; }
 #include "zhip_device_emu_wave.hpp"
 #include "../../python-zstandard_amd/csrc/zhip_encode_wave.hpp"
 #include "../../python-zstandard_amd/csrc/zhip_cparams.hpp"
+#include "../../python-zstandard_amd/csrc/zhip_encode_plan.hpp"
 #include <assert.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -45,7 +46,10 @@ extern "C" int emu_wave_frames(const uint8_t* src, const uint64_t* srcSegs, uint
     g_H = H;
     a.workspace = (uint8_t*)malloc((size_t)nBlocks * ZE_E2_STRIDE + ZHIP_ENC_STRIDE);
     a.meta = (ZeMeta*)calloc(n ? n : 1, sizeof(ZeMeta));
-    a.arenaLit = ZE_ARENA_LIT; a.arenaStride = finder == 1 ? (uint32_t)(ZE_ARENA_LIT + 512) : (uint32_t)ZE_ARENA_STRIDE;
+    ZePlanIn in; in.rows = a.rows; in.n = n;
+    // the product's plans. (On purpose not the product's: under the default finder only the lane-serial match kernel runs here, so its slots keep the literal area the flat
+    // kernel's batches do without.)
+    a.arenaLit = ZE_ARENA_LIT; a.arenaStride = finder == 1 ? ze_wave_plan(in).arenaStride : (uint32_t)ZE_ARENA_STRIDE;
     a.arena = (uint8_t*)malloc((size_t)(n ? n : 1) * a.arenaStride);
     a.bigList = (uint32_t*)calloc(n ? n : 1, 4); a.bigCount = &bigCount;
     static uint8_t idlePad[64]; a.idle = idlePad;
@@ -59,16 +63,8 @@ extern "C" int emu_wave_frames(const uint8_t* src, const uint64_t* srcSegs, uint
             if (a.meta[i].mode == 4) assert(a.meta[i].nbSeq <= ZE_SEQ_CAP && (uint64_t)a.meta[i].nbSeq * 4 <= srcSegs[2 * (size_t)i + 1]);
         }
     } else {
-        uint32_t stride = 4u << 10;
-        for (int t = 2; t < 4; t++) {
-            const int32_t* r = a.rows.r[t];
-            if (r[6] != 1 && r[6] != 2) continue;
-            const int w = r[0] < (t == 2 ? 17 : 14) ? r[0] : (t == 2 ? 17 : 14);
-            const int h = r[2] > w + 1 ? w + 1 : r[2], cl = r[1] > w ? w : r[1];
-            const uint32_t bytes = (4u << h) + (r[6] == 2 ? (4u << cl) : 0u);
-            if (bytes > stride) stride = bytes;
-        }
-        a.tableStride = stride; a.e1Lanes = ZE_E1_LANES;
+        const ZePlan p = ze_encode_plan(in);
+        a.tableStride = p.tableStride; a.e1Lanes = p.e1Lanes;
         a.laneTables = (uint8_t*)malloc((size_t)nBlocks * a.e1Lanes * a.tableStride); memset(a.laneTables, 0xA5, (size_t)nBlocks * a.e1Lanes * a.tableStride);
         zhemu::run_grid(nBlocks, e1_lane, &a);
     }
