@@ -1050,6 +1050,15 @@ ZH_DEV void zq_commit(uint32_t* col, int32_t off, const ZpVec16& v)             
     q[0] = v.a; q[16] = v.b; q[32] = v.c; q[48] = v.d;
     if (r0 == 0) col[ZQ_ROWS << 4] = v.a;
 }
+// the same for every lane on every trip, no exec edit: the mirror write goes to row 32 for a block at row 0 and to the block's own first
+// row (the dword zq_commit has just put there) for any other -- ((row - 1) & 31) + 1 in byte addresses
+ZH_DEV void zq_commit_all(uint32_t* col, int32_t off, const ZpVec16& v)
+{
+    uint32_t* q = col + ((((uint32_t)off >> 2) & (ZQ_ROWS - 1)) << 4);
+    q[0] = v.a; q[16] = v.b; q[32] = v.c; q[48] = v.d;
+    uint32_t* mq = (uint32_t*)((uint8_t*)col + ((((uint32_t)off << 4) - 64u) & ((ZQ_ROWS - 1) << 6)));
+    mq[16] = v.a;
+}
 ZH_DEV ZpVec16 zq_fetch(const uint8_t* p0, int32_t off) { return *(const ZpVec16*)(p0 + (uint32_t)(off < 0 ? 0 : off)); }
 
 #ifndef ZQ_FENCES
@@ -1101,7 +1110,8 @@ ZH_DEVFN void zp_seqq_body(const ZhipPipeArgs& a, ZpSeqQLDS& L)
 #pragma unroll
             for (uint32_t q = 0; q < ZP_FSE_CELLS / 128; q++) dstw[lane + 64 * q] = r[q];
         }
-        uint32_t* const col = L.ring + (active ? slot : 0u);
+        static_assert(ZQ_FRAMES <= 15, "the ring's last column is where the lanes without a frame write");
+        uint32_t* const col = L.ring + (active ? slot : 15u);
         const bool idle = isSpare || !active;                                      // idle lanes decode the one-cell table: no bits, the same state for ever
         const uint16_t* const Tm = idle ? (const uint16_t*)&L.spare : (const uint16_t*)(L.tab + (size_t)slot * ZP_K2_STRIDE) + tabOff;
         ZdMeta* const m = a.meta + (active ? i : 0u);
@@ -1109,7 +1119,7 @@ ZH_DEVFN void zp_seqq_body(const ZhipPipeArgs& a, ZpSeqQLDS& L)
         const uint32_t f = a.first + fi;
         uint32_t nbSeq = 0, logs = 0;
         int32_t pos = 0, pb = -(1 << 30), fin = 0;
-        const uint8_t* p0 = nullptr;
+        const uint8_t* p0 = (const uint8_t*)a.counters;                               // (lanes without a stream fetch too: sixteen bytes that are always there)
         bool ok = active;
         ZpVec16 v0, v1; v0.a = v0.b = v0.c = v0.d = 0; v1 = v0;
         int32_t tb = 0;
@@ -1181,17 +1191,22 @@ ZH_DEVFN void zp_seqq_body(const ZhipPipeArgs& a, ZpSeqQLDS& L)
         const uint32_t outStep = isOF && active ? 2u : 0u;
         uint32_t g1lo = 0, g1hi = 0, g2lo = 0, g2hi = 0, g3lo = 0, g3hi = 0;       // the group's first three packed sequences
         ZpVec16 w0, w1; w0.a = w0.b = w0.c = w0.d = 0; w1 = w0;                       // the group as stored
-        int32_t boff = ZP_NOBLK, posEnd = pos; ZpVec16 blk = v0;
+        int32_t boff = tb - 16 * (int32_t)role, posEnd = pos; ZpVec16 blk = v0;       // (the first trip's commit: the block that is there already)
         // The wave is alone on its SIMD and issues one instruction every ~6.5 cycles whatever it is (r02l: time = instructions x steps), so
         // the body is written for instruction count first -- then software-pipelined by hand (as K2 above) so the LDS round trips of the
         // chain are covered: the value / repeat-offset / pack / store work of sequence n - 1 sits right behind the requests of sequence n.
         uint32_t pe0 = 0, pe1 = 0, pqE = 0, pbits = 0, pbase = 1;               // pending pieces of n - 1 (value 1 everywhere: "repeat rep0", a no-op)
         for (uint32_t n0 = 0; n0 < nTrips; n0 += 4) {
             zh_sync();                                       // (every lane is past the previous step's reads: the emulator's lanes are free-running fibers)
-            if (boff != ZP_NOBLK) { zq_commit(col, boff, blk); boff = ZP_NOBLK; }
-            {   // a block may replace ring bytes [off + 128, off + 144) once nothing at or above them will be read again
-                const int32_t t = pb + 128 - (((pos >> 5) << 2) + 4);
-                if ((int32_t)(role * 16) <= t) { boff = pb - 16 * (int32_t)role; blk = zq_fetch(p0, boff); }
+            // Ring upkeep without exec edits (three nests of them cost ~7 scalar instructions per body, and this wave's time is its instruction
+            // count): every lane commits a block and fetches one on every trip. A lane whose ring slot is not free yet fetches the block that
+            // slot HOLDS (128 bytes up: fetched on an earlier trip, so committed by now) and writes the same bytes over it -- the slot's next
+            // block is fetched on a later trip and so committed behind this write. Offsets below the stream's start are clamped by zq_fetch
+            // as before (rows nobody reads), lanes without a frame write the ring's spare column.
+            zq_commit_all(col, boff, blk);
+            {   const int32_t t = pb + 128 - (((pos >> 5) << 2) + 4);
+                boff = pb - 16 * (int32_t)role + ((int32_t)(role * 16) <= t ? 0 : 128);
+                blk = zq_fetch(p0, boff);
                 int32_t cnt = (t >> 4) + 1; cnt = cnt < 0 ? 0 : cnt > 4 ? 4 : cnt;
                 pb -= 16 * cnt; }
 #pragma unroll
@@ -1202,7 +1217,7 @@ ZH_DEVFN void zp_seqq_body(const ZhipPipeArgs& a, ZpSeqQLDS& L)
                 // ---- sequence n - 1: value, choice of the offset (RFC 8878 3.1.1.5: idx 0 / 1 / 2 = a repeat offset, 3 = rep0 - 1 or a new one)
                 const uint32_t val = pbase + zh_bfe(zh_alignbit(pe1, pe0, pqE), 0, pbits);
                 const uint32_t mlv = zh_quad<1>(val), llv = zh_quad<2>(val);
-                const uint32_t idx = val - 1 + (llv == 0);
+                const uint32_t idx = val - (llv < 1u ? llv : 1u);                  // val - 1 + (llv == 0): a compare and a subtract with borrow, not compare / add with carry / add
                 // rep0 - 1 == 0 is no offset: libzstd 1.5.7 forces -1 (zstd.c:46941). It travels as offset 0, which K3 refuses (its range check is on
                 // offset - 1: zero wraps to the largest value there is). A new offset beyond the packed form is saturated; K3 knows what to do.
                 // (round 4: straight-line selects -- the nested ternary became an exec-mask if / else of 4 scalar instructions + 2 s_nop per step, in a
@@ -1210,7 +1225,12 @@ ZH_DEVFN void zp_seqq_body(const ZhipPipeArgs& a, ZpSeqQLDS& L)
                 const uint32_t vm3 = val - 3;
                 const uint32_t newOff = vm3 < ZP_OF_LIMIT ? vm3 : ZP_OF_LIMIT;
                 const uint32_t c3 = val > 3 ? newOff : rep0 - 1;
-                uint32_t offset = idx == 2 ? rep2 : c3; offset = idx == 1 ? rep1 : offset; offset = idx == 0 ? rep0 : offset;
+                // (a tree, not a chain of three selects: four compares instead of five -- the history update below shares two of them -- and no select
+                // waits on the one before it. gfx950 wants two wait states between a VALU write of VCC / an SGPR and the VALU that reads it as a mask;
+                // in the chain the scheduler found nothing to put there in three steps of four and the hazard pass filled in s_nop, 7 per body)
+                const bool i0 = idx == 0, i2 = idx == 2, le1 = idx <= 1;
+                const uint32_t a01 = i0 ? rep0 : rep1, b23 = i2 ? rep2 : c3;
+                const uint32_t offset = le1 ? a01 : b23;
                 ZQ_F2();
                 // ---- the chain: cell -> bit counts -> where my state bits are -> next state
                 const uint32_t sym = cell >> 10, x = cell & 1023;
@@ -1218,7 +1238,7 @@ ZH_DEVFN void zp_seqq_body(const ZhipPipeArgs& a, ZpSeqQLDS& L)
                 const uint32_t nb = (uint32_t)__builtin_clz(x) - kk;
                 ZQ_F2();
                 // ---- sequence n - 1: history (idx 0: as it was, 1: swap the first two, else: push), pack, store
-                rep2 = idx <= 1 ? rep2 : rep1; rep1 = idx == 0 ? rep1 : rep0; rep0 = offset;
+                rep2 = le1 ? rep2 : rep1; rep1 = i0 ? rep1 : rep0; rep0 = offset;
                 if (MB) {                                                   // trip n has just applied sequence n - 1
                     const bool wasLast = n == nbSeq;
                     fin0 = wasLast ? rep0 : fin0; fin1 = wasLast ? rep1 : fin1; fin2 = wasLast ? rep2 : fin2;
@@ -1256,6 +1276,7 @@ ZH_DEVFN void zp_seqq_body(const ZhipPipeArgs& a, ZpSeqQLDS& L)
                 pbase = isOF ? 1u << (sym & 31) : inf & 0xFFFFFFu;
                 ZQ_F2();
                 state = (x << nb) + zh_bfe(zh_alignbit(s1, s0, (uint32_t)qS), 0, nb);
+                state = zh_pin(state);                  // (as ONE value: left alone, LLVM adds x << nb into the next step's cell address on its own -- two more instructions per step)
             }
             // the stores' source registers stay untouched to here: reused as temporaries right behind the store, the write-after-read
             // wait (vmcnt counts in order) also sat out the ring's block load issued just before it -- a load round trip per group (r02x)

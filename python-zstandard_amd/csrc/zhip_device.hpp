@@ -46,7 +46,7 @@ template <int K> ZH_DEV uint32_t zh_quad(uint32_t v) { return (uint32_t)__builti
 // v + (v of quad lane CTRL[2r+1:2r] for lane r of the quad): one v_add_u32_dpp
 // (r03f: written as update_dpp(0, v, CTRL, 0xf, 0xf, bound_ctrl) LLVM's DPP combiner folds 7 of the 32 quad moves of K2's unrolled body into their
 // consumers -- 320 -> 313 instructions -- but the K2 built that way reports corrupt streams on the MI355X where the emulator and this form
-// agree with libzstd: not adopted)
+// agree with libzstd: not adopted. Round 7 checked the folded listing against the DPP rules and found nothing wrong with it -- DESIGN.md 5.17)
 template <int CTRL> ZH_DEV uint32_t zh_quad_add(uint32_t acc, uint32_t v) { return acc + (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xf, 0xf, false); }
 ZH_DEV uint32_t zh_atomic_inc(uint32_t* p) { return atomicAdd(p, 1u); }
 ZH_DEV uint32_t zh_atomic_add(uint32_t* p, uint32_t v) { return atomicAdd(p, v); }
@@ -80,6 +80,13 @@ ZH_DEV uint32_t zh_alignbit(uint32_t hi, uint32_t lo, uint32_t sh) { return __bu
 #endif
 
 // ------------------------------------------------------------------------------------- common helpers
+// the value exists in a register here (the optimizer does not reassociate across this point); not ordered against anything. The emulator
+// has nothing to pin.
+#ifndef ZHIP_EMU
+ZH_DEV uint32_t zh_pin(uint32_t v) { asm("" : "+v"(v)); return v; }
+#else
+ZH_DEV uint32_t zh_pin(uint32_t v) { return v; }
+#endif
 typedef uint64_t __attribute__((aligned(1))) zh_u64u;
 typedef uint32_t __attribute__((aligned(1))) zh_u32u;
 typedef uint16_t __attribute__((aligned(1))) zh_u16u;
