@@ -8,6 +8,8 @@
 #   k3w{4,5}    -DZP_K3_MINWAVES=n   K3 at n waves per SIMD (default 6)
 #   k3d{2,3}    -DZP_K3D_MINWAVES=n  K3's dictionary instantiation (default 4)
 #   asm2k       -DZP_ASM_BYTES=2048  K3: 2 KiB batch assembly buffer
+#   lit{1,2}    -DZP_K3_LITCOPIES=n  K3: one copy of the block code with the literal mode a run-time value (rounds 1-7) / two (decoded literals + the rest) instead of three
+#   k3cu24      -DZHIP_K3_PER_CU=24  K3's grid fixed at 24 waves per CU instead of the occupancy query's value
 #   own32       -DZP_LIT_SHORT=32 -DZP_FAR_SHORT=32   K3: own-lane items up to 32 bytes (round 2's shape)
 #   nohist      -DZP_HIST_KEEP=0u -DZP_HIST_SLIDE=0u  K3 without the LDS history in front of the batch (round 6 A/B)
 #   nok0        -DZHIP_K0=0          decode pipeline without K0 (the lane-per-frame parser pass in front of K1)
@@ -35,6 +37,9 @@ for v in "$@"; do
     k3d2) build k3d2 -DZP_K3D_MINWAVES=2 & ;;
     k3d3) build k3d3 -DZP_K3D_MINWAVES=3 & ;;
     asm2k) build asm2k -DZP_ASM_BYTES=2048 & ;;
+    lit1) build lit1 -DZP_K3_LITCOPIES=1 & ;;              # K3's block code as rounds 1-7 had it: one copy, the literal mode tested in every batch (A/B of round 8: profiles/r14_*)
+    lit2) build lit2 -DZP_K3_LITCOPIES=2 & ;;              # two copies (80 VGPRs + 16 bytes of scratch in the dictionary-less kernel)
+    k3cu24) build k3cu24 -DZHIP_K3_PER_CU=24 & ;;
     nt1) build nt1 -DZP_K3_NT=1 & ;;                      # K3: sequences and decoded literals read with streaming (nt) loads
     zqnost) build zqnost -DZQ_DIAG_NOSTORE & ;;             # DIAGNOSTIC: K2 without its sequence stores
     zqnt) build zqnt -DZQ_NT_STORE & ;;                    # K2: sequences stored with non-temporal stores

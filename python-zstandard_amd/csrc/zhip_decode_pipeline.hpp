@@ -1373,15 +1373,31 @@ ZH_DEV uint32_t zp_sym_resolve(uint32_t v, uint32_t R0, uint32_t R1, uint32_t R2
 #define ZP_HIST_SLIDE (2u * ZP_HIST_KEEP + 16u)             // ... once more than this many lie in front of the batch (2 576): a batch always finds ZP_ASM_BYTES - ZP_HIST_SLIDE bytes of room
 #endif
 static_assert((ZP_HIST_SLIDE >= 2 * ZP_HIST_KEEP + 16 || ZP_HIST_KEEP == 0) && ZP_HIST_KEEP % 16 == 0 && ZP_HIST_SLIDE < ZP_ASM_BYTES, "the slide's source and destination must not overlap");      // (-DZP_HIST_KEEP=0u -DZP_HIST_SLIDE=0u: no history, rounds 1-5's form, for A/B)
-template <bool DICT, bool PROF, bool MB>
+// LM: the copy of the block's code by literal mode (round 8). A block's literal mode cannot change inside it, yet as run-time values `litRLE` and `arenaLit`
+// were tested again in every batch (~146 per frame of the bench corpus: scalar compare / select / branch chains in a loop that is out of SGPRs), and the loop
+// carried the exact-form loads of raw literals and three RLE loops that a frame with Huffman literals never runs. In a copy the mode is a constant:
+//   ZP_LM_ARENA  the literals were decoded into the block's literal slot (Huffman and treeless blocks, and what the generic parse left there): no RLE code,
+//                no exact-form literal loads
+//   ZP_LM_RAW    raw literals, read in place from the frame (exact-form loads, no RLE code)
+//   ZP_LM_RLE    one literal value: no literal loads at all
+//   ZP_LM_ANY    the mode as the run-time value it was (rounds 1-7's loop), for the instantiations that have no registers for copies, see zp_exec_block_by_mode
+// ZP_K3_LITCOPIES: 3 = ARENA + RAW + RLE (the product), 2 = ARENA + ANY, 1 = ANY alone (rounds 1-7, the A/B build). Two copies put the dictionary-less kernel
+// over its 80 registers (16 bytes of scratch: what the frame loop keeps live across both copies adds to the larger copy's 77); of three, each needs fewer
+// than ANY and the kernel stays at 77 without scratch (profiles/r14_k3_batch_loop_literal_modes.txt).
+#ifndef ZP_K3_LITCOPIES
+#define ZP_K3_LITCOPIES 3
+#endif
+enum { ZP_LM_ANY = 0, ZP_LM_ARENA = 1, ZP_LM_RAW = 2, ZP_LM_RLE = 3 };
+template <bool DICT, bool PROF, bool MB, int LM>
 ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m, uint32_t t, const uint8_t* src, uint8_t* dst, uint32_t cap, uint64_t cap64,
                            uint32_t blockMax, uint32_t& opRef, uint32_t R0, uint32_t R1, uint32_t R2, ZdProf& P)
 {
     const uint32_t lane = zh_lane();
     const uint64_t* seqs = a.seqArena + a.bases[2 * (size_t)t];
-    const bool litRLE = m.litMode == 2;
+    const bool litRLE = LM == ZP_LM_ANY ? m.litMode == 2 : LM == ZP_LM_RLE;
+    const bool litRaw = LM == ZP_LM_ANY ? m.litMode == 0 : LM == ZP_LM_RAW;
     const uint32_t rleByte = m.litOff;
-    const uint8_t* litPtr = m.litMode == 0 ? src + m.litOff : a.litArena + (size_t)a.bases[2 * (size_t)t + 1] * 16;
+    const uint8_t* litPtr = litRaw ? src + m.litOff : a.litArena + (size_t)a.bases[2 * (size_t)t + 1] * 16;
     const uint8_t* const dictEnd = DICT ? a.dictContent + a.dictContentSize : dst;       // position -k of the frame = dictEnd[-k]
     const uint32_t dictSize = DICT ? a.dictContentSize : 0u;
     // Round 6: the assembly buffer keeps what it flushed. A batch is ~0.9 KiB of the buffer's 4: instead of starting every batch at its front, batches are
@@ -1457,7 +1473,7 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
             // the same economy on the global side where reading past the item cannot leave mapped memory: decoded literals live in our own
             // arena (256 bytes of slack per frame); a match source at least 32 bytes below the end of the frame's output slot stays inside it.
             // Lanes without an item read their frame's first bytes. Raw literals (read from the caller's source) keep the exact form.
-            const bool arenaLit = m.litMode != 0;                                   // (frame-uniform)
+            const bool arenaLit = !litRaw;                                          // (block-uniform; a constant in every copy but ZP_LM_ANY, like litRLE)
             if (arenaLit && !litRLE) {
                 const uint8_t* q = litPtr + (shortL ? litStart : 0u);
                 rl[0] = ZP_LIT_LD64(q); rl[3] = ZP_LIT_LD64(q + (shortL && myLL >= 8 ? myLL - 8 : 0u));
@@ -1646,6 +1662,20 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
     return 0;
 }
 
+// the block's copy by its literal mode (ZdMeta.litMode: 0 raw in the frame, 2 RLE; everything else sits decoded in the block's literal slot)
+template <bool DICT, bool PROF, bool MB>
+ZH_DEVFN int zp_exec_block_by_mode(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m, uint32_t t, const uint8_t* src, uint8_t* dst, uint32_t cap, uint64_t cap64,
+                                   uint32_t blockMax, uint32_t& opRef, uint32_t R0, uint32_t R1, uint32_t R2, ZdProf& P)
+{
+    // The dictionary instantiations sit at their launch bound's 128 registers with any second copy (113 -> 127 / 128 and 16-48 bytes of scratch): they keep the run-time mode.
+    constexpr int copies = DICT ? 1 : ZP_K3_LITCOPIES;
+#define ZP_XB(LM_) zp_exec_block<DICT, PROF, MB, LM_>(a, L, m, t, src, dst, cap, cap64, blockMax, opRef, R0, R1, R2, P)
+    if constexpr (copies >= 2) { if (m.litMode != 0 && m.litMode != 2) return ZP_XB(ZP_LM_ARENA); }
+    if constexpr (copies >= 3) { if (m.litMode == 0) return ZP_XB(ZP_LM_RAW); return ZP_XB(ZP_LM_RLE); }
+    else return ZP_XB(ZP_LM_ANY);
+#undef ZP_XB
+}
+
 
 // what ends a frame: the content size it announced, its checksum (zstd.c:44264-44277). All lanes call.
 ZH_DEVFN int zp_exec_frame_end(ZpExecLDS& L, const uint8_t* dst, uint32_t op, uint32_t fcsLo, uint32_t fcsHi, uint32_t hasChecksum, uint32_t checksum, uint32_t ckLater)
@@ -1681,7 +1711,7 @@ ZH_DEVFN int zp_exec_frame(const ZhipPipeArgs& a, ZpExecLDS& L, uint32_t i, uint
 #ifdef ZP_K3_DIAG_FLOOR          // DIAGNOSTIC ONLY (wrong bytes): the batch loop reduced to its memory traffic -- tests/ubench/k3_floor_diag.hpp
     int e = zp_exec_block_floor<DICT, PROF, false>(a, L, m, i, src, dst, cap, cap64, m.blockMax, op);
 #else
-    int e = zp_exec_block<DICT, PROF, false>(a, L, m, i, src, dst, cap, cap64, m.blockMax, op, 1, 4, 8, P);
+    int e = zp_exec_block_by_mode<DICT, PROF, false>(a, L, m, i, src, dst, cap, cap64, m.blockMax, op, 1, 4, 8, P);
 #endif
     if (e) return e;
     e = zp_exec_frame_end(L, dst, op, m.fcsLo, m.fcsHi, m.hasChecksum, m.checksum, a.ckLater);
@@ -1719,7 +1749,7 @@ ZH_DEVFN int zp_exec_frame_mb(const ZhipPipeArgs& a, ZpExecLDS& L, uint32_t i, u
             op += size;
             continue;
         }
-        const int e = zp_exec_block<DICT, false, true>(a, L, m, t, src, dst, cap, cap64, rec.blockMax, op, R0, R1, R2, P);
+        const int e = zp_exec_block_by_mode<DICT, false, true>(a, L, m, t, src, dst, cap, cap64, rec.blockMax, op, R0, R1, R2, P);
         if (e) return e;
         zd_fence();
         if (m.nbSeq) {

@@ -73,6 +73,11 @@ ZH_GLOBAL __launch_bounds__(64) void zhip_decode_seq_mb_kernel(ZhipPipeArgs a)
 #define ZP_K3_MINWAVES 6         // 77 VGPRs: own-lane items <= 16 bytes (zhip_decode_pipeline.hpp: ZP_LIT_SHORT / ZP_FAR_SHORT, r03g: 113 -> 96) and the phase timers
                                  // in their own instantiation (r03n: 96 -> 77). Six waves per SIMD; seven (72 VGPRs) and eight measured the same
 #endif
+#ifndef ZHIP_K3_PER_CU
+#define ZHIP_K3_PER_CU 0         // K3's grid in waves per CU (knob.k3PerCU); 0: what the occupancy query says for zhip_decode_exec_kernel. A build-time value for A/B
+                                 // (build_variants.sh k3cu24). Round 8's three copies of the block code leave the kernel's registers, and so the query's 24, where they were;
+                                 // the one build that had 70 VGPRs (query: 28) measured the same at 24 and 28 (profiles/r14_k3_batch_loop_literal_modes.txt, section 4): left at 0
+#endif
 ZH_GLOBAL __launch_bounds__(64, ZP_K3_MINWAVES) void zhip_decode_exec_kernel(ZhipPipeArgs a)
 {
     __shared__ ZpExecLDS L;
@@ -423,7 +428,7 @@ struct zhip_ctx {
         // decode pipeline
         size_t dchunk = ZHIP_DCHUNK;        // frames (several-block mode: block slots) per chunk
         int nslot = 2; bool nslotSet = false;   // chunk slots on their own streams (small frames get a third unless ZHIP_NSLOT says otherwise)
-        int k1PerCU = 0, k3PerCU = 0;       // waves per CU of K1 / K3 (0: what the occupancy query says)
+        int k1PerCU = 0, k3PerCU = ZHIP_K3_PER_CU;       // waves per CU of K1 / K3 (0: what the occupancy query says)
         // encode (the rest: ZeEncodeKnobs)
         int waveH = ZHIP_WAVE_HLOG;         // ZHIP_WAVE_HLOG: table cells of the wave match finder, log2 (12, 13, 14)
         bool e1fPick = true;                // ZHIP_E1F_PICK=0: take the flat tables where the first allocation put them (zhip_compress_batch_device)
