@@ -20,6 +20,7 @@
 #include "zhip_encode_wave.hpp"
 #include "zhip_cparams.hpp"
 #include "zhip_encode_plan.hpp"
+#include "zhip_decode_plan.hpp"
 #include "zhip_seekable.hpp"
 
 #define ZHIP_LDS_BYTES (160u * 1024u)      // per CU on gfx950
@@ -72,11 +73,6 @@ ZH_GLOBAL __launch_bounds__(64) void zhip_decode_seq_mb_kernel(ZhipPipeArgs a)
 #ifndef ZP_K3_MINWAVES
 #define ZP_K3_MINWAVES 6         // 77 VGPRs: own-lane items <= 16 bytes (zhip_decode_pipeline.hpp: ZP_LIT_SHORT / ZP_FAR_SHORT, r03g: 113 -> 96) and the phase timers
                                  // in their own instantiation (r03n: 96 -> 77). Six waves per SIMD; seven (72 VGPRs) and eight measured the same
-#endif
-#ifndef ZHIP_K3_PER_CU
-#define ZHIP_K3_PER_CU 0         // K3's grid in waves per CU (knob.k3PerCU); 0: what the occupancy query says for zhip_decode_exec_kernel. A build-time value for A/B
-                                 // (build_variants.sh k3cu24). Round 8's three copies of the block code leave the kernel's registers, and so the query's 24, where they were;
-                                 // the one build that had 70 VGPRs (query: 28) measured the same at 24 and 28 (profiles/r14_k3_batch_loop_literal_modes.txt, section 4): left at 0
 #endif
 ZH_GLOBAL __launch_bounds__(64, ZP_K3_MINWAVES) void zhip_decode_exec_kernel(ZhipPipeArgs a)
 {
@@ -316,9 +312,6 @@ extern "C" int64_t zhip_find_frame_compressed_size(const void* src, size_t n) { 
 extern "C" void zhip_get_cparams(int level, uint64_t srcSizeHint, size_t dictSize, zhip_compression_parameters* out) { if (out) zh_get_cparams(level, srcSizeHint, dictSize, out); }
 
 // ------------------------------------------------------------------------------------------ context
-#ifndef ZHIP_NSLOT
-#define ZHIP_NSLOT 3
-#endif
 #ifndef ZHIP_E1LDS_PROBES
 #define ZHIP_E1LDS_PROBES 2       // probes per trip of the LDS-source match kernel (small batches: one source per CU)
 #endif
@@ -327,9 +320,6 @@ extern "C" void zhip_get_cparams(int level, uint64_t srcSizeHint, size_t dictSiz
 #endif
 #ifndef ZHIP_TRAILER_LATER
 #define ZHIP_TRAILER_LATER 1     // compress: checksum trailers by EX after the entropy kernel; 0: by the entropy kernel on one lane per frame (A/B build)
-#endif
-#ifndef ZHIP_SIDE
-#define ZHIP_SIDE 1              // K1b beside K2 on a side stream; 0: the decode kernels one after the other on one stream, two chunk slots (rounds 1-5; A/B build)
 #endif
 #ifndef ZHIP_PICK_MIN
 #define ZHIP_PICK_MIN 16384       // sources per launch from which a context's first flat-search launch picks its tables' placement (49 152 while a probe was a whole launch: with probes at ~9 ms per
@@ -340,12 +330,6 @@ extern "C" void zhip_get_cparams(int level, uint64_t srcSizeHint, size_t dictSiz
 #endif
 #ifndef ZHIP_PICK_STUDY
 #define ZHIP_PICK_STUDY 0        // 1: DIAGNOSTIC build -- the placement pick also times eight candidate allocations whole and over the sources' first bytes, and prints them
-#endif
-#ifndef ZHIP_K0
-#define ZHIP_K0 1                // K0 (zhip_decode_pre_kernel) in front of K1; 0: K1 parses every description itself (A/B build)
-#endif
-#ifndef ZHIP_DCHUNK
-#define ZHIP_DCHUNK 65536        // frames per chunk of the decode pipeline (r02zl: 301 GB/s in one 65 536-frame chunk against 297 in two of 32 768: longer launches amortise their tails, and the two chunk slots overlap little anyway)
 #endif
 static thread_local int g_reserveRc = ZHIP_ERR_HIP;      // why the last failed DevBuf::reserve failed (ZHIP_ERR_NO_MEMORY or ZHIP_ERR_HIP)
 // (device bytes are accounted per CONTEXT -- zhip_ctx::device_bytes sums its buffers -- not in a thread-local counter: a context may be
@@ -383,7 +367,7 @@ struct zhip_ctx {
     int numCU = 0;
     int decBlocksPerCU = 0;
     int encBlocksPerCU = 0;
-    int k1PerCU = 0, k2PerCU = 0, k3PerCU = 0;
+    int k1PerCU = 0, k3PerCU = 0;
     DevBuf pipeMeta, pipeLit, pipeCounters, pipeFallback, pipeFse, pipeOrder, pipeHuf, pipeOrderLit, pipeItemFrame, pipeItemReps, pipeFrameRecs, pipeBases, pipePre;
     hipStream_t slotStream[ZHIP_NSLOT] = {};
     hipStream_t sideStream[ZHIP_NSLOT] = {};
@@ -392,11 +376,6 @@ struct zhip_ctx {
     int matchFinder = ZHIP_FINDER_LIBZSTD;     // zhip_ctx_set_match_finder
     int wavePerCU[3] = {0, 0, 0};      // resident workgroups per CU of the wave match kernel at H = 12, 13, 14
     size_t srcMaxHint = 0;             // largest source of the batch being launched when the caller knows it (host-buffer API), else 0
-    size_t dstMaxHint = 0;             // the same for the decode direction: largest announced content size of the batch (host-buffer API), else 0
-    bool hostPipe = false;             // the host-buffer pipeline is the caller (decompress_batch_one): its chunks' kernels are far from its bound -- the copies over the link -- and it
-                                       // already keeps three streams busy; the decode step's side stream only added a queue for those copies to share (65 536 x 128 KiB inside a process
-                                       // with other streams: 46-48 -> 38-43 GB/s with it, r06zl), so K1b stays on the chunk's stream there
-    size_t dstSlotsHint = 0;           // decode, host-buffer API: block slots the frames of the batch being launched are expected to need (1 per frame of one block, 2 per 128 KiB + 2 above), else 0
     size_t itemHint = 0;               // zhip_ctx_set_size_hint: what a device-API caller says about its items' uncompressed sizes (0 = nothing)
     zhip_cparams cparams = {3, 1, 0, 1, nullptr, 0, 0, 0, {0, 0, 0, 0, 0, 0, 0}};
     ZeRows rows = {};                  // cparams resolved per source-size class (zhip_cparams.hpp)
@@ -421,14 +400,9 @@ struct zhip_ctx {
     bool hpReady = false; hipStream_t hpH2D = nullptr, hpCompute = nullptr, hpD2H = nullptr;     // host pipeline: copy-in, kernels, copy-out
     void* hpStage[2] = {nullptr, nullptr}; size_t hpStageCap[2] = {0, 0}; hipEvent_t hpStageFree[2] = {nullptr, nullptr}; int hpNextSlot = 0;
     // bring-up / tuning knobs, read from the environment ONCE when the context is created (never in a launch path)
-    struct Knobs : ZeEncodeKnobs {      // (the encode knobs the launch plan reads: ZeEncodeKnobs, zhip_encode_plan.hpp)
+    struct Knobs : ZeEncodeKnobs, ZdDecodeKnobs {      // (the knobs the launch plans read: ZeEncodeKnobs, zhip_encode_plan.hpp; ZdDecodeKnobs, zhip_decode_plan.hpp)
         // bring-up aids
         bool prof = false;                  // ZHIP_PROF: the kernels' phase timers (a separate instantiation of K3; printed to stderr)
-        size_t k0Min = 6144;                // ZHIP_K0_MIN: frames per chunk from which K0 runs in front of K1 (a GPU test sets 0: K0 on every batch)
-        // decode pipeline
-        size_t dchunk = ZHIP_DCHUNK;        // frames (several-block mode: block slots) per chunk
-        int nslot = 2; bool nslotSet = false;   // chunk slots on their own streams (small frames get a third unless ZHIP_NSLOT says otherwise)
-        int k1PerCU = 0, k3PerCU = ZHIP_K3_PER_CU;       // waves per CU of K1 / K3 (0: what the occupancy query says)
         // encode (the rest: ZeEncodeKnobs)
         int waveH = ZHIP_WAVE_HLOG;         // ZHIP_WAVE_HLOG: table cells of the wave match finder, log2 (12, 13, 14)
         bool e1fPick = true;                // ZHIP_E1F_PICK=0: take the flat tables where the first allocation put them (zhip_compress_batch_device)
@@ -484,8 +458,6 @@ extern "C" zhip_ctx* zhip_ctx_create(void)
     c->encBlocksPerCU = nb;
     nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_decode_lit_kernel, 64, 0) != hipSuccess || nb < 1) nb = 8;
     c->k1PerCU = nb;
-    nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_decode_seq_kernel, 64, 0) != hipSuccess || nb < 1) nb = 3;
-    c->k2PerCU = nb;
     nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_decode_exec_kernel, 64, 0) != hipSuccess || nb < 1) nb = 16;
     c->k3PerCU = nb;
     nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_encode_match_kernel, 64, 0) != hipSuccess || nb < 1) nb = 4;
@@ -728,277 +700,267 @@ extern "C" int zhip_ctx_set_cparams(zhip_ctx* c, const zhip_cparams* p)
 }
 
 // ------------------------------------------------------------------------------------------ device-resident decode
-extern "C" int zhip_decompress_batch_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
-                                            void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
-                                            int32_t* d_status, void* streamv)
+// a chunk's timing events. Nothing is created while the context's timers are off, and every call is then a no-op; an event is destroyed with the owner unless a KTimer took it
+// (a timer owns both events of its pairs; a pair that a second timer reads as well is LENT to that one, before the give that hands its events over) -- a HIP call that fails
+// in the middle of a chunk leaks none
+struct ChunkEvents {
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~ChunkEvents() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
+    hipError_t create(int count) { for (int i = 0; i < count; i++) { const hipError_t e = hipEventCreate(&ev[i]); if (e != hipSuccess) return e; } return hipSuccess; }
+    hipError_t record(int i, hipStream_t stream) { return ev[i] ? hipEventRecord(ev[i], stream) : hipSuccess; }
+    void give(KTimer& t, int i, int j) { if (ev[i] && ev[j]) { t.pending.emplace_back(ev[i], ev[j]); ev[i] = ev[j] = nullptr; } }
+    void lend(KTimer& t, int i, int j) { if (ev[i] && ev[j]) t.shared.emplace_back(ev[i], ev[j]); }      // (borrowed pairs are always drained before any destroy: drain_shared)
+};
+// ordering only: every stream of `to` waits for what `from` holds now. The event is made, recorded, waited for and destroyed here: none can outlive a failing call
+static hipError_t streams_wait(hipStream_t from, const hipStream_t* to, int count)
 {
-    if (!c) return ZHIP_ERR_UNSUPPORTED;
-    if (n == 0) return 0;
-    if (n > 0x7FFFFFFFu) { g_lastError = "too many frames in one launch"; return ZHIP_ERR_UNSUPPORTED; }
-    hipStream_t stream = (hipStream_t)streamv;
-    size_t maxBlocks = (size_t)c->numCU * (size_t)c->decBlocksPerCU;
-    uint32_t grid = (uint32_t)(n < maxBlocks ? n : maxBlocks);
-    if (c->scratch.reserve((size_t)grid * ZHIP_LIT_STRIDE)) return g_reserveRc;
-    if (c->counter.reserve(64)) return g_reserveRc;
-    HIP_TRY(hipMemsetAsync(c->counter.p, 0, 4, stream));
-    const uint32_t* d_fallbackList = nullptr; const uint32_t* d_fallbackCount = nullptr;
-    const bool usePipeline = true;
-    if (usePipeline) {
-        // phase-split fast path for single-block, dictionary-less frames (zhip_decode_pipeline.hpp); everything it declines
-        // lands in the fallback list consumed by the generic kernel below.
-        // Chunks of frames flow through K1 -> K2 -> K3 on ZHIP_NSLOT internal streams (slot = chunk % NSLOT, each slot has its own
-        // arenas and counters), so that different chunks' kernels overlap on the GPU: each phase is latency-bound with idle issue
-        // slots, and their LDS footprints differ, which is exactly when co-residency pays.
-        const size_t chunkMax = c->knob.dchunk; int slotMax = c->knob.nslot;      // measured on MI355X (profiles/README.md, r01c / r02f / r02zl): 65 536 frames per chunk, 2 slots
-        // Frames of several blocks (the caller's size hint says so: the host API sets it from the items it sees): the several-block mode --
-        // the arenas' slots are per BLOCK, a chunk is as many frames as fit `chunkMax` slots at the estimate below (libzstd cuts a block of
-        // 128 KiB where the data changes; frames with more blocks than their share still work while the chunk has slots left, then
-        // they are the generic kernel's)
-        const uint64_t sizeHint = c->dstMaxHint ? c->dstMaxHint : c->itemHint;
-        // (small frames -- the caller says so -- are short kernels with launch gaps between them: a third chunk slot fills them. 262 144 x 4 KiB with the
-        // shared dictionary: 123 -> 134 GB/s, r05q; frames of 128 KiB: the kernels are long, two slots overlap little as it is)
-        if (!c->knob.nslotSet && sizeHint && sizeHint <= 16384 && slotMax < 3) slotMax = 3;
-        const bool mb = sizeHint > ZF_BLOCK_MAX && sizeHint <= 0x7FFFFFFFull;     // (larger frames are the generic kernel's anyway)
-        // K1b beside K2 on a side stream (below) -- not for batches of small frames: their kernels are short, the three chunk slots overlap them already, and the
-        // side streams only added queues (262 144 x 4 KiB with the dictionary: 199 -> 187 GB/s, r06p)
-        const bool side = ZHIP_SIDE && !c->hostPipe && !(sizeHint && sizeHint <= 16384);
-        // (with the side stream a batch of several chunks runs them one after the other on ONE slot stream: two slots' kernels side by side mix K3 with the next chunk's
-        // K2 -- each slows the other, section 4.1 of DESIGN.md -- and the side stream has taken the tail the second slot used to fill. 131 072 x 128 KiB: 360 GB/s on two
-        // slots with or without the side stream, 365-366 on one slot with it, and half the scratch (r06s). A single 128 KiB frame: 3.6 -> 2.4 ms, its two chains run together)
-        if (side) slotMax = 1;
-        // (two slots per 128 KiB decide how many frames make a chunk -- the slots are a pool, a frame may take more than its share; a chunk of
-        // FEW frames has no pool to lean on and gets four: 64 x 128 KiB of changing data in one frame came as 235 blocks, r03x)
-        // (the host-buffer API knows every frame's size and says how many slots the batch should need in all -- a batch of mostly small frames
-        // with a few large ones is then not cut into chunks sized for the large ones: chunks are made for half the pool, the pool is twice
-        // what the chunk is expected to use)
-        const size_t perFrame = mb ? (size_t)(2 * ((sizeHint + ZF_BLOCK_MAX - 1) / ZF_BLOCK_MAX) + 2) : 1;
-        const size_t slotsHint = mb ? c->dstSlotsHint : 0;
-        const size_t chunkFrames = !mb ? chunkMax : slotsHint ? (size_t)((double)n * (double)(chunkMax / 2) / (double)slotsHint) + 1 : (chunkMax / perFrame ? chunkMax / perFrame : 1);
-        const size_t chunk = n < chunkFrames ? n : chunkFrames;
-        auto slotsFor = [&](size_t frames) {
-            if (!mb) return frames;
-            if (slotsHint) { const size_t want = 2 * (size_t)((double)frames * (double)slotsHint / (double)n + 1.0) + 64; return want < frames ? frames : want; }
-            const size_t lo = frames * perFrame, hi = 2 * lo < chunkMax ? 2 * lo : chunkMax; return lo > hi ? lo : hi; };
-        const size_t slots = slotsFor(chunk);                                           // item slots per chunk (== frames without the mode)
-        if (slots > 0x7FFFFFFFu) { g_lastError = "frame too large for the block arenas"; return ZHIP_ERR_UNSUPPORTED; }
-        const size_t nChunks = (n + chunk - 1) / chunk;
-        const int nslot = (int)(nChunks < (size_t)slotMax ? nChunks : (size_t)slotMax);
-        // ONE compact arena holds literals and sequences (a "frame" below is an ITEM -- a block -- in the several-block mode): K1 claims what a
-        // frame's literals need, K2 what a group's sequences need, from a per-chunk budget (ZhipPipeArgs.bases). A block's literals and sequences
-        // trade off -- every sequence costs at least three bytes of output -- so the budget is common: 160 KiB per frame on average (the ratio-3 bench
-        // corpus needs 45 KiB + 76 KiB, Huffman-only data 128 KiB + nothing, 4-symbol noise 3 + 150 KiB; the worst case, a match every three bytes, 350 KiB):
-        // 10 GiB per 65 536-frame chunk instead of the 8 + 22 GiB of fixed slots, with up to 1 024 frames' worth of worst case as the floor so that small
-        // batches never run out. What does not fit goes to the generic kernel (correct, slower).
-        const size_t floorFrames = slots < 1024 ? slots : 1024;
-        // (frames the caller says are SMALL cannot need more than their own worst case -- literals of the frame's size + 256, a sequence per three bytes in
-        // rooms of the group's longest + 8 --: 4 x the size + 1 KiB; 4 KiB documents get 17 KiB each instead of 160)
-        const size_t smallWorst = !mb && sizeHint && sizeHint < ZF_BLOCK_MAX ? 4 * (size_t)sizeHint + 1024 : (size_t)0;
-        const size_t roomPerFrame = smallWorst && smallWorst < (160u << 10) ? smallWorst : (size_t)(160u << 10);
-        size_t arenaBudget16 = slots * (roomPerFrame / 16);
-        const size_t worstFrame = smallWorst ? smallWorst : (size_t)(ZP_SEQ_STRIDE + ZP_LIT_STRIDE);
-        if (arenaBudget16 < floorFrames * (worstFrame / 16)) arenaBudget16 = floorFrames * (worstFrame / 16);
-        if (arenaBudget16 > 0xFFFFFFF0u) arenaBudget16 = 0xFFFFFFF0u;
-        const size_t arenaBytes = arenaBudget16 * 16 + 512;
-        if (c->pipeBases.reserve(nslot * slots * 2 * sizeof(uint32_t))) return g_reserveRc;
-        if (c->pipeMeta.reserve(nslot * slots * sizeof(ZdMeta)) || c->pipeLit.reserve(nslot * arenaBytes + ZP_LIT_FRONT) || c->pipeCounters.reserve((8 + (size_t)ZHIP_NSLOT * ZP_CNT_WORDS) * 4) || c->pipeFallback.reserve(n * 4 + 16) ||
-            c->pipeFse.reserve(nslot * slots * ZP_FSE_CELLS * sizeof(uint16_t)) || c->pipeOrder.reserve(nslot * slots * sizeof(uint32_t)) ||
-            c->pipeHuf.reserve(nslot * slots * ZP_HUF_CELLS * sizeof(uint16_t)) || c->pipeOrderLit.reserve(nslot * slots * sizeof(uint32_t))) return g_reserveRc;
-        // K0's records (one per frame; not in the several-block mode, whose K1 walks a frame's blocks in order, nor for dictionary batches, whose lane pass finishes what has no table of its own)
-        // (... nor for small batches: K0 is a lane-serial walk of ~0.1 ms whatever the batch, which pays from ~6 000 frames on -- 2 048 frames 3.53 -> 3.62 ms with it, 8 192
-        // 4.66 -> 4.62, 16 384 7.17 -> 6.96, 32 768 12.5 -> 12.0, 65 536 23.4 -> 22.4; `profiles/r06z2_k0_by_batch_size.txt`)
-        const bool pre = ZHIP_K0 && !mb && !c->dictHasEntropy && chunk >= c->knob.k0Min;
-        if (pre && c->pipePre.reserve(nslot * slots * sizeof(ZpPre))) return g_reserveRc;
-        if (mb && (c->pipeItemFrame.reserve(nslot * slots * sizeof(uint32_t)) || c->pipeItemReps.reserve(nslot * slots * 4 * sizeof(uint32_t)) ||
-                   c->pipeFrameRecs.reserve(nslot * chunk * sizeof(ZpFrameRec)))) return g_reserveRc;
-        for (int sidx = 0; sidx < nslot; sidx++) if (!c->slotStream[sidx]) HIP_TRY(hipStreamCreateWithFlags(&c->slotStream[sidx], hipStreamNonBlocking));
-        HIP_TRY(hipMemsetAsync(c->pipeCounters.p, 0, (8 + (size_t)ZHIP_NSLOT * ZP_CNT_WORDS) * 4, stream));
-        hipEvent_t evStart; HIP_TRY(hipEventCreateWithFlags(&evStart, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(evStart, stream));
-        for (int sidx = 0; sidx < nslot; sidx++) HIP_TRY(hipStreamWaitEvent(c->slotStream[sidx], evStart, 0));
-        (void)hipEventDestroy(evStart);
-        ZhipPipeArgs pa; memset(&pa, 0, sizeof pa);
-        pa.src = (const uint8_t*)d_src; pa.srcSegs = (const uint64_t*)d_srcSegs; pa.dst = (uint8_t*)d_dst; pa.dstSegs = (const uint64_t*)d_dstSegs;
-        pa.outSizes = d_outSizes; pa.status = d_status; pa.fallbackList = (uint32_t*)c->pipeFallback.p;
-        pa.maxWindowSize = c->maxWindowSize; pa.magicless = c->dformat == ZHIP_FORMAT_ZSTD1_MAGICLESS;
-        if (c->dictSize) {                                  // dictionary frames take the pipeline too (r02v; the generic kernel rebuilt the dictionary's tables per frame)
-            pa.dictID = c->dictID;
-            pa.dictContent = (const uint8_t*)c->dictBlob.p + c->dictContentOffset;
-            pa.dictContentSize = c->dictSize - c->dictContentOffset;
-            pa.dictEntropy = c->dictHasEntropy ? (const ZhipDictEntropy*)c->dictEntropy.p : nullptr;
-            pa.dictTables = c->dictHasEntropy ? (const ZhipDictTables*)c->dictTables.p : nullptr;
-        }
-        if (c->knob.prof) {
-            if (!c->profPipe && (c->dictSize || mb))
-                fprintf(stderr, "[zhip-prof] K3's phase timers exist in the dictionary-less single-block kernel only: with a dictionary or frames of several blocks they read zero\n");
-            if (!c->profPipe) HIP_TRY(hipMalloc((void**)&c->profPipe, 32 * 8));
-            HIP_TRY(hipMemsetAsync(c->profPipe, 0, 32 * 8, stream));
-            pa.prof = c->profPipe;
-        }
-        uint32_t* counters = (uint32_t*)c->pipeCounters.p;        // [0] = fallback length, then 8 words per slot
-        pa.fallbackCount = counters;
-        size_t ci = 0;
-        for (size_t first = 0; first < n; first += chunk, ci++) {
-            const int sidx = (int)(ci % nslot);
-            hipStream_t ss = c->slotStream[sidx];
-            const size_t cnt = n - first < chunk ? n - first : chunk;
-            pa.first = (uint32_t)first; pa.count = (uint32_t)cnt;
-            pa.meta = (ZdMeta*)c->pipeMeta.p + (size_t)sidx * slots;
-            pa.litArena = (uint8_t*)c->pipeLit.p + ZP_LIT_FRONT + (size_t)sidx * arenaBytes;     // (ZP_LIT_FRONT = 256 bytes in front: K2's parked / first stores of a room at 0 land there)
-            pa.seqArena = (uint64_t*)pa.litArena;
-            pa.bases = (uint32_t*)c->pipeBases.p + (size_t)sidx * slots * 2; pa.arenaBudget16 = (uint32_t)arenaBudget16;
-            pa.fseTables = (uint16_t*)c->pipeFse.p + (size_t)sidx * slots * ZP_FSE_CELLS;
-            pa.order = (uint32_t*)c->pipeOrder.p + (size_t)sidx * slots;
-            pa.hufTables = (uint16_t*)c->pipeHuf.p + (size_t)sidx * slots * ZP_HUF_CELLS;
-            pa.orderLit = (uint32_t*)c->pipeOrderLit.p + (size_t)sidx * slots;
-            if (mb) {
-                pa.itemCap = (uint32_t)slotsFor(cnt);
-                pa.itemFrame = (uint32_t*)c->pipeItemFrame.p + (size_t)sidx * slots;
-                pa.itemReps = (uint32_t*)c->pipeItemReps.p + (size_t)sidx * slots * 4;
-                pa.frameRecs = (ZpFrameRec*)c->pipeFrameRecs.p + (size_t)sidx * chunk;
-            }
-            const size_t items = mb ? (size_t)pa.itemCap : cnt;                         // K1b / K2 / KB work items (an upper bound in the several-block mode)
-            pa.counters = counters + 8 + ZP_CNT_WORDS * sidx;
-            if (ci >= (size_t)nslot) HIP_TRY(hipMemsetAsync(pa.counters, 0, ZP_CNT_WORDS * 4, ss));
-            size_t g1m = (size_t)c->numCU * c->k1PerCU, g3m = (size_t)c->numCU * c->k3PerCU;
-            if (c->knob.k3PerCU) g3m = (size_t)c->numCU * (size_t)c->knob.k3PerCU;
-            if (c->knob.k1PerCU) g1m = (size_t)c->numCU * (size_t)c->knob.k1PerCU;
-            // K2 and K1b are sized by LDS: as many one-wave workgroups per CU as their table sets fit (K2: 15 frames per wave -> 4)
-            const size_t w2 = (items + ZQ_FRAMES - 1) / ZQ_FRAMES, g2m = (size_t)c->numCU * (ZHIP_LDS_BYTES / sizeof(ZpSeqQLDS));
-            // dictionary batches: a lane-per-frame pass first (zhip_decode_lit_lanes_kernel: frames whose tables are all the dictionary's are nothing but header
-            // arithmetic), K1 then only over the frames that pass listed
-            pa.k1Lanes = !mb && c->dictHasEntropy ? 1u : 0u;
-            pa.ckLater = 1;
-            pa.pre = pre ? (ZpPre*)c->pipePre.p + (size_t)sidx * slots : nullptr;
-            const size_t tasks1 = cnt;
-            const uint32_t g1 = (uint32_t)(tasks1 < g1m ? tasks1 : g1m), g2 = (uint32_t)(w2 < g2m ? w2 : g2m), g3 = (uint32_t)(cnt < g3m ? cnt : g3m);
-            const size_t wh = (items + ZP_HUF_FRAMES - 1) / ZP_HUF_FRAMES, ghm = (size_t)c->numCU * (ZHIP_LDS_BYTES / sizeof(ZpHufKernelLDS));
-            const uint32_t gh = (uint32_t)(wh < ghm ? wh : ghm);
-            const bool tm = c->timing;
-            hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}, evh = nullptr, evh2 = nullptr;
-            if (tm) {
-                for (int i = 0; i < 4; i++) HIP_TRY(hipEventCreate(&ev[i]));
-                HIP_TRY(hipEventCreate(&evh)); HIP_TRY(hipEventCreate(&evh2));
-                HIP_TRY(hipEventRecord(ev[0], ss));
-            }
-            if (mb) hipLaunchKernelGGL(zhip_decode_lit_mb_kernel, dim3(g1), dim3(64), 0, ss, pa);
-            else {
-                if (pa.pre) { const size_t w = (cnt + 63) / 64, gm = (size_t)c->numCU * 7; hipLaunchKernelGGL(zhip_decode_pre_kernel, dim3((uint32_t)(w < gm ? w : gm)), dim3(64), 0, ss, pa); }      // (7 waves of 21.3 KiB of LDS per CU)
-                if (pa.k1Lanes) { const size_t w = (cnt + 63) / 64; hipLaunchKernelGGL(zhip_decode_lit_lanes_kernel, dim3((uint32_t)(w < g1m ? w : g1m)), dim3(64), 0, ss, pa); }
-                hipLaunchKernelGGL(zhip_decode_lit_kernel, dim3(g1), dim3(64), 0, ss, pa);
-            }
-            hipLaunchKernelGGL(zhip_decode_bin_kernel, dim3(2 * (items < 4096 ? 1u : 64u)), dim3(64), 0, ss, pa);      // tiny; timed with K1
-            hipEvent_t evS0 = nullptr, evS1 = nullptr;
-            if (side) {
-                // K1b and K2 need nothing of each other: both follow K1 and the bins, K3 follows both. K2's 15-frame groups are long (~1.9 ms at 128 KiB) and a wave gets 4.27 of
-                // them at 65 536 frames, so K2 ends with three quarters of its waves gone for a group's time, and K1b then starts on an empty chip. K1b goes to a side stream BEHIND
-                // K2's launch instead: K2's one-wave workgroups are all resident at once, K1b's land where K2's have drained (two K2 waves' LDS make room for one of K1b's).
-                // 65 536 x 128 KiB: 24.35 -> 23.3 ms (K1b's 3.35 ms cost 2.4 beyond K2's end), frames of several blocks 150 -> 158 GB/s (r06p). The other order (K1b first)
-                // LOSES, 26.2 ms: K1b's short groups keep handing LDS to K2 piecemeal and the mix holds three waves per CU where K2 alone holds four.
-                if (!c->sideStream[sidx]) HIP_TRY(hipStreamCreateWithFlags(&c->sideStream[sidx], hipStreamNonBlocking));
-                hipStream_t sd = c->sideStream[sidx];
-                hipEvent_t evBin, evSide; HIP_TRY(hipEventCreateWithFlags(&evBin, hipEventDisableTiming)); HIP_TRY(hipEventCreateWithFlags(&evSide, hipEventDisableTiming));
-                if (tm) { HIP_TRY(hipEventRecord(evh, ss)); HIP_TRY(hipEventRecord(evh2, ss)); HIP_TRY(hipEventCreate(&evS0)); HIP_TRY(hipEventCreate(&evS1)); }
-                HIP_TRY(hipEventRecord(evBin, ss));
-                HIP_TRY(hipStreamWaitEvent(sd, evBin, 0));
-                if (mb) hipLaunchKernelGGL(zhip_decode_seq_mb_kernel, dim3(g2), dim3(64), 0, ss, pa);
-                else hipLaunchKernelGGL(zhip_decode_seq_kernel, dim3(g2), dim3(64), 0, ss, pa);
-                if (tm) { HIP_TRY(hipEventRecord(ev[1], ss)); HIP_TRY(hipEventRecord(evS0, ss)); }       // (two events at K2's end: one closes K2's pair, one opens K1b's)
-                hipLaunchKernelGGL(zhip_decode_huf_kernel, dim3(gh), dim3(64), 0, sd, pa);
-                if (tm) HIP_TRY(hipEventRecord(evS1, sd));
-                HIP_TRY(hipEventRecord(evSide, sd));
-                HIP_TRY(hipStreamWaitEvent(ss, evSide, 0));
-                (void)hipEventDestroy(evBin); (void)hipEventDestroy(evSide);
-                if (tm) HIP_TRY(hipEventRecord(ev[2], ss));
-            } else {
-                if (tm) { HIP_TRY(hipEventRecord(evh, ss)); HIP_TRY(hipEventRecord(evh2, ss)); }
-                hipLaunchKernelGGL(zhip_decode_huf_kernel, dim3(gh), dim3(64), 0, ss, pa);
-                if (tm) HIP_TRY(hipEventRecord(ev[1], ss));
-                if (mb) hipLaunchKernelGGL(zhip_decode_seq_mb_kernel, dim3(g2), dim3(64), 0, ss, pa);
-                else hipLaunchKernelGGL(zhip_decode_seq_kernel, dim3(g2), dim3(64), 0, ss, pa);
-                if (tm) HIP_TRY(hipEventRecord(ev[2], ss));
-            }
-            if (mb && pa.dictContent) hipLaunchKernelGGL(zhip_decode_exec_mb_dict_kernel, dim3(g3), dim3(64), 0, ss, pa);
-            else if (mb) hipLaunchKernelGGL(zhip_decode_exec_mb_kernel, dim3(g3), dim3(64), 0, ss, pa);
-            else if (pa.dictContent) hipLaunchKernelGGL(zhip_decode_exec_dict_kernel, dim3(g3), dim3(64), 0, ss, pa);
-            else if (pa.prof) hipLaunchKernelGGL(zhip_decode_exec_prof_kernel, dim3(g3), dim3(64), 0, ss, pa);      // (ZHIP_PROF with a dictionary or frames of several blocks: K3's timers read zero -- said once at context creation)
-            else hipLaunchKernelGGL(zhip_decode_exec_kernel, dim3(g3), dim3(64), 0, ss, pa);
-            { const size_t w = (cnt + 63) / 64, gm = (size_t)c->numCU * 8; hipLaunchKernelGGL(zhip_decode_check_kernel, dim3((uint32_t)(w < gm ? w : gm)), dim3(64), 0, ss, pa); }      // KX (returns at once when no frame carries a checksum; timed with K3)
-            if (tm) HIP_TRY(hipEventRecord(ev[3], ss));
-            HIP_TRY(hipGetLastError());
-            if (tm) {
-                // consecutive events bracket one kernel each (same stream, nothing in between). Ownership: K1's timer owns
-                // (ev[0], evh), K1b's (evh2, ev[1]), K3's (ev[2], ev[3]); K2's pair (ev[1], ev[2]) is borrowed and always drained
-                // before any destroy.
-                c->timer[2].pending.emplace_back(ev[0], evh);          // K1 (+ the two bin waves)
-                if (side) {
-                    // K2's pair is its own now; K1b's is what it costs the step: from K2's END (on the main stream) to its own end on the side stream -- its first part
-                    // runs inside K2's tail --, so that the kernels' times still add up to the step (a K1b that ends before K2 counts zero)
-                    c->timer[3].pending.emplace_back(evh2, ev[1]);
-                    c->timer[7].pending.emplace_back(evS0, evS1);
-                } else {
-                    c->timer[7].pending.emplace_back(evh2, ev[1]);         // K1b
-                    c->timer[3].shared.emplace_back(ev[1], ev[2]);
-                }
-                c->timer[9].shared.emplace_back(ev[0], ev[3]);             // the chunk's pipeline, K1's start to K3's end: what the step costs now that two of its kernels overlap
-                c->timer[4].pending.emplace_back(ev[2], ev[3]);
-            }
-        }
-        if (pa.prof) {
-            HIP_TRY(hipDeviceSynchronize());
-            unsigned long long h[32];
-            HIP_TRY(hipMemcpy(h, pa.prof, sizeof h, hipMemcpyDeviceToHost));
-            static const char* nm[10] = {"header", "huf-table", "huf-decode", "seq-header+fse", "K3 load+scan", "-", "K3 literal/far fetch", "K3 near rounds", "K3 flush", "tail"};
-            for (int k = 0; k < 2; k++) {
-                unsigned long long tot = 0; for (int q = 0; q < 10; q++) tot += h[16 * k + q];
-                fprintf(stderr, "[zhip-prof] %s: %.0f wave-cycles per frame\n", k ? "K3" : "K1", (double)tot / (double)n);
-                for (int q = 0; q < 10; q++) if (h[16 * k + q]) fprintf(stderr, "[zhip-prof]    %-22s %6.2f%% %10.0f cyc/frame\n", nm[q], 100.0 * h[16 * k + q] / (tot ? tot : 1), (double)h[16 * k + q] / (double)n);
-            }
-        }
-        for (int sidx = 0; sidx < nslot; sidx++) {                 // the caller's stream continues after every slot has drained
-            hipEvent_t evEnd; HIP_TRY(hipEventCreateWithFlags(&evEnd, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(evEnd, c->slotStream[sidx]));
-            HIP_TRY(hipStreamWaitEvent(stream, evEnd, 0));
-            (void)hipEventDestroy(evEnd);
-        }
-        d_fallbackList = (const uint32_t*)c->pipeFallback.p; d_fallbackCount = (const uint32_t*)c->pipeCounters.p;
-        // the generic kernel only sees the (usually empty) fallback list: a small grid is enough
-        // (unless the caller says its frames exceed one block: then the list is the whole batch)
-        if (grid > 1024 && (mb || !(sizeHint > ZF_BLOCK_MAX))) grid = 1024;
+    hipEvent_t e = nullptr;
+    hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    if (r != hipSuccess) return r;
+    r = hipEventRecord(e, from);
+    for (int i = 0; i < count && r == hipSuccess; i++) r = hipStreamWaitEvent(to[i], e, 0);
+    (void)hipEventDestroy(e);
+    return r;
+}
+// a table of the kernels' phase timers (ZHIP_PROF): a line per phase with its share of `tot` and its wave-cycles per frame (`skipZero`: phases that counted nothing are left out)
+static void print_prof_rows(const unsigned long long* h, const char* const* names, int count, unsigned long long tot, double frames, bool skipZero)
+{
+    for (int q = 0; q < count; q++) if (h[q] || !skipZero) fprintf(stderr, "[zhip-prof]    %-22s %6.2f%% %10.0f cyc/frame\n", names[q], 100.0 * h[q] / (tot ? tot : 1), (double)h[q] / frames);
+}
+// the dictionary fields that ZhipPipeArgs and ZhipDecodeArgs share
+template <class Args> static void set_dict_args(const zhip_ctx* c, Args& a)
+{
+    if (!c->dictSize) return;
+    a.dictID = c->dictID;
+    a.dictContent = (const uint8_t*)c->dictBlob.p + c->dictContentOffset;
+    a.dictContentSize = c->dictSize - c->dictContentOffset;
+    a.dictEntropy = c->dictHasEntropy ? (const ZhipDictEntropy*)c->dictEntropy.p : nullptr;
+}
+// the launch plan's inputs (zhip_decode_plan.hpp) as this context has them
+static ZdPlanIn decode_plan_inputs(const zhip_ctx* c, size_t n, const ZdHints& hint)
+{
+    ZdPlanIn in;
+    in.n = n; in.hint = hint; in.dict = ZdPlanDict{c->dictSize != 0, c->dictHasEntropy}; in.prof = c->knob.prof; in.knob = c->knob;
+    in.dev.numCU = c->numCU; in.dev.decBlocksPerCU = c->decBlocksPerCU; in.dev.k1PerCU = c->k1PerCU; in.dev.k3PerCU = c->k3PerCU;
+    in.dev.k2LdsPerCU = ZHIP_LDS_BYTES / sizeof(ZpSeqQLDS); in.dev.k1bLdsPerCU = ZHIP_LDS_BYTES / sizeof(ZpHufKernelLDS); in.dev.k2Frames = ZQ_FRAMES;
+    return in;
+}
+// the pipeline's buffers at the plan's sizes
+static int reserve_decode(zhip_ctx* c, const ZdPlan& p)
+{
+    if (c->pipeBases.reserve(p.basesBytes)) return g_reserveRc;
+    if (c->pipeMeta.reserve(p.metaBytes) || c->pipeLit.reserve(p.litBytes) || c->pipeCounters.reserve(p.countersBytes) || c->pipeFallback.reserve(p.fallbackBytes) ||
+        c->pipeFse.reserve(p.fseBytes) || c->pipeOrder.reserve(p.orderBytes) || c->pipeHuf.reserve(p.hufBytes) || c->pipeOrderLit.reserve(p.orderLitBytes)) return g_reserveRc;
+    if (p.pre && c->pipePre.reserve(p.preBytes)) return g_reserveRc;
+    if (p.mb && (c->pipeItemFrame.reserve(p.itemFrameBytes) || c->pipeItemReps.reserve(p.itemRepsBytes) || c->pipeFrameRecs.reserve(p.frameRecsBytes))) return g_reserveRc;
+    return 0;
+}
+// the pipeline's arguments that are the same for every chunk of the call
+static int pipe_args_init(zhip_ctx* c, ZhipPipeArgs& pa, const ZdPlan& p, const void* d_src, const zhip_segment* d_srcSegs, void* d_dst, const zhip_segment* d_dstSegs,
+                          uint64_t* d_outSizes, int32_t* d_status, hipStream_t stream)
+{
+    memset(&pa, 0, sizeof pa);
+    pa.src = (const uint8_t*)d_src; pa.srcSegs = (const uint64_t*)d_srcSegs; pa.dst = (uint8_t*)d_dst; pa.dstSegs = (const uint64_t*)d_dstSegs;
+    pa.outSizes = d_outSizes; pa.status = d_status; pa.fallbackList = (uint32_t*)c->pipeFallback.p;
+    pa.maxWindowSize = c->maxWindowSize; pa.magicless = c->dformat == ZHIP_FORMAT_ZSTD1_MAGICLESS;
+    set_dict_args(c, pa);                               // dictionary frames take the pipeline too (r02v; the generic kernel rebuilt the dictionary's tables per frame)
+    pa.dictTables = pa.dictEntropy ? (const ZhipDictTables*)c->dictTables.p : nullptr;
+    if (c->knob.prof) {
+        if (!c->profPipe && (c->dictSize || p.mb))
+            fprintf(stderr, "[zhip-prof] K3's phase timers exist in the dictionary-less single-block kernel only: with a dictionary or frames of several blocks they read zero\n");
+        if (!c->profPipe) HIP_TRY(hipMalloc((void**)&c->profPipe, 32 * 8));
+        HIP_TRY(hipMemsetAsync(c->profPipe, 0, 32 * 8, stream));
+        pa.prof = c->profPipe;
     }
+    pa.fallbackCount = (uint32_t*)c->pipeCounters.p;          // [0] = fallback length, then 8 words per slot
+    pa.arenaBudget16 = (uint32_t)p.arenaBudget16;
+    pa.k1Lanes = p.k1Lanes ? 1u : 0u;
+    pa.ckLater = 1;
+    return 0;
+}
+// ... and those of one chunk: frames [first, first + cnt) in the arenas of slot `sidx`
+static void pipe_args_chunk(const zhip_ctx* c, ZhipPipeArgs& pa, const ZdPlan& p, const ZdChunkPlan& k, int sidx, size_t first, size_t cnt)
+{
+    const size_t slots = p.slots;
+    pa.first = (uint32_t)first; pa.count = (uint32_t)cnt;
+    pa.meta = (ZdMeta*)c->pipeMeta.p + (size_t)sidx * slots;
+    pa.litArena = (uint8_t*)c->pipeLit.p + ZP_LIT_FRONT + (size_t)sidx * p.arenaBytes;     // (ZP_LIT_FRONT = 256 bytes in front: K2's parked / first stores of a room at 0 land there)
+    pa.seqArena = (uint64_t*)pa.litArena;
+    pa.bases = (uint32_t*)c->pipeBases.p + (size_t)sidx * slots * 2;
+    pa.fseTables = (uint16_t*)c->pipeFse.p + (size_t)sidx * slots * ZP_FSE_CELLS;
+    pa.order = (uint32_t*)c->pipeOrder.p + (size_t)sidx * slots;
+    pa.hufTables = (uint16_t*)c->pipeHuf.p + (size_t)sidx * slots * ZP_HUF_CELLS;
+    pa.orderLit = (uint32_t*)c->pipeOrderLit.p + (size_t)sidx * slots;
+    if (p.mb) {
+        pa.itemCap = k.itemCap;
+        pa.itemFrame = (uint32_t*)c->pipeItemFrame.p + (size_t)sidx * slots;
+        pa.itemReps = (uint32_t*)c->pipeItemReps.p + (size_t)sidx * slots * 4;
+        pa.frameRecs = (ZpFrameRec*)c->pipeFrameRecs.p + (size_t)sidx * p.chunk;
+    }
+    pa.counters = (uint32_t*)c->pipeCounters.p + 8 + ZP_CNT_WORDS * sidx;
+    pa.pre = p.pre ? (ZpPre*)c->pipePre.p + (size_t)sidx * slots : nullptr;
+}
+// K2 and K3 in the form the chunk's plan names (zd_decode_chunk_plan)
+static void launch_k2(const ZdChunkPlan& k, hipStream_t ss, const ZhipPipeArgs& pa)
+{
+    if (k.k2 == ZD_K2_MB) hipLaunchKernelGGL(zhip_decode_seq_mb_kernel, dim3(k.g2), dim3(64), 0, ss, pa);
+    else hipLaunchKernelGGL(zhip_decode_seq_kernel, dim3(k.g2), dim3(64), 0, ss, pa);
+}
+static void launch_k3(const ZdChunkPlan& k, hipStream_t ss, const ZhipPipeArgs& pa)
+{
+    const dim3 g(k.g3), b(64);
+    if (k.k3 == ZD_K3_MB_DICT) hipLaunchKernelGGL(zhip_decode_exec_mb_dict_kernel, g, b, 0, ss, pa);
+    else if (k.k3 == ZD_K3_MB) hipLaunchKernelGGL(zhip_decode_exec_mb_kernel, g, b, 0, ss, pa);
+    else if (k.k3 == ZD_K3_DICT) hipLaunchKernelGGL(zhip_decode_exec_dict_kernel, g, b, 0, ss, pa);
+    else if (k.k3 == ZD_K3_PROF) hipLaunchKernelGGL(zhip_decode_exec_prof_kernel, g, b, 0, ss, pa);
+    else hipLaunchKernelGGL(zhip_decode_exec_kernel, g, b, 0, ss, pa);
+}
+// a chunk's kernels on its slot's stream (K0 / the lane pass, K1, the bins, K1b and K2, K3, KX), and its timers
+static int launch_decode_chunk(zhip_ctx* c, const ZdPlan& p, const ZdChunkPlan& k, const ZhipPipeArgs& pa, int sidx)
+{
+    hipStream_t ss = c->slotStream[sidx];
+    // the timing events, in the order they are recorded on the chunk's stream: 0 K1's start; 4 and 5 the bins' end; 1 K1b's end (with the side stream: K2's); 2 K3's start; 3 KX's end.
+    // With the side stream two more: 6 at K2's end again, 7 K1b's end on the side stream
+    ChunkEvents ev;
+    if (c->timing) HIP_TRY(ev.create(p.side ? 8 : 6));
+    HIP_TRY(ev.record(0, ss));
+    if (k.k1 == ZD_K1_MB) hipLaunchKernelGGL(zhip_decode_lit_mb_kernel, dim3(k.g1), dim3(64), 0, ss, pa);
+    else {
+        if (k.gPre) hipLaunchKernelGGL(zhip_decode_pre_kernel, dim3(k.gPre), dim3(64), 0, ss, pa);
+        if (k.k1 == ZD_K1_LANES) hipLaunchKernelGGL(zhip_decode_lit_lanes_kernel, dim3(k.gLanes), dim3(64), 0, ss, pa);
+        hipLaunchKernelGGL(zhip_decode_lit_kernel, dim3(k.g1), dim3(64), 0, ss, pa);
+    }
+    hipLaunchKernelGGL(zhip_decode_bin_kernel, dim3(k.gBin), dim3(64), 0, ss, pa);      // tiny; timed with K1
+    HIP_TRY(ev.record(4, ss)); HIP_TRY(ev.record(5, ss));
+    if (p.side) {
+        // K1b and K2 need nothing of each other: both follow K1 and the bins, K3 follows both. K2's 15-frame groups are long (~1.9 ms at 128 KiB) and a wave gets 4.27 of
+        // them at 65 536 frames, so K2 ends with three quarters of its waves gone for a group's time, and K1b then starts on an empty chip. K1b goes to a side stream BEHIND
+        // K2's launch instead: K2's one-wave workgroups are all resident at once, K1b's land where K2's have drained (two K2 waves' LDS make room for one of K1b's).
+        // 65 536 x 128 KiB: 24.35 -> 23.3 ms (K1b's 3.35 ms cost 2.4 beyond K2's end), frames of several blocks 150 -> 158 GB/s (r06p). The other order (K1b first)
+        // LOSES, 26.2 ms: K1b's short groups keep handing LDS to K2 piecemeal and the mix holds three waves per CU where K2 alone holds four.
+        if (!c->sideStream[sidx]) HIP_TRY(hipStreamCreateWithFlags(&c->sideStream[sidx], hipStreamNonBlocking));
+        hipStream_t sd = c->sideStream[sidx];
+        HIP_TRY(streams_wait(ss, &sd, 1));                      // the bins -> the side stream
+        launch_k2(k, ss, pa);
+        HIP_TRY(ev.record(1, ss)); HIP_TRY(ev.record(6, ss));       // (two events at K2's end: one closes K2's pair, one opens K1b's)
+        hipLaunchKernelGGL(zhip_decode_huf_kernel, dim3(k.gHuf), dim3(64), 0, sd, pa);
+        HIP_TRY(ev.record(7, sd));
+        HIP_TRY(streams_wait(sd, &ss, 1));                      // the side stream -> the chunk's
+    } else {
+        hipLaunchKernelGGL(zhip_decode_huf_kernel, dim3(k.gHuf), dim3(64), 0, ss, pa);
+        HIP_TRY(ev.record(1, ss));
+        launch_k2(k, ss, pa);
+    }
+    HIP_TRY(ev.record(2, ss));
+    launch_k3(k, ss, pa);
+    hipLaunchKernelGGL(zhip_decode_check_kernel, dim3(k.gCheck), dim3(64), 0, ss, pa);      // KX (returns at once when no frame carries a checksum; timed with K3)
+    HIP_TRY(ev.record(3, ss));
+    HIP_TRY(hipGetLastError());
+    // consecutive events bracket one kernel each (same stream, nothing in between). Ownership: K1's timer owns
+    // (ev[0], ev[4]), K1b's (ev[5], ev[1]), K3's (ev[2], ev[3]); K2's pair (ev[1], ev[2]) is borrowed and always drained
+    // before any destroy.
+    ev.lend(c->timer[9], 0, 3);                // the chunk's pipeline, K1's start to K3's end: what the step costs now that two of its kernels overlap
+    if (!p.side) ev.lend(c->timer[3], 1, 2);
+    ev.give(c->timer[2], 0, 4);                // K1 (+ the two bin waves)
+    if (p.side) {
+        // K2's pair is its own now; K1b's is what it costs the step: from K2's END (on the main stream) to its own end on the side stream -- its first part
+        // runs inside K2's tail --, so that the kernels' times still add up to the step (a K1b that ends before K2 counts zero)
+        ev.give(c->timer[3], 5, 1);
+        ev.give(c->timer[7], 6, 7);
+    } else ev.give(c->timer[7], 5, 1);         // K1b
+    ev.give(c->timer[4], 2, 3);
+    return 0;
+}
+// the pipeline kernels' phase timers of a call over n frames (ZHIP_PROF)
+static int print_pipe_prof(const unsigned long long* d_prof, size_t n)
+{
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned long long h[32];
+    HIP_TRY(hipMemcpy(h, d_prof, sizeof h, hipMemcpyDeviceToHost));
+    static const char* nm[10] = {"header", "huf-table", "huf-decode", "seq-header+fse", "K3 load+scan", "-", "K3 literal/far fetch", "K3 near rounds", "K3 flush", "tail"};
+    for (int k = 0; k < 2; k++) {
+        unsigned long long tot = 0; for (int q = 0; q < 10; q++) tot += h[16 * k + q];
+        fprintf(stderr, "[zhip-prof] %s: %.0f wave-cycles per frame\n", k ? "K3" : "K1", (double)tot / (double)n);
+        print_prof_rows(h + 16 * k, nm, 10, tot, (double)n, true);
+    }
+    return 0;
+}
+// the generic kernel over the pipeline's fallback list, on the caller's stream
+static int launch_decode_generic(zhip_ctx* c, uint32_t grid, const void* d_src, const zhip_segment* d_srcSegs, size_t n, void* d_dst, const zhip_segment* d_dstSegs,
+                                 uint64_t* d_outSizes, int32_t* d_status, hipStream_t stream)
+{
     ZhipDecodeArgs a; memset(&a, 0, sizeof a);
     a.src = (const uint8_t*)d_src; a.srcSegs = (const uint64_t*)d_srcSegs; a.dst = (uint8_t*)d_dst;
     a.dstSegs = (const uint64_t*)d_dstSegs; a.outSizes = d_outSizes; a.status = d_status;
     a.scratch = (uint8_t*)c->scratch.p; a.counter = (uint32_t*)c->counter.p; a.n = (uint32_t)n;
     a.maxWindowSize = c->maxWindowSize; a.magicless = c->dformat == ZHIP_FORMAT_ZSTD1_MAGICLESS;
-    a.frameList = d_fallbackList; a.listCount = d_fallbackCount;
-    if (c->dictSize) {
-        a.dictID = c->dictID;
-        a.dictContent = (const uint8_t*)c->dictBlob.p + c->dictContentOffset;
-        a.dictContentSize = c->dictSize - c->dictContentOffset;
-        a.dictEntropy = c->dictHasEntropy ? (const ZhipDictEntropy*)c->dictEntropy.p : nullptr;
-    }
+    a.frameList = (const uint32_t*)c->pipeFallback.p; a.listCount = (const uint32_t*)c->pipeCounters.p;
+    set_dict_args(c, a);
     const bool prof = c->knob.prof;
     if (prof) {
         if (!c->profDecode) HIP_TRY(hipMalloc((void**)&c->profDecode, ZP_N * 8));
         HIP_TRY(hipMemsetAsync(c->profDecode, 0, ZP_N * 8, stream));
         a.prof = c->profDecode;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) { HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1)); HIP_TRY(hipEventRecord(e0, stream)); }
+    ChunkEvents ev;
+    if (c->timing) HIP_TRY(ev.create(2));
+    HIP_TRY(ev.record(0, stream));
     hipLaunchKernelGGL(zhip_decode_frames_kernel, dim3(grid), dim3(64), 0, stream, a);
     HIP_TRY(hipGetLastError());
-    if (c->timing) HIP_TRY(hipEventRecord(e1, stream));
-    if (c->timing) c->timer[0].pending.emplace_back(e0, e1);
+    HIP_TRY(ev.record(1, stream));
+    ev.give(c->timer[0], 0, 1);
     if (prof) {
         unsigned long long h[ZP_N];
         HIP_TRY(hipMemcpy(h, c->profDecode, sizeof h, hipMemcpyDeviceToHost));
         static const char* names[ZP_N] = {"header/misc", "huf-table", "huf-decode", "seq-tables", "stage", "seq-decode(lane0)", "exec1(global->lds)", "exec2(lds rounds)", "flush", "raw/lastlit"};
         unsigned long long tot = 0; for (int i = 0; i < ZP_N; i++) tot += h[i];
         fprintf(stderr, "[zhip-prof] grid=%u (CUs %d x %d blocks) frames=%u wave-cycles total=%.3e (%.0f per frame)\n", grid, c->numCU, c->decBlocksPerCU, a.n, (double)tot, (double)tot / a.n);
-        for (int i = 0; i < ZP_N; i++) fprintf(stderr, "[zhip-prof]   %-22s %6.2f%%  %10.0f cyc/frame\n", names[i], 100.0 * h[i] / (tot ? tot : 1), (double)h[i] / a.n);
+        print_prof_rows(h, names, ZP_N, tot, (double)a.n, false);
     }
     if (c->timer[0].pending.size() > 1024) { HIP_TRY(hipStreamSynchronize(stream)); for (int i = 0; i < ZHIP_NTIMER; i++) drain_shared(c->timer[i]); for (int i = 0; i < ZHIP_NTIMER; i++) drain_timer(c->timer[i]); }
     return 0;
+}
+// zhip_decompress_batch_device under what the caller knows about the batch's frames (ZdHints): validate, plan, reserve, fork the slot streams off the caller's, the chunks,
+// join, the generic kernel. The phase-split fast path (zhip_decode_pipeline.hpp) takes single-block frames and, under a size hint, frames of several blocks; everything it
+// declines lands in the fallback list consumed by the generic kernel behind it. Every decision is the launch plan's (zhip_decode_plan.hpp).
+static int decompress_batch(zhip_ctx* c, const ZdHints& hint, const void* d_src, const zhip_segment* d_srcSegs, size_t n, void* d_dst, const zhip_segment* d_dstSegs,
+                            uint64_t* d_outSizes, int32_t* d_status, void* streamv)
+{
+    if (n == 0) return 0;
+    if (n > 0x7FFFFFFFu) { g_lastError = "too many frames in one launch"; return ZHIP_ERR_UNSUPPORTED; }
+    hipStream_t stream = (hipStream_t)streamv;
+    const ZdPlanIn in = decode_plan_inputs(c, n, hint);
+    const ZdPlan p = zd_decode_plan(in);
+    if (c->scratch.reserve(p.scratchBytes)) return g_reserveRc;
+    if (c->counter.reserve(p.counterBytes)) return g_reserveRc;
+    HIP_TRY(hipMemsetAsync(c->counter.p, 0, 4, stream));
+    if (p.tooLarge) { g_lastError = "frame too large for the block arenas"; return ZHIP_ERR_UNSUPPORTED; }
+    if (int rc = reserve_decode(c, p)) return rc;
+    for (int sidx = 0; sidx < p.nslot; sidx++) if (!c->slotStream[sidx]) HIP_TRY(hipStreamCreateWithFlags(&c->slotStream[sidx], hipStreamNonBlocking));
+    HIP_TRY(hipMemsetAsync(c->pipeCounters.p, 0, p.countersBytes, stream));
+    HIP_TRY(streams_wait(stream, c->slotStream, p.nslot));                 // the slots start after everything queued on the caller's stream
+    ZhipPipeArgs pa;
+    if (int rc = pipe_args_init(c, pa, p, d_src, d_srcSegs, d_dst, d_dstSegs, d_outSizes, d_status, stream)) return rc;
+    size_t ci = 0;
+    for (size_t first = 0; first < n; first += p.chunk, ci++) {
+        const int sidx = (int)(ci % p.nslot);
+        const size_t cnt = n - first < p.chunk ? n - first : p.chunk;
+        const ZdChunkPlan k = zd_decode_chunk_plan(in, p, cnt);
+        pipe_args_chunk(c, pa, p, k, sidx, first, cnt);
+        if (ci >= (size_t)p.nslot) HIP_TRY(hipMemsetAsync(pa.counters, 0, ZP_CNT_WORDS * 4, c->slotStream[sidx]));
+        if (int rc = launch_decode_chunk(c, p, k, pa, sidx)) return rc;
+    }
+    if (pa.prof) if (int rc = print_pipe_prof(pa.prof, n)) return rc;
+    for (int sidx = 0; sidx < p.nslot; sidx++) HIP_TRY(streams_wait(c->slotStream[sidx], &stream, 1));      // the caller's stream continues after every slot has drained
+    return launch_decode_generic(c, p.genericGrid, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, stream);
+}
+extern "C" int zhip_decompress_batch_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
+                                            void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
+                                            int32_t* d_status, void* streamv)
+{
+    if (!c) return ZHIP_ERR_UNSUPPORTED;
+    ZdHints hint; hint.size = c->itemHint;
+    return decompress_batch(c, hint, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, streamv);
 }
 // the LDS-source match kernel at one source size per CU slot -- the fast strategy's (FAST) or the double-fast one's -- of the four sizes the one the plan's shape names
 template <uint32_t BYTES, bool FAST> static void launch_lds_at(dim3 g, hipStream_t stream, const ZhipEncodeArgs& a)
@@ -1066,15 +1028,6 @@ static ZePlanIn plan_inputs(const zhip_ctx* c, size_t n)
     in.knob = c->knob;
     return in;
 }
-// a chunk's timing events. Nothing is created while the context's timers are off, and every call is then a no-op; an event is destroyed with the owner unless a KTimer took it
-// (a timer owns both events of its pairs, so two stages share none) -- a HIP call that fails in the middle of a chunk leaks none
-struct ChunkEvents {
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~ChunkEvents() { for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x); }
-    hipError_t create(int count) { for (int i = 0; i < count; i++) { const hipError_t e = hipEventCreate(&ev[i]); if (e != hipSuccess) return e; } return hipSuccess; }
-    hipError_t record(int i, hipStream_t stream) { return ev[i] ? hipEventRecord(ev[i], stream) : hipSuccess; }
-    void give(KTimer& t, int i, int j) { if (ev[i] && ev[j]) { t.pending.emplace_back(ev[i], ev[j]); ev[i] = ev[j] = nullptr; } }
-};
 // E2 over the chunk, g2 waves, and EX behind it for checksummed frames (timed with E2)
 static void launch_entropy(const zhip_ctx* c, ZhipEncodeArgs& a, uint32_t g2, size_t cnt, hipStream_t stream)
 {
@@ -1358,7 +1311,7 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
                                       "  stream: constants", "  stream: state chains", "  stream: pack + OR", "  stream: flush"};      // (the last four: -DZE_PROF_STREAM builds only)
         unsigned long long tot = 0; for (int q = 0; q <= ZEP_REST; q++) tot += h[q];
         fprintf(stderr, "[zhip-prof] E2: %.0f wave-cycles per frame\n", (double)tot / (double)n);
-        for (int q = 0; q < ZEP_N; q++) fprintf(stderr, "[zhip-prof]    %-22s %6.2f%% %10.0f cyc/frame\n", nm[q], 100.0 * h[q] / (tot ? tot : 1), (double)h[q] / (double)n);
+        print_prof_rows(h, nm, ZEP_N, tot, (double)n, false);
         a.prof = nullptr;
     }
     if (!p.mbc) {   // inputs above 128 KiB (multi-block frames): the generic one-wave-per-frame kernel over the list E1 made (usually empty)
@@ -1764,21 +1717,9 @@ static int decompress_batch_one(const zhip_dparams* params, const zhip_item* ite
         const uint64_t outBytes = segs[n + hi - 1].offset + segs[n + hi - 1].length - segs[n + lo].offset;
         if (upload_items(c, items, segs.data(), lo, hi, evUp)) return fail(ZHIP_ERR_HIP);
         if (hipStreamWaitEvent(c->hpCompute, evUp, 0) != hipSuccess) return fail(ZHIP_ERR_HIP);
-        {   uint64_t mx = 0, slotsWanted = 0; size_t several = 0;
-            for (size_t i = lo; i < hi; i++) {
-                const uint64_t len = segs[n + i].length;
-                if (len > mx) mx = len;
-                // (a frame's block count is known where its block headers could be walked: the slots it will take; else the estimate from its size)
-                slotsWanted += nBlocks[i] > 1 ? (uint64_t)nBlocks[i] + 1 : len <= ZF_BLOCK_MAX ? 1 : 2 * ((len + ZF_BLOCK_MAX - 1) / ZF_BLOCK_MAX) + 2;
-                several += nBlocks[i] > 1 && len <= ZF_BLOCK_MAX;
-            }
-            // frames of one block's size cut into SEVERAL blocks (the block splitter of levels 16+): from one in sixteen on the chunk takes the several-block mode -- a size hint just
-            // above a block says so --, below that the few go to the generic kernel as before
-            if (several * 16 >= cnt && mx <= ZF_BLOCK_MAX) mx = ZF_BLOCK_MAX + 1;
-            c->dstMaxHint = (size_t)mx; c->dstSlotsHint = (size_t)slotsWanted; }
-        c->hostPipe = true;
-        r = zhip_decompress_batch_device(c, c->hSrc.p, dSegs + lo, cnt, c->hDst.p, dSegs + n + lo, dSizes + lo, dStatus + lo, c->hpCompute);
-        c->hostPipe = false; c->dstMaxHint = 0; c->dstSlotsHint = 0;
+        ZdHints hint = zd_host_hint(&segs[n + lo].length, 2, nBlocks.data() + lo, cnt);      // (the frames' content sizes: the length of every destination segment)
+        if (!hint.size) hint.size = c->itemHint;
+        r = decompress_batch(c, hint, c->hSrc.p, dSegs + lo, cnt, c->hDst.p, dSegs + n + lo, dSizes + lo, dStatus + lo, c->hpCompute);
         if (r) return fail(r);
         if (hipEventRecord(evK, c->hpCompute) != hipSuccess || hipStreamWaitEvent(c->hpD2H, evK, 0) != hipSuccess) return fail(ZHIP_ERR_HIP);
         // the chunk's output goes straight into its (pinned) result payload
@@ -2298,6 +2239,12 @@ extern "C" int zhip_seekable_open_device(zhip_ctx* c, const void* d_stream, uint
     *out = h;
     return 0;
 }
+// what the readers tell the batch decode about their frames. Frames above one block: the several-block mode, for these launches only
+static ZdHints seekable_hints(const zhip_ctx* c, const zhip_seekable* h)
+{
+    ZdHints hint; hint.size = h->maxFrameContent > ZF_BLOCK_MAX ? (uint64_t)h->maxFrameContent : (uint64_t)c->itemHint;
+    return hint;
+}
 
 extern "C" int zhip_seekable_decompress_device(zhip_ctx* c, zhip_seekable* h, uint64_t offset, uint64_t length, void* d_dst, int32_t* d_status, void* streamv)
 {
@@ -2333,11 +2280,7 @@ extern "C" int zhip_seekable_decompress_device(zhip_ctx* c, zhip_seekable* h, ui
     HIP_TRY(hipMemsetAsync(a.worst, 0, 4, stream));
     hipLaunchKernelGGL(zhip_seekable_range_segs_kernel, dim3(zsk_lane_grid(c, (uint64_t)f1 - f0 + 1)), dim3(64), 0, stream, a);
     HIP_TRY(hipGetLastError());
-    // frames above one block: the several-block mode, for these launches only
-    const size_t hintWas = c->dstMaxHint;
-    if (h->maxFrameContent > ZF_BLOCK_MAX) c->dstMaxHint = h->maxFrameContent;
-    const int rc = zhip_decompress_batch_device(c, h->stream, (const zhip_segment*)a.srcSegs, count, a.dstBase, (const zhip_segment*)a.dstSegs, (uint64_t*)(m + oSizes), a.status, stream);
-    c->dstMaxHint = hintWas;
+    const int rc = decompress_batch(c, seekable_hints(c, h), h->stream, (const zhip_segment*)a.srcSegs, count, a.dstBase, (const zhip_segment*)a.dstSegs, (uint64_t*)(m + oSizes), a.status, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(zhip_seekable_range_verify_kernel, dim3(zsk_lane_grid(c, count)), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(zhip_seekable_range_finish_kernel, dim3(zsk_lane_grid(c, (uint64_t)edgeBytes / 16 + 1)), dim3(64), 0, stream, a);
@@ -2427,9 +2370,7 @@ extern "C" int zhip_seekable_decompress_ranges_device(zhip_ctx* c, zhip_seekable
     a.dst = (uint8_t*)d_dst; a.scratch = plan.scratchMax ? (uint8_t*)h->gScratch.p : a.dst; a.dstBase = a.scratch < a.dst ? a.scratch : a.dst;
     a.srcSegs = (uint64_t*)(m + oSrcSegs); a.dstSegs = (uint64_t*)(m + oDstSegs); a.frameOf = (uint32_t*)(m + oFrameOf);
     a.outSizes = (const uint64_t*)(m + oSizes); a.status = (int32_t*)(m + oStatus); a.worst = (uint32_t*)(m + oWorst); a.outStatus = d_status;
-    // frames above one block: the several-block mode, for these launches only
-    const size_t hintWas = c->dstMaxHint;
-    if (h->maxFrameContent > ZF_BLOCK_MAX) c->dstMaxHint = h->maxFrameContent;
+    const ZdHints hints = seekable_hints(c, h);
     int rc = 0;
     for (size_t p = 0; p < plan.passes.size() && !rc; p++) {
         const ZskGatherPass& ps = plan.passes[p];
@@ -2438,7 +2379,7 @@ extern "C" int zhip_seekable_decompress_ranges_device(zhip_ctx* c, zhip_seekable
         a.item0 = ps.item0; a.count = ps.item1 - ps.item0; a.last = p + 1 == plan.passes.size() ? 1u : 0u;
         hipLaunchKernelGGL(zhip_seekable_gather_segs_kernel, dim3(zsk_lane_grid(c, ps.frames)), dim3(64), 0, stream, a);
         if (a.count) {
-            rc = zhip_decompress_batch_device(c, h->stream, (const zhip_segment*)a.srcSegs + a.item0, a.count, a.dstBase, (const zhip_segment*)a.dstSegs + a.item0,
+            rc = decompress_batch(c, hints, h->stream, (const zhip_segment*)a.srcSegs + a.item0, a.count, a.dstBase, (const zhip_segment*)a.dstSegs + a.item0,
                                               (uint64_t*)(m + oSizes) + a.item0, a.status + a.item0, stream);
             if (rc) break;
             hipLaunchKernelGGL(zhip_seekable_gather_verify_kernel, dim3(zsk_lane_grid(c, a.count)), dim3(64), 0, stream, a);
@@ -2449,7 +2390,6 @@ extern "C" int zhip_seekable_decompress_ranges_device(zhip_ctx* c, zhip_seekable
         }
         if (hipGetLastError() != hipSuccess) { g_lastError = "seekable ranges: a launch failed"; rc = ZHIP_ERR_HIP; }
     }
-    c->dstMaxHint = hintWas;
     return rc;
 }
 

@@ -7,6 +7,7 @@ extern "C" { long zd_trace_pos = -1; long zd_cur_frame = -1; long zd_stat[16]; }
 #include "../../python-zstandard_amd/csrc/zhip_encode_kernel.hpp"
 #include "../../python-zstandard_amd/csrc/zhip_cparams.hpp"
 #include "../../python-zstandard_amd/csrc/zhip_encode_plan.hpp"
+#include "../../python-zstandard_amd/csrc/zhip_decode_plan.hpp"
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
@@ -122,20 +123,25 @@ static void kb_lane(void* p) { zp_bin_body(*(const ZhipPipeArgs*)p, g_binlds); }
 static ZpHufKernelLDS g_huflds;
 static void kh_lane(void* p) { zp_huf_body(*(const ZhipPipeArgs*)p, g_huflds); }
 static ZpSeqQLDS g_seqqlds;
-static void k2_lane(void* p) { const ZhipPipeArgs& a = *(const ZhipPipeArgs*)p; if (a.itemCap) zp_seqq_body<true>(a, g_seqqlds); else zp_seqq_body<false>(a, g_seqqlds); }
+static ZdChunkPlan g_dk;                         // the chunk's plan (zd_decode_chunk_plan): which form of K2 and K3 the lanes below run
+static void k2_lane(void* p) { const ZhipPipeArgs& a = *(const ZhipPipeArgs*)p; if (g_dk.k2 == ZD_K2_MB) zp_seqq_body<true>(a, g_seqqlds); else zp_seqq_body<false>(a, g_seqqlds); }
 static void k3_lane(void* p)
 {
     const ZhipPipeArgs& a = *(const ZhipPipeArgs*)p;
-    if (a.itemCap) { if (a.dictContent) zp_exec_body<true, false, true>(a, g_xlds); else zp_exec_body<false, false, true>(a, g_xlds); }
-    else if (a.dictContent) zp_exec_body<true, false>(a, g_xlds); else zp_exec_body<false, false>(a, g_xlds);
+    if (g_dk.k3 == ZD_K3_MB_DICT) zp_exec_body<true, false, true>(a, g_xlds);
+    else if (g_dk.k3 == ZD_K3_MB) zp_exec_body<false, false, true>(a, g_xlds);
+    else if (g_dk.k3 == ZD_K3_DICT) zp_exec_body<true, false>(a, g_xlds);
+    else zp_exec_body<false, false>(a, g_xlds);          // (ZD_K3_PROF never: the harness does not ask for the phase timers)
 }
+// the LDS facts of the launch plan's device inputs (emu_decode_plan.cpp): bytes of K2's and K1b's workgroups, frames per wave of K2
+extern "C" void emu_decode_lds_facts(uint64_t* out) { out[0] = sizeof(ZpSeqQLDS); out[1] = sizeof(ZpHufKernelLDS); out[2] = ZQ_FRAMES; }
 static void kx_lane(void* p) { zp_check_body(*(const ZhipPipeArgs*)p); }
 static uint32_t g_ckLater = 1;                  // content checksums verified by KX after K3 (a lane per frame), as the product does; 0: by K1 / K3 on one lane (rounds 1-5)
 extern "C" void emu_set_check_later(uint32_t v) { g_ckLater = v; }
 static void k1mb_lane(void* p) { zp_lit_mb_body(*(const ZhipPipeArgs*)p, g_lds); }
 static uint64_t g_arenaBudget16 = 0;                    // compact decode arena: != 0 overrides the harness' worst-case budget, in 16-byte units (what runs out is the generic kernel's)
 extern "C" void emu_set_arena_budget(uint64_t units16) { g_arenaBudget16 = units16; }
-static uint32_t g_mbPerFrame = 0;              // several-block mode of the pipeline harness: item slots per frame (0 = off), mirrors zhip_decompress_batch_device
+static uint32_t g_mbPerFrame = 0;              // several-block mode of the pipeline harness: item slots per frame (0 = off)
 extern "C" void emu_set_blocks(uint32_t perFrame) { g_mbPerFrame = perFrame; }
 // decompression dictionary for the pipeline harness (mirrors zhip_ctx_set_ddict): blob, parsed entropy section, ready-made tables
 static std::vector<uint8_t> g_ddBlob; static ZhipDictEntropy g_ddEntropy; static ZhipDictTables g_ddTables; static bool g_ddHas = false, g_ddEnt = false;
@@ -169,11 +175,21 @@ extern "C" int emu_decompress_pipeline(const uint8_t* src, const uint64_t* srcSe
     ZhipPipeArgs a; memset(&a, 0, sizeof(a));
     static uint32_t counters[ZP_CNT_WORDS + 1]; memset(counters, 0, sizeof counters);      // the slot's words (incl. the work orders' bin counters), then the fallback length
     if (chunk == 0 || chunk > n) chunk = n ? n : 1;
-    const bool mb = g_mbPerFrame != 0;
+    // the product's launch plan (zhip_decode_plan.hpp) under the harness's hooks: emu_set_blocks turns the several-block mode on (a size hint just above a block stands for it),
+    // emu_set_k0 is the build's K0 switch, the chunk is the caller's; the dictionary is emu_set_ddict's. Read from it: the mode, K0, the lane pass, and per chunk the forms of K1, K2 and K3
+    ZdPlanIn in;
+    in.n = n ? n : 1; in.hint.size = g_mbPerFrame ? (uint64_t)ZF_BLOCK_MAX + 1 : 0; in.knob.dchunk = chunk; in.k0Build = g_k0 != 0;
+    in.dict.present = g_ddHas; in.dict.hasEntropy = g_ddHas && g_ddEnt;
+    in.knob.k0Min = 0;          // (on purpose not the product's: K0 on small batches too -- the product starts it at 6 144 frames a chunk, more than a test here decodes)
+    in.dev.numCU = in.dev.decBlocksPerCU = in.dev.k1PerCU = in.dev.k3PerCU = 1; in.dev.k2LdsPerCU = in.dev.k1bLdsPerCU = 1; in.dev.k2Frames = ZQ_FRAMES;      // (on purpose: grids are the caller's nBlocks here)
+    const ZdPlan p = zd_decode_plan(in);
+    const bool mb = p.mb;
+    // (on purpose not the product's: the slots per frame are emu_set_blocks' number, not the plan's estimate from a size hint)
     const size_t slots = (size_t)chunk * (mb ? g_mbPerFrame : 1u);
     a.src = src; a.srcSegs = srcSegs; a.dst = dst; a.dstSegs = dstSegs; a.outSizes = outSizes; a.status = status;
     a.meta = (ZdMeta*)calloc(slots, sizeof(ZdMeta));
-    // (ONE compact arena for literals and sequences with a budget -- worst case by default: every frame a full literal slot and its K2 group's longest possible room)
+    // (ONE compact arena for literals and sequences with a budget -- on purpose not the plan's 160 KiB a frame but the worst case, every frame a full literal slot and its K2 group's
+    // longest possible room, unless emu_set_arena_budget overrides it)
     const size_t arenaBudget16 = g_arenaBudget16 ? (size_t)g_arenaBudget16 : slots * ((ZP_SEQ_STRIDE * 2 + ZP_LIT_STRIDE) / 16 + 1);
     uint8_t* const litAlloc = (uint8_t*)malloc(arenaBudget16 * 16 + 512 + ZP_LIT_FRONT); a.litArena = litAlloc + ZP_LIT_FRONT; a.seqArena = (uint64_t*)a.litArena;
     a.bases = (uint32_t*)malloc(slots * 8); memset(a.bases, 0xA5, slots * 8); a.arenaBudget16 = (uint32_t)arenaBudget16;
@@ -190,24 +206,24 @@ extern "C" int emu_decompress_pipeline(const uint8_t* src, const uint64_t* srcSe
         a.dictID = g_ddEnt ? g_ddEntropy.dictID : 0u; a.dictContent = g_ddBlob.data() + co; a.dictContentSize = (uint32_t)(g_ddBlob.size() - 64) - co;
         a.dictEntropy = g_ddEnt ? &g_ddEntropy : nullptr; a.dictTables = g_ddEnt ? &g_ddTables : nullptr;
     }
-    a.k1Lanes = g_k1Lanes && a.dictEntropy ? 1u : 0u;       // (mirrors zhip_decompress_batch_device; cleared below in the several-block mode)
     ZpPre* pre = nullptr;
     a.ckLater = g_ckLater;
     for (uint32_t first = 0; first < n; first += chunk) {
         a.first = first; a.count = n - first < chunk ? n - first : chunk;
         for (uint32_t q = 0; q < ZP_CNT_WORDS; q++) counters[q] = 0;
         memset(&g_lds, 0xA5, sizeof g_lds); memset(&g_xlds, 0xA5, sizeof g_xlds); memset(&g_binlds, 0xA5, sizeof g_binlds);   // LDS is not zeroed on hardware
-        a.itemCap = mb ? a.count * g_mbPerFrame : 0u;
-        if (mb) a.k1Lanes = 0;
+        g_dk = zd_decode_chunk_plan(in, p, a.count);
+        a.itemCap = g_dk.itemCap ? a.count * g_mbPerFrame : 0u;          // (emu_set_blocks' slots per frame, as above)
+        a.k1Lanes = g_dk.k1 == ZD_K1_LANES && g_k1Lanes ? 1u : 0u;      // (emu_set_k1_lanes(0): a wave per frame where the plan says the lane pass)
         if (a.k1Lanes) zhemu::run_grid(nBlocks, k1lanes_lane, &a);
         a.pre = nullptr;
-        if (g_k0 && !mb && !a.dictEntropy) {          // (mirrors zhip_decompress_batch_device)
+        if (p.pre) {
             if (!pre) pre = (ZpPre*)malloc(slots * sizeof(ZpPre));
             memset(pre, 0xA5, slots * sizeof(ZpPre)); memset(&g_prelds, 0xA5, sizeof g_prelds);
             a.pre = pre;
             zhemu::run_grid(nBlocks, k0_lane, &a);
         }
-        zhemu::run_grid(nBlocks, mb ? k1mb_lane : k1_lane, &a);
+        zhemu::run_grid(nBlocks, g_dk.k1 == ZD_K1_MB ? k1mb_lane : k1_lane, &a);
         zhemu::run_grid(2 * (a.count < 8 ? 1u : 3u), kb_lane, &a);
         memset(&g_huflds, 0xA5, sizeof g_huflds);
         zhemu::run_grid(nBlocks, kh_lane, &a);
