@@ -9,13 +9,17 @@
 #   k3d{2,3}    -DZP_K3D_MINWAVES=n  K3's dictionary instantiation (default 4)
 #   asm2k       -DZP_ASM_BYTES=2048  K3: 2 KiB batch assembly buffer
 #   lit{1,2}    -DZP_K3_LITCOPIES=n  K3: one copy of the block code with the literal mode a run-time value (rounds 1-7) / two (decoded literals + the rest) instead of three
+#   nosbase     -DZP_K3_SBASE=0      K3: the batch loop's global addresses as 64-bit lane values instead of scalar base + 32-bit lane offset (rounds 1-8)
+#   nounitrec   -DZP_K3_UNITREC=0    K3: the long items handed to their 16-byte units through seven narrow LDS arrays instead of one 16-byte record per lane (rounds 2-8)
+#   nounitown   -DZP_K3_UNITOWN=0    K3: the first 64 units of a batch find their item by the binary search over the unit prefix sums too, like those from 64 on
+#   k3r8        all three of the above: round 8's batch loop;  unitreconly  the records without the other two
 #   k3cu24      -DZHIP_K3_PER_CU=24  K3's grid fixed at 24 waves per CU instead of the occupancy query's value
 #   own32       -DZP_LIT_SHORT=32 -DZP_FAR_SHORT=32   K3: own-lane items up to 32 bytes (round 2's shape)
 #   nohist      -DZP_HIST_KEEP=0u -DZP_HIST_SLIDE=0u  K3 without the LDS history in front of the batch (round 6 A/B)
 #   nok0        -DZHIP_K0=0          decode pipeline without K0 (the lane-per-frame parser pass in front of K1)
 #   dchunk32k   -DZHIP_DCHUNK=32768  decode pipeline in chunks of 32 768 frames (two slot streams) instead of one of 65 536
 #   e1l{16,32,64} -DZE_E1_LANES=n    lane-serial match kernel (fast-strategy batches): n frames per wave instead of 8
-# Emulator-verified shapes: tests/test_emu_kernels.py::test_decode_shape_variants_stay_correct.
+# Emulator-verified shapes: tests/test_emu_kernels.py::test_decode_shape_variants_stay_correct, tests/test_emu_k3_units.py::test_the_a_b_builds_stay_correct.
 # usage: build_variants.sh name [name ...]
 set -e
 cd "$(dirname "$0")"
@@ -39,6 +43,11 @@ for v in "$@"; do
     asm2k) build asm2k -DZP_ASM_BYTES=2048 & ;;
     lit1) build lit1 -DZP_K3_LITCOPIES=1 & ;;              # K3's block code as rounds 1-7 had it: one copy, the literal mode tested in every batch (A/B of round 8: profiles/r14_*)
     lit2) build lit2 -DZP_K3_LITCOPIES=2 & ;;              # two copies (80 VGPRs + 16 bytes of scratch in the dictionary-less kernel)
+    nosbase) build nosbase -DZP_K3_SBASE=0 & ;;           # K3's batch loop with 64-bit lane addresses for its gathers (rounds 1-8), the unit records kept (A/B of round 9: profiles/r16_*)
+    nounitrec) build nounitrec -DZP_K3_UNITREC=0 & ;;      # the long-item hand-off through seven narrow LDS arrays (rounds 2-8), the scalar bases kept
+    nounitown) build nounitown -DZP_K3_UNITOWN=0 & ;;     # every unit finds its item by the binary search (the records and the scalar bases kept)
+    k3r8) build k3r8 -DZP_K3_SBASE=0 -DZP_K3_UNITREC=0 & ;;   # all three: round 8's batch loop from this source (without the records there is no start mask)
+    unitreconly) build unitreconly -DZP_K3_SBASE=0 -DZP_K3_UNITOWN=0 & ;;   # the records alone
     k3cu24) build k3cu24 -DZHIP_K3_PER_CU=24 & ;;
     nt1) build nt1 -DZP_K3_NT=1 & ;;                      # K3: sequences and decoded literals read with streaming (nt) loads
     zqnost) build zqnost -DZQ_DIAG_NOSTORE & ;;             # DIAGNOSTIC: K2 without its sequence stores

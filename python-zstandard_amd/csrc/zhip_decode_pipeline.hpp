@@ -1300,14 +1300,52 @@ ZH_DEVFN void zp_seqq_body(const ZhipPipeArgs& a, ZpSeqQLDS& L)
 #ifndef ZP_ASM_BYTES
 #define ZP_ASM_BYTES ZD_ASM_BYTES       // K3's batch assembly buffer (LDS per wave = this + 1.6 KiB): smaller buffers leave room for a K2 wave beside sixteen K3 waves
 #endif
+// Round 9. ZP_K3_UNITREC: what a lane hands to the 16-byte units of its long items, as ONE 16-byte record (1, the product) or as the seven narrow arrays of rounds 2-8
+// (0, the A/B build). A unit lane read five or six of those cells back, one ds_read_u16 / ds_read_b32 each, behind the six dependent reads of its search.
+//   w[0]  srcM   the match item's source, frame-relative, signed (negative: inside the dictionary)
+//   w[1]  srcL   bits 0-16: where the literal run starts in the block's literals (a long run has 17 bytes at least and a block at most ZF_BLOCK_MAX = 2^17 literals)
+//         dstL   bits 17-29: where the run goes in the batch (below ZP_ASM_BYTES)
+//   w[2]  lenL   bits 0-12, lenM bits 13-25 (a batch's item is at most ZP_ASM_BYTES long)
+//   w[3]  dstM   bits 0-12; bits 13-22: the item's first unit (the exclusive prefix sum -- uEnd[j - 1] is not read again); bits 23-31: its literal units
+// A field is exact wherever a unit reads it: a lane with units is active, in a batch that fits the buffer, and its literal fields are read only if its run is a
+// long one. Other lanes write what their registers hold (an idle lane's prefix sums are not cut back), each into its own record, which no unit finds: the unit
+// prefix sums do not move over a lane without units.
+#ifndef ZP_K3_UNITREC
+#define ZP_K3_UNITREC 1
+#endif
+// ZP_K3_UNITOWN: the first 64 units of a batch find their item through a start mask and one LDS read (1, the product) or by the six dependent reads of the binary
+// search over the unit prefix sums, like the units from 64 on (0, the A/B build)
+#ifndef ZP_K3_UNITOWN
+#define ZP_K3_UNITOWN 1
+#endif
+#if !ZP_K3_UNITREC
+#undef ZP_K3_UNITOWN
+#define ZP_K3_UNITOWN 0
+#endif
+struct alignas(16) ZpUnitRec { uint32_t w[4]; };
+static_assert(ZP_ASM_BYTES < (1u << 13), "ZpUnitRec: lengths up to and positions below ZP_ASM_BYTES in 13 bits");
+static_assert(ZF_BLOCK_MAX <= (1u << 17), "ZpUnitRec: a long literal run starts below 2^17");
+// units of a batch: an item of n > 16 bytes has (n + 15) / 16, a batch has at most 128 long items (two per lane) and ZP_ASM_BYTES bytes
+static_assert((ZP_ASM_BYTES + 15u * 128u) / 16u < (1u << 10), "ZpUnitRec: an item's first unit in 10 bits");
+static_assert((ZP_ASM_BYTES + 15u) / 16u < (1u << 9), "ZpUnitRec: an item's literal units in 9 bits");
 struct ZpExecLDS {
     uint8_t asmb[ZP_ASM_BYTES + 64]; uint16_t mBeg[64]; uint16_t mEnd[64]; uint32_t misc[8];
 #if defined(ZP_K3_DIAG_FLOOR) && defined(ZP_FLOOR_LDSPAD)
     uint8_t floorPad[ZP_FLOOR_LDSPAD];               // (diagnostic builds: the LDS a window over the recent output would take, i.e. its occupancy)
 #endif
     // the batch's long items (literal runs / far matches above ZD_COOP_LEN bytes), staged together in 16-byte units
+#if ZP_K3_UNITREC
+    ZpUnitRec rec[64]; uint16_t uEnd[64];            // one record per item lane (a 16-byte store, a 16-byte load per unit); the unit prefix sums stay dense for the search
+#if ZP_K3_UNITOWN
+    uint8_t own[64];                                 // own[u]: the lane of the item whose first unit is u, 0xFF where no item starts (the first 64 units)
+#endif
+#else
     uint16_t uEnd[64], uLit[64], dstL[64], dstM[64], lenL[64], lenM[64]; uint32_t srcL[64], srcM[64];
+#endif
 };
+#if ZP_K3_UNITREC
+static_assert(sizeof(ZpExecLDS) <= ZP_ASM_BYTES + 1632, "K3's waves per CU rest on this size (5 728 bytes at ZP_ASM_BYTES = 4 096)");
+#endif
 
 // K3's time is its instruction count (r02 SQ counters: issue-bound, 37 % scalar -- mostly exec-mask bookkeeping of predicated piece loads
 // and stores). A piece that is READ from LDS needs none of it: reading past an item is harmless there (the buffer has 64 bytes of slack),
@@ -1387,17 +1425,46 @@ static_assert((ZP_HIST_SLIDE >= 2 * ZP_HIST_KEEP + 16 || ZP_HIST_KEEP == 0) && Z
 #ifndef ZP_K3_LITCOPIES
 #define ZP_K3_LITCOPIES 3
 #endif
+#ifndef ZP_K3_SBASE
+#define ZP_K3_SBASE 1            // the dictionary-less batch loop addresses global memory as scalar base + unsigned 32-bit lane offset (round 9; 0 = rounds 1-8's 64-bit lane addresses, the A/B build)
+#endif
 enum { ZP_LM_ANY = 0, ZP_LM_ARENA = 1, ZP_LM_RAW = 2, ZP_LM_RLE = 3 };
+// zd_ld32's exact form (no byte read outside [off, off + len)) over a base and an unsigned lane offset
+ZH_DEV void zp_ld32_at(const uint8_t* base, uint32_t off, uint32_t len, uint64_t r[4])
+{
+    const bool ge8 = len >= 8;
+    const uint32_t o2 = len & 4, o1 = o2 + (len & 2);
+    uint64_t a0 = 0, a1 = 0, a2 = 0, a3 = 0; uint32_t b4 = 0, b2 = 0, b1 = 0;
+    if (ge8) a0 = zh_ld64(base + off);
+    if (len > 16) a1 = zh_ld64(base + (off + 8));
+    if (len > 24) a2 = zh_ld64(base + (off + 16));
+    if (ge8) a3 = zh_ld64(base + (off + len - 8));
+    if (!ge8 && (len & 4)) b4 = zh_ld32(base + off);
+    if (!ge8 && (len & 2)) b2 = zh_ld16(base + (off + o2));
+    if (!ge8 && (len & 1)) b1 = base[off + o1];
+    r[0] = a0; r[1] = a1; r[2] = a2;
+    r[3] = ge8 ? a3 : (uint64_t)b4 | ((uint64_t)b2 << (8 * o2)) | ((uint64_t)b1 << (8 * o1));
+}
 template <bool DICT, bool PROF, bool MB, int LM>
 ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m, uint32_t t, const uint8_t* src, uint8_t* dst, uint32_t cap, uint64_t cap64,
                            uint32_t blockMax, uint32_t& opRef, uint32_t R0, uint32_t R1, uint32_t R2, ZdProf& P)
 {
     const uint32_t lane = zh_lane();
+    // Round 9 (ZP_K3_SBASE): without a dictionary every global address of the batch loop is one of three wave-uniform bases -- the frame's slot, the block's
+    // literals, the block's sequences -- plus a lane offset that fits 32 unsigned bits. The bases are made scalar once per block and every address is written
+    // `base + (uint32_t)offset`, the form for which the compiler has the scalar-base global instructions; as `v[lo:hi], off` each address was a 64-bit vector
+    // add with a sign extension in front of it. t, src and dst derive from the frame index, which zp_exec_body reads with zh_first: the same in every lane.
+    // The dictionary instantiations choose a base per lane (the slot or the dictionary) and keep their addressing, and so do the units' loads, which choose
+    // between the literals and the slot (ZP_UNIT_GLOBAL). An offset must be computed INSIDE the loop to be seen as 32 bits: instruction selection works block by
+    // block, and a zero extension the compiler has hoisted out of the loop (of lane * 16, say) leaves a 64-bit vector add behind.
+    constexpr bool SB = ZP_K3_SBASE && !DICT;
+    if (SB) dst = zh_uniform_ptr(dst);
     const uint64_t* seqs = a.seqArena + a.bases[2 * (size_t)t];
     const bool litRLE = LM == ZP_LM_ANY ? m.litMode == 2 : LM == ZP_LM_RLE;
     const bool litRaw = LM == ZP_LM_ANY ? m.litMode == 0 : LM == ZP_LM_RAW;
     const uint32_t rleByte = m.litOff;
     const uint8_t* litPtr = litRaw ? src + m.litOff : a.litArena + (size_t)a.bases[2 * (size_t)t + 1] * 16;
+    if (SB) { seqs = zh_uniform_ptr(seqs); litPtr = zh_uniform_ptr(litPtr); }
     const uint8_t* const dictEnd = DICT ? a.dictContent + a.dictContentSize : dst;       // position -k of the frame = dictEnd[-k]
     const uint32_t dictSize = DICT ? a.dictContentSize : 0u;
     // Round 6: the assembly buffer keeps what it flushed. A batch is ~0.9 KiB of the buffer's 4: instead of starting every batch at its front, batches are
@@ -1417,7 +1484,10 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
     // below ob are in global memory, bytes from ob on only in LDS: "far" = the whole source lies below ob.
     uint32_t carry = 0;
     const uint32_t nbSeq = m.nbSeq;
-    uint64_t qNext = lane < nbSeq ? ZP_SEQ_LD(seqs + lane) : 0;      // the next batch's sequences are requested a batch ahead
+    // (SB: the byte offset as ONE 32-bit value computed in the loop -- a block has fewer than 2^18 sequences, eight bytes each. Split into a uniform part and
+    // the lane's, the compiler hoists the lane's 64-bit half out of the loop, and what instruction selection then sees in the loop is a 64-bit vector add again)
+#define ZP_SEQ_AT(first) (SB ? ZP_SEQ_LD((const uint64_t*)((const uint8_t*)seqs + ((first) + lane) * 8u)) : ZP_SEQ_LD(seqs + (first) + lane))
+    uint64_t qNext = lane < nbSeq ? ZP_SEQ_AT(0u) : 0;               // the next batch's sequences are requested a batch ahead
     const uint32_t lane0 = lane;
     while (done < nbSeq) {
         const uint32_t avail = nbSeq - done < 64 ? nbSeq - done : 64;
@@ -1430,7 +1500,7 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
         uint32_t cnt = (uint32_t)zh_popc64(fits);          // fits is a prefix mask (incT is monotone)
         const bool big = cnt == 0;
         if (big) cnt = 1;
-        qNext = done + cnt + lane < nbSeq ? ZP_SEQ_LD(seqs + done + cnt + lane) : 0;
+        qNext = done + cnt + lane < nbSeq ? ZP_SEQ_AT(done + cnt) : 0;
         const bool act = lane < cnt;
         if (!act) { myLL = 0; myML = 0; myOF = 1; }
         // (wave-uniform lane indices: v_readlane into SGPRs -- written as shuffles these totals, and op / lp / carry computed from them, lived in
@@ -1475,11 +1545,17 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
             // Lanes without an item read their frame's first bytes. Raw literals (read from the caller's source) keep the exact form.
             const bool arenaLit = !litRaw;                                          // (block-uniform; a constant in every copy but ZP_LM_ANY, like litRLE)
             if (arenaLit && !litRLE) {
+                if (SB) {           // litStart + myLL <= m.litSize <= ZF_BLOCK_MAX for an active lane (checked above): the sums are small unsigned numbers
+                    const uint32_t q = shortL ? litStart : 0u;
+                    rl[0] = ZP_LIT_LD64(litPtr + q); rl[3] = ZP_LIT_LD64(litPtr + (q + (shortL && myLL >= 8 ? myLL - 8 : 0u)));
+                    if (ZP_LIT_SHORT > 16) { rl[1] = ZP_LIT_LD64(litPtr + (q + 8)); rl[2] = ZP_LIT_LD64(litPtr + (q + 16)); } else { rl[1] = 0; rl[2] = 0; }
+                } else {
                 const uint8_t* q = litPtr + (shortL ? litStart : 0u);
                 rl[0] = ZP_LIT_LD64(q); rl[3] = ZP_LIT_LD64(q + (shortL && myLL >= 8 ? myLL - 8 : 0u));
                 if (ZP_LIT_SHORT > 16) { rl[1] = ZP_LIT_LD64(q + 8); rl[2] = ZP_LIT_LD64(q + 16); } else { rl[1] = 0; rl[2] = 0; }
+                }
             } else
-            if (shortL && !litRLE) zd_ld32(litPtr + litStart, myLL, rl);
+            if (shortL && !litRLE) { if (SB) zp_ld32_at(litPtr, litStart, myLL, rl); else zd_ld32(litPtr + litStart, myLL, rl); }
             // a near match whose source starts before the batch: that part is global memory too and is fetched here like a far
             // match (byte by byte in the dependency rounds it was a memory round trip per byte). A lane has one or the other, so
             // both go through ONE pair of piece loads / stores (r02l: K3's time is its instruction count, a pair is ~85 of ~770 per batch)
@@ -1493,19 +1569,67 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
             const uint8_t* const mSrc = !DICT || sAbs >= 0 ? dst + sAbs : dictEnd + sAbs;
             const bool shortM = (farM || pre) && lenMi <= ZP_FAR_SHORT && !strad;
             const bool inH = (farM || pre) && sAbs >= (int32_t)(ob - hOff);          // the source starts inside the history: staged from LDS (sAbs >= 0 then)
-            if (!zh_ballot(shortM && !inH && sAbs >= 0 && (uint64_t)sAbs + 32 > cap64) && cap64 >= 32) {     // (the dictionary's buffer has its own slack)
+            // Without a dictionary a source that is dereferenced is a position of the frame: the offset check above refused every myOF > ob + mRel, so sAbs >= 0 for
+            // every lane with a match, and (uint32_t)sAbs is that position. A far or pre-batch source lies below ob, so sAbs < ob <= cap <= 0x7FFFFFFF and
+            // sAbs + 32 does not wrap in 32 bits. `cap` is the slot's size clamped to 0x7FFFFFFF: where the slot is smaller the two tests are the same test; where it is
+            // larger the clamped one can only say "too close to the end" for a source that is not (above 0x7FFFFFFF - 32), and that sends the batch through the exact
+            // loads, which are right for every slot. It never takes the slack form where the 64-bit test refused it.
+            const bool slack = SB ? !zh_ballot(shortM && !inH && (uint32_t)sAbs + 32 > cap) && cap >= 32
+                                  : !zh_ballot(shortM && !inH && sAbs >= 0 && (uint64_t)sAbs + 32 > cap64) && cap64 >= 32;     // (the dictionary's buffer has its own slack)
+            if (slack && SB) {
+                const uint32_t q = shortM && !inH ? (uint32_t)sAbs : 0u;           // (lanes without such an item read their frame's first bytes)
+                rm[0] = ZP_FAR_LD64(dst + q); rm[3] = ZP_FAR_LD64(dst + (q + (shortM && lenMi >= 8 ? lenMi - 8 : 0u)));
+                if (ZP_FAR_SHORT > 16) { rm[1] = ZP_FAR_LD64(dst + (q + 8)); rm[2] = ZP_FAR_LD64(dst + (q + 16)); } else { rm[1] = 0; rm[2] = 0; }
+            } else
+            if (slack) {
                 const uint8_t* q = shortM && !inH ? mSrc : dst;
                 rm[0] = ZP_FAR_LD64(q); rm[3] = ZP_FAR_LD64(q + (shortM && lenMi >= 8 ? lenMi - 8 : 0u));
                 if (ZP_FAR_SHORT > 16) { rm[1] = ZP_FAR_LD64(q + 8); rm[2] = ZP_FAR_LD64(q + 16); } else { rm[1] = 0; rm[2] = 0; }
             } else
-            if (shortM && !inH) zd_ld32(mSrc, lenMi, rm);
+            if (shortM && !inH) { if (SB) zp_ld32_at(dst, (uint32_t)sAbs, lenMi, rm); else zd_ld32(mSrc, lenMi, rm); }
             if (shortM && inH) { const uint8_t* hq = asmb + (sAbs - (int32_t)ob); rm[0] = zh_ld64(hq); rm[1] = 0; rm[2] = 0; rm[3] = zh_ld64(hq + (lenMi >= 8 ? lenMi - 8 : 0u)); }
             const bool longL = act && myLL > ZP_LIT_SHORT && !litRLE, longM = (farM || pre) && !shortM && !strad;
             const uint32_t uL = longL ? (myLL + 15) >> 4 : 0u, uM = longM ? (lenMi + 15) >> 4 : 0u;
             const uint32_t ue = zh_scan_add(uL + uM);
             const uint32_t U = zh_bcast(ue, 63);
             zh_v16 uv; uv.lo = 0; uv.hi = 0; uint8_t* udp = asmb;
+            // a unit's 16 bytes from global memory: of a literal run at `lo_` in the block's literals, or of a match source at frame position sm_ + off_. ONE load from a
+            // base chosen per lane (a 64-bit select and a 64-bit add), with scalar bases too: as two loads under the lane's choice, each from its scalar base, the batch
+            // loop was 20 instructions shorter and K3 0.1 ms slower in every pair (round 9, profiles/r16_*)
+#define ZP_UNIT_GLOBAL(isL_, lo_, sm_, off_) uv = zh_ld128((isL_) ? litPtr + (lo_) : (!DICT || (sm_) >= 0 ? dst + (sm_) : dictEnd + (sm_)) + (off_))
             if (U) {
+#if ZP_K3_UNITREC
+                ZpUnitRec mine;
+                mine.w[0] = (uint32_t)sAbs; mine.w[1] = litStart | (oRel << 17); mine.w[2] = myLL | (lenMi << 13); mine.w[3] = mRel | ((ue - (uL + uM)) << 13) | (uL << 23);
+                L.rec[lane] = mine;
+#if ZP_K3_UNITOWN
+                // the first 64 units find their item without the search: an item lane whose first unit is below 64 leaves its number at own[that unit]; the
+                // ballot of "my slot is an item's first" is the wave's start mask, and unit u belongs to the item that starts at the highest set bit at or below u
+                L.own[lane] = 0xFF;
+                zh_wave_fence();                                                    // (the marks below land on slots other lanes have just cleared)
+                const uint32_t first = ue - (uL + uM);
+                if (uL + uM && first < 64) L.own[first] = (uint8_t)lane;
+                if (U > 64) L.uEnd[lane] = (uint16_t)ue;
+                ZP_BSYNC();
+                const uint64_t starts = zh_ballot(L.own[lane] != 0xFF);
+#define ZP_UNIT_J0(j_) j_ = L.own[63 - zh_clz64(starts & (~0ull >> (63 - lane)))]
+#else
+                L.uEnd[lane] = (uint16_t)ue;
+                ZP_BSYNC();
+#define ZP_UNIT_J0(j_) ZP_UNIT_J(lane, j_)
+#endif
+#define ZP_UNIT_J(u, j_) for (uint32_t stp_ = 32; stp_; stp_ >>= 1) if (L.uEnd[j_ + stp_ - 1] <= (u)) j_ += stp_
+#define ZP_UNIT0() do { uint32_t j_ = 0; ZP_UNIT_J0(j_); ZP_UNIT_DO(lane, j_); } while (0)
+#define ZP_UNIT(u) do { uint32_t j_ = 0; ZP_UNIT_J(u, j_); ZP_UNIT_DO(u, j_); } while (0)
+#define ZP_UNIT_DO(u, j_) do { \
+                    const ZpUnitRec r_ = L.rec[j_]; \
+                    uint32_t k_ = (u) - ((r_.w[3] >> 13) & 0x3FFu); const uint32_t nl_ = r_.w[3] >> 23; const bool isL_ = k_ < nl_; if (!isL_) k_ -= nl_; \
+                    const uint32_t len_ = (isL_ ? r_.w[2] : r_.w[2] >> 13) & 0x1FFFu; const uint32_t off_ = 16 * k_ + 16 <= len_ ? 16 * k_ : len_ - 16; \
+                    const int32_t sm_ = (int32_t)r_.w[0]; \
+                    if (!isL_ && sm_ >= (int32_t)(ob - hOff)) { const uint8_t* h_ = asmb + (sm_ - (int32_t)ob) + off_; uv.lo = zh_ld64(h_); uv.hi = zh_ld64(h_ + 8); } \
+                    else ZP_UNIT_GLOBAL(isL_, (r_.w[1] & 0x1FFFFu) + off_, sm_, off_); \
+                    udp = asmb + ((isL_ ? r_.w[1] >> 17 : r_.w[3]) & 0x1FFFu) + off_; } while (0)
+#else
                 L.uEnd[lane] = (uint16_t)ue; L.uLit[lane] = (uint16_t)uL;
                 L.srcL[lane] = litStart; L.dstL[lane] = (uint16_t)oRel; L.lenL[lane] = (uint16_t)myLL;
                 L.srcM[lane] = (uint32_t)sAbs; L.dstM[lane] = (uint16_t)mRel; L.lenM[lane] = (uint16_t)lenMi;
@@ -1515,9 +1639,11 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
                     const uint32_t len_ = isL_ ? L.lenL[j_] : L.lenM[j_]; const uint32_t off_ = 16 * k_ + 16 <= len_ ? 16 * k_ : len_ - 16; \
                     const int32_t sm_ = (int32_t)L.srcM[j_]; \
                     if (!isL_ && sm_ >= (int32_t)(ob - hOff)) { const uint8_t* h_ = asmb + (sm_ - (int32_t)ob) + off_; uv.lo = zh_ld64(h_); uv.hi = zh_ld64(h_ + 8); } \
-                    else uv = zh_ld128(isL_ ? litPtr + L.srcL[j_] + off_ : (!DICT || sm_ >= 0 ? dst + sm_ : dictEnd + sm_) + off_); \
+                    else ZP_UNIT_GLOBAL(isL_, L.srcL[j_] + off_, sm_, off_); \
                     udp = asmb + (isL_ ? L.dstL[j_] : L.dstM[j_]) + off_; } while (0)
-                if (lane < U) ZP_UNIT(lane);
+#define ZP_UNIT0() ZP_UNIT(lane)
+#endif
+                if (lane < U) ZP_UNIT0();
             }
             if (litRLE) { for (int k = 0; k < 4; k++) rl[k] = 0x0101010101010101ull * rleByte; }      // (frame-uniform)
             if (shortL) zd_st32(asmb + oRel, myLL, rl);
@@ -1532,6 +1658,11 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
                 if (lane < U) { zh_st64(udp, uv.lo); zh_st64(udp + 8, uv.hi); }
                 for (uint32_t u = lane + 64; u < U; u += 64) { ZP_UNIT(u); zh_st64(udp, uv.lo); zh_st64(udp + 8, uv.hi); }
 #undef ZP_UNIT
+#undef ZP_UNIT0
+#undef ZP_UNIT_J
+#undef ZP_UNIT_J0
+#undef ZP_UNIT_DO
+#undef ZP_UNIT_GLOBAL
             }
         }
         if (litRLE) {
@@ -1606,14 +1737,14 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
                     if (fof >= 64) {
                         for (uint32_t c = 0; c < fml; c += 64) {
                             const uint32_t j = c + lane;
-                            if (j < fml) { const int32_t sp = fs + (int32_t)j; asmb[Frel + j] = sp >= (int32_t)(ob - hOff) ? asmb[sp - (int32_t)ob] : (DICT ? (uint8_t)zd_hist_byte(dst, dictEnd, sp) : dst[sp]); }
+                            if (j < fml) { const int32_t sp = fs + (int32_t)j; asmb[Frel + j] = sp >= (int32_t)(ob - hOff) ? asmb[sp - (int32_t)ob] : (DICT ? (uint8_t)zd_hist_byte(dst, dictEnd, sp) : SB ? dst[(uint32_t)sp] : dst[sp]); }
                             if (fof < fml) ZP_BSYNC();
                         }
                     } else {
                         uint32_t idx = lane % fof; const uint32_t adv = 64 % fof;
                         for (uint32_t j = lane; j < fml; j += 64) {
                             const int32_t sp = fs + (int32_t)idx;
-                            asmb[Frel + j] = sp >= (int32_t)(ob - hOff) ? asmb[sp - (int32_t)ob] : (DICT ? (uint8_t)zd_hist_byte(dst, dictEnd, sp) : dst[sp]);
+                            asmb[Frel + j] = sp >= (int32_t)(ob - hOff) ? asmb[sp - (int32_t)ob] : (DICT ? (uint8_t)zd_hist_byte(dst, dictEnd, sp) : SB ? dst[(uint32_t)sp] : dst[sp]);
                             idx += adv; if (idx >= fof) idx -= fof;
                         }
                     }
@@ -1633,10 +1764,11 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
         {
             // (round 4: the first 1 KiB -- nearly always all of it -- as straight-line code, the loop only behind a uniform test. As one loop the
             // compiler unrolled it by two with eight 4-byte stores per trip and a remainder loop: 63 instructions of the batch's ~700)
-            uint8_t* out = dst + ob;
-            const uint32_t j0 = lane * 16;
-            if (j0 < whole) { const zh_v16 v = *(const zh_v16*)(asmb + j0); *(zh_v16*)(out + j0) = v; }
-            if (whole > 1024) for (uint32_t j = j0 + 1024; j < whole; j += 1024) { const zh_v16 v = *(const zh_v16*)(asmb + zh_opaque(j)); *(zh_v16*)(out + j) = v; }
+            // (SB: ob + j <= op + totT <= cap <= 0x7FFFFFFF -- the store's offset from the slot's base as one 32-bit sum made here, for the same reason as ZP_SEQ_AT's)
+            uint8_t* out = SB ? dst : dst + ob;
+            const uint32_t j0 = lane * 16, o0 = SB ? ob : 0u;
+            if (j0 < whole) { const zh_v16 v = *(const zh_v16*)(asmb + j0); *(zh_v16*)(out + (o0 + j0)) = v; }
+            if (whole > 1024) for (uint32_t j = j0 + 1024; j < whole; j += 1024) { const zh_v16 v = *(const zh_v16*)(asmb + zh_opaque(j)); *(zh_v16*)(out + (o0 + j)) = v; }
         }
         carry = totB - whole;
         hOff += whole;                                                     // what left stays as history; the tail is where the next batch starts: nothing moves
@@ -1660,6 +1792,7 @@ ZH_DEVFN int zp_exec_block(const ZhipPipeArgs& a, ZpExecLDS& L, const ZdMeta& m,
     op += rest;
     opRef = op;
     return 0;
+#undef ZP_SEQ_AT
 }
 
 // the block's copy by its literal mode (ZdMeta.litMode: 0 raw in the frame, 2 RLE; everything else sits decoded in the block's literal slot)

@@ -87,6 +87,21 @@ ZH_DEV uint32_t zh_pin(uint32_t v) { asm("" : "+v"(v)); return v; }
 #else
 ZH_DEV uint32_t zh_pin(uint32_t v) { return v; }
 #endif
+// a pointer every lane of the wave holds the same value of, said so that the compiler keeps it in a scalar register pair: an access `p + (uint32_t)lane_offset`
+// can then take the scalar-base form of the global instructions (the offset a single VGPR) instead of a 64-bit vector add per address. The caller guarantees
+// the uniformity, and that p points to global memory (never LDS); the emulator's lanes each have the value anyway.
+#ifndef ZHIP_EMU
+template <class T> ZH_DEV T* zh_uniform_ptr(T* p)
+{
+    // (the value comes back from its two halves as a pointer to GLOBAL memory: rebuilt from an integer as a plain pointer it is a generic one to the
+    // compiler, and every access through it a flat instruction, which waits on the LDS counter as well as on the memory counter)
+    const uint64_t v = (uint64_t)p;
+    const uint64_t u = (uint64_t)zh_first((uint32_t)v) | ((uint64_t)zh_first((uint32_t)(v >> 32)) << 32);
+    return (T*)(__attribute__((address_space(1))) T*)u;
+}
+#else
+template <class T> ZH_DEV T* zh_uniform_ptr(T* p) { return p; }
+#endif
 typedef uint64_t __attribute__((aligned(1))) zh_u64u;
 typedef uint32_t __attribute__((aligned(1))) zh_u32u;
 typedef uint16_t __attribute__((aligned(1))) zh_u16u;
