@@ -349,6 +349,39 @@ int  zhip_seekable_decompress_frames_device(zhip_ctx*, zhip_seekable*, const uin
                                             const uint64_t* dstOffsets /* host, may be NULL */, void* d_dst, uint64_t dstCapacity,
                                             int32_t* d_status /* [2 + 2 * nFrames] */, zhip_seekable_gather_stats* stats, void* stream);
 
+/* EDIT: a new stream out of frames of an opened one and of new records -- append, replace, drop, reorder, repeat -- without recompressing what is kept. The new
+ * stream holds nPicks frames in pick order and the table behind them. A ZHIP_PICK_FRAME pick is frame `index` of `old`: its bytes verbatim and its table entry
+ * as it is, checksum word included -- any writer's frame, empty, skippable, of several blocks, of another level or dictionary; nothing looks inside it. A
+ * ZHIP_PICK_RECORD pick is record `index` of d_records, compressed exactly as zhip_seekable_compress_records_device compresses it: the context's level,
+ * parameters, flags, dictionary and match finder, maxRecordBytes the size hint for this call only, the same pre-check (72). A frame or a record may be picked
+ * any number of times; a record nobody picks is compressed and dropped; zero picks give the 17-byte stream. With old == NULL and picks RECORD 0 .. n-1 the
+ * stream is the records call's byte for byte. picks is a HOST array, read before the call returns: it travels through pinned memory the handle owns (the
+ * context, without a handle). A device-resident pick list is not offered: the host must know the item counts without a wait.
+ * Checksums: with `old` the new table carries checksum words exactly when the old one does, and flags & ZHIP_SEEKABLE_CHECKSUM must say the same (else
+ * ZHIP_ERR_UNSUPPORTED); a new record's word is the XXH64 low word of its source bytes; with old == NULL the flag decides.
+ * Checked on the host before anything is queued, and nothing -- d_status included -- is written where a check fails: NULL arguments, nPicks > 2^27, a pick that
+ * is neither kind, a FRAME pick with old == NULL, the records call's bounds on nRecords and maxRecordBytes (ZHIP_ERR_UNSUPPORTED); a frame index >= nFrames or
+ * a record index >= nRecords (ZHIP_ERR_SIZE_MISMATCH, the position in zhip_last_error()); [d_dst, d_dst + dstCapacity) overlapping the old stream
+ * (ZHIP_ERR_UNSUPPORTED) -- but for the one form that is APPEND IN PLACE: d_dst is the old stream's base and the picks begin with FRAME 0 .. nFrames-1 in order.
+ * Then the kept frames are neither read nor written, the new frames start where the old table started (its entries are kept aside in context scratch first),
+ * and the buffer must have room for the bound. After a successful append in place the handle describes bytes that no longer exist: close it and open the
+ * stream again before any other call on it.
+ * Asynchronous and stream-ordered under the rules of the other seekable calls, no host wait except while scratch grows. d_status = {code, index}, and
+ * zhip_ctx_sync(ctx, stream, d_status, 1, &err) works on it: 72 from the records' pre-check with the RECORD index; else the lowest pick POSITION whose record the
+ * compressor refused keeps its code (40); else the capacity: 70 at the first pick whose frame ends beyond dstCapacity, the last pick where only the table does
+ * not fit. Every failure sets *d_streamSize = 0 and writes nothing into d_dst -- in place the old stream, table included, is intact and readable. Nothing at
+ * or beyond d_dst + dstCapacity is ever written.
+ * zhip_seekable_edit_bound: the kept picks' compressed sizes (from the handle's host copy of the table: no wait) + zhip_compress_bound(maxRecordBytes) per
+ * RECORD pick + the table; 0 for arguments the edit call would refuse on sight (record indices are not checked: the bound does not know nRecords). */
+enum { ZHIP_PICK_FRAME = 0, ZHIP_PICK_RECORD = 1 };
+typedef struct { uint32_t from, index; } zhip_seekable_pick;   /* frame `index` of the opened stream, kept as it is; or record `index` of d_records, compressed by this call */
+uint64_t zhip_seekable_edit_bound(const zhip_seekable* old, const zhip_seekable_pick* picks, size_t nPicks, uint64_t maxRecordBytes, int flags);
+int zhip_seekable_edit_device(zhip_ctx*, zhip_seekable* old /* may be NULL */,
+                              const zhip_seekable_pick* picks /* HOST, read before the call returns */, size_t nPicks,
+                              const void* d_src, uint64_t srcSize, const zhip_segment* d_records /* DEVICE */, size_t nRecords,
+                              uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
+                              void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status /* [2] */, void* stream);
+
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,
  * 4 K3, 5 / 6 the lane-serial match kernel (the greedy strategy's zhip_encode_match_greedy_kernel where that runs in its place) and the entropy kernel, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,

@@ -54,6 +54,10 @@ class SeekableGatherStats(C.Structure):
     _fields_ = [("items", C.c_uint64), ("inPlace", C.c_uint64), ("scratchBytes", C.c_uint64), ("copyJobs", C.c_uint64), ("passes", C.c_uint64)]
 
 
+class SeekablePick(C.Structure):
+    _fields_ = [("from_", C.c_uint32), ("index", C.c_uint32)]
+
+
 class DParams(C.Structure):
     _fields_ = [("dict", C.c_void_p), ("dictSize", C.c_size_t), ("maxWindowSize", C.c_uint64), ("dictType", C.c_int),
                 ("format", C.c_int)]
@@ -61,6 +65,7 @@ class DParams(C.Structure):
 
 DICT_AUTO, DICT_RAWCONTENT, DICT_FULLDICT = 0, 1, 2
 SEEKABLE_CHECKSUM = 1
+PICK_FRAME, PICK_RECORD = 0, 1
 FORMAT_ZSTD1, FORMAT_ZSTD1_MAGICLESS = 0, 1
 
 
@@ -133,6 +138,8 @@ def lib():
         "zhip_seekable_compress_records_device": (C.c_int, [vp, vp, u64, vp, sz, u64, u64, C.c_int, vp, u64, vp, vp, vp]),
         "zhip_seekable_frame_offsets": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp]),
         "zhip_seekable_decompress_frames_device": (C.c_int, [vp, vp, vp, sz, vp, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
+        "zhip_seekable_edit_bound": (u64, [vp, vp, sz, u64, C.c_int]),
+        "zhip_seekable_edit_device": (C.c_int, [vp, vp, vp, sz, vp, u64, vp, sz, u64, u64, C.c_int, vp, u64, vp, vp, vp]),
     }
     for name, (res, args) in protos.items():
         f = getattr(L, name)
@@ -155,6 +162,7 @@ EXPORTED_SYMBOLS = [
     "zhip_seekable_decompress_device", "zhip_seekable_decompress_ranges_device", "zhip_seekable_set_scratch_limit",
     "zhip_seekable_records_bound", "zhip_seekable_compress_records_device", "zhip_seekable_frame_offsets", "zhip_seekable_decompress_frames_device",
     "zhip_compress_sequences_device", "zhip_ctx_entropy_grid", "zhip_ctx_set_match_finder",
+    "zhip_seekable_edit_bound", "zhip_seekable_edit_device",
 ]
 
 

@@ -111,6 +111,7 @@ ZH_DEV uint64_t zh_ld64(const uint8_t* p) { return *(const zh_u64u*)p; }
 ZH_DEV uint32_t zh_ld32(const uint8_t* p) { return *(const zh_u32u*)p; }
 ZH_DEV uint32_t zh_ld16(const uint8_t* p) { return *(const zh_u16u*)p; }
 ZH_DEV uint32_t zh_ld24(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16); }
+ZH_DEV void zh_st128(uint8_t* p, zh_v16 v) { *(zh_v16*)p = v; }              // 16 bytes to any address: one global_store_dwordx4
 ZH_DEV void zh_st64(uint8_t* p, uint64_t v) { *(zh_u64u*)p = v; }
 ZH_DEV void zh_st32(uint8_t* p, uint32_t v) { *(zh_u32u*)p = v; }
 ZH_DEV void zh_st16(uint8_t* p, uint16_t v) { *(zh_u16u*)p = v; }

@@ -362,6 +362,9 @@ struct KTimer {
     double totalMs = 0; uint64_t launches = 0;
 };
 
+// pinned memory a host table is uploaded from: written again only after the event behind its upload has completed (zsk_take_slot)
+struct ZskPinSlot { void* p; size_t cap; hipEvent_t done; };
+
 struct zhip_ctx {
     int device = 0;
     int numCU = 0;
@@ -396,6 +399,7 @@ struct zhip_ctx {
     // host-API staging
     DevBuf hSrc, hDst, hSegs, hStatus, hDense;
     DevBuf skSlots, skMeta;            // seekable streams: the chunks' compressBound-sized slots; segments, sizes, statuses and the scan's cells
+    std::vector<ZskPinSlot> skPins;    // the pick list of an edit without an opened stream travels through these
     void* pinned = nullptr; size_t pinnedCap = 0;
     bool hpReady = false; hipStream_t hpH2D = nullptr, hpCompute = nullptr, hpD2H = nullptr;     // host pipeline: copy-in, kernels, copy-out
     void* hpStage[2] = {nullptr, nullptr}; size_t hpStageCap[2] = {0, 0}; hipEvent_t hpStageFree[2] = {nullptr, nullptr}; int hpNextSlot = 0;
@@ -503,6 +507,7 @@ extern "C" void zhip_ctx_destroy(zhip_ctx* c)
     c->cdictBlob.release(); c->cdictEntropy.release(); c->cdictDigest.release(); c->cdictTables.release();
     c->hSrc.release(); c->hDst.release(); c->hSegs.release(); c->hStatus.release(); c->hDense.release();
     c->skSlots.release(); c->skMeta.release();
+    for (ZskPinSlot& x : c->skPins) { if (x.p) (void)hipHostFree(x.p); (void)hipEventDestroy(x.done); }
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->profDecode) (void)hipFree(c->profDecode);
     if (c->profPipe) (void)hipFree(c->profPipe);
@@ -2109,37 +2114,39 @@ extern "C" uint64_t zhip_seekable_records_bound(uint64_t maxContentBytes, uint64
     return zsk_records_bound(maxContentBytes, nRecords, flags & ZHIP_SEEKABLE_CHECKSUM);
 }
 
-// zhip_seekable_compress_device with the caller's record table in the place of the fixed cut: the pre-check (two scans, a verdict), the segments, the batch,
-// then the fixed-size call's tail -- the scan of the sizes, its verdict, the (records) table writer, the compaction
-extern "C" int zhip_seekable_compress_records_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, const zhip_segment* d_records, size_t nRecords,
-                                                     uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
-                                                     void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+// where the records call keeps its arrays in the context's meta area; a caller with arrays of its own (the edit call) puts them behind metaBytes
+struct ZskRecordsLayout { size_t oSrcSegs, oSlotSegs, oSizes, oOffs, oLenOffs, oSlotOffs, oPartSum, oPartBad, oPreBad, oGo, oStatus, metaBytes; };
+static ZskRecordsLayout zsk_records_layout(size_t n)
 {
-    if (!c || !d_streamSize || !d_status || (nRecords && !d_records) || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) { g_lastError = "seekable compress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
-    if (nRecords > ZSK_MAX_FRAMES || maxRecordBytes > ZSK_MAX_CONTENT) { g_lastError = "seekable compress: at most 2^27 records of at most 2^30 bytes"; return ZHIP_ERR_UNSUPPORTED; }
-    hipStream_t stream = (hipStream_t)streamv;
-    const size_t n = nRecords;
+    ZskRecordsLayout l;
+    l.oSrcSegs = 0; l.oSlotSegs = l.oSrcSegs + zsk_up16(n * 16); l.oSizes = l.oSlotSegs + zsk_up16(n * 16); l.oOffs = l.oSizes + zsk_up16(n * 8);
+    l.oLenOffs = l.oOffs + zsk_up16((n + 1) * 8); l.oSlotOffs = l.oLenOffs + zsk_up16((n + 1) * 8); l.oPartSum = l.oSlotOffs + zsk_up16((n + 1) * 8);
+    l.oPartBad = l.oPartSum + ZSK_SCAN_GRID * 8; l.oPreBad = l.oPartBad + ZSK_SCAN_GRID * 8; l.oGo = l.oPreBad + ZSK_SCAN_GRID * 8; l.oStatus = l.oGo + 16;
+    l.metaBytes = zsk_up16(l.oStatus + zsk_up16(n * 4));
+    return l;
+}
+// The front half of a call that compresses a caller's record table: the pre-check (two scans, a verdict), the segments, the batch into the context's slots.
+// Reserves the meta area (the layout's bytes and extraMeta behind them) and the slots, fills *r with everything but the caller's dst / streamSize / outStatus.
+static int zsk_records_front(zhip_ctx* c, const ZskRecordsLayout& l, size_t extraMeta, const void* d_src, uint64_t srcSize, const zhip_segment* d_records, size_t n,
+                             uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags, hipStream_t stream, ZskRecordsArgs* out)
+{
     maxContentBytes = zsk_records_content_cap(maxContentBytes, n, maxRecordBytes);
     // (growing either area frees the old one, which waits for the device: the wait the stream-order rules allow)
-    const size_t oSrcSegs = 0, oSlotSegs = oSrcSegs + zsk_up16(n * 16), oSizes = oSlotSegs + zsk_up16(n * 16), oOffs = oSizes + zsk_up16(n * 8),
-                 oLenOffs = oOffs + zsk_up16((n + 1) * 8), oSlotOffs = oLenOffs + zsk_up16((n + 1) * 8), oPartSum = oSlotOffs + zsk_up16((n + 1) * 8),
-                 oPartBad = oPartSum + ZSK_SCAN_GRID * 8, oPreBad = oPartBad + ZSK_SCAN_GRID * 8, oGo = oPreBad + ZSK_SCAN_GRID * 8, oStatus = oGo + 16, metaBytes = oStatus + zsk_up16(n * 4);
-    if (c->skMeta.reserve(metaBytes)) return g_reserveRc;
+    if (c->skMeta.reserve(l.metaBytes + extraMeta)) return g_reserveRc;
     if (n && c->skSlots.reserve((size_t)zsk_records_slot_bytes(maxContentBytes, n))) return g_reserveRc;
     uint8_t* const m = (uint8_t*)c->skMeta.p;
-    uint32_t* const words = (uint32_t*)(m + oGo);                          // go, pre, the pre-check's status pair
+    uint32_t* const words = (uint32_t*)(m + l.oGo);                        // go, pre, the pre-check's status pair
     ZskRecordsArgs r; memset(&r, 0, sizeof r);
     r.src = (const uint8_t*)d_src; r.srcSize = srcSize; r.records = (const uint64_t*)d_records; r.n = (uint32_t)n; r.checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1u : 0u;
-    r.maxContent = maxContentBytes; r.lenOffs = (const uint64_t*)(m + oLenOffs); r.slotOffs = (const uint64_t*)(m + oSlotOffs); r.partBad = (const uint64_t*)(m + oPreBad);
-    r.srcSegs = (uint64_t*)(m + oSrcSegs); r.slotSegs = (uint64_t*)(m + oSlotSegs); r.pre = words + 1; r.preStatus = (int32_t*)(words + 2);
-    r.outSizes = (const uint64_t*)(m + oSizes); r.status = (int32_t*)(m + oStatus); r.offs = (const uint64_t*)(m + oOffs); r.go = words;
-    r.dst = (uint8_t*)d_dst; r.streamSize = d_streamSize; r.outStatus = d_status;
+    r.maxContent = maxContentBytes; r.lenOffs = (const uint64_t*)(m + l.oLenOffs); r.slotOffs = (const uint64_t*)(m + l.oSlotOffs); r.partBad = (const uint64_t*)(m + l.oPreBad);
+    r.srcSegs = (uint64_t*)(m + l.oSrcSegs); r.slotSegs = (uint64_t*)(m + l.oSlotSegs); r.pre = words + 1; r.preStatus = (int32_t*)(words + 2);
+    r.outSizes = (const uint64_t*)(m + l.oSizes); r.status = (int32_t*)(m + l.oStatus); r.offs = (const uint64_t*)(m + l.oOffs); r.go = words;
     ZskScanArgs s; memset(&s, 0, sizeof s);
     s.in = (const uint8_t*)d_records + 8; s.stride = 16; s.mode = 3; s.n = (uint32_t)n; s.limit64 = maxRecordBytes; s.srcSize = srcSize;
-    s.offs = (uint64_t*)(m + oLenOffs); s.partSum = (uint64_t*)(m + oPartSum); s.partBad = (uint64_t*)(m + oPreBad);
+    s.offs = (uint64_t*)(m + l.oLenOffs); s.partSum = (uint64_t*)(m + l.oPartSum); s.partBad = (uint64_t*)(m + l.oPreBad);
     uint32_t span; r.nPart = zsk_scan_shape(s.n, &span);
     if (int rc = zsk_launch_scan(s, stream)) return rc;
-    s.mode = 4; s.offs = (uint64_t*)(m + oSlotOffs); s.partBad = (uint64_t*)(m + oPartBad);
+    s.mode = 4; s.offs = (uint64_t*)(m + l.oSlotOffs); s.partBad = (uint64_t*)(m + l.oPartBad);
     if (int rc = zsk_launch_scan(s, stream)) return rc;
     hipLaunchKernelGGL(zhip_seekable_records_verdict_kernel, dim3(1), dim3(64), 0, stream, r);
     HIP_TRY(hipGetLastError());
@@ -2149,15 +2156,34 @@ extern "C" int zhip_seekable_compress_records_device(zhip_ctx* c, const void* d_
         // the batch's largest source is what the caller says it is; the caller's own size hint is not touched
         const size_t hintWas = c->srcMaxHint;
         c->srcMaxHint = (size_t)maxRecordBytes;
-        const int rc = zhip_compress_batch_device(c, d_src, (const zhip_segment*)r.srcSegs, n, c->skSlots.p, (const zhip_segment*)r.slotSegs, (uint64_t*)(m + oSizes), r.status, stream);
+        const int rc = zhip_compress_batch_device(c, d_src, (const zhip_segment*)r.srcSegs, n, c->skSlots.p, (const zhip_segment*)r.slotSegs, (uint64_t*)(m + l.oSizes), r.status, stream);
         c->srcMaxHint = hintWas;
         if (rc) return rc;
     }
+    *out = r;
+    return 0;
+}
+
+// zhip_seekable_compress_device with the caller's record table in the place of the fixed cut: the front half above, then the fixed-size call's tail -- the
+// scan of the sizes, its verdict, the (records) table writer, the compaction
+extern "C" int zhip_seekable_compress_records_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, const zhip_segment* d_records, size_t nRecords,
+                                                     uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
+                                                     void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+{
+    if (!c || !d_streamSize || !d_status || (nRecords && !d_records) || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) { g_lastError = "seekable compress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
+    if (nRecords > ZSK_MAX_FRAMES || maxRecordBytes > ZSK_MAX_CONTENT) { g_lastError = "seekable compress: at most 2^27 records of at most 2^30 bytes"; return ZHIP_ERR_UNSUPPORTED; }
+    hipStream_t stream = (hipStream_t)streamv;
+    const size_t n = nRecords;
+    const ZskRecordsLayout l = zsk_records_layout(n);
+    ZskRecordsArgs r;
+    if (int rc = zsk_records_front(c, l, 0, d_src, srcSize, d_records, n, maxContentBytes, maxRecordBytes, flags, stream, &r)) return rc;
+    uint8_t* const m = (uint8_t*)c->skMeta.p;
+    r.dst = (uint8_t*)d_dst; r.streamSize = d_streamSize; r.outStatus = d_status;
     ZskCompressArgs a; memset(&a, 0, sizeof a);
-    a.n = (uint32_t)n; a.checksum = r.checksum; a.nPart = r.nPart; a.outSizes = r.outSizes; a.status = r.status; a.offs = r.offs; a.partBad = (const uint64_t*)(m + oPartBad);
-    a.dst = (uint8_t*)d_dst; a.dstCapacity = dstCapacity; a.streamSize = d_streamSize; a.outStatus = d_status; a.go = words;
-    memset(&s, 0, sizeof s);
-    s.in = m + oSizes; s.status = r.status; s.mode = 0; s.n = (uint32_t)n; s.offs = (uint64_t*)(m + oOffs); s.partSum = (uint64_t*)(m + oPartSum); s.partBad = (uint64_t*)(m + oPartBad);
+    a.n = (uint32_t)n; a.checksum = r.checksum; a.nPart = r.nPart; a.outSizes = r.outSizes; a.status = r.status; a.offs = r.offs; a.partBad = (const uint64_t*)(m + l.oPartBad);
+    a.dst = (uint8_t*)d_dst; a.dstCapacity = dstCapacity; a.streamSize = d_streamSize; a.outStatus = d_status; a.go = (uint32_t*)(m + l.oGo);
+    ZskScanArgs s; memset(&s, 0, sizeof s);
+    s.in = m + l.oSizes; s.status = r.status; s.mode = 0; s.n = (uint32_t)n; s.offs = (uint64_t*)(m + l.oOffs); s.partSum = (uint64_t*)(m + l.oPartSum); s.partBad = (uint64_t*)(m + l.oPartBad);
     if (int rc = zsk_launch_scan(s, stream)) return rc;
     hipLaunchKernelGGL(zhip_seekable_verdict_kernel, dim3(1), dim3(64), 0, stream, a);
     hipLaunchKernelGGL(zhip_seekable_records_table_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, r);
@@ -2178,11 +2204,12 @@ struct zhip_seekable {
     DevBuf prefix;                       // the table's scans: compressed offsets, decompressed offsets, place among the frames with content -- [n + 1] each
     DevBuf meta, edge;                   // a range call's segments / sizes / statuses, and where its partly covered frames are decoded
     std::vector<uint64_t> dOff, place;   // the host's copies: which frames cover a range, and how many of them go to the decoder
+    std::vector<uint64_t> cOff;          // and where a frame's bytes lie: what an edit keeps of the stream (zhip_seekable_edit_bound)
     // the many-ranges call: its plan's tables on the device, its item arrays and per-range words, its scratch frames; the pinned slots the tables are
     // uploaded from (a slot is written again only after the event behind its upload has completed)
     DevBuf gTables, gMeta, gScratch;
     uint64_t scratchLimit = 0;           // 0 = ZSK_SCRATCH_DEFAULT
-    struct Slot { void* p; size_t cap; hipEvent_t done; };
+    typedef ZskPinSlot Slot;
     std::vector<Slot> slots;
 };
 
@@ -2226,8 +2253,8 @@ extern "C" int zhip_seekable_open_device(zhip_ctx* c, const void* d_stream, uint
     uint32_t span; const uint32_t grid = zsk_scan_shape(lay.n, &span);
     std::vector<uint64_t> bad(grid);
     uint64_t compressedTotal = 0;
-    h->dOff.resize(n + 1); h->place.resize(n + 1);
-    if (hipMemcpyAsync(h->dOff.data(), pre + col, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemcpyAsync(h->place.data(), pre + 2 * col, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+    h->cOff.resize(n + 1); h->dOff.resize(n + 1); h->place.resize(n + 1);
+    if (hipMemcpyAsync(h->cOff.data(), pre, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemcpyAsync(h->dOff.data(), pre + col, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemcpyAsync(h->place.data(), pre + 2 * col, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
         hipMemcpyAsync(bad.data(), pm + 3 * part, grid * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemcpyAsync(&compressedTotal, pre + n * 8, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess) { g_lastError = "seekable open: reading the table's scans failed"; return fail(ZHIP_ERR_HIP, 0); }
     uint64_t lowestBad = ZSK_NONE;
@@ -2291,21 +2318,21 @@ extern "C" int zhip_seekable_decompress_device(zhip_ctx* c, zhip_seekable* h, ui
 extern "C" void zhip_seekable_set_scratch_limit(zhip_seekable* h, uint64_t bytes) { if (h) h->scratchLimit = bytes; }
 
 // a pinned slot of at least `bytes` that no upload still reads: one whose event has completed (grown where too small), else a new one
-static int zsk_take_slot(zhip_seekable* h, size_t bytes, zhip_seekable::Slot** out)
+static int zsk_take_slot(std::vector<ZskPinSlot>& slots, size_t bytes, ZskPinSlot** out)
 {
-    zhip_seekable::Slot* s = nullptr;
-    for (zhip_seekable::Slot& x : h->slots) if (hipEventQuery(x.done) == hipSuccess) { s = &x; break; }
+    ZskPinSlot* s = nullptr;
+    for (ZskPinSlot& x : slots) if (hipEventQuery(x.done) == hipSuccess) { s = &x; break; }
     (void)hipGetLastError();                                               // (hipErrorNotReady of a slot still in flight is no failure)
     if (!s) {
-        zhip_seekable::Slot x = {nullptr, 0, nullptr};
+        ZskPinSlot x = {nullptr, 0, nullptr};
         HIP_TRY(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
-        h->slots.push_back(x); s = &h->slots.back();
+        slots.push_back(x); s = &slots.back();
     }
     if (s->cap < bytes) {
         if (s->p) { (void)hipHostFree(s->p); s->p = nullptr; s->cap = 0; }
         const size_t want = bytes + (bytes >> 2) + 4096;
         const hipError_t e = hipHostMalloc(&s->p, want, hipHostMallocDefault);
-        if (e != hipSuccess) { s->p = nullptr; (void)hipGetLastError(); g_lastError = "seekable ranges: no pinned memory for the plan's tables"; return ZHIP_ERR_NO_MEMORY; }
+        if (e != hipSuccess) { s->p = nullptr; (void)hipGetLastError(); g_lastError = "seekable: no pinned memory for the call's tables"; return ZHIP_ERR_NO_MEMORY; }
         s->cap = want;
     }
     *out = s;
@@ -2352,7 +2379,7 @@ extern "C" int zhip_seekable_decompress_ranges_device(zhip_ctx* c, zhip_seekable
         h->gScratch.cap = (size_t)plan.scratchMax;
     }
     zhip_seekable::Slot* slot = nullptr;
-    if (int rc = zsk_take_slot(h, tableBytes, &slot)) return rc;
+    if (int rc = zsk_take_slot(h->slots, tableBytes, &slot)) return rc;
     uint8_t* const pin = (uint8_t*)slot->p;
     memcpy(pin + oRanges, plan.ranges.data(), R * sizeof(ZskGatherRange));
     if (S) memcpy(pin + oSegs, plan.segs.data(), S * sizeof(ZskGatherSeg));
@@ -2417,4 +2444,95 @@ extern "C" int zhip_seekable_decompress_frames_device(zhip_ctx* c, zhip_seekable
         return ZHIP_ERR_SIZE_MISMATCH;
     }
     return zhip_seekable_decompress_ranges_device(c, h, rg.data(), nFrames, d_dst, dstCapacity, d_status, stats, streamv);
+}
+
+// ------------------------------------------------------------------------------------------ seekable streams: edit
+extern "C" uint64_t zhip_seekable_edit_bound(const zhip_seekable* old, const zhip_seekable_pick* picks, size_t nPicks, uint64_t maxRecordBytes, int flags)
+{
+    static_assert(sizeof(zhip_seekable_pick) == sizeof(ZskEditPick) && ZHIP_PICK_FRAME == ZSK_PICK_FRAME && ZHIP_PICK_RECORD == ZSK_PICK_RECORD, "the kernels read the caller's picks as they are");
+    if ((flags & ~ZHIP_SEEKABLE_CHECKSUM) || (nPicks && !picks) || nPicks > ZSK_MAX_FRAMES || maxRecordBytes > ZSK_MAX_CONTENT) return 0;
+    const int checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1 : 0;
+    if (old && old->lay.checksum != checksum) return 0;
+    size_t bad = 0;
+    if (zsk_edit_check((const ZskEditPick*)picks, nPicks, old != nullptr, old ? old->lay.n : 0, ZSK_MAX_FRAMES, &bad)) return 0;
+    return zsk_edit_bound((const ZskEditPick*)picks, nPicks, old ? old->cOff.data() : nullptr, maxRecordBytes, checksum);
+}
+
+// The records call's front half (where there are records), then everything per PICK: sizes, the two scans, the verdict, the copy, the table.
+extern "C" int zhip_seekable_edit_device(zhip_ctx* c, zhip_seekable* old, const zhip_seekable_pick* picks, size_t nPicks,
+                                         const void* d_src, uint64_t srcSize, const zhip_segment* d_records, size_t nRecords,
+                                         uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
+                                         void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+{
+    if (!c || !d_dst || !d_streamSize || !d_status || (nPicks && !picks) || (nRecords && !d_records) || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) { g_lastError = "seekable edit: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
+    if (nPicks > ZSK_MAX_FRAMES) { g_lastError = "seekable edit: at most 2^27 picks"; return ZHIP_ERR_UNSUPPORTED; }
+    if (nRecords > ZSK_MAX_FRAMES || maxRecordBytes > ZSK_MAX_CONTENT) { g_lastError = "seekable edit: at most 2^27 records of at most 2^30 bytes"; return ZHIP_ERR_UNSUPPORTED; }
+    const uint32_t checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1u : 0u;
+    if (old && (uint32_t)old->lay.checksum != checksum) { g_lastError = "seekable edit: ZHIP_SEEKABLE_CHECKSUM must be set exactly when the opened stream's table has checksums"; return ZHIP_ERR_UNSUPPORTED; }
+    const ZskEditPick* const pk = (const ZskEditPick*)picks;
+    const uint32_t nOld = old ? old->lay.n : 0;
+    size_t bad = 0;
+    if (const int why = zsk_edit_check(pk, nPicks, old != nullptr, nOld, nRecords, &bad)) {
+        char buf[200];
+        if (why == 1) snprintf(buf, sizeof buf, "seekable edit: position %zu is %s", bad, pk[bad].from > ZSK_PICK_RECORD ? "neither a frame nor a record pick" : "a frame pick, and no stream is opened");
+        else snprintf(buf, sizeof buf, "seekable edit: position %zu names %s %u, there are %llu", bad, pk[bad].from == ZSK_PICK_FRAME ? "frame" : "record", pk[bad].index,
+                      (unsigned long long)(pk[bad].from == ZSK_PICK_FRAME ? (uint64_t)nOld : (uint64_t)nRecords));
+        g_lastError = buf;
+        return why == 1 ? ZHIP_ERR_UNSUPPORTED : ZHIP_ERR_SIZE_MISMATCH;
+    }
+    bool inPlace = false;
+    if (old) {
+        const uint8_t* const d0 = (const uint8_t*)d_dst; const uint8_t* const o0 = old->stream;
+        if (d0 < o0 + old->streamSize && o0 < d0 + dstCapacity) {
+            inPlace = d0 == o0 && zsk_edit_is_append(pk, nPicks, nOld);
+            if (!inPlace) { g_lastError = "seekable edit: the destination overlaps the opened stream (allowed only at its base, with picks that begin with every frame in order)"; return ZHIP_ERR_UNSUPPORTED; }
+        }
+    }
+    hipStream_t stream = (hipStream_t)streamv;
+    const size_t n = nPicks, entry = zsk_entry_size((int)checksum);
+    const ZskRecordsLayout l = zsk_records_layout(nRecords);
+    const size_t oPicks = nRecords ? l.metaBytes : 0, oPickSize = oPicks + zsk_up16(n * 8), oOffs = oPickSize + zsk_up16(n * 8), oTileOffs = oOffs + zsk_up16((n + 1) * 8),
+                 oPartSum = oTileOffs + zsk_up16((n + 1) * 8), oPartBad = oPartSum + ZSK_SCAN_GRID * 8, oTileBad = oPartBad + ZSK_SCAN_GRID * 8, oGo = oTileBad + ZSK_SCAN_GRID * 8,
+                 oPickStatus = oGo + 16, oStash = oPickStatus + zsk_up16(n * 4), end = oStash + (inPlace ? zsk_up16((size_t)nOld * entry) : 0);
+    ZskPinSlot* slot = nullptr;
+    if (n) if (int rc = zsk_take_slot(old ? old->slots : c->skPins, n * sizeof(ZskEditPick), &slot)) return rc;
+    ZskEditArgs e; memset(&e, 0, sizeof e);
+    if (nRecords) {
+        ZskRecordsArgs r;
+        if (int rc = zsk_records_front(c, l, end - l.metaBytes, d_src, srcSize, d_records, nRecords, maxContentBytes, maxRecordBytes, flags, stream, &r)) return rc;
+        e.src = r.src; e.records = r.records; e.slots = (const uint8_t*)c->skSlots.p; e.slotSegs = r.slotSegs; e.recSizes = r.outSizes; e.recStatus = r.status; e.pre = r.pre; e.preStatus = r.preStatus;
+    } else if (c->skMeta.reserve(end)) return g_reserveRc;      // (growing the area frees the old one, which waits for the device: the wait the stream-order rules allow)
+    uint8_t* const m = (uint8_t*)c->skMeta.p;
+    if (old) {
+        e.old = old->stream; e.cOff = (const uint64_t*)old->prefix.p; e.oldEntries = old->stream + old->lay.tableOffset + ZSK_HEADER;
+        if (inPlace && nOld) {      // the new frames overwrite the old table: its entries are kept aside first
+            HIP_TRY(hipMemcpyAsync(m + oStash, e.oldEntries, (size_t)nOld * entry, hipMemcpyDeviceToDevice, stream));
+            e.oldEntries = m + oStash;
+        }
+        if (inPlace) e.firstPick = nOld;
+    }
+    if (n) {
+        memcpy(slot->p, pk, n * sizeof(ZskEditPick));
+        HIP_TRY(hipMemcpyAsync(m + oPicks, slot->p, n * sizeof(ZskEditPick), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(slot->done, stream));
+    }
+    e.picks = (const ZskEditPick*)(m + oPicks); e.pickSize = (uint64_t*)(m + oPickSize); e.pickStatus = (int32_t*)(m + oPickStatus); e.tileOffs = (const uint64_t*)(m + oTileOffs);
+    ZskCompressArgs& a = e.v;
+    a.n = (uint32_t)n; a.checksum = checksum; a.status = e.pickStatus; a.outSizes = e.pickSize; a.offs = (const uint64_t*)(m + oOffs); a.partBad = (const uint64_t*)(m + oPartBad);
+    a.dst = (uint8_t*)d_dst; a.dstCapacity = dstCapacity; a.streamSize = d_streamSize; a.outStatus = d_status; a.go = (uint32_t*)(m + oGo);
+    uint32_t span; a.nPart = zsk_scan_shape(a.n, &span);
+    hipLaunchKernelGGL(zhip_seekable_edit_sizes_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, e);
+    HIP_TRY(hipGetLastError());
+    ZskScanArgs s; memset(&s, 0, sizeof s);
+    s.in = m + oPickSize; s.status = e.pickStatus; s.mode = 0; s.n = (uint32_t)n; s.offs = (uint64_t*)(m + oOffs); s.partSum = (uint64_t*)(m + oPartSum); s.partBad = (uint64_t*)(m + oPartBad);
+    if (int rc = zsk_launch_scan(s, stream)) return rc;
+    s.mode = 5; s.status = nullptr; s.offs = (uint64_t*)(m + oTileOffs); s.partBad = (uint64_t*)(m + oTileBad);
+    if (int rc = zsk_launch_scan(s, stream)) return rc;
+    hipLaunchKernelGGL(zhip_seekable_edit_verdict_kernel, dim3(1), dim3(64), 0, stream, e);
+    // the copy's grid is fixed (the host knows only bounds): the tiles of dstCapacity bytes and one more per pick cover every stream that fits
+    const uint64_t tilesMost = dstCapacity / ZSK_COPY_TILE + n + 1, gmax = (uint64_t)(c->numCU > 0 ? c->numCU : 1) * 32;
+    hipLaunchKernelGGL(zhip_seekable_edit_copy_kernel, dim3((uint32_t)(tilesMost < gmax ? tilesMost : gmax)), dim3(64), 0, stream, e);
+    hipLaunchKernelGGL(zhip_seekable_edit_table_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, e);
+    HIP_TRY(hipGetLastError());
+    return 0;
 }

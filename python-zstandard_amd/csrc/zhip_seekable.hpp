@@ -4,8 +4,8 @@
 //
 // (all little-endian; an entry is Compressed_Size, Decompressed_Size and, with bit 7 of the descriptor, the low 32 bits of XXH64 of the frame's content).
 // What is here: the format's arithmetic and checks (plain functions, host and device), and the kernels around the batch calls -- chunk segments, a
-// multi-workgroup exclusive scan of 64-bit sizes, the table writer, their twins for a caller's record table (one frame per record), and the range pieces
-// (segment builder, size / checksum verifier, edge copy).
+// multi-workgroup exclusive scan of 64-bit sizes, the table writer, their twins for a caller's record table (one frame per record), the range pieces
+// (segment builder, size / checksum verifier, edge copy), and the edit pieces (pick sizes, verdict, the tiled copy of kept and new frames, the table).
 // Every kernel is one-wave workgroups written against zhip_device.hpp, so the same bodies run under the host wave emulator (tests/emu/emu_seekable.cpp).
 #pragma once
 #include "zhip_device.hpp"
@@ -38,6 +38,7 @@
 #define ZSK_SCAN_PER_LANE 4u
 #define ZSK_SCAN_TILE (ZSK_SCAN_LANES * ZSK_SCAN_PER_LANE)
 #define ZSK_SCAN_GRID 1024u
+#define ZSK_COPY_TILE 4096u                  // bytes one workgroup copies per step: 4 x 16 bytes per lane
 
 ZSK_HD uint64_t zsk_compress_bound(uint64_t n) { return n + (n >> 8) + (n < (128u << 10) ? (((128u << 10) - n) >> 11) : 0); }      // == zhip_compress_bound
 ZSK_HD uint64_t zsk_frame_count(uint64_t srcSize, uint32_t frameSize) { return frameSize ? srcSize / frameSize + (srcSize % frameSize ? 1 : 0) : 0; }
@@ -103,6 +104,7 @@ ZH_DEV uint64_t zsk_wave_scan64(uint64_t v)          // inclusive
 //   mode 3: in = the 64-bit length column of a record table (record i's length at in + i * stride, its offset 8 bytes in front; 8-byte aligned); an item counts
 //           its length and is "bad" where the length is above limit64, or offset + length ends beyond srcSize or wraps
 //   mode 4: the same column, an item counts (zsk_compress_bound(length) + 15) & ~15 -- the distance to the next record's slot; no item is bad
+//   mode 5: in = uint64_t[n]; an item counts the copy tiles of that many bytes, ceil(size / ZSK_COPY_TILE); no item is bad
 struct ZskScanArgs {
     const uint8_t* in; const int32_t* status; uint32_t stride, mode, limit, n;
     uint32_t span;                    // items per workgroup: whole tiles (zsk_scan_shape)
@@ -120,6 +122,7 @@ static inline uint32_t zsk_scan_shape(uint32_t n, uint32_t* span)
 ZH_DEV uint64_t zsk_scan_item(const ZskScanArgs& a, uint32_t i, bool* bad)
 {
     if (a.mode == 0) { const bool b = a.status[i] != 0; *bad = b; return b ? 0 : ((const uint64_t*)a.in)[i]; }
+    if (a.mode == 5) { *bad = false; return (((const uint64_t*)a.in)[i] + ZSK_COPY_TILE - 1) / ZSK_COPY_TILE; }
     if (a.mode >= 3) {
         const uint64_t* const rec = (const uint64_t*)(a.in + (size_t)i * a.stride);
         const uint64_t len = rec[0];
@@ -426,7 +429,6 @@ ZH_DEV void zsk_range_finish_body(const ZskRangeArgs& a)
 // The plan is a host function over the open call's dOff / place columns: O(R log R) + segments + jobs, never O(frames of the stream).
 #define ZSK_MAX_RANGES 0x8000000u            // 2^27
 #define ZSK_SCRATCH_DEFAULT 0x40000000ull    // 1 GiB: holds the largest frame the format allows
-#define ZSK_COPY_TILE 4096u                  // bytes one workgroup copies per step: 4 x 16 bytes per lane
 struct ZskGatherRange { uint64_t offset, length, dstOffset; uint32_t f0, f1; };      // f0 .. f1: the frames of the first and last byte (length 0: f0 = 1, f1 = 0)
 // frames first .. first + frames - 1 share a home: content byte dOff[first] lies at `home` from d_dst (inPlace) or from the scratch; framePrefix counts the
 // pass's frames in front (a lane of the segment builder bisects it), item is the batch item of the segment's first frame with content, counted over the call
@@ -630,6 +632,125 @@ ZH_DEV void zsk_gather_finish_body(const ZskGatherArgs& a)
     if (zh_lane() == 0) { a.outStatus[0] = first != ZSK_NONE ? a.status[~a.worst[first]] : 0; a.outStatus[1] = first != ZSK_NONE ? (int32_t)first : 0; }
 }
 
+// ------------------------------------------------------------------------------------------------ edit: a new stream from kept frames and new records
+// The new stream is nPicks frames in pick order and a table: a FRAME pick is frame `index` of the opened stream, its bytes and its table entry as they are;
+// a RECORD pick is record `index` of the caller's record table, compressed by this call into its slot (the records call's front half). Nothing looks inside
+// a frame. A lane per pick writes its size and status; the scan in mode 0 and zsk_verdict_body over the picks give the offsets, the stream size, the status
+// and the go word; the scan in mode 5 gives the picks' copy tiles in front; the copy kernel moves every pick to its place, a workgroup per tile; the table
+// writer follows it on the stream. In place (d_dst is the old stream's base and the picks begin with every old frame in order) the kept prefix is where
+// it belongs -- the copy starts behind it -- and the new frames start where the old table started, so the old entries are read from a stash.
+static_assert(ZSK_COPY_TILE == 4 * 64 * 16, "zsk_edit_copy_body moves a whole tile as four 16-byte accesses per lane");
+#define ZSK_PICK_FRAME 0u
+#define ZSK_PICK_RECORD 1u
+struct ZskEditPick { uint32_t from, index; };
+struct ZskEditArgs {
+    ZskCompressArgs v;                          // zsk_verdict_body's: n = nPicks, status = pickStatus, offs, partBad, dstCapacity, streamSize, outStatus, go
+    const ZskEditPick* picks;
+    const uint8_t* old; const uint64_t* cOff;   // the opened stream and its compressed offsets [nFrames + 1] (NULL without one)
+    const uint8_t* oldEntries;                  // its table's entries: in the stream or, in place, in the stash
+    const uint8_t* src; const uint64_t* records;             // the caller's source and record table [nRecords][2]
+    const uint8_t* slots; const uint64_t* slotSegs;          // where the batch put record j's frame
+    const uint64_t* recSizes; const int32_t* recStatus;      // [nRecords]: what zhip_compress_batch_device wrote
+    const uint32_t* pre; const int32_t* preStatus;           // the records' pre-check (NULL without records)
+    uint64_t* pickSize; int32_t* pickStatus;    // [nPicks]
+    const uint64_t* tileOffs;                   // [nPicks + 1]: the scan of the picks' copy tiles (mode 5)
+    uint32_t firstPick;                         // the copy starts at this pick: in place the frames of the kept prefix are where they belong, and nobody walks their tiles
+};
+// a lane per pick: its frame's size and status
+ZH_DEV void zsk_edit_sizes_body(const ZskEditArgs& e)
+{
+    for (uint64_t k = (uint64_t)zh_block() * 64 + zh_lane(); k < e.v.n; k += (uint64_t)zh_nblocks() * 64) {
+        const ZskEditPick p = e.picks[k];
+        uint64_t size; int32_t status = 0;
+        if (p.from == ZSK_PICK_FRAME) size = e.cOff[p.index + 1] - e.cOff[p.index];
+        else { status = e.recStatus[p.index]; size = status ? 0 : e.recSizes[p.index]; }
+        e.pickSize[k] = size; e.pickStatus[k] = status;
+    }
+}
+// one wave: zsk_verdict_body over the picks; a failed record pre-check then puts its status over the verdict (the batch compressed the harmless form)
+ZH_DEV void zsk_edit_verdict_body(const ZskEditArgs& e)
+{
+    zsk_verdict_body(e.v);
+    if (zh_lane() != 0 || !e.pre || *e.pre) return;
+    e.v.outStatus[0] = e.preStatus[0]; e.v.outStatus[1] = e.preStatus[1];
+    *e.v.streamSize = 0; *e.v.go = 0;
+}
+// a workgroup per ZSK_COPY_TILE bytes of a pick, over a fixed grid (the tile count is the device's): it bisects the tile prefix for its pick and copies from
+// the old stream or from the record's slot, 16 bytes per lane, whatever the two addresses are modulo 16; the bytes behind the last whole 16 go one per lane.
+// Only bytes [offs[k], offs[k + 1]) of the destination are written: the neighbouring picks are other workgroups'. A failed stream copies nothing.
+ZH_DEV void zsk_edit_copy_body(const ZskEditArgs& e)
+{
+    if (!*e.v.go) return;
+    const uint64_t tiles = e.tileOffs[e.v.n];
+    for (uint64_t t = e.tileOffs[e.firstPick] + zh_block(); t < tiles; t += zh_nblocks()) {
+        uint32_t lo = e.firstPick, hi = e.v.n;                               // the last pick whose tile prefix <= t: the picks behind it of no bytes share its prefix
+        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (e.tileOffs[mid] <= t) lo = mid; else hi = mid; }
+        const ZskEditPick p = e.picks[lo];
+        const uint8_t* const from = p.from == ZSK_PICK_FRAME ? e.old + e.cOff[p.index] : e.slots + e.slotSegs[2 * (uint64_t)p.index];
+        uint8_t* const to = e.v.dst + e.v.offs[lo];
+        const uint64_t off = (t - e.tileOffs[lo]) * ZSK_COPY_TILE, left = e.pickSize[lo] - off;
+        const uint32_t bytes = left < ZSK_COPY_TILE ? (uint32_t)left : ZSK_COPY_TILE, whole = bytes & ~15u;
+        const uint8_t* const s = from + off; uint8_t* const d = to + off;
+        if (bytes == ZSK_COPY_TILE) {                                        // a whole tile: its four loads are in flight together
+            const uint32_t j = zh_lane() * 16;
+            const zh_v16 v0 = zh_ld128_nt(s + j), v1 = zh_ld128_nt(s + j + 1024), v2 = zh_ld128_nt(s + j + 2048), v3 = zh_ld128_nt(s + j + 3072);      // (read once: streaming loads)
+            zh_st128(d + j, v0); zh_st128(d + j + 1024, v1); zh_st128(d + j + 2048, v2); zh_st128(d + j + 3072, v3);
+            continue;
+        }
+        for (uint32_t j = zh_lane() * 16; j < whole; j += 64 * 16) zh_st128(d + j, zh_ld128_nt(s + j));
+        if (zh_lane() < bytes - whole) d[whole + zh_lane()] = s[whole + zh_lane()];
+    }
+}
+// a lane per pick: a kept frame's entry as it was (the checksum word included), a record's (frame size, length, XXH64 low word of its source bytes);
+// lane 0 of the grid: the table frame's header and footer. A failed stream writes nothing
+ZH_DEV void zsk_edit_table_body(const ZskEditArgs& e)
+{
+    if (!*e.v.go) return;
+    const uint32_t entry = zsk_entry_size((int)e.v.checksum);
+    uint8_t* const table = e.v.dst + e.v.offs[e.v.n];
+    for (uint64_t k = (uint64_t)zh_block() * 64 + zh_lane(); k < e.v.n; k += (uint64_t)zh_nblocks() * 64) {
+        const ZskEditPick p = e.picks[k];
+        uint8_t* const w = table + ZSK_HEADER + k * entry;
+        if (p.from == ZSK_PICK_FRAME) {
+            const uint8_t* const was = e.oldEntries + (uint64_t)p.index * entry;
+            for (uint32_t j = 0; j < entry; j += 4) zh_st32(w + j, zh_ld32(was + j));
+        } else {
+            const uint64_t at = e.records[2 * (uint64_t)p.index]; const uint32_t len = (uint32_t)e.records[2 * (uint64_t)p.index + 1];
+            zh_st32(w, (uint32_t)e.pickSize[k]); zh_st32(w + 4, len);
+            if (e.v.checksum) zh_st32(w + 8, (uint32_t)ze_xxh64(e.src + at, len));
+        }
+    }
+    if (zh_block() != 0 || zh_lane() != 0) return;
+    uint8_t* const f = table + ZSK_HEADER + (uint64_t)e.v.n * entry;
+    zh_st32(table, ZSK_SKIP_MAGIC); zh_st32(table + 4, e.v.n * entry + ZSK_FOOTER);
+    zh_st32(f, e.v.n); f[4] = e.v.checksum ? 0x80 : 0; zh_st32(f + 5, ZSK_SEEK_MAGIC);
+}
+// the host's checks of a pick list: 0, 1 (a pick that is neither kind, or a FRAME pick without a stream), 2 (an index that is no frame / no record; *bad = its position)
+static inline int zsk_edit_check(const ZskEditPick* picks, size_t nPicks, bool haveOld, uint32_t nFrames, uint64_t nRecords, size_t* bad)
+{
+    for (size_t k = 0; k < nPicks; k++) {
+        *bad = k;
+        if (picks[k].from > ZSK_PICK_RECORD || (picks[k].from == ZSK_PICK_FRAME && !haveOld)) return 1;
+        if (picks[k].index >= (picks[k].from == ZSK_PICK_FRAME ? (uint64_t)nFrames : nRecords)) return 2;
+    }
+    return 0;
+}
+// the append form: the picks begin with every frame of the opened stream, in order
+static inline bool zsk_edit_is_append(const ZskEditPick* picks, size_t nPicks, uint32_t nFrames)
+{
+    if (nPicks < nFrames) return false;
+    for (uint32_t k = 0; k < nFrames; k++) if (picks[k].from != ZSK_PICK_FRAME || picks[k].index != k) return false;
+    return true;
+}
+// worst-case bytes of the new stream: the kept frames as they are, every record at zsk_compress_bound(maxRecord) (monotonic: it covers a shorter record), the
+// table. The picks have passed zsk_edit_check. C = the opened stream's compressed offsets (host)
+static inline uint64_t zsk_edit_bound(const ZskEditPick* picks, size_t nPicks, const uint64_t* C, uint64_t maxRecord, int checksum)
+{
+    uint64_t total = zsk_table_size(nPicks, checksum);
+    for (size_t k = 0; k < nPicks; k++) total += picks[k].from == ZSK_PICK_FRAME ? C[picks[k].index + 1] - C[picks[k].index] : zsk_compress_bound(maxRecord);
+    return total;
+}
+
 #ifndef ZHIP_EMU
 __global__ __launch_bounds__(64) void zhip_seekable_scan_reduce_kernel(ZskScanArgs a) { zsk_scan_reduce_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_scan_write_kernel(ZskScanArgs a) { zsk_scan_write_body(a); }
@@ -645,4 +766,8 @@ __global__ __launch_bounds__(64) void zhip_seekable_range_finish_kernel(ZskRange
 __global__ __launch_bounds__(64) void zhip_seekable_gather_segs_kernel(ZskGatherArgs a) { zsk_gather_segs_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_gather_verify_kernel(ZskGatherArgs a) { zsk_gather_verify_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_gather_finish_kernel(ZskGatherArgs a) { zsk_gather_finish_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_edit_sizes_kernel(ZskEditArgs e) { zsk_edit_sizes_body(e); }
+__global__ __launch_bounds__(64) void zhip_seekable_edit_verdict_kernel(ZskEditArgs e) { zsk_edit_verdict_body(e); }
+__global__ __launch_bounds__(64) void zhip_seekable_edit_copy_kernel(ZskEditArgs e) { zsk_edit_copy_body(e); }
+__global__ __launch_bounds__(64) void zhip_seekable_edit_table_kernel(ZskEditArgs e) { zsk_edit_table_body(e); }
 #endif

@@ -162,33 +162,25 @@ class DeviceBatchContext:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return dst[:int(size[0])]
 
-    def seekable_compress_records(self, src, records, max_content_bytes=None, max_record_bytes=None, checksum=False, stream=None):
-        """One frame per record: records[i] = (offset, length) of record i in src (a uint8 CUDA tensor), anywhere in it, in any order, with gaps or sharing
-        bytes, length 0 allowed; the stream's content is the records concatenated in index order. records: an (n, 2) int64 CUDA tensor -- it may have been
-        written by work queued on `stream`, nothing is waited for; max_content_bytes (an upper bound on the lengths' sum) and max_record_bytes (on every
-        length, at most 2^30) are then required, and the device checks them -- or a host sequence / array of (offset, length), which is uploaded and gives both
-        bounds itself. Returns a uint8 CUDA tensor of exactly the stream's size, as seekable_compress does. Waits for the size. A record outside src or above
-        a bound raises ZstdError (srcSize_wrong) with its index. SeekableStream.read_records reads records back by index."""
+    def _records_table(self, src, records, max_content_bytes, max_record_bytes, s, what="seekable compress"):
+        """records as seekable_compress_records takes them -> (the (n, 2) int64 CUDA table, n, max_content_bytes, max_record_bytes)"""
         import numpy as np
-        self._ensure_cparams()
-        self._check(src, torch.uint8)
-        s = stream if stream is not None else torch.cuda.current_stream()
         if isinstance(records, torch.Tensor) and records.is_cuda:
             if max_content_bytes is None or max_record_bytes is None:
-                raise ZstdError("seekable compress: a device-resident record table needs max_content_bytes and max_record_bytes")
+                raise ZstdError("%s: a device-resident record table needs max_content_bytes and max_record_bytes" % what)
             self._check(records, torch.int64)
             if records.dim() != 2 or records.shape[1] != 2:
-                raise ZstdError("seekable compress: records must have the shape (n, 2)")
+                raise ZstdError("%s: records must have the shape (n, 2)" % what)
             table = records
         else:
             try:
                 r = np.asarray(records.cpu() if isinstance(records, torch.Tensor) else records if len(records) else np.zeros((0, 2), dtype=np.int64))
             except Exception:
-                raise ZstdError("seekable compress: records must be a sequence of (offset, length)")
+                raise ZstdError("%s: records must be a sequence of (offset, length)" % what)
             if r.ndim != 2 or r.shape[1] != 2 or r.dtype.kind not in "iu":
-                raise ZstdError("seekable compress: records must be a sequence of (offset, length) or an integer array of shape (n, 2)")
+                raise ZstdError("%s: records must be a sequence of (offset, length) or an integer array of shape (n, 2)" % what)
             if r.shape[0] and ((r.astype(object) < 0).any() or (r.astype(object) >= 1 << 63).any()):
-                raise ZstdError("seekable compress: records must not be negative")
+                raise ZstdError("%s: records must not be negative" % what)
             r = np.ascontiguousarray(r.astype(np.int64))
             if max_content_bytes is None:
                 max_content_bytes = int(r[:, 1].sum()) if r.shape[0] else 0
@@ -199,7 +191,20 @@ class DeviceBatchContext:
         n = int(table.shape[0])
         max_content_bytes, max_record_bytes = int(max_content_bytes), int(max_record_bytes)
         if max_content_bytes < 0 or not 0 <= max_record_bytes <= 1 << 30 or n > 1 << 27:
-            raise ZstdError("seekable compress: at most 2^27 records of at most 2^30 bytes")
+            raise ZstdError("%s: at most 2^27 records of at most 2^30 bytes" % what)
+        return table, n, max_content_bytes, max_record_bytes
+
+    def seekable_compress_records(self, src, records, max_content_bytes=None, max_record_bytes=None, checksum=False, stream=None):
+        """One frame per record: records[i] = (offset, length) of record i in src (a uint8 CUDA tensor), anywhere in it, in any order, with gaps or sharing
+        bytes, length 0 allowed; the stream's content is the records concatenated in index order. records: an (n, 2) int64 CUDA tensor -- it may have been
+        written by work queued on `stream`, nothing is waited for; max_content_bytes (an upper bound on the lengths' sum) and max_record_bytes (on every
+        length, at most 2^30) are then required, and the device checks them -- or a host sequence / array of (offset, length), which is uploaded and gives both
+        bounds itself. Returns a uint8 CUDA tensor of exactly the stream's size, as seekable_compress does. Waits for the size. A record outside src or above
+        a bound raises ZstdError (srcSize_wrong) with its index. SeekableStream.read_records reads records back by index."""
+        self._ensure_cparams()
+        self._check(src, torch.uint8)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        table, n, max_content_bytes, max_record_bytes = self._records_table(src, records, max_content_bytes, max_record_bytes, s)
         flags = _lib.SEEKABLE_CHECKSUM if checksum else 0
         bound = self.L.zhip_seekable_records_bound(min(max_content_bytes, n * max_record_bytes), n, flags)
         if not bound:
@@ -219,6 +224,74 @@ class DeviceBatchContext:
         if rc:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return dst[:int(size[0])]
+
+    def _edit(self, old, picks, src, records, max_content_bytes, max_record_bytes, checksum, out, stream):
+        """zhip_seekable_edit_device behind seekable_edit (old None) and SeekableStream.edit (old: the opened stream) -> out[:size], or a view of a new tensor
+        sized by zhip_seekable_edit_bound"""
+        import numpy as np
+        try:
+            p = np.asarray(picks if len(picks) else np.zeros((0, 2), dtype=np.int64))
+        except Exception:
+            raise ZstdError("seekable edit: picks must be a sequence of (0 | 1, index)")
+        if p.ndim != 2 or p.shape[1] != 2 or p.dtype.kind not in "iu":
+            raise ZstdError("seekable edit: picks must be a sequence of (0 | 1, index) or an integer array of shape (k, 2)")
+        k = p.shape[0]
+        if k > 1 << 27:
+            raise ZstdError("seekable edit: at most 2^27 picks")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if records is None:
+            table, n, max_content_bytes, max_record_bytes = None, 0, 0, 0
+        else:
+            if src is None:
+                raise ZstdError("seekable edit: records need src")
+            self._ensure_cparams()
+            self._check(src, torch.uint8)
+            table, n, max_content_bytes, max_record_bytes = self._records_table(src, records, max_content_bytes, max_record_bytes, s, "seekable edit")
+        n_frames = old.n_frames if old is not None else 0
+        if k:
+            if (p < 0).any():
+                raise ZstdError("seekable edit: position %d is negative" % int(np.nonzero((p < 0).any(axis=1))[0][0]))
+            kind, index = p[:, 0].astype(np.uint64), p[:, 1].astype(np.uint64)
+            wrong = np.nonzero((kind != _lib.PICK_FRAME) & (kind != _lib.PICK_RECORD))[0]
+            if len(wrong):
+                raise ZstdError("seekable edit: position %d is neither a frame (0) nor a record (1) pick" % int(wrong[0]))
+            if old is None and (kind == _lib.PICK_FRAME).any():
+                raise ZstdError("seekable edit: position %d picks a frame, and no stream is opened" % int(np.nonzero(kind == _lib.PICK_FRAME)[0][0]))
+            wrong = np.nonzero(index >= np.where(kind == _lib.PICK_FRAME, np.uint64(n_frames), np.uint64(n)))[0]
+            if len(wrong):
+                w = int(wrong[0])
+                raise ZstdError("seekable edit: position %d names %s %d, there are %d" % ((w, "frame", int(index[w]), n_frames) if kind[w] == _lib.PICK_FRAME
+                                                                                          else (w, "record", int(index[w]), n)))
+        pk = np.ascontiguousarray(p.astype(np.uint32)) if k else np.zeros((1, 2), dtype=np.uint32)
+        device = old.tensor.device if old is not None else src.device if src is not None else torch.device("cuda", torch.cuda.current_device())
+        flags = _lib.SEEKABLE_CHECKSUM if checksum else 0
+        handle = old.handle if old is not None else None
+        bound = self.L.zhip_seekable_edit_bound(handle, pk.ctypes.data, k, max_record_bytes, flags)
+        if not bound:
+            raise ZstdError("seekable edit: bad arguments")
+        with torch.cuda.stream(s):
+            if out is None:
+                out = torch.empty(bound, dtype=torch.uint8, device=device)
+            size = torch.zeros(1, dtype=torch.int64, device=device)
+            status = torch.zeros(2, dtype=torch.int32, device=device)
+        self._check(out, torch.uint8)
+        rc = self.L.zhip_seekable_edit_device(self.ctx, handle, pk.ctypes.data, k, src.data_ptr() if n else None, src.numel() if n else 0, table.data_ptr() if n else None, n,
+                                              max_content_bytes, max_record_bytes, flags, out.data_ptr(), out.numel(), size.data_ptr(), status.data_ptr(), s.cuda_stream)
+        if rc:
+            raise ZstdError("seekable edit failed: %s" % _lib.last_error())
+        err = _lib.Error()
+        rc = self.L.zhip_ctx_sync(self.ctx, s.cuda_stream, status.data_ptr(), 1, C.byref(err))
+        if rc == _lib.ERR_ZSTD:
+            code, index = (int(x) for x in status)
+            raise ZstdError("seekable edit: %s %d: %s" % ("record" if code == 72 else "position", index, _lib.error_name(err.zstdErr)))
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return out[:int(size[0])]
+
+    def seekable_edit(self, picks, src=None, records=None, max_content_bytes=None, max_record_bytes=None, checksum=False, out=None, stream=None):
+        """SeekableStream.edit without an opened stream: every pick is (1, record index). With picks (1, 0) .. (1, n - 1) the result is
+        seekable_compress_records' byte for byte; a record may be picked any number of times or not at all."""
+        return self._edit(None, picks, src, records, max_content_bytes, max_record_bytes, checksum, out, stream)
 
     def kernel_time(self, direction):
         """(average ms per launch, launches) of the dominant kernel since the last call, from HIP events on the launch stream."""
@@ -432,6 +505,79 @@ class SeekableStream:
         if rc:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return [out[offs[k]:offs[k] + lengths[k]] for k in range(n)]
+
+    def edit(self, picks, src=None, records=None, max_content_bytes=None, max_record_bytes=None, out=None, stream=None):
+        """A NEW stream out of this stream's frames and of new records, without recompressing what is kept: picks, an integer array of shape (k, 2), names the
+        new stream's frames in order -- (0, i): frame i of this stream, its bytes and its table entry as they are; (1, j): record j of `records`, compressed by
+        this call with the context's level, parameters, dictionary and match finder. A frame or a record may be picked any number of times; a record nobody
+        picks is dropped. records / src / max_content_bytes / max_record_bytes: as in DeviceBatchContext.seekable_compress_records (an (n, 2) int64 CUDA tensor
+        may have been written by work queued on `stream` and needs both bounds). The new table has checksums exactly when this stream's has. Returns a uint8
+        CUDA tensor of exactly the new stream's size: out[:size] -- `out` must not overlap this stream's tensor --, or a view of a new tensor sized by the bound.
+        Waits for the status only; ZstdError names the record (a record outside src or above a bound) or the position in picks (a record the level refuses, a
+        frame that ends beyond `out`)."""
+        if self.handle is None:
+            raise ZstdError("the seekable stream is closed")
+        return self.ctx._edit(self, picks, src, records, max_content_bytes, max_record_bytes, self.has_checksums, out, stream)
+
+    @staticmethod
+    def _count(records):
+        return int(records.shape[0]) if hasattr(records, "shape") else len(records)
+
+    def _picks(self, frames, n_records=0):
+        import numpy as np
+        p = np.zeros((len(frames) + n_records, 2), dtype=np.int64)
+        p[:len(frames), 1] = frames
+        p[len(frames):, 0] = _lib.PICK_RECORD
+        p[len(frames):, 1] = np.arange(n_records)
+        return p
+
+    def append_records(self, src, records, buffer=None, max_content_bytes=None, max_record_bytes=None, stream=None):
+        """this stream's frames, then one new frame per record: edit() with picks (0, 0) .. (0, n_frames - 1), (1, 0) .. (1, n - 1). With `buffer` -- a uint8 CUDA
+        tensor that starts where this stream's tensor starts (the same data_ptr()) and has room for the bound -- the append is IN PLACE: the kept frames are
+        neither read nor written, the new frames start where the old table started; this object is closed (it describes bytes that no longer exist) and
+        buffer[:new size] is returned: open it again to read. A failed append in place leaves the old stream as it was, and this object open."""
+        import numpy as np
+        picks = self._picks(np.arange(self.n_frames), self._count(records))
+        if buffer is None:
+            return self.edit(picks, src, records, max_content_bytes, max_record_bytes, None, stream)
+        DeviceBatchContext._check(buffer, torch.uint8)
+        if buffer.data_ptr() != self.tensor.data_ptr():
+            raise ZstdError("seekable append: buffer must start where the stream's tensor starts")
+        out = self.edit(picks, src, records, max_content_bytes, max_record_bytes, buffer, stream)
+        self.close()
+        return out
+
+    def replace_records(self, indices, src, records, max_content_bytes=None, max_record_bytes=None, stream=None):
+        """frame indices[j] gives way to record j of `records` (an index named twice keeps the later record); every other frame is kept"""
+        import numpy as np
+        idx = np.asarray(indices if len(indices) else np.zeros(0, dtype=np.int64))
+        if idx.ndim != 1 or idx.dtype.kind not in "iu" or len(idx) != self._count(records):
+            raise ZstdError("seekable replace: one frame index per record")
+        wrong = np.nonzero((idx < 0) | (idx >= self.n_frames))[0]
+        if len(wrong):
+            raise ZstdError("seekable replace: position %d names frame %d, the table has %d" % (int(wrong[0]), int(idx[wrong[0]]), self.n_frames))
+        picks = self._picks(np.arange(self.n_frames))
+        picks[idx, 0] = _lib.PICK_RECORD
+        picks[idx, 1] = np.arange(len(idx))
+        return self.edit(picks, src, records, max_content_bytes, max_record_bytes, None, stream)
+
+    def delete_records(self, indices, stream=None):
+        """the stream without the frames named by `indices`"""
+        import numpy as np
+        idx = np.asarray(indices if len(indices) else np.zeros(0, dtype=np.int64))
+        if idx.ndim != 1 or idx.dtype.kind not in "iu":
+            raise ZstdError("seekable delete: indices must be a sequence of frame indices")
+        wrong = np.nonzero((idx < 0) | (idx >= self.n_frames))[0]
+        if len(wrong):
+            raise ZstdError("seekable delete: position %d names frame %d, the table has %d" % (int(wrong[0]), int(idx[wrong[0]]), self.n_frames))
+        keep = np.ones(self.n_frames, dtype=bool)
+        keep[idx] = False
+        return self.edit(self._picks(np.nonzero(keep)[0]), stream=stream)
+
+    def reorder(self, order, stream=None):
+        """the frames named by `order`, in that order -- a permutation lays an epoch's sample order out contiguously; `order` may repeat or omit frames"""
+        import numpy as np
+        return self.edit(self._picks(np.asarray(order if len(order) else np.zeros(0, dtype=np.int64))), stream=stream)
 
     def close(self):
         if self.handle is not None:

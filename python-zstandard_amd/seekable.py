@@ -2,7 +2,7 @@
 appends the seek table; ``decompress`` reads any byte range of such a stream by decoding only the frames that cover it, ``decompress_ranges`` many ranges as one batch. The streams are ordinary zstd:
 ``zstd -d`` and ``ZstdDecompressor`` decompress them whole (the table is a skippable frame). Built on ``device.DeviceBatchContext.seekable_compress`` and
 ``device.SeekableStream``; the data crosses the link once each way. ``compress_records`` / ``decompress_records`` do the same for a list of records of any
-sizes: one frame per record, read back by index."""
+sizes: one frame per record, read back by index; ``append_records`` / ``edit`` make a new stream out of an old one's frames and new records."""
 import torch
 
 from .backend_hip import ZstdError
@@ -100,3 +100,36 @@ def decompress_records(data, indices, **ctx_kw):
             st.close()
     finally:
         ctx.close()
+
+
+def _edited(data, records, level, match_finder, ctx_kw, call):
+    """call(opened stream, source tensor, record table) -> the new stream's bytes"""
+    if len(data) == 0:
+        raise ZstdError("not a seekable stream: empty input")
+    raws = [bytes(r) for r in records]
+    table, at = [], 0
+    for r in raws:
+        table.append((at, len(r))); at += len(r)
+    ctx = DeviceBatchContext(level=level, match_finder=match_finder, **ctx_kw)
+    try:
+        st = SeekableStream(ctx, _to_device(data))
+        try:
+            return call(st, _to_device(b"".join(raws)), table).cpu().numpy().tobytes()
+        finally:
+            st.close()
+    finally:
+        ctx.close()
+
+
+def edit(data, picks, records=None, level=3, match_finder="libzstd", **ctx_kw):
+    """a seekable stream (bytes) and a pick list -> a new seekable stream (bytes), what is kept not recompressed: picks is a sequence of (0, i) -- frame i of
+    `data`, its bytes and its table entry as they are -- and (1, j) -- records[j] (a list of bytes), compressed as in ``compress_records``. A frame or a record
+    may be picked any number of times; the table has checksums exactly when that of `data` has. Raises ZstdError."""
+    if records is None:
+        return _edited(data, [], level, match_finder, ctx_kw, lambda st, src, table: st.edit(picks))
+    return _edited(data, records, level, match_finder, ctx_kw, lambda st, src, table: st.edit(picks, src, table))
+
+
+def append_records(data, records, level=3, match_finder="libzstd", **ctx_kw):
+    """a seekable stream (bytes) with one more frame per record of `records` (a list of bytes) behind its own: ``edit`` with every frame kept. Raises ZstdError."""
+    return _edited(data, records, level, match_finder, ctx_kw, lambda st, src, table: st.append_records(src, table))
