@@ -21,7 +21,7 @@
 #include "zhip_cparams.hpp"
 #include "zhip_encode_plan.hpp"
 #include "zhip_decode_plan.hpp"
-#include "zhip_seekable.hpp"
+#include "zhip_seekable_calls.hpp"
 
 #define ZHIP_LDS_BYTES (160u * 1024u)      // per CU on gfx950
 static_assert(sizeof(ZpSeqQLDS) <= ZHIP_LDS_BYTES && sizeof(ZpHufKernelLDS) <= ZHIP_LDS_BYTES, "a workgroup's LDS must fit a CU");
@@ -2042,280 +2042,14 @@ extern "C" int zhip_decompress_batch(const zhip_dparams* params, const zhip_item
 // One large buffer as the batch the kernels are fast at: chunks of frameSize bytes -> zhip_compress_batch_device -> frames back to back + the seek table;
 // a range read is zhip_decompress_batch_device over the frames that cover it. Everything between the batch calls is the small kernels of zhip_seekable.hpp,
 // queued on the caller's stream: no call here waits on the host except where scratch grows, and zhip_seekable_open_device, which reads the table's shape.
-static uint32_t zsk_lane_grid(const zhip_ctx* c, uint64_t lanes)
-{
-    const uint64_t w = (lanes + 63) / 64, gm = (uint64_t)(c->numCU > 0 ? c->numCU : 1) * 8;
-    return (uint32_t)(w < 1 ? 1 : w < gm ? w : gm);
-}
-static int zsk_launch_scan(ZskScanArgs a, hipStream_t stream)
-{
-    const uint32_t grid = zsk_scan_shape(a.n, &a.span);
-    hipLaunchKernelGGL(zhip_seekable_scan_reduce_kernel, dim3(grid), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(zhip_seekable_scan_write_kernel, dim3(grid), dim3(64), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-static size_t zsk_up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-extern "C" uint64_t zhip_seekable_frame_count(uint64_t srcSize, uint32_t frameSize) { return zsk_frame_count(srcSize, frameSize); }
-extern "C" uint64_t zhip_seekable_bound(uint64_t srcSize, uint32_t frameSize, int flags)
-{
-    if (flags & ~ZHIP_SEEKABLE_CHECKSUM) return 0;
-    return zsk_bound(srcSize, frameSize, flags & ZHIP_SEEKABLE_CHECKSUM);
-}
-
-extern "C" int zhip_seekable_compress_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, uint32_t frameSize, int flags,
-                                             void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
-{
-    if (!c || !d_streamSize || !d_status || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) { g_lastError = "seekable compress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
-    if (!zsk_args_ok(srcSize, frameSize)) { g_lastError = "seekable compress: frameSize must be 1 ... 2^30 and the frame count at most 2^27"; return ZHIP_ERR_UNSUPPORTED; }
-    hipStream_t stream = (hipStream_t)streamv;
-    const size_t n = (size_t)zsk_frame_count(srcSize, frameSize);
-    // (growing either area frees the old one, which waits for the device: the wait the stream-order rules allow)
-    const size_t oSrcSegs = 0, oSlotSegs = oSrcSegs + zsk_up16(n * 16), oSizes = oSlotSegs + zsk_up16(n * 16), oOffs = oSizes + zsk_up16(n * 8),
-                 oPartSum = oOffs + zsk_up16((n + 1) * 8), oPartBad = oPartSum + ZSK_SCAN_GRID * 8, oGo = oPartBad + ZSK_SCAN_GRID * 8, oStatus = oGo + 16, metaBytes = oStatus + zsk_up16(n * 4);
-    if (c->skMeta.reserve(metaBytes)) return g_reserveRc;
-    if (n && c->skSlots.reserve((size_t)(n * zsk_slot_stride(frameSize)))) return g_reserveRc;
-    uint8_t* const m = (uint8_t*)c->skMeta.p;
-    ZskCompressArgs a; memset(&a, 0, sizeof a);
-    a.src = (const uint8_t*)d_src; a.srcSize = srcSize; a.frameSize = frameSize; a.n = (uint32_t)n; a.checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1u : 0u;
-    a.srcSegs = (uint64_t*)(m + oSrcSegs); a.slotSegs = (uint64_t*)(m + oSlotSegs); a.outSizes = (const uint64_t*)(m + oSizes); a.status = (int32_t*)(m + oStatus);
-    a.offs = (const uint64_t*)(m + oOffs); a.partBad = (const uint64_t*)(m + oPartBad);
-    a.dst = (uint8_t*)d_dst; a.dstCapacity = dstCapacity; a.streamSize = d_streamSize; a.outStatus = d_status; a.go = (uint32_t*)(m + oGo);
-    if (n) {
-        hipLaunchKernelGGL(zhip_seekable_chunk_segs_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, a);
-        HIP_TRY(hipGetLastError());
-        // the batch knows its largest source, as the host-buffer calls' batches do; the caller's own size hint is not touched
-        const size_t hintWas = c->srcMaxHint;
-        c->srcMaxHint = (size_t)(srcSize < frameSize ? srcSize : frameSize);
-        const int rc = zhip_compress_batch_device(c, d_src, (const zhip_segment*)a.srcSegs, n, c->skSlots.p, (const zhip_segment*)a.slotSegs, (uint64_t*)(m + oSizes), a.status, stream);
-        c->srcMaxHint = hintWas;
-        if (rc) return rc;
-    }
-    ZskScanArgs s; memset(&s, 0, sizeof s);
-    s.in = m + oSizes; s.status = a.status; s.mode = 0; s.n = (uint32_t)n; s.offs = (uint64_t*)(m + oOffs); s.partSum = (uint64_t*)(m + oPartSum); s.partBad = (uint64_t*)(m + oPartBad);
-    uint32_t span; a.nPart = zsk_scan_shape(s.n, &span);
-    if (int rc = zsk_launch_scan(s, stream)) return rc;
-    hipLaunchKernelGGL(zhip_seekable_verdict_kernel, dim3(1), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(zhip_seekable_table_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    if (n) {
-        const size_t gmax = (size_t)c->numCU * 16;
-        hipLaunchKernelGGL(zhip_compact_kernel, dim3((uint32_t)(n < gmax ? n : gmax)), dim3(64), 0, stream, (const uint8_t*)c->skSlots.p, (const zhip_segment*)a.slotSegs, a.outSizes,
-                           (const int32_t*)a.status, a.offs, (uint32_t)n, (uint8_t*)d_dst);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-extern "C" uint64_t zhip_seekable_records_bound(uint64_t maxContentBytes, uint64_t nRecords, int flags)
-{
-    if (flags & ~ZHIP_SEEKABLE_CHECKSUM) return 0;
-    return zsk_records_bound(maxContentBytes, nRecords, flags & ZHIP_SEEKABLE_CHECKSUM);
-}
-
-// where the records call keeps its arrays in the context's meta area; a caller with arrays of its own (the edit call) puts them behind metaBytes
-struct ZskRecordsLayout { size_t oSrcSegs, oSlotSegs, oSizes, oOffs, oLenOffs, oSlotOffs, oPartSum, oPartBad, oPreBad, oGo, oStatus, metaBytes; };
-static ZskRecordsLayout zsk_records_layout(size_t n)
-{
-    ZskRecordsLayout l;
-    l.oSrcSegs = 0; l.oSlotSegs = l.oSrcSegs + zsk_up16(n * 16); l.oSizes = l.oSlotSegs + zsk_up16(n * 16); l.oOffs = l.oSizes + zsk_up16(n * 8);
-    l.oLenOffs = l.oOffs + zsk_up16((n + 1) * 8); l.oSlotOffs = l.oLenOffs + zsk_up16((n + 1) * 8); l.oPartSum = l.oSlotOffs + zsk_up16((n + 1) * 8);
-    l.oPartBad = l.oPartSum + ZSK_SCAN_GRID * 8; l.oPreBad = l.oPartBad + ZSK_SCAN_GRID * 8; l.oGo = l.oPreBad + ZSK_SCAN_GRID * 8; l.oStatus = l.oGo + 16;
-    l.metaBytes = zsk_up16(l.oStatus + zsk_up16(n * 4));
-    return l;
-}
-// The front half of a call that compresses a caller's record table: the pre-check (two scans, a verdict), the segments, the batch into the context's slots.
-// Reserves the meta area (the layout's bytes and extraMeta behind them) and the slots, fills *r with everything but the caller's dst / streamSize / outStatus.
-static int zsk_records_front(zhip_ctx* c, const ZskRecordsLayout& l, size_t extraMeta, const void* d_src, uint64_t srcSize, const zhip_segment* d_records, size_t n,
-                             uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags, hipStream_t stream, ZskRecordsArgs* out)
-{
-    maxContentBytes = zsk_records_content_cap(maxContentBytes, n, maxRecordBytes);
-    // (growing either area frees the old one, which waits for the device: the wait the stream-order rules allow)
-    if (c->skMeta.reserve(l.metaBytes + extraMeta)) return g_reserveRc;
-    if (n && c->skSlots.reserve((size_t)zsk_records_slot_bytes(maxContentBytes, n))) return g_reserveRc;
-    uint8_t* const m = (uint8_t*)c->skMeta.p;
-    uint32_t* const words = (uint32_t*)(m + l.oGo);                        // go, pre, the pre-check's status pair
-    ZskRecordsArgs r; memset(&r, 0, sizeof r);
-    r.src = (const uint8_t*)d_src; r.srcSize = srcSize; r.records = (const uint64_t*)d_records; r.n = (uint32_t)n; r.checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1u : 0u;
-    r.maxContent = maxContentBytes; r.lenOffs = (const uint64_t*)(m + l.oLenOffs); r.slotOffs = (const uint64_t*)(m + l.oSlotOffs); r.partBad = (const uint64_t*)(m + l.oPreBad);
-    r.srcSegs = (uint64_t*)(m + l.oSrcSegs); r.slotSegs = (uint64_t*)(m + l.oSlotSegs); r.pre = words + 1; r.preStatus = (int32_t*)(words + 2);
-    r.outSizes = (const uint64_t*)(m + l.oSizes); r.status = (int32_t*)(m + l.oStatus); r.offs = (const uint64_t*)(m + l.oOffs); r.go = words;
-    ZskScanArgs s; memset(&s, 0, sizeof s);
-    s.in = (const uint8_t*)d_records + 8; s.stride = 16; s.mode = 3; s.n = (uint32_t)n; s.limit64 = maxRecordBytes; s.srcSize = srcSize;
-    s.offs = (uint64_t*)(m + l.oLenOffs); s.partSum = (uint64_t*)(m + l.oPartSum); s.partBad = (uint64_t*)(m + l.oPreBad);
-    uint32_t span; r.nPart = zsk_scan_shape(s.n, &span);
-    if (int rc = zsk_launch_scan(s, stream)) return rc;
-    s.mode = 4; s.offs = (uint64_t*)(m + l.oSlotOffs); s.partBad = (uint64_t*)(m + l.oPartBad);
-    if (int rc = zsk_launch_scan(s, stream)) return rc;
-    hipLaunchKernelGGL(zhip_seekable_records_verdict_kernel, dim3(1), dim3(64), 0, stream, r);
-    HIP_TRY(hipGetLastError());
-    if (n) {
-        hipLaunchKernelGGL(zhip_seekable_records_segs_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, r);
-        HIP_TRY(hipGetLastError());
-        // the batch's largest source is what the caller says it is; the caller's own size hint is not touched
-        const size_t hintWas = c->srcMaxHint;
-        c->srcMaxHint = (size_t)maxRecordBytes;
-        const int rc = zhip_compress_batch_device(c, d_src, (const zhip_segment*)r.srcSegs, n, c->skSlots.p, (const zhip_segment*)r.slotSegs, (uint64_t*)(m + l.oSizes), r.status, stream);
-        c->srcMaxHint = hintWas;
-        if (rc) return rc;
-    }
-    *out = r;
-    return 0;
-}
-
-// zhip_seekable_compress_device with the caller's record table in the place of the fixed cut: the front half above, then the fixed-size call's tail -- the
-// scan of the sizes, its verdict, the (records) table writer, the compaction
-extern "C" int zhip_seekable_compress_records_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, const zhip_segment* d_records, size_t nRecords,
-                                                     uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
-                                                     void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
-{
-    if (!c || !d_streamSize || !d_status || (nRecords && !d_records) || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) { g_lastError = "seekable compress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
-    if (nRecords > ZSK_MAX_FRAMES || maxRecordBytes > ZSK_MAX_CONTENT) { g_lastError = "seekable compress: at most 2^27 records of at most 2^30 bytes"; return ZHIP_ERR_UNSUPPORTED; }
-    hipStream_t stream = (hipStream_t)streamv;
-    const size_t n = nRecords;
-    const ZskRecordsLayout l = zsk_records_layout(n);
-    ZskRecordsArgs r;
-    if (int rc = zsk_records_front(c, l, 0, d_src, srcSize, d_records, n, maxContentBytes, maxRecordBytes, flags, stream, &r)) return rc;
-    uint8_t* const m = (uint8_t*)c->skMeta.p;
-    r.dst = (uint8_t*)d_dst; r.streamSize = d_streamSize; r.outStatus = d_status;
-    ZskCompressArgs a; memset(&a, 0, sizeof a);
-    a.n = (uint32_t)n; a.checksum = r.checksum; a.nPart = r.nPart; a.outSizes = r.outSizes; a.status = r.status; a.offs = r.offs; a.partBad = (const uint64_t*)(m + l.oPartBad);
-    a.dst = (uint8_t*)d_dst; a.dstCapacity = dstCapacity; a.streamSize = d_streamSize; a.outStatus = d_status; a.go = (uint32_t*)(m + l.oGo);
-    ZskScanArgs s; memset(&s, 0, sizeof s);
-    s.in = m + l.oSizes; s.status = r.status; s.mode = 0; s.n = (uint32_t)n; s.offs = (uint64_t*)(m + l.oOffs); s.partSum = (uint64_t*)(m + l.oPartSum); s.partBad = (uint64_t*)(m + l.oPartBad);
-    if (int rc = zsk_launch_scan(s, stream)) return rc;
-    hipLaunchKernelGGL(zhip_seekable_verdict_kernel, dim3(1), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(zhip_seekable_records_table_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, r);
-    HIP_TRY(hipGetLastError());
-    if (n) {
-        const size_t gmax = (size_t)c->numCU * 16;
-        hipLaunchKernelGGL(zhip_compact_kernel, dim3((uint32_t)(n < gmax ? n : gmax)), dim3(64), 0, stream, (const uint8_t*)c->skSlots.p, (const zhip_segment*)r.slotSegs, r.outSizes,
-                           (const int32_t*)r.status, r.offs, (uint32_t)n, (uint8_t*)d_dst);
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
-}
-
-struct zhip_seekable {
-    const uint8_t* stream = nullptr; uint64_t streamSize = 0;
-    ZskLayout lay = {0, 8, 0, 0};
-    uint64_t contentSize = 0; uint32_t maxFrameContent = 0;
-    DevBuf prefix;                       // the table's scans: compressed offsets, decompressed offsets, place among the frames with content -- [n + 1] each
+struct zhip_seekable : ZskOpened {
+    DevBuf prefix;                       // the table's scans (ZskOpened::pre points into it)
     DevBuf meta, edge;                   // a range call's segments / sizes / statuses, and where its partly covered frames are decoded
-    std::vector<uint64_t> dOff, place;   // the host's copies: which frames cover a range, and how many of them go to the decoder
-    std::vector<uint64_t> cOff;          // and where a frame's bytes lie: what an edit keeps of the stream (zhip_seekable_edit_bound)
     // the many-ranges call: its plan's tables on the device, its item arrays and per-range words, its scratch frames; the pinned slots the tables are
     // uploaded from (a slot is written again only after the event behind its upload has completed)
     DevBuf gTables, gMeta, gScratch;
-    uint64_t scratchLimit = 0;           // 0 = ZSK_SCRATCH_DEFAULT
-    typedef ZskPinSlot Slot;
-    std::vector<Slot> slots;
+    std::vector<ZskPinSlot> slots;
 };
-
-extern "C" void zhip_seekable_close(zhip_seekable* h)
-{
-    if (!h) return;
-    h->prefix.release(); h->meta.release(); h->edge.release();
-    h->gTables.release(); h->gMeta.release(); h->gScratch.release();      // (hipFree waits for the device: no upload from a slot is in flight behind it)
-    for (zhip_seekable::Slot& s : h->slots) { if (s.p) (void)hipHostFree(s.p); (void)hipEventDestroy(s.done); }
-    delete h;
-}
-
-extern "C" int zhip_seekable_open_device(zhip_ctx* c, const void* d_stream, uint64_t streamSize, void* streamv, zhip_seekable** out, zhip_seekable_info* info, zhip_error* err)
-{
-    if (err) memset(err, 0, sizeof *err);
-    if (out) *out = nullptr;
-    if (!c || !d_stream || !out) { g_lastError = "seekable open: bad arguments"; return set_err(err, ZHIP_ERR_UNSUPPORTED, 0, 0); }
-    hipStream_t stream = (hipStream_t)streamv;
-    const uint8_t* const base = (const uint8_t*)d_stream;
-    ZskLayout lay;
-    if (streamSize < ZSK_HEADER + ZSK_FOOTER) return set_err(err, ZHIP_ERR_ZSTD, 0, ZSK_ERR_CORRUPT);
-    uint8_t foot[ZSK_FOOTER], head[ZSK_HEADER];
-    if (hipMemcpyAsync(foot, base + streamSize - ZSK_FOOTER, ZSK_FOOTER, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { g_lastError = "seekable open: reading the footer failed"; return set_err(err, ZHIP_ERR_HIP, 0, 0); }
-    if (int e = zsk_parse_footer(foot, streamSize, &lay)) return set_err(err, ZHIP_ERR_ZSTD, 0, e);
-    if (hipMemcpyAsync(head, base + lay.tableOffset, ZSK_HEADER, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { g_lastError = "seekable open: reading the table's header failed"; return set_err(err, ZHIP_ERR_HIP, 0, 0); }
-    if (int e = zsk_check_header(head, &lay)) return set_err(err, ZHIP_ERR_ZSTD, 0, e);
-    // every entry now lies inside the stream; the kernels check what the entries SAY and build the offsets
-    zhip_seekable* h = new zhip_seekable();
-    auto fail = [&](int kind, int zerr) { zhip_seekable_close(h); return set_err(err, kind, 0, zerr); };
-    h->stream = base; h->streamSize = streamSize; h->lay = lay;
-    const size_t n = lay.n, col = zsk_up16((n + 1) * 8), part = ZSK_SCAN_GRID * 8;
-    if (h->prefix.reserve(3 * col) || h->meta.reserve(6 * part)) return fail(g_reserveRc, 0);
-    uint8_t* const pre = (uint8_t*)h->prefix.p; uint8_t* const pm = (uint8_t*)h->meta.p;
-    const uint8_t* const entries = base + lay.tableOffset + ZSK_HEADER;
-    for (int k = 0; k < 3; k++) {
-        ZskScanArgs s; memset(&s, 0, sizeof s);
-        s.in = entries + (k ? 4 : 0); s.stride = lay.entry; s.mode = k == 2 ? 2u : 1u; s.limit = k == 1 ? ZSK_MAX_CONTENT : 0xFFFFFFFFu; s.n = lay.n;
-        s.offs = (uint64_t*)(pre + k * col); s.partSum = (uint64_t*)(pm + 2 * k * part); s.partBad = (uint64_t*)(pm + (2 * k + 1) * part);
-        if (zsk_launch_scan(s, stream)) return fail(ZHIP_ERR_HIP, 0);
-    }
-    uint32_t span; const uint32_t grid = zsk_scan_shape(lay.n, &span);
-    std::vector<uint64_t> bad(grid);
-    uint64_t compressedTotal = 0;
-    h->cOff.resize(n + 1); h->dOff.resize(n + 1); h->place.resize(n + 1);
-    if (hipMemcpyAsync(h->cOff.data(), pre, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemcpyAsync(h->dOff.data(), pre + col, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemcpyAsync(h->place.data(), pre + 2 * col, (n + 1) * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipMemcpyAsync(bad.data(), pm + 3 * part, grid * 8, hipMemcpyDeviceToHost, stream) != hipSuccess || hipMemcpyAsync(&compressedTotal, pre + n * 8, 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-        hipStreamSynchronize(stream) != hipSuccess) { g_lastError = "seekable open: reading the table's scans failed"; return fail(ZHIP_ERR_HIP, 0); }
-    uint64_t lowestBad = ZSK_NONE;
-    for (uint64_t b : bad) if (b < lowestBad) lowestBad = b;
-    if (int e = zsk_table_verdict(lowestBad, compressedTotal, &lay)) { if (err) err->index = lowestBad != ZSK_NONE ? (size_t)lowestBad : 0; return fail(ZHIP_ERR_ZSTD, e) ; }
-    h->contentSize = h->dOff[n];
-    for (size_t i = 0; i < n; i++) { const uint64_t d = h->dOff[i + 1] - h->dOff[i]; if (d > h->maxFrameContent) h->maxFrameContent = (uint32_t)d; }
-    if (info) { info->streamSize = streamSize; info->contentSize = h->contentSize; info->nFrames = lay.n; info->maxFrameContent = h->maxFrameContent; info->checksumFlag = lay.checksum; }
-    *out = h;
-    return 0;
-}
-// what the readers tell the batch decode about their frames. Frames above one block: the several-block mode, for these launches only
-static ZdHints seekable_hints(const zhip_ctx* c, const zhip_seekable* h)
-{
-    ZdHints hint; hint.size = h->maxFrameContent > ZF_BLOCK_MAX ? (uint64_t)h->maxFrameContent : (uint64_t)c->itemHint;
-    return hint;
-}
-
-extern "C" int zhip_seekable_decompress_device(zhip_ctx* c, zhip_seekable* h, uint64_t offset, uint64_t length, void* d_dst, int32_t* d_status, void* streamv)
-{
-    if (!c || !h || !d_status) { g_lastError = "seekable decompress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
-    hipStream_t stream = (hipStream_t)streamv;
-    const uint64_t end = offset + length;
-    if (end < offset || end > h->contentSize) {
-        char buf[160]; snprintf(buf, sizeof buf, "seekable decompress: the range ends at %llu, the content at %llu", (unsigned long long)end, (unsigned long long)h->contentSize);
-        g_lastError = buf;
-        return ZHIP_ERR_SIZE_MISMATCH;
-    }
-    if (!length) { HIP_TRY(hipMemsetAsync(d_status, 0, 2 * sizeof(int32_t), stream)); return 0; }
-    if (!d_dst) { g_lastError = "seekable decompress: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
-    // the frames that hold the range's first and last byte (both hold content: upper_bound steps over frames of none)
-    const std::vector<uint64_t>& D = h->dOff;
-    const uint32_t f0 = (uint32_t)(std::upper_bound(D.begin(), D.end(), offset) - D.begin() - 1), f1 = (uint32_t)(std::upper_bound(D.begin(), D.end(), end - 1) - D.begin() - 1);
-    const size_t count = (size_t)(h->place[f1 + 1] - h->place[f0]);
-    const bool cut0 = D[f0] < offset || D[f0 + 1] > end, cut1 = f1 != f0 && D[f1 + 1] > end;
-    const size_t edgeBytes = (size_t)((cut0 ? D[f0 + 1] - D[f0] : 0) + (cut1 ? D[f1 + 1] - D[f1] : 0));
-    const size_t oSrcSegs = 0, oDstSegs = oSrcSegs + zsk_up16(count * 16), oSizes = oDstSegs + zsk_up16(count * 16), oFrameOf = oSizes + zsk_up16(count * 8), oStatus = oFrameOf + zsk_up16(count * 4),
-                 oWorst = oStatus + zsk_up16(count * 4), metaBytes = oWorst + 16;
-    if (h->meta.reserve(metaBytes)) return g_reserveRc;
-    if (edgeBytes && h->edge.reserve(edgeBytes)) return g_reserveRc;
-    uint8_t* const m = (uint8_t*)h->meta.p; uint8_t* const pre = (uint8_t*)h->prefix.p;
-    const size_t col = zsk_up16(((size_t)h->lay.n + 1) * 8);
-    ZskRangeArgs a; memset(&a, 0, sizeof a);
-    a.cOff = (const uint64_t*)pre; a.dOff = (const uint64_t*)(pre + col); a.place = (const uint64_t*)(pre + 2 * col);
-    a.table = h->stream + h->lay.tableOffset + ZSK_HEADER; a.entry = h->lay.entry; a.checksum = (uint32_t)h->lay.checksum;
-    a.f0 = f0; a.f1 = f1; a.count = (uint32_t)count; a.offset = offset; a.length = length;
-    a.dst = (uint8_t*)d_dst; a.edge = edgeBytes ? (uint8_t*)h->edge.p : a.dst; a.dstBase = a.edge < a.dst ? a.edge : a.dst;
-    a.srcSegs = (uint64_t*)(m + oSrcSegs); a.dstSegs = (uint64_t*)(m + oDstSegs); a.frameOf = (uint32_t*)(m + oFrameOf);
-    a.outSizes = (const uint64_t*)(m + oSizes); a.status = (int32_t*)(m + oStatus); a.worst = (uint32_t*)(m + oWorst); a.outStatus = d_status;
-    HIP_TRY(hipMemsetAsync(a.worst, 0, 4, stream));
-    hipLaunchKernelGGL(zhip_seekable_range_segs_kernel, dim3(zsk_lane_grid(c, (uint64_t)f1 - f0 + 1)), dim3(64), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    const int rc = decompress_batch(c, seekable_hints(c, h), h->stream, (const zhip_segment*)a.srcSegs, count, a.dstBase, (const zhip_segment*)a.dstSegs, (uint64_t*)(m + oSizes), a.status, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(zhip_seekable_range_verify_kernel, dim3(zsk_lane_grid(c, count)), dim3(64), 0, stream, a);
-    hipLaunchKernelGGL(zhip_seekable_range_finish_kernel, dim3(zsk_lane_grid(c, (uint64_t)edgeBytes / 16 + 1)), dim3(64), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-extern "C" void zhip_seekable_set_scratch_limit(zhip_seekable* h, uint64_t bytes) { if (h) h->scratchLimit = bytes; }
 
 // a pinned slot of at least `bytes` that no upload still reads: one whose event has completed (grown where too small), else a new one
 static int zsk_take_slot(std::vector<ZskPinSlot>& slots, size_t bytes, ZskPinSlot** out)
@@ -2339,85 +2073,137 @@ static int zsk_take_slot(std::vector<ZskPinSlot>& slots, size_t bytes, ZskPinSlo
     return 0;
 }
 
+// The backend the sequences of zhip_seekable_calls.hpp run over: the context's and the handle's areas, the kernels on the caller's stream
+struct ZskHipBackend {
+    zhip_ctx* c; zhip_seekable* h; hipStream_t stream;
+    int numCU; std::string& err;
+    ZskPinSlot* slot = nullptr;
+    ZskHipBackend(zhip_ctx* c_, zhip_seekable* h_, void* streamv) : c(c_), h(h_), stream((hipStream_t)streamv), numCU(c_ ? c_->numCU : 0), err(g_lastError) {}
+    int reserve(ZskArea area, size_t bytes, uint8_t** base)
+    {
+        if (area == ZSK_A_PIN) {
+            if (int rc = zsk_take_slot(h ? h->slots : c->skPins, bytes, &slot)) return rc;
+            *base = (uint8_t*)slot->p;
+            return 0;
+        }
+        if (area == ZSK_A_G_SCRATCH) {      // at exactly its bytes
+            DevBuf& s = h->gScratch;
+            if (bytes > s.cap) {
+                s.release();
+                const hipError_t e = hipMalloc(&s.p, bytes);
+                if (e != hipSuccess) { s.p = nullptr; (void)hipGetLastError(); g_lastError = "out of device memory"; return ZHIP_ERR_NO_MEMORY; }
+                s.cap = bytes;
+            }
+            *base = (uint8_t*)s.p;
+            return 0;
+        }
+        DevBuf& d = area == ZSK_A_SK_META ? c->skMeta : area == ZSK_A_SK_SLOTS ? c->skSlots : area == ZSK_A_PREFIX ? h->prefix : area == ZSK_A_META ? h->meta : area == ZSK_A_EDGE ? h->edge :
+                    area == ZSK_A_G_TABLES ? h->gTables : h->gMeta;
+        if (d.reserve(bytes)) return g_reserveRc;
+        *base = (uint8_t*)d.p;
+        return 0;
+    }
+    void launch(ZskKernel k, uint32_t grid, const void* args)
+    {
+#define ZSK_X(id, name, A) case ZSK_K_##id: hipLaunchKernelGGL(zhip_seekable_##name##_kernel, dim3(grid), dim3(64), 0, stream, *(const A*)args); break;
+        switch (k) { ZSK_KERNELS(ZSK_X) default: break; }
+#undef ZSK_X
+    }
+    int check() { HIP_TRY(hipGetLastError()); return 0; }
+    int compress(const uint8_t* src, const uint64_t* srcSegs, size_t n, uint8_t* slots, const uint64_t* slotSegs, uint64_t* outSizes, int32_t* status, size_t srcMax)
+    {
+        const size_t hintWas = c->srcMaxHint;
+        c->srcMaxHint = srcMax;
+        const int rc = zhip_compress_batch_device(c, src, (const zhip_segment*)srcSegs, n, slots, (const zhip_segment*)slotSegs, outSizes, status, stream);
+        c->srcMaxHint = hintWas;
+        return rc;
+    }
+    int decompress(const ZskOpened& o, const uint64_t* srcSegs, size_t n, uint8_t* dstBase, const uint64_t* dstSegs, uint64_t* outSizes, int32_t* status)
+    {
+        // what the readers tell the batch decode about their frames. Frames above one block: the several-block mode, for these launches only
+        ZdHints hint; hint.size = o.maxFrameContent > ZF_BLOCK_MAX ? (uint64_t)o.maxFrameContent : (uint64_t)c->itemHint;
+        return decompress_batch(c, hint, o.stream, (const zhip_segment*)srcSegs, n, dstBase, (const zhip_segment*)dstSegs, outSizes, status, stream);
+    }
+    void compact(uint32_t grid, const uint8_t* slots, const uint64_t* slotSegs, const uint64_t* sizes, const int32_t* status, const uint64_t* offs, uint32_t n, uint8_t* dst)
+    {
+        hipLaunchKernelGGL(zhip_compact_kernel, dim3(grid), dim3(64), 0, stream, slots, (const zhip_segment*)slotSegs, sizes, status, offs, n, dst);
+    }
+    int zero(void* p, size_t bytes) { HIP_TRY(hipMemsetAsync(p, 0, bytes, stream)); return 0; }
+    int copy(void* dst, const void* src, size_t bytes, ZskCopy kind)
+    {
+        HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind == ZSK_COPY_TO_HOST ? hipMemcpyDeviceToHost : kind == ZSK_COPY_FROM_PIN ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, stream));
+        if (kind == ZSK_COPY_FROM_PIN) HIP_TRY(hipEventRecord(slot->done, stream));
+        return 0;
+    }
+    int wait() { HIP_TRY(hipStreamSynchronize(stream)); return 0; }
+};
+
+extern "C" uint64_t zhip_seekable_frame_count(uint64_t srcSize, uint32_t frameSize) { return zsk_frame_count(srcSize, frameSize); }
+extern "C" uint64_t zhip_seekable_bound(uint64_t srcSize, uint32_t frameSize, int flags)
+{
+    if (flags & ~ZHIP_SEEKABLE_CHECKSUM) return 0;
+    return zsk_bound(srcSize, frameSize, flags & ZHIP_SEEKABLE_CHECKSUM);
+}
+
+extern "C" int zhip_seekable_compress_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, uint32_t frameSize, int flags,
+                                             void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+{
+    ZskHipBackend b(c, nullptr, streamv);
+    return zsk_compress(b, c != nullptr, d_src, srcSize, frameSize, flags, d_dst, dstCapacity, d_streamSize, d_status);
+}
+
+extern "C" uint64_t zhip_seekable_records_bound(uint64_t maxContentBytes, uint64_t nRecords, int flags)
+{
+    if (flags & ~ZHIP_SEEKABLE_CHECKSUM) return 0;
+    return zsk_records_bound(maxContentBytes, nRecords, flags & ZHIP_SEEKABLE_CHECKSUM);
+}
+
+extern "C" int zhip_seekable_compress_records_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, const zhip_segment* d_records, size_t nRecords,
+                                                     uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
+                                                     void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+{
+    ZskHipBackend b(c, nullptr, streamv);
+    return zsk_compress_records(b, c != nullptr, d_src, srcSize, d_records, nRecords, maxContentBytes, maxRecordBytes, flags, d_dst, dstCapacity, d_streamSize, d_status);
+}
+
+extern "C" void zhip_seekable_close(zhip_seekable* h)
+{
+    if (!h) return;
+    h->prefix.release(); h->meta.release(); h->edge.release();
+    h->gTables.release(); h->gMeta.release(); h->gScratch.release();      // (hipFree waits for the device: no upload from a slot is in flight behind it)
+    for (ZskPinSlot& s : h->slots) { if (s.p) (void)hipHostFree(s.p); (void)hipEventDestroy(s.done); }
+    delete h;
+}
+
+extern "C" int zhip_seekable_open_device(zhip_ctx* c, const void* d_stream, uint64_t streamSize, void* streamv, zhip_seekable** out, zhip_seekable_info* info, zhip_error* err)
+{
+    if (err) memset(err, 0, sizeof *err);
+    if (out) *out = nullptr;
+    if (!c || !d_stream || !out) { g_lastError = "seekable open: bad arguments"; return set_err(err, ZHIP_ERR_UNSUPPORTED, 0, 0); }
+    zhip_seekable* h = new zhip_seekable();
+    ZskHipBackend b(c, h, streamv);
+    int zerr = 0; size_t index = 0;
+    if (const int kind = zsk_open(b, d_stream, streamSize, h, &zerr, &index)) { zhip_seekable_close(h); return set_err(err, kind, index, zerr); }
+    if (info) { info->streamSize = streamSize; info->contentSize = h->contentSize; info->nFrames = h->lay.n; info->maxFrameContent = h->maxFrameContent; info->checksumFlag = h->lay.checksum; }
+    *out = h;
+    return 0;
+}
+
+extern "C" int zhip_seekable_decompress_device(zhip_ctx* c, zhip_seekable* h, uint64_t offset, uint64_t length, void* d_dst, int32_t* d_status, void* streamv)
+{
+    ZskHipBackend b(c, h, streamv);
+    return zsk_range(b, c != nullptr, h, offset, length, d_dst, d_status);
+}
+
+extern "C" void zhip_seekable_set_scratch_limit(zhip_seekable* h, uint64_t bytes) { if (h) h->scratchLimit = bytes; }
+
 extern "C" int zhip_seekable_decompress_ranges_device(zhip_ctx* c, zhip_seekable* h, const zhip_seekable_range* ranges, size_t nRanges, void* d_dst, uint64_t dstCapacity,
                                                       int32_t* d_status, zhip_seekable_gather_stats* stats, void* streamv)
 {
     static_assert(sizeof(zhip_seekable_range) == 24, "the plan reads the ranges as [R][3]");
-    if (!c || !h || !d_status || (nRanges && !ranges) || nRanges > ZSK_MAX_RANGES) { g_lastError = "seekable ranges: bad arguments (NULL, or more than 2^27 ranges)"; return ZHIP_ERR_UNSUPPORTED; }
-    hipStream_t stream = (hipStream_t)streamv;
-    const uint64_t* const rg = (const uint64_t*)ranges;
-    size_t bad = 0, other = 0;
-    if (const int why = zsk_gather_check(rg, nRanges, h->contentSize, dstCapacity, &bad, &other)) {
-        char buf[224];
-        if (why == 1) snprintf(buf, sizeof buf, "seekable ranges: range %zu ends at %llu + %llu, the content at %llu", bad, (unsigned long long)ranges[bad].offset, (unsigned long long)ranges[bad].length, (unsigned long long)h->contentSize);
-        else if (why == 2) snprintf(buf, sizeof buf, "seekable ranges: range %zu goes to %llu + %llu, the capacity is %llu", bad, (unsigned long long)ranges[bad].dstOffset, (unsigned long long)ranges[bad].length, (unsigned long long)dstCapacity);
-        else snprintf(buf, sizeof buf, "seekable ranges: the destinations of ranges %zu and %zu overlap", other, bad);
-        g_lastError = buf;
-        return why == 3 ? ZHIP_ERR_UNSUPPORTED : ZHIP_ERR_SIZE_MISMATCH;
-    }
-    bool any = false;
-    for (size_t r = 0; r < nRanges; r++) any = any || ranges[r].length;
-    if (any && !d_dst) { g_lastError = "seekable ranges: bad arguments (no destination)"; return ZHIP_ERR_UNSUPPORTED; }
-    if (stats) memset(stats, 0, sizeof *stats);
-    if (!any) { HIP_TRY(hipMemsetAsync(d_status, 0, (2 + 2 * nRanges) * sizeof(int32_t), stream)); return 0; }
-
-    ZskGatherPlan plan;
-    zsk_gather_plan(h->dOff.data(), h->place.data(), h->lay.n, rg, nRanges, h->scratchLimit, &plan);
-    if (stats) { stats->items = plan.items; stats->inPlace = plan.inPlace; stats->scratchBytes = plan.scratchBytes; stats->copyJobs = plan.jobs.size(); stats->passes = plan.passes.size(); }
-    const size_t R = nRanges, S = plan.segs.size(), J = plan.jobs.size(), count = (size_t)plan.items;
-    // the tables: ranges, segments, jobs (32 bytes an entry each)
-    const size_t oRanges = 0, oSegs = oRanges + R * sizeof(ZskGatherRange), oJobs = oSegs + S * sizeof(ZskGatherSeg), tableBytes = oJobs + J * sizeof(ZskGatherJob);
-    const size_t oSrcSegs = 0, oDstSegs = oSrcSegs + zsk_up16(count * 16), oSizes = oDstSegs + zsk_up16(count * 16), oFrameOf = oSizes + zsk_up16(count * 8), oStatus = oFrameOf + zsk_up16(count * 4),
-                 oWorst = oStatus + zsk_up16(count * 4), metaBytes = oWorst + zsk_up16(R * 4);
-    // (growing an area frees the old one, which waits for the device: the wait the stream-order rules allow. The scratch is allocated at exactly what the
-    // largest pass needs: it never exceeds max(limit, largest scratch frame))
-    if (h->gTables.reserve(tableBytes) || h->gMeta.reserve(metaBytes)) return g_reserveRc;
-    if (plan.scratchMax > h->gScratch.cap) {
-        h->gScratch.release();
-        const hipError_t e = hipMalloc(&h->gScratch.p, (size_t)plan.scratchMax);
-        if (e != hipSuccess) { h->gScratch.p = nullptr; (void)hipGetLastError(); g_lastError = "out of device memory"; return ZHIP_ERR_NO_MEMORY; }
-        h->gScratch.cap = (size_t)plan.scratchMax;
-    }
-    zhip_seekable::Slot* slot = nullptr;
-    if (int rc = zsk_take_slot(h->slots, tableBytes, &slot)) return rc;
-    uint8_t* const pin = (uint8_t*)slot->p;
-    memcpy(pin + oRanges, plan.ranges.data(), R * sizeof(ZskGatherRange));
-    if (S) memcpy(pin + oSegs, plan.segs.data(), S * sizeof(ZskGatherSeg));
-    if (J) memcpy(pin + oJobs, plan.jobs.data(), J * sizeof(ZskGatherJob));
-    uint8_t* const t = (uint8_t*)h->gTables.p; uint8_t* const m = (uint8_t*)h->gMeta.p; uint8_t* const pre = (uint8_t*)h->prefix.p;
-    HIP_TRY(hipMemcpyAsync(t, pin, tableBytes, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipEventRecord(slot->done, stream));
-    HIP_TRY(hipMemsetAsync(m + oWorst, 0, R * 4, stream));
-
-    const size_t col = zsk_up16(((size_t)h->lay.n + 1) * 8);
-    ZskGatherArgs a; memset(&a, 0, sizeof a);
-    a.cOff = (const uint64_t*)pre; a.dOff = (const uint64_t*)(pre + col); a.place = (const uint64_t*)(pre + 2 * col);
-    a.table = h->stream + h->lay.tableOffset + ZSK_HEADER; a.entry = h->lay.entry; a.checksum = (uint32_t)h->lay.checksum;
-    a.ranges = (const ZskGatherRange*)(t + oRanges); a.nRanges = (uint32_t)R;
-    a.dst = (uint8_t*)d_dst; a.scratch = plan.scratchMax ? (uint8_t*)h->gScratch.p : a.dst; a.dstBase = a.scratch < a.dst ? a.scratch : a.dst;
-    a.srcSegs = (uint64_t*)(m + oSrcSegs); a.dstSegs = (uint64_t*)(m + oDstSegs); a.frameOf = (uint32_t*)(m + oFrameOf);
-    a.outSizes = (const uint64_t*)(m + oSizes); a.status = (int32_t*)(m + oStatus); a.worst = (uint32_t*)(m + oWorst); a.outStatus = d_status;
-    const ZdHints hints = seekable_hints(c, h);
-    int rc = 0;
-    for (size_t p = 0; p < plan.passes.size() && !rc; p++) {
-        const ZskGatherPass& ps = plan.passes[p];
-        a.segs = (const ZskGatherSeg*)(t + oSegs) + ps.seg0; a.nSegs = ps.seg1 - ps.seg0; a.frames = ps.frames;
-        a.jobs = (const ZskGatherJob*)(t + oJobs) + ps.job0; a.nJobs = ps.job1 - ps.job0; a.tiles = ps.tiles;
-        a.item0 = ps.item0; a.count = ps.item1 - ps.item0; a.last = p + 1 == plan.passes.size() ? 1u : 0u;
-        hipLaunchKernelGGL(zhip_seekable_gather_segs_kernel, dim3(zsk_lane_grid(c, ps.frames)), dim3(64), 0, stream, a);
-        if (a.count) {
-            rc = decompress_batch(c, hints, h->stream, (const zhip_segment*)a.srcSegs + a.item0, a.count, a.dstBase, (const zhip_segment*)a.dstSegs + a.item0,
-                                              (uint64_t*)(m + oSizes) + a.item0, a.status + a.item0, stream);
-            if (rc) break;
-            hipLaunchKernelGGL(zhip_seekable_gather_verify_kernel, dim3(zsk_lane_grid(c, a.count)), dim3(64), 0, stream, a);
-        }
-        if (a.tiles || a.last) {
-            const uint64_t lanes = a.tiles * 64 > (a.last ? R : 0) ? a.tiles * 64 : R;
-            hipLaunchKernelGGL(zhip_seekable_gather_finish_kernel, dim3(zsk_lane_grid(c, lanes)), dim3(64), 0, stream, a);
-        }
-        if (hipGetLastError() != hipSuccess) { g_lastError = "seekable ranges: a launch failed"; rc = ZHIP_ERR_HIP; }
-    }
-    return rc;
+    ZskHipBackend b(c, h, streamv);
+    size_t bad = 0;
+    return zsk_ranges(b, c != nullptr, h, (const uint64_t*)ranges, nRanges, d_dst, dstCapacity, d_status, stats, &bad);
 }
 
 extern "C" int zhip_seekable_frame_offsets(const zhip_seekable* h, uint32_t first, uint32_t count, uint64_t* out)
@@ -2458,81 +2244,11 @@ extern "C" uint64_t zhip_seekable_edit_bound(const zhip_seekable* old, const zhi
     return zsk_edit_bound((const ZskEditPick*)picks, nPicks, old ? old->cOff.data() : nullptr, maxRecordBytes, checksum);
 }
 
-// The records call's front half (where there are records), then everything per PICK: sizes, the two scans, the verdict, the copy, the table.
 extern "C" int zhip_seekable_edit_device(zhip_ctx* c, zhip_seekable* old, const zhip_seekable_pick* picks, size_t nPicks,
                                          const void* d_src, uint64_t srcSize, const zhip_segment* d_records, size_t nRecords,
                                          uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
                                          void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
 {
-    if (!c || !d_dst || !d_streamSize || !d_status || (nPicks && !picks) || (nRecords && !d_records) || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) { g_lastError = "seekable edit: bad arguments"; return ZHIP_ERR_UNSUPPORTED; }
-    if (nPicks > ZSK_MAX_FRAMES) { g_lastError = "seekable edit: at most 2^27 picks"; return ZHIP_ERR_UNSUPPORTED; }
-    if (nRecords > ZSK_MAX_FRAMES || maxRecordBytes > ZSK_MAX_CONTENT) { g_lastError = "seekable edit: at most 2^27 records of at most 2^30 bytes"; return ZHIP_ERR_UNSUPPORTED; }
-    const uint32_t checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1u : 0u;
-    if (old && (uint32_t)old->lay.checksum != checksum) { g_lastError = "seekable edit: ZHIP_SEEKABLE_CHECKSUM must be set exactly when the opened stream's table has checksums"; return ZHIP_ERR_UNSUPPORTED; }
-    const ZskEditPick* const pk = (const ZskEditPick*)picks;
-    const uint32_t nOld = old ? old->lay.n : 0;
-    size_t bad = 0;
-    if (const int why = zsk_edit_check(pk, nPicks, old != nullptr, nOld, nRecords, &bad)) {
-        char buf[200];
-        if (why == 1) snprintf(buf, sizeof buf, "seekable edit: position %zu is %s", bad, pk[bad].from > ZSK_PICK_RECORD ? "neither a frame nor a record pick" : "a frame pick, and no stream is opened");
-        else snprintf(buf, sizeof buf, "seekable edit: position %zu names %s %u, there are %llu", bad, pk[bad].from == ZSK_PICK_FRAME ? "frame" : "record", pk[bad].index,
-                      (unsigned long long)(pk[bad].from == ZSK_PICK_FRAME ? (uint64_t)nOld : (uint64_t)nRecords));
-        g_lastError = buf;
-        return why == 1 ? ZHIP_ERR_UNSUPPORTED : ZHIP_ERR_SIZE_MISMATCH;
-    }
-    bool inPlace = false;
-    if (old) {
-        const uint8_t* const d0 = (const uint8_t*)d_dst; const uint8_t* const o0 = old->stream;
-        if (d0 < o0 + old->streamSize && o0 < d0 + dstCapacity) {
-            inPlace = d0 == o0 && zsk_edit_is_append(pk, nPicks, nOld);
-            if (!inPlace) { g_lastError = "seekable edit: the destination overlaps the opened stream (allowed only at its base, with picks that begin with every frame in order)"; return ZHIP_ERR_UNSUPPORTED; }
-        }
-    }
-    hipStream_t stream = (hipStream_t)streamv;
-    const size_t n = nPicks, entry = zsk_entry_size((int)checksum);
-    const ZskRecordsLayout l = zsk_records_layout(nRecords);
-    const size_t oPicks = nRecords ? l.metaBytes : 0, oPickSize = oPicks + zsk_up16(n * 8), oOffs = oPickSize + zsk_up16(n * 8), oTileOffs = oOffs + zsk_up16((n + 1) * 8),
-                 oPartSum = oTileOffs + zsk_up16((n + 1) * 8), oPartBad = oPartSum + ZSK_SCAN_GRID * 8, oTileBad = oPartBad + ZSK_SCAN_GRID * 8, oGo = oTileBad + ZSK_SCAN_GRID * 8,
-                 oPickStatus = oGo + 16, oStash = oPickStatus + zsk_up16(n * 4), end = oStash + (inPlace ? zsk_up16((size_t)nOld * entry) : 0);
-    ZskPinSlot* slot = nullptr;
-    if (n) if (int rc = zsk_take_slot(old ? old->slots : c->skPins, n * sizeof(ZskEditPick), &slot)) return rc;
-    ZskEditArgs e; memset(&e, 0, sizeof e);
-    if (nRecords) {
-        ZskRecordsArgs r;
-        if (int rc = zsk_records_front(c, l, end - l.metaBytes, d_src, srcSize, d_records, nRecords, maxContentBytes, maxRecordBytes, flags, stream, &r)) return rc;
-        e.src = r.src; e.records = r.records; e.slots = (const uint8_t*)c->skSlots.p; e.slotSegs = r.slotSegs; e.recSizes = r.outSizes; e.recStatus = r.status; e.pre = r.pre; e.preStatus = r.preStatus;
-    } else if (c->skMeta.reserve(end)) return g_reserveRc;      // (growing the area frees the old one, which waits for the device: the wait the stream-order rules allow)
-    uint8_t* const m = (uint8_t*)c->skMeta.p;
-    if (old) {
-        e.old = old->stream; e.cOff = (const uint64_t*)old->prefix.p; e.oldEntries = old->stream + old->lay.tableOffset + ZSK_HEADER;
-        if (inPlace && nOld) {      // the new frames overwrite the old table: its entries are kept aside first
-            HIP_TRY(hipMemcpyAsync(m + oStash, e.oldEntries, (size_t)nOld * entry, hipMemcpyDeviceToDevice, stream));
-            e.oldEntries = m + oStash;
-        }
-        if (inPlace) e.firstPick = nOld;
-    }
-    if (n) {
-        memcpy(slot->p, pk, n * sizeof(ZskEditPick));
-        HIP_TRY(hipMemcpyAsync(m + oPicks, slot->p, n * sizeof(ZskEditPick), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(slot->done, stream));
-    }
-    e.picks = (const ZskEditPick*)(m + oPicks); e.pickSize = (uint64_t*)(m + oPickSize); e.pickStatus = (int32_t*)(m + oPickStatus); e.tileOffs = (const uint64_t*)(m + oTileOffs);
-    ZskCompressArgs& a = e.v;
-    a.n = (uint32_t)n; a.checksum = checksum; a.status = e.pickStatus; a.outSizes = e.pickSize; a.offs = (const uint64_t*)(m + oOffs); a.partBad = (const uint64_t*)(m + oPartBad);
-    a.dst = (uint8_t*)d_dst; a.dstCapacity = dstCapacity; a.streamSize = d_streamSize; a.outStatus = d_status; a.go = (uint32_t*)(m + oGo);
-    uint32_t span; a.nPart = zsk_scan_shape(a.n, &span);
-    hipLaunchKernelGGL(zhip_seekable_edit_sizes_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, e);
-    HIP_TRY(hipGetLastError());
-    ZskScanArgs s; memset(&s, 0, sizeof s);
-    s.in = m + oPickSize; s.status = e.pickStatus; s.mode = 0; s.n = (uint32_t)n; s.offs = (uint64_t*)(m + oOffs); s.partSum = (uint64_t*)(m + oPartSum); s.partBad = (uint64_t*)(m + oPartBad);
-    if (int rc = zsk_launch_scan(s, stream)) return rc;
-    s.mode = 5; s.status = nullptr; s.offs = (uint64_t*)(m + oTileOffs); s.partBad = (uint64_t*)(m + oTileBad);
-    if (int rc = zsk_launch_scan(s, stream)) return rc;
-    hipLaunchKernelGGL(zhip_seekable_edit_verdict_kernel, dim3(1), dim3(64), 0, stream, e);
-    // the copy's grid is fixed (the host knows only bounds): the tiles of dstCapacity bytes and one more per pick cover every stream that fits
-    const uint64_t tilesMost = dstCapacity / ZSK_COPY_TILE + n + 1, gmax = (uint64_t)(c->numCU > 0 ? c->numCU : 1) * 32;
-    hipLaunchKernelGGL(zhip_seekable_edit_copy_kernel, dim3((uint32_t)(tilesMost < gmax ? tilesMost : gmax)), dim3(64), 0, stream, e);
-    hipLaunchKernelGGL(zhip_seekable_edit_table_kernel, dim3(zsk_lane_grid(c, n)), dim3(64), 0, stream, e);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    ZskHipBackend b(c, old, streamv);
+    return zsk_edit(b, c != nullptr, old, (const ZskEditPick*)picks, nPicks, d_src, srcSize, d_records, nRecords, maxContentBytes, maxRecordBytes, flags, d_dst, dstCapacity, d_streamSize, d_status);
 }

@@ -1,19 +1,13 @@
 // tests/emu/emu_seekable_edit.cpp -- the edit call (zhip_seekable_edit_device) on the host wave emulator: the library's own host checks (zsk_edit_check,
 // zsk_edit_is_append, zsk_edit_bound) and the bodies of its kernels -- pick sizes, the two scans, the verdict, the tiled copy, the table writer -- of
-// python-zstandard_amd/csrc/zhip_seekable.hpp, launched in the order the library launches them. The kernels do not look inside a frame, so any bytes serve as
-// frames; the records' front half is the test's: it says what the batch wrote (sizes, statuses, slots) and what the pre-check found.
+// python-zstandard_amd/csrc/zhip_seekable.hpp, under the library's own per-pick sequence (zsk_edit_picks of zhip_seekable_calls.hpp). The kernels do not look inside
+// a frame, so any bytes serve as frames; the records' front half is the test's: it says what the batch wrote (sizes, statuses, slots) and what the pre-check found.
 // Test infrastructure only (tests/test_emu_seekable_edit.py, built by tests/seekable_edit_cases.py). With -DZSK_EDIT_MAIN this is a stand-alone program that
 // runs the cases of a file (see main) -- the form the sanitizer build takes.
-#include "emu_seekable_records.cpp"     // open_stream, lane_grid, the scan's lanes
+#include "emu_seekable_records.cpp"     // open_stream, run_scan
 
-static void edit_sizes_lane(void* p) { zsk_edit_sizes_body(*(const ZskEditArgs*)p); }
-static void edit_verdict_lane(void* p) { zsk_edit_verdict_body(*(const ZskEditArgs*)p); }
-static void edit_copy_lane(void* p) { zsk_edit_copy_body(*(const ZskEditArgs*)p); }
-static void edit_table_lane(void* p) { zsk_edit_table_body(*(const ZskEditArgs*)p); }
-
-#define EMU_EDIT_COPY_GRID 24u          // fewer workgroups than most cases have tiles: the stride over the tiles is walked
-
-extern "C" void emu_edit_tiles(uint32_t* out) { out[0] = ZSK_COPY_TILE; out[1] = EMU_EDIT_COPY_GRID; }
+// the copy tile's bytes, and the copy's grid at its cap (the library's formula for the emulator's one CU)
+extern "C" void emu_edit_tiles(uint32_t* out) { out[0] = ZSK_COPY_TILE; out[1] = zsk_edit_copy_grid(1, ~0ull, 0); }
 
 // mode 5 of the scan alone: the copy tiles in front of every item
 extern "C" void emu_edit_tile_scan(const uint64_t* sizes, uint32_t n, uint64_t* offs)
@@ -37,7 +31,7 @@ extern "C" uint64_t emu_edit_bound(const uint8_t* old, uint64_t oldSize, const u
 // src and records [nRecords][2] for the table's lengths and checksums; slots / slotSegs [nRecords][2], recSizes, recStatus [nRecords]: what the batch wrote;
 // pre: -1 = no pre-check ran (no records), else its go word with preStatus[2]. dst holds dstCapacity bytes. poison: in place, the kept frames' bytes are set
 // to 0xC3 once the old entries are stashed -- they are neither read nor written from there on.
-// Returns 0, 6 (ZHIP_ERR_UNSUPPORTED) or 3 (ZHIP_ERR_SIZE_MISMATCH; info[7] = the position) where the host refuses -- nothing is written then --, or the
+// Returns 0, or the library's code (zsk_edit_call_check; info[7] = the position it names) where the host refuses -- nothing is written then --, or the
 // open's error code. outStatus[2]; offsOut / tileOffsOut (where given) [nPicks + 1]; info[0] = the stream size, info[1] = the go word, info[2] = 1: in place.
 extern "C" int emu_edit_run(const uint8_t* old, uint64_t oldSize, const uint32_t* picks, uint32_t nPicks, const uint8_t* src, const uint64_t* records, uint32_t nRecords,
                             const uint8_t* slots, const uint64_t* slotSegs, const uint64_t* recSizes, const int32_t* recStatus, int32_t pre, const int32_t* preStatus,
@@ -46,57 +40,26 @@ extern "C" int emu_edit_run(const uint8_t* old, uint64_t oldSize, const uint32_t
     memset(info, 0, 8 * sizeof(uint64_t));
     Opened o;
     if (old) if (int e = open_stream(old, oldSize, &o)) return e;
-    if (nPicks > ZSK_MAX_FRAMES || nRecords > ZSK_MAX_FRAMES) return 6;
-    if (old && (uint32_t)o.lay.checksum != checksum) return 6;
+    EmuBackend& b = o.b;
+    const ZskOpened* const opened = old ? &o : nullptr;
     const ZskEditPick* const pk = (const ZskEditPick*)picks;
-    const uint32_t nOld = old ? o.lay.n : 0;
-    size_t bad = 0;
-    if (const int why = zsk_edit_check(pk, nPicks, old != nullptr, nOld, nRecords, &bad)) { info[7] = bad; return why == 1 ? 6 : 3; }
-    bool inPlace = false;
-    if (old && dst < old + oldSize && old < dst + dstCapacity) {
-        inPlace = dst == old && zsk_edit_is_append(pk, nPicks, nOld);
-        if (!inPlace) return 6;
-    }
+    bool inPlace = false; size_t bad = 0;
+    if (const int rc = zsk_edit_call_check(true, opened, pk, nPicks, records, nRecords, 0, checksum ? ZHIP_SEEKABLE_CHECKSUM : 0, dst, dstCapacity, &inPlace, &bad, b.err)) { info[7] = bad; return rc; }
     info[2] = inPlace;
-    const uint32_t n = nPicks, entry = zsk_entry_size((int)checksum);
-    std::vector<ZskEditPick> dpicks(pk, pk + n);                            // (the upload)
-    std::vector<uint64_t> pickSize(n, 0xA5A5A5A5A5A5A5A5ull), offs((size_t)n + 1, 0xA5A5A5A5A5A5A5A5ull), tileOffs((size_t)n + 1, 0xA5A5A5A5A5A5A5A5ull);
-    std::vector<int32_t> pickStatus(n, -1);
-    std::vector<uint8_t> stash;
-    uint64_t streamSize = ~0ull; uint32_t go = 7, preWord = pre > 0 ? 1u : 0u;
-    ZskEditArgs e; memset(&e, 0, sizeof e);
+    const ZskEditLayout l = zsk_edit_layout(nPicks, nRecords, old ? o.lay.n : 0, inPlace, zsk_entry_size((int)checksum));
+    uint8_t* pin = nullptr; uint8_t* m = nullptr;
+    if (nPicks) b.reserve(ZSK_A_PIN, nPicks * sizeof(ZskEditPick), &pin);
+    b.reserve(ZSK_A_SK_META, l.end, &m);
+    uint64_t streamSize = ~0ull; uint32_t preWord = pre > 0 ? 1u : 0u;
+    ZskEditArgs e; memset(&e, 0, sizeof e);               // the records' results: the test's
     if (nRecords) { e.src = src; e.records = records; e.slots = slots; e.slotSegs = slotSegs; e.recSizes = recSizes; e.recStatus = recStatus; }
     if (pre >= 0) { e.pre = &preWord; e.preStatus = preStatus; }
-    if (old) {
-        e.old = old; e.cOff = o.cOff.data(); e.oldEntries = old + o.lay.tableOffset + ZSK_HEADER;
-        if (inPlace && nOld) {
-            stash.assign(e.oldEntries, e.oldEntries + (size_t)nOld * entry); e.oldEntries = stash.data();
-            if (poison) memset(dst, 0xC3, (size_t)o.lay.tableOffset);
-        }
-        if (inPlace) e.firstPick = nOld;
-    }
-    e.picks = dpicks.data(); e.pickSize = pickSize.data(); e.pickStatus = pickStatus.data(); e.tileOffs = tileOffs.data();
-    ZskCompressArgs& a = e.v;
-    a.n = n; a.checksum = checksum; a.status = pickStatus.data(); a.outSizes = pickSize.data(); a.offs = offs.data();
-    a.dst = dst; a.dstCapacity = dstCapacity; a.streamSize = &streamSize; a.outStatus = outStatus; a.go = &go;
-    ZskScanArgs s; memset(&s, 0, sizeof s);
-    s.in = (const uint8_t*)pickSize.data(); s.status = pickStatus.data(); s.mode = 0; s.n = n; s.offs = offs.data();
-    a.nPart = zsk_scan_shape(n, &s.span);
-    std::vector<uint64_t> sum(a.nPart), partBad(a.nPart), tileBad(a.nPart);
-    s.partSum = sum.data(); s.partBad = partBad.data(); a.partBad = partBad.data();
-    zhemu::run_grid(lane_grid(n), edit_sizes_lane, &e);
-    zhemu::run_grid(a.nPart, scan_reduce_lane, &s);
-    zhemu::run_grid(a.nPart, scan_write_lane, &s);
-    s.mode = 5; s.status = nullptr; s.offs = tileOffs.data(); s.partBad = tileBad.data();
-    zhemu::run_grid(a.nPart, scan_reduce_lane, &s);
-    zhemu::run_grid(a.nPart, scan_write_lane, &s);
-    zhemu::run_grid(1, edit_verdict_lane, &e);
-    const uint64_t tilesMost = dstCapacity / ZSK_COPY_TILE + n + 1;
-    zhemu::run_grid((uint32_t)(tilesMost < EMU_EDIT_COPY_GRID ? tilesMost : EMU_EDIT_COPY_GRID), edit_copy_lane, &e);
-    zhemu::run_grid(lane_grid(n), edit_table_lane, &e);
-    info[0] = streamSize; info[1] = go;
-    if (offsOut) memcpy(offsOut, offs.data(), ((size_t)n + 1) * 8);
-    if (tileOffsOut) memcpy(tileOffsOut, tileOffs.data(), ((size_t)n + 1) * 8);
+    if (inPlace && poison) { b.poisonAt = dst; b.poisonBytes = (size_t)o.lay.tableOffset; }
+    if (const int rc = zsk_edit_picks(b, opened, pk, nPicks, inPlace, checksum, l, m, pin, e, dst, dstCapacity, &streamSize, outStatus)) return rc;
+    if (b.traceOnly) return 0;
+    info[0] = streamSize; info[1] = *b.sawEdit.v.go;
+    if (offsOut) memcpy(offsOut, b.sawEdit.v.offs, ((size_t)nPicks + 1) * 8);
+    if (tileOffsOut) memcpy(tileOffsOut, b.sawEdit.tileOffs, ((size_t)nPicks + 1) * 8);
     return 0;
 }
 

@@ -2,14 +2,8 @@
 // (zsk_gather_check, zsk_gather_plan) and the bodies of its three kernels, launched pass by pass as the library launches them. Test infrastructure only
 // (tests/test_emu_seekable_ranges.py, built by tests/seekable_range_cases.py). The decoder is replaced by a copy from the content the test says the stream holds.
 // With -DZSK_RANGES_MAIN this is a stand-alone program that runs the cases of a file (see main) -- the form the sanitizer build takes.
-#include "emu_seekable.cpp"     // the open call's checks and scans (open_stream), lane_grid
+#include "emu_seekable.cpp"     // open_stream, the backend
 #include <stdio.h>
-
-static void gather_segs_lane(void* p) { zsk_gather_segs_body(*(const ZskGatherArgs*)p); }
-static void gather_verify_lane(void* p) { zsk_gather_verify_body(*(const ZskGatherArgs*)p); }
-static void gather_finish_lane(void* p) { zsk_gather_finish_body(*(const ZskGatherArgs*)p); }
-
-static int check_code(int why) { return why == 0 ? 0 : why == 3 ? 6 : 3; }       // ZHIP_ERR_UNSUPPORTED : ZHIP_ERR_SIZE_MISMATCH, as the library maps them
 
 static void put_stats(const ZskGatherPlan& plan, uint64_t* stats)
 {
@@ -17,7 +11,7 @@ static void put_stats(const ZskGatherPlan& plan, uint64_t* stats)
     stats[5] = plan.segs.size(); stats[6] = plan.scratchMax;
 }
 
-// the checks and the plan alone. rg = [R][3]. Returns 0, 3 / 6 (a rejected call; stats[7] = the range's index) or the open's error code.
+// the checks and the plan alone. rg = [R][3]. Returns 0, the library's code for a rejected call (stats[7] = the range's index) or the open's error code.
 // stats[8] = items, inPlace, scratchBytes, copyJobs, passes, segments, scratchMax, -; segsOut [segCap][6] = first, frames, item, home, inPlace, pass;
 // jobsOut [jobCap][4] = pass, src, dst, bytes; passOut [passCap][4] = scratch, item0, item1, tiles; rangeOut [R][2] = f0, f1
 extern "C" int emu_gather_plan(const uint8_t* stream, uint64_t size, const uint64_t* rg, uint64_t R, uint64_t dstCapacity, uint64_t limit, uint64_t* stats,
@@ -25,9 +19,9 @@ extern "C" int emu_gather_plan(const uint8_t* stream, uint64_t size, const uint6
 {
     Opened o;
     if (int e = open_stream(stream, size, &o)) return e;
-    size_t bad = 0, other = 0;
+    size_t bad = 0; bool any = false;
     memset(stats, 0, 8 * sizeof(uint64_t));
-    if (const int why = zsk_gather_check(rg, (size_t)R, o.dOff[o.lay.n], dstCapacity, &bad, &other)) { stats[7] = bad; return check_code(why); }
+    if (const int rc = zsk_ranges_check(true, rg, (size_t)R, o.contentSize, stream, dstCapacity, &bad, &any, o.b.err)) { stats[7] = bad; return rc; }
     ZskGatherPlan plan;
     zsk_gather_plan(o.dOff.data(), o.place.data(), o.lay.n, rg, (size_t)R, limit, &plan);
     put_stats(plan, stats);
@@ -46,65 +40,24 @@ extern "C" int emu_gather_plan(const uint8_t* stream, uint64_t size, const uint6
 }
 
 // The whole call. Frame f "decodes" to content[dOff[f], dOff[f + 1]), except frame shortFrame (-1: none), which comes out one byte short, and frame codeFrame
-// (-1: none), for which the decoder reports `code` and writes nothing. dst has dstCapacity bytes. Returns 0, 3 / 6 (rejected: nothing written), the open's
-// error code, or a negative number where a segment or a table lies outside its buffer. outStatus [2 + 2R]; stats as emu_gather_plan;
-// itemsOut (where given) [itemCap][5] = frame, 0 (d_dst) / 1 (scratch), offset there, length, pass.
+// (-1: none), for which the decoder reports `code` and writes nothing. dst has dstCapacity bytes. Returns 0, the library's code (rejected: nothing written), the
+// open's error code, or a negative number where a segment lies outside its buffer. outStatus [2 + 2R]; stats as emu_gather_plan, from what the library's call
+// reports and what the backend was asked to reserve; itemsOut (where given) [itemCap][5] = frame, 0 (d_dst) / 1 (scratch), offset there, length, pass.
 extern "C" int emu_gather_run(const uint8_t* stream, uint64_t size, const uint8_t* content, const uint64_t* rg, uint64_t R, uint8_t* dst, uint64_t dstCapacity, uint64_t limit,
                               int64_t shortFrame, int64_t codeFrame, int32_t code, int32_t* outStatus, uint64_t* stats, uint64_t* itemsOut, uint64_t itemCap)
 {
     Opened o;
     if (int e = open_stream(stream, size, &o)) return e;
-    const std::vector<uint64_t>& D = o.dOff;
-    size_t bad = 0, other = 0;
     memset(stats, 0, 8 * sizeof(uint64_t));
-    if (const int why = zsk_gather_check(rg, (size_t)R, D[o.lay.n], dstCapacity, &bad, &other)) { stats[7] = bad; return check_code(why); }
-    bool any = false;
-    for (size_t r = 0; r < (size_t)R; r++) any = any || rg[3 * r + 1];
-    if (!any) { memset(outStatus, 0, (2 + 2 * (size_t)R) * sizeof(int32_t)); return 0; }
-    ZskGatherPlan plan;
-    zsk_gather_plan(D.data(), o.place.data(), o.lay.n, rg, (size_t)R, limit, &plan);
-    put_stats(plan, stats);
-    const size_t count = (size_t)plan.items;
-    if (itemsOut && count > itemCap) return -3;
-    // the "device" copies of the tables: exactly as long as the plan's, so that a read beyond one is a read beyond an allocation
-    std::vector<ZskGatherRange> dRanges(plan.ranges); std::vector<ZskGatherSeg> dSegs(plan.segs); std::vector<ZskGatherJob> dJobs(plan.jobs);
-    std::vector<uint8_t> scratch((size_t)plan.scratchMax + 1, 0xEE);
-    std::vector<uint64_t> srcSegs(2 * count, ~0ull), dstSegs(2 * count, ~0ull), outSizes(count, 0);
-    std::vector<uint32_t> frameOf(count, ~0u), worst((size_t)R, 0); std::vector<int32_t> status(count, -1);
-    ZskGatherArgs a; memset(&a, 0, sizeof a);
-    a.cOff = o.cOff.data(); a.dOff = o.dOff.data(); a.place = o.place.data();
-    a.table = stream + o.lay.tableOffset + ZSK_HEADER; a.entry = o.lay.entry; a.checksum = (uint32_t)o.lay.checksum;
-    a.ranges = dRanges.data(); a.nRanges = (uint32_t)R;
-    a.dst = dst; a.scratch = plan.scratchMax ? scratch.data() : dst; a.dstBase = a.scratch < a.dst ? a.scratch : a.dst;
-    a.srcSegs = srcSegs.data(); a.dstSegs = dstSegs.data(); a.frameOf = frameOf.data(); a.outSizes = outSizes.data(); a.status = status.data();
-    a.worst = worst.data(); a.outStatus = outStatus;
-    for (size_t p = 0; p < plan.passes.size(); p++) {
-        const ZskGatherPass& ps = plan.passes[p];
-        a.segs = dSegs.data() + ps.seg0; a.nSegs = ps.seg1 - ps.seg0; a.frames = ps.frames;
-        a.jobs = dJobs.data() + ps.job0; a.nJobs = ps.job1 - ps.job0; a.tiles = ps.tiles;
-        a.item0 = ps.item0; a.count = ps.item1 - ps.item0; a.last = p + 1 == plan.passes.size() ? 1u : 0u;
-        if (ps.scratch > plan.scratchMax) return -4;
-        zhemu::run_grid(lane_grid(ps.frames), gather_segs_lane, &a);
-        for (size_t k = ps.item0; k < ps.item1; k++) {                     // the stand-in for the decoder
-            const uint32_t f = frameOf[k];
-            if (f >= o.lay.n || dstSegs[2 * k + 1] != D[f + 1] - D[f] || !dstSegs[2 * k + 1]) return -1;
-            uint8_t* const home = a.dstBase + dstSegs[2 * k];
-            const uint64_t len = dstSegs[2 * k + 1];
-            const bool inDst = dstCapacity && home >= dst && home + len <= dst + dstCapacity, inScratch = ps.scratch && home >= scratch.data() && home + len <= scratch.data() + ps.scratch;
-            if (!(inDst || inScratch) || srcSegs[2 * k] != o.cOff[f] || srcSegs[2 * k + 1] != o.cOff[f + 1] - o.cOff[f]) return -1;      // a segment outside its buffer
-            if (k > ps.item0 && frameOf[k - 1] >= f) return -5;            // items ascend with frames
-            if ((int64_t)f == codeFrame) { status[k] = code; outSizes[k] = 0; }
-            else {
-                const uint64_t out = len - ((int64_t)f == shortFrame ? 1 : 0);
-                memcpy(home, content + D[f], out);
-                outSizes[k] = out; status[k] = 0;
-            }
-            if (itemsOut) { uint64_t* q = itemsOut + 5 * k; q[0] = f; q[1] = inDst ? 0 : 1; q[2] = inDst ? (uint64_t)(home - dst) : (uint64_t)(home - scratch.data()); q[3] = len; q[4] = p; }
-        }
-        if (a.count) zhemu::run_grid(lane_grid(a.count), gather_verify_lane, &a);
-        if (a.tiles || a.last) zhemu::run_grid(lane_grid(a.tiles * 64 > (a.last ? R : 0) ? a.tiles * 64 : R), gather_finish_lane, &a);
-    }
-    return scratch[(size_t)plan.scratchMax] == 0xEE ? 0 : -2;
+    o.scratchLimit = limit;
+    EmuBackend& b = o.b; b.content = content; b.shortFrame = shortFrame; b.codeFrame = codeFrame; b.code = code; b.dst = dst; b.dstBytes = dstCapacity; b.itemsOut = itemsOut; b.itemCap = itemCap;
+    zhip_seekable_gather_stats g; memset(&g, 0, sizeof g);
+    size_t bad = 0;
+    const int rc = zsk_ranges(b, true, &o, rg, (size_t)R, dst, dstCapacity, outStatus, &g, &bad);
+    if (rc > 0) stats[7] = bad;
+    stats[0] = g.items; stats[1] = g.inPlace; stats[2] = g.scratchBytes; stats[3] = g.copyJobs; stats[4] = g.passes;
+    if (g.passes) { stats[5] = b.areas[ZSK_A_G_TABLES].bytes / 32 - R - g.copyJobs; stats[6] = b.areas[ZSK_A_G_SCRATCH].bytes; }
+    return rc;
 }
 
 #ifdef ZSK_RANGES_MAIN

@@ -1,14 +1,10 @@
 // tests/emu/emu_seekable_records.cpp -- one frame per record (zhip_seekable_compress_records_device) and reads by frame index (zhip_seekable_frame_offsets,
 // zhip_seekable_decompress_frames_device) on the host wave emulator: the two record modes of the scan, the pre-check's verdict, the segment writer and the table
-// writer of python-zstandard_amd/csrc/zhip_seekable.hpp, launched in the order and the grids the library launches them in, with the batch call and the
-// compaction replaced by stand-ins that refuse a segment outside its buffer; the index -> range mapping through the library's own plan and gather kernels.
+// writer of python-zstandard_amd/csrc/zhip_seekable.hpp under the library's own sequence (zsk_compress_records of zhip_seekable_calls.hpp), with the batch call
+// and the compaction replaced by the backend's stand-ins that refuse a segment outside its buffer; the index -> range mapping through the library's own plan.
 // Test infrastructure only (tests/test_emu_seekable_records.py, built by tests/seekable_record_cases.py). With -DZSK_RECORDS_MAIN this is a stand-alone
 // program that runs the cases of a file (see main) -- the form the sanitizer build takes.
-#include "emu_seekable_ranges.cpp"     // open_stream, run_scan, lane_grid, emu_gather_run
-
-static void records_verdict_lane(void* p) { zsk_records_verdict_body(*(const ZskRecordsArgs*)p); }
-static void records_segs_lane(void* p) { zsk_records_segs_body(*(const ZskRecordsArgs*)p); }
-static void records_table_lane(void* p) { zsk_records_table_body(*(const ZskRecordsArgs*)p); }
+#include "emu_seekable_ranges.cpp"     // open_stream, run_scan, emu_gather_run
 
 // one of the two record modes of the scan (3: lengths with the per-record checks, 4: slot strides); records = [n][2] (offset, length). Returns the lowest bad record
 extern "C" uint64_t emu_records_scan(const uint64_t* records, uint32_t n, uint32_t mode, uint64_t limit64, uint64_t srcSize, uint64_t* offs)
@@ -28,68 +24,28 @@ extern "C" uint64_t emu_records_compress(const uint8_t* src, uint64_t srcSize, c
                                          int32_t* outStatus, uint64_t* info)
 {
     memset(info, 0, 4 * sizeof(uint64_t));
-    if (n > ZSK_MAX_FRAMES || maxRecord > ZSK_MAX_CONTENT) return ~0ull;
-    maxContent = zsk_records_content_cap(maxContent, n, maxRecord);
-    const uint64_t slotBytes = n ? zsk_records_slot_bytes(maxContent, n) : 0;
-    info[0] = slotBytes;
-    std::vector<uint8_t> slots((size_t)slotBytes);
-    std::vector<uint64_t> lenOffs((size_t)n + 1, 0xA5A5A5A5A5A5A5A5ull), slotOffs((size_t)n + 1, 0xA5A5A5A5A5A5A5A5ull), offs((size_t)n + 1, 0xA5A5A5A5A5A5A5A5ull), outSizes(n, 0);
-    std::vector<int32_t> status(n, -1);
-    uint64_t streamSize = ~0ull; uint32_t go = 7, pre = 7; int32_t preStatus[2] = {-1, -1};
-    ZskRecordsArgs r; memset(&r, 0, sizeof r);
-    r.src = src; r.srcSize = srcSize; r.records = records; r.n = n; r.checksum = checksum; r.maxContent = maxContent;
-    r.lenOffs = lenOffs.data(); r.slotOffs = slotOffs.data(); r.srcSegs = srcSegs; r.slotSegs = slotSegs; r.pre = &pre; r.preStatus = preStatus;
-    r.outSizes = outSizes.data(); r.status = status.data(); r.offs = offs.data(); r.go = &go; r.dst = dst; r.streamSize = &streamSize; r.outStatus = outStatus;
-    ZskScanArgs s; memset(&s, 0, sizeof s);
-    s.in = (const uint8_t*)records + 8; s.stride = 16; s.mode = 3; s.n = n; s.limit64 = maxRecord; s.srcSize = srcSize; s.offs = lenOffs.data();
-    r.nPart = zsk_scan_shape(n, &s.span);
-    std::vector<uint64_t> sum(r.nPart), preBad(r.nPart), bad(r.nPart);
-    s.partSum = sum.data(); s.partBad = preBad.data(); r.partBad = preBad.data();
-    zhemu::run_grid(r.nPart, scan_reduce_lane, &s);
-    zhemu::run_grid(r.nPart, scan_write_lane, &s);
-    s.mode = 4; s.offs = slotOffs.data(); s.partBad = bad.data();
-    zhemu::run_grid(r.nPart, scan_reduce_lane, &s);
-    zhemu::run_grid(r.nPart, scan_write_lane, &s);
-    zhemu::run_grid(1, records_verdict_lane, &r);
-    info[1] = pre;
-    if (n) zhemu::run_grid(lane_grid(n), records_segs_lane, &r);
-    for (uint32_t i = 0; i < n; i++) {                                      // the stand-in for zhip_compress_batch_device
-        const uint64_t so = srcSegs[2 * i], sl = srcSegs[2 * i + 1], to = slotSegs[2 * i], tl = slotSegs[2 * i + 1];
-        if (so + sl < so || so + sl > srcSize || to + tl < to || to + tl > slotBytes || tl < zsk_compress_bound(sl)) { if (!info[2]) info[2] = 1 + i; status[i] = 64; continue; }
-        status[i] = givenStatus[i]; outSizes[i] = givenSizes[i];
-        if (!status[i] && outSizes[i] > tl) status[i] = ZSK_ERR_DSTSIZE;       // (no frame is larger than its slot)
-        if (!status[i]) for (uint64_t j = 0; j < outSizes[i]; j++) slots[(size_t)(to + j)] = (uint8_t)(31 * i + j);
-    }
-    ZskCompressArgs a; memset(&a, 0, sizeof a);
-    a.n = n; a.checksum = checksum; a.nPart = r.nPart; a.outSizes = outSizes.data(); a.status = status.data(); a.offs = offs.data(); a.partBad = bad.data();
-    a.dst = dst; a.dstCapacity = dstCapacity; a.streamSize = &streamSize; a.outStatus = outStatus; a.go = &go;
-    memset(&s, 0, sizeof s);
-    s.in = (const uint8_t*)outSizes.data(); s.status = status.data(); s.mode = 0; s.n = n; s.offs = offs.data(); s.partSum = sum.data(); s.partBad = bad.data();
-    zsk_scan_shape(n, &s.span);
-    zhemu::run_grid(r.nPart, scan_reduce_lane, &s);
-    zhemu::run_grid(r.nPart, scan_write_lane, &s);
-    zhemu::run_grid(1, verdict_lane, &a);
-    zhemu::run_grid(lane_grid(n), records_table_lane, &r);
-    for (uint32_t i = 0; i < n; i++) {                                      // the stand-in for zhip_compact_kernel
-        if (status[i]) continue;
-        info[3]++;
-        memcpy(dst + offs[i], slots.data() + slotSegs[2 * i], (size_t)outSizes[i]);
-    }
+    EmuBackend b; b.givenSizes = givenSizes; b.givenStatus = givenStatus; b.srcSize = srcSize;
+    uint64_t streamSize = ~0ull;
+    if (zsk_compress_records(b, true, src, srcSize, (const zhip_segment*)records, n, maxContent, maxRecord, checksum ? ZHIP_SEEKABLE_CHECKSUM : 0, dst, dstCapacity, &streamSize, outStatus)) return ~0ull;
+    info[0] = b.areas[ZSK_A_SK_SLOTS].bytes; info[2] = b.refused; info[3] = b.copied;
+    if (b.traceOnly) return streamSize;
+    info[1] = *b.sawRecords.pre;
+    if (n) { memcpy(srcSegs, b.sawRecords.srcSegs, (size_t)n * 16); memcpy(slotSegs, b.sawRecords.slotSegs, (size_t)n * 16); }
     return streamSize;
 }
 
 extern "C" uint64_t emu_records_bound(uint64_t maxContent, uint64_t n, int checksum) { return zsk_records_bound(maxContent, n, checksum); }
 
-// zhip_seekable_frame_offsets on a stream in host memory: 0, 3 (ZHIP_ERR_SIZE_MISMATCH) or the open's error code
+// zhip_seekable_frame_offsets on a stream in host memory: 0, ZHIP_ERR_SIZE_MISMATCH or the open's error code
 extern "C" int emu_frame_offsets(const uint8_t* stream, uint64_t size, uint32_t first, uint32_t count, uint64_t* out)
 {
     Opened o;
     if (int e = open_stream(stream, size, &o)) return e;
-    return zsk_frame_offsets(o.dOff.data(), o.lay.n, first, count, out) ? 0 : 3;
+    return zsk_frame_offsets(o.dOff.data(), o.lay.n, first, count, out) ? 0 : ZHIP_ERR_SIZE_MISMATCH;
 }
 
 // zhip_seekable_decompress_frames_device with the decoder replaced by a copy (emu_gather_run): the indices become ranges -- rgOut (where given) [nFrames][3] --
-// and the many-ranges path runs them. Returns what emu_gather_run returns, or 3 with stats[7] = the position of an index that is no frame of the table
+// and the many-ranges path runs them. Returns what emu_gather_run returns, or ZHIP_ERR_SIZE_MISMATCH with stats[7] = the position of an index that is no frame of the table
 extern "C" int emu_frames_run(const uint8_t* stream, uint64_t size, const uint8_t* content, const uint32_t* frames, uint64_t nFrames, const uint64_t* dstOffsets, uint8_t* dst,
                               uint64_t dstCapacity, uint64_t limit, int32_t* outStatus, uint64_t* stats, uint64_t* rgOut, uint64_t* itemsOut, uint64_t itemCap)
 {
@@ -98,7 +54,7 @@ extern "C" int emu_frames_run(const uint8_t* stream, uint64_t size, const uint8_
     memset(stats, 0, 8 * sizeof(uint64_t));
     std::vector<uint64_t> rg(3 * (size_t)nFrames + 3);
     const size_t bad = zsk_frames_to_ranges(o.dOff.data(), o.lay.n, frames, (size_t)nFrames, dstOffsets, rg.data());
-    if (bad != nFrames) { stats[7] = bad; return 3; }
+    if (bad != nFrames) { stats[7] = bad; return ZHIP_ERR_SIZE_MISMATCH; }
     if (rgOut) memcpy(rgOut, rg.data(), 3 * (size_t)nFrames * 8);
     return emu_gather_run(stream, size, content, rg.data(), nFrames, dst, dstCapacity, limit, -1, -1, 0, outStatus, stats, itemsOut, itemCap);
 }

@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 SKIP_MAGIC, SEEK_MAGIC = 0x184D2A5E, 0x8F92EAB1
 MAX_FRAMES, MAX_CONTENT = 1 << 27, 1 << 30
+UNSUPPORTED, SIZE_MISMATCH = 6, 3            # ZHIP_ERR_UNSUPPORTED, ZHIP_ERR_SIZE_MISMATCH (include/zstd_hip.h): what a refused call returns, emulated or not
 
 # (srcSize, frameSize) of the streams the GPU suite writes
 CASES = [(0, 4096), (1, 4096), (4095, 4096), (4096, 4096), (4097, 4096), (5 * 4096 + 17, 4096), (5, 1), (3 * 131072 + 1, 131072), (2 * 131072 + 20000, 131072)]

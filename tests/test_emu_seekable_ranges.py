@@ -200,15 +200,15 @@ def test_rejected_calls(lib):
     rc, status, dst, _, _ = rc_.run(lib, stream, content, good, cap)
     assert rc == 0 and status == [0] * 8
     for bad, want, index in [
-            (good + [(total, 1, 400)], 3, 3),                               # beyond the content
-            (good + [(1 << 63, 1 << 63, 400)], 3, 3),                       # offset + length wraps
-            ([(0, 0, 0), (0, total + 1, 0)], 3, 1),
-            (good[:2] + [(total - 1, 2, 299)], 3, 2),
-            ([(0, 100, 0), (0, 100, cap - 99)], 3, 1),                      # the destination ends beyond the capacity
-            ([(0, 100, (1 << 64) - 50)], 3, 0),                             # dstOffset + length wraps
-            ([(0, 100, 0), (200, 50, 150), (4000, 100, 99)], 6, 2),         # destinations overlap by one byte
-            ([(0, 100, 20), (0, 100, 20)], 6, 1),
-            ([(0, 100, 0), (0, 10, 50)], 6, 1)]:                            # one inside the other
+            (good + [(total, 1, 400)], sc.SIZE_MISMATCH, 3),                               # beyond the content
+            (good + [(1 << 63, 1 << 63, 400)], sc.SIZE_MISMATCH, 3),                       # offset + length wraps
+            ([(0, 0, 0), (0, total + 1, 0)], sc.SIZE_MISMATCH, 1),
+            (good[:2] + [(total - 1, 2, 299)], sc.SIZE_MISMATCH, 2),
+            ([(0, 100, 0), (0, 100, cap - 99)], sc.SIZE_MISMATCH, 1),                      # the destination ends beyond the capacity
+            ([(0, 100, (1 << 64) - 50)], sc.SIZE_MISMATCH, 0),                             # dstOffset + length wraps
+            ([(0, 100, 0), (200, 50, 150), (4000, 100, 99)], sc.UNSUPPORTED, 2),         # destinations overlap by one byte
+            ([(0, 100, 20), (0, 100, 20)], sc.UNSUPPORTED, 1),
+            ([(0, 100, 0), (0, 10, 50)], sc.UNSUPPORTED, 1)]:                            # one inside the other
         rc, status, dst, stats, _ = rc_.run(lib, stream, content, bad, cap)
         assert rc == want and stats[7] == index, bad
         assert (dst == rc_.GUARD_BYTE).all() and status == [-1] * (2 + 2 * len(bad)), "a rejected call writes nothing"

@@ -217,7 +217,7 @@ def test_frame_offsets(lib, n):
         assert rc == 0 and got == d[first:first + count + 1], (first, count)
     for first, count in [(0, n + 1), (n + 1, 0), (n, 1), (1, n), ((1 << 32) - 1, 2)]:
         if first + count > n:
-            assert rec.frame_offsets(lib, stream, first, count)[0] == 3, (first, count)
+            assert rec.frame_offsets(lib, stream, first, count)[0] == sc.SIZE_MISMATCH, (first, count)
 
 
 @pytest.mark.parametrize("checksum", [False, True])
@@ -258,11 +258,11 @@ def test_reads_by_index(lib, n, checksum):
     # an index equal to nFrames: refused with its position, nothing written
     for frames, pos in (([n], 0), ([0, n], 1), (list(range(n)) + [n + 5], n)):
         rc, status, dst, stats, _ = rec.frames_run(lib, stream, content, frames)
-        assert rc == 3 and stats[7] == pos and (dst == rec.GUARD_BYTE).all() and status == [-1] * (2 + 2 * len(frames))
+        assert rc == sc.SIZE_MISMATCH and stats[7] == pos and (dst == rec.GUARD_BYTE).all() and status == [-1] * (2 + 2 * len(frames))
     # overlapping destinations are the many-ranges call's refusal
     if n >= 7 and sizes[0] and sizes[2]:
         rc, _, dst, stats, _ = rec.frames_run(lib, stream, content, [0, 2], dst_offsets=[0, sizes[0] - 1], capacity=sizes[0] + sizes[2])
-        assert rc == 6 and stats[7] == 1 and (dst == rec.GUARD_BYTE).all()
+        assert rc == sc.UNSUPPORTED and stats[7] == 1 and (dst == rec.GUARD_BYTE).all()
 
 
 # ---------------------------------------------------------------------------------------------------- 7. the sanitizer run
