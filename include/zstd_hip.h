@@ -382,6 +382,50 @@ int zhip_seekable_edit_device(zhip_ctx*, zhip_seekable* old /* may be NULL */,
                               uint64_t maxContentBytes, uint64_t maxRecordBytes, int flags,
                               void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status /* [2] */, void* stream);
 
+/* TYPED STREAMS: a tensor of elementSize-byte elements (2, 4 or 8) stored as one BYTE PLANE per frame, so that every byte position of the elements gets
+ * entropy tables of its own. frameSize keeps its meaning as the content bytes of one frame; it is the number of elements of one GROUP. The source
+ * (srcSize a multiple of elementSize) is cut into groups of frameSize elements, a last one of e <= frameSize; group g becomes the elementSize frames
+ * g * elementSize + p, frame g * elementSize + p holding byte p of every element of the group in element order. Behind the last plane frame stands the MARKER,
+ * a skippable frame of 24 bytes -- magic 0x184D2A5D, Frame_Size 16, then four little-endian words: 'Z' 'H' 'P' 'L', version 1, elementSize, frameSize -- with a
+ * seek-table entry of its own (Compressed_Size 24, Decompressed_Size 0, with checksums 0x51D8E999: the low word of XXH64 of nothing); the standard table is last.
+ * The stream stays an ordinary seekable stream: the table's sizes sum to the content size, the checksums are those of the plane frames' content, and every
+ * zstd decoder -- zhip_seekable_decompress_device, _ranges_, _frames_ and zhip_seekable_edit_device on a typed handle included -- sees its literal, PLANAR
+ * content. Only zhip_seekable_decompress_typed_ranges_device puts the elements back together.
+ *
+ * zhip_planes_split_device / zhip_planes_join_device are the two transposition kernels on their own, over whole buffers of `size` bytes: split writes group
+ * g's plane p to d_dst + g * elementSize * frameSize + p * e_g, join is its inverse. Asynchronous, stream-ordered, no wait, no memory taken. d_src and d_dst
+ * must not overlap. ZHIP_ERR_UNSUPPORTED: an elementSize other than 2, 4, 8, a size that is no multiple of it, frameSize 0 or above 2^30.
+ *
+ * zhip_seekable_compress_typed_device: the split kernel writes a planar copy of the source into context scratch (srcSize bytes, kept between calls like the
+ * other areas) with the record table of the n * elementSize planes, zhip_seekable_compress_records_device's sequence compresses them as they are (so the
+ * frames are byte for byte libzstd's frames of the planes; under the wave match finder valid but not libzstd's, as for every call), and two small kernels put
+ * the marker in. The status, the failure rules and the guards are the records call's; a stream whose marker and entry do not fit dstCapacity fails with 70 like
+ * one whose table does not. elementSize 1 is zhip_seekable_compress_device, the same bytes. ZHIP_ERR_UNSUPPORTED beyond the plain call's: elementSize not in
+ * {1, 2, 4, 8}, srcSize no multiple of it, frameSize 0 or above 2^30, more than 2^27 - 1 plane frames.
+ * zhip_seekable_typed_bound: the records bound for the plane frames, plus the marker and its entry; 0 = invalid arguments.
+ *
+ * zhip_seekable_open_device recognises a typed stream: where the last entry is (24, 0) it reads those 24 bytes (the one extra copy and wait, only then). No
+ * tag: a plain stream. A tag with version 1, an elementSize of 2, 4 or 8 and frames that are whole groups of equally sized planes, frameSize elements each but
+ * for a shorter last group: a typed one. A tag and anything else: ZHIP_ERR_ZSTD with corruption_detected (20) at the first frame that does not fit.
+ * zhip_seekable_element_size: 1 for a plain stream; zhip_seekable_group_elements: frameSize (0 for a plain stream).
+ *
+ * zhip_seekable_decompress_typed_ranges_device: zhip_seekable_decompress_ranges_device in ELEMENT order -- offsets and lengths count bytes of the tensor, may
+ * start and end inside an element, overlap, repeat, come in any order, be empty; the same host checks, the same d_status shape ({code, range index}, then per
+ * range {code, frame index} of the first failing plane frame among those it needs), the same guards. The host plans planar ranges (a run of whole groups is
+ * one, a partly covered group elementSize of them, rounded out to whole elements), the many-ranges call decodes them into a planar buffer the handle owns, the
+ * join kernel moves the elements to d_dst. The planar buffer is bounded by the handle's scratch limit: ranges are taken in passes and cut at group boundaries;
+ * one piece above the limit is held whole. stats: the sums over the passes' many-ranges calls, `passes` the typed passes. A plain handle: ZHIP_ERR_UNSUPPORTED. */
+int      zhip_planes_split_device(zhip_ctx*, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, void* d_dst, void* stream);
+int      zhip_planes_join_device(zhip_ctx*, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, void* d_dst, void* stream);
+uint64_t zhip_seekable_typed_bound(uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, int flags);
+int      zhip_seekable_compress_typed_device(zhip_ctx*, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, int flags,
+                                             void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status /* [2] */, void* stream);
+uint32_t zhip_seekable_element_size(const zhip_seekable*);
+uint32_t zhip_seekable_group_elements(const zhip_seekable*);
+int      zhip_seekable_decompress_typed_ranges_device(zhip_ctx*, zhip_seekable*, const zhip_seekable_range* ranges, size_t nRanges,
+                                                      void* d_dst, uint64_t dstCapacity, int32_t* d_status /* [2 + 2 * nRanges] */,
+                                                      zhip_seekable_gather_stats* stats /* host, may be NULL */, void* stream);
+
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,
  * 4 K3, 5 / 6 the lane-serial match kernel (the greedy strategy's zhip_encode_match_greedy_kernel where that runs in its place) and the entropy kernel, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,

@@ -140,6 +140,13 @@ def lib():
         "zhip_seekable_decompress_frames_device": (C.c_int, [vp, vp, vp, sz, vp, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
         "zhip_seekable_edit_bound": (u64, [vp, vp, sz, u64, C.c_int]),
         "zhip_seekable_edit_device": (C.c_int, [vp, vp, vp, sz, vp, u64, vp, sz, u64, u64, C.c_int, vp, u64, vp, vp, vp]),
+        "zhip_planes_split_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp]),
+        "zhip_planes_join_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp]),
+        "zhip_seekable_typed_bound": (u64, [u64, C.c_uint32, C.c_uint32, C.c_int]),
+        "zhip_seekable_compress_typed_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, C.c_int, vp, u64, vp, vp, vp]),
+        "zhip_seekable_element_size": (C.c_uint32, [vp]),
+        "zhip_seekable_group_elements": (C.c_uint32, [vp]),
+        "zhip_seekable_decompress_typed_ranges_device": (C.c_int, [vp, vp, vp, sz, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
     }
     for name, (res, args) in protos.items():
         f = getattr(L, name)
@@ -163,6 +170,8 @@ EXPORTED_SYMBOLS = [
     "zhip_seekable_records_bound", "zhip_seekable_compress_records_device", "zhip_seekable_frame_offsets", "zhip_seekable_decompress_frames_device",
     "zhip_compress_sequences_device", "zhip_ctx_entropy_grid", "zhip_ctx_set_match_finder",
     "zhip_seekable_edit_bound", "zhip_seekable_edit_device",
+    "zhip_planes_split_device", "zhip_planes_join_device", "zhip_seekable_typed_bound", "zhip_seekable_compress_typed_device",
+    "zhip_seekable_element_size", "zhip_seekable_group_elements", "zhip_seekable_decompress_typed_ranges_device",
 ]
 
 

@@ -22,6 +22,7 @@
 #include "zhip_encode_plan.hpp"
 #include "zhip_decode_plan.hpp"
 #include "zhip_seekable_calls.hpp"
+#include "zhip_seekable_typed_calls.hpp"
 
 #define ZHIP_LDS_BYTES (160u * 1024u)      // per CU on gfx950
 static_assert(sizeof(ZpSeqQLDS) <= ZHIP_LDS_BYTES && sizeof(ZpHufKernelLDS) <= ZHIP_LDS_BYTES, "a workgroup's LDS must fit a CU");
@@ -400,6 +401,7 @@ struct zhip_ctx {
     DevBuf hSrc, hDst, hSegs, hStatus, hDense;
     DevBuf skSlots, skMeta;            // seekable streams: the chunks' compressBound-sized slots; segments, sizes, statuses and the scan's cells
     std::vector<ZskPinSlot> skPins;    // the pick list of an edit without an opened stream travels through these
+    DevBuf skStaging, skRecords, skStash;      // typed seekable compress: the planar copy of the source (its bytes), the plane frames' records, the seal's stash
     void* pinned = nullptr; size_t pinnedCap = 0;
     bool hpReady = false; hipStream_t hpH2D = nullptr, hpCompute = nullptr, hpD2H = nullptr;     // host pipeline: copy-in, kernels, copy-out
     void* hpStage[2] = {nullptr, nullptr}; size_t hpStageCap[2] = {0, 0}; hipEvent_t hpStageFree[2] = {nullptr, nullptr}; int hpNextSlot = 0;
@@ -506,7 +508,7 @@ extern "C" void zhip_ctx_destroy(zhip_ctx* c)
     c->scratch.release(); c->counter.release(); c->encWorkspace.release(); c->encMeta.release(); c->encArena.release(); c->encTables.release(); c->encBigList.release(); c->encBigWs.release(); c->encFlatTables.release(); c->encE1List.release(); c->encMbBlocks.release(); c->encMbCount.release(); c->encMbSeqs.release(); c->dictBlob.release(); c->dictEntropy.release(); c->dictTables.release();
     c->cdictBlob.release(); c->cdictEntropy.release(); c->cdictDigest.release(); c->cdictTables.release();
     c->hSrc.release(); c->hDst.release(); c->hSegs.release(); c->hStatus.release(); c->hDense.release();
-    c->skSlots.release(); c->skMeta.release();
+    c->skSlots.release(); c->skMeta.release(); c->skStaging.release(); c->skRecords.release(); c->skStash.release();
     for (ZskPinSlot& x : c->skPins) { if (x.p) (void)hipHostFree(x.p); (void)hipEventDestroy(x.done); }
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->profDecode) (void)hipFree(c->profDecode);
@@ -2042,13 +2044,14 @@ extern "C" int zhip_decompress_batch(const zhip_dparams* params, const zhip_item
 // One large buffer as the batch the kernels are fast at: chunks of frameSize bytes -> zhip_compress_batch_device -> frames back to back + the seek table;
 // a range read is zhip_decompress_batch_device over the frames that cover it. Everything between the batch calls is the small kernels of zhip_seekable.hpp,
 // queued on the caller's stream: no call here waits on the host except where scratch grows, and zhip_seekable_open_device, which reads the table's shape.
-struct zhip_seekable : ZskOpened {
+struct zhip_seekable : ZskTypedOpened {
     DevBuf prefix;                       // the table's scans (ZskOpened::pre points into it)
     DevBuf meta, edge;                   // a range call's segments / sizes / statuses, and where its partly covered frames are decoded
     // the many-ranges call: its plan's tables on the device, its item arrays and per-range words, its scratch frames; the pinned slots the tables are
     // uploaded from (a slot is written again only after the event behind its upload has completed)
     DevBuf gTables, gMeta, gScratch;
     std::vector<ZskPinSlot> slots;
+    DevBuf tPlanar, tTables, tStatus;     // a typed read: the planar buffer the many-ranges call fills (at exactly its bytes), the jobs and owners, the passes' status arrays
 };
 
 // a pinned slot of at least `bytes` that no upload still reads: one whose event has completed (grown where too small), else a new one
@@ -2137,6 +2140,34 @@ struct ZskHipBackend {
     }
     int wait() { HIP_TRY(hipStreamSynchronize(stream)); return 0; }
 };
+// and what the typed calls of zhip_seekable_typed_calls.hpp need on top: their areas, their kernels
+struct ZskHipTypedBackend : ZskHipBackend {
+    using ZskHipBackend::ZskHipBackend;
+    int reserve_typed(ZskTypedArea area, size_t bytes, uint8_t** base)
+    {
+        if (area == ZSKT_A_PLANAR) {        // at exactly its bytes, as the many-ranges scratch
+            DevBuf& s = h->tPlanar;
+            if (bytes > s.cap) {
+                s.release();
+                const hipError_t e = hipMalloc(&s.p, bytes);
+                if (e != hipSuccess) { s.p = nullptr; (void)hipGetLastError(); g_lastError = "out of device memory"; return ZHIP_ERR_NO_MEMORY; }
+                s.cap = bytes;
+            }
+            *base = (uint8_t*)s.p;
+            return 0;
+        }
+        DevBuf& d = area == ZSKT_A_STAGING ? c->skStaging : area == ZSKT_A_RECORDS ? c->skRecords : area == ZSKT_A_STASH ? c->skStash : area == ZSKT_A_TABLES ? h->tTables : h->tStatus;
+        if (d.reserve(bytes)) return g_reserveRc;
+        *base = (uint8_t*)d.p;
+        return 0;
+    }
+    void launch_typed(ZskTypedKernel k, uint32_t grid, const void* args)
+    {
+#define ZSKT_X(id, name, A) case ZSKT_K_##id: hipLaunchKernelGGL(zhip_seekable_##name##_kernel, dim3(grid), dim3(64), 0, stream, *(const A*)args); break;
+        switch (k) { ZSKT_KERNELS(ZSKT_X) default: break; }
+#undef ZSKT_X
+    }
+};
 
 extern "C" uint64_t zhip_seekable_frame_count(uint64_t srcSize, uint32_t frameSize) { return zsk_frame_count(srcSize, frameSize); }
 extern "C" uint64_t zhip_seekable_bound(uint64_t srcSize, uint32_t frameSize, int flags)
@@ -2170,7 +2201,7 @@ extern "C" void zhip_seekable_close(zhip_seekable* h)
 {
     if (!h) return;
     h->prefix.release(); h->meta.release(); h->edge.release();
-    h->gTables.release(); h->gMeta.release(); h->gScratch.release();      // (hipFree waits for the device: no upload from a slot is in flight behind it)
+    h->gTables.release(); h->gMeta.release(); h->gScratch.release(); h->tPlanar.release(); h->tTables.release(); h->tStatus.release();      // (hipFree waits for the device: no upload from a slot is in flight behind it)
     for (ZskPinSlot& s : h->slots) { if (s.p) (void)hipHostFree(s.p); (void)hipEventDestroy(s.done); }
     delete h;
 }
@@ -2181,9 +2212,10 @@ extern "C" int zhip_seekable_open_device(zhip_ctx* c, const void* d_stream, uint
     if (out) *out = nullptr;
     if (!c || !d_stream || !out) { g_lastError = "seekable open: bad arguments"; return set_err(err, ZHIP_ERR_UNSUPPORTED, 0, 0); }
     zhip_seekable* h = new zhip_seekable();
-    ZskHipBackend b(c, h, streamv);
+    ZskHipTypedBackend b(c, h, streamv);
     int zerr = 0; size_t index = 0;
     if (const int kind = zsk_open(b, d_stream, streamSize, h, &zerr, &index)) { zhip_seekable_close(h); return set_err(err, kind, index, zerr); }
+    if (const int kind = zsk_typed_probe(b, h, &zerr, &index)) { zhip_seekable_close(h); return set_err(err, kind, index, zerr); }
     if (info) { info->streamSize = streamSize; info->contentSize = h->contentSize; info->nFrames = h->lay.n; info->maxFrameContent = h->maxFrameContent; info->checksumFlag = h->lay.checksum; }
     *out = h;
     return 0;
@@ -2251,4 +2283,37 @@ extern "C" int zhip_seekable_edit_device(zhip_ctx* c, zhip_seekable* old, const 
 {
     ZskHipBackend b(c, old, streamv);
     return zsk_edit(b, c != nullptr, old, (const ZskEditPick*)picks, nPicks, d_src, srcSize, d_records, nRecords, maxContentBytes, maxRecordBytes, flags, d_dst, dstCapacity, d_streamSize, d_status);
+}
+
+// ------------------------------------------------------------------------------------------ seekable streams: typed (zhip_seekable_typed.hpp)
+extern "C" int zhip_planes_split_device(zhip_ctx* c, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, void* d_dst, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_planes_split(b, c != nullptr, d_src, size, elementSize, frameSize, d_dst);
+}
+extern "C" int zhip_planes_join_device(zhip_ctx* c, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, void* d_dst, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_planes_join(b, c != nullptr, d_src, size, elementSize, frameSize, d_dst);
+}
+extern "C" uint64_t zhip_seekable_typed_bound(uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, int flags)
+{
+    if (flags & ~ZHIP_SEEKABLE_CHECKSUM) return 0;
+    if (elementSize == 1) return zsk_bound(srcSize, frameSize, flags & ZHIP_SEEKABLE_CHECKSUM);
+    return zsk_typed_bound(srcSize, frameSize, elementSize, flags & ZHIP_SEEKABLE_CHECKSUM);
+}
+extern "C" int zhip_seekable_compress_typed_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, int flags,
+                                                   void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_typed_compress(b, c != nullptr, d_src, srcSize, frameSize, elementSize, flags, d_dst, dstCapacity, d_streamSize, d_status);
+}
+extern "C" uint32_t zhip_seekable_element_size(const zhip_seekable* h) { return h ? h->elementSize : 0; }
+extern "C" uint32_t zhip_seekable_group_elements(const zhip_seekable* h) { return h ? h->groupElements : 0; }
+extern "C" int zhip_seekable_decompress_typed_ranges_device(zhip_ctx* c, zhip_seekable* h, const zhip_seekable_range* ranges, size_t nRanges, void* d_dst, uint64_t dstCapacity,
+                                                            int32_t* d_status, zhip_seekable_gather_stats* stats, void* streamv)
+{
+    ZskHipTypedBackend b(c, h, streamv);
+    size_t bad = 0;
+    return zsk_typed_ranges(b, c != nullptr, h, (const uint64_t*)ranges, nRanges, d_dst, dstCapacity, d_status, stats, &bad);
 }

@@ -1,0 +1,173 @@
+// zhip_seekable_typed_calls.hpp -- HOST side of the typed seekable calls, free of HIP, beside zhip_seekable_calls.hpp: the checks, the layouts and the
+// sequences as function templates over a backend. The typed calls are built AROUND the plain ones -- typed compress is the split kernel, the records call on
+// the staging buffer and the seal; a typed read is the many-ranges call into a planar buffer, the join kernel and the status reducer -- so zsk_compress_records,
+// zsk_open and zsk_ranges run as they are, with their own kernels, areas and traces, and nothing of zhip_seekable_calls.hpp changes.
+//
+// The backend is one of zhip_seekable_calls.hpp's, extended by:
+//     int  reserve_typed(ZskTypedArea, size_t bytes, uint8_t** base)                    as reserve(); the areas are kept between calls like the others
+//     void launch_typed(ZskTypedKernel, uint32_t grid, const void* args)                one-wave workgroups
+#pragma once
+#include "zhip_seekable_calls.hpp"
+#include "zhip_seekable_typed.hpp"
+
+#define ZSKT_KERNELS(X) \
+    X(PLANES_SPLIT, planes_split, ZskPlanesArgs) X(PLANES_JOIN, planes_join, ZskJoinArgs) X(SEAL_STASH, seal_stash, ZskSealArgs) X(SEAL, seal, ZskSealArgs) \
+    X(TYPED_STATUS, typed_status, ZskTypedStatusArgs)
+#define ZSKT_X(id, name, args) ZSKT_K_##id,
+enum ZskTypedKernel { ZSKT_KERNELS(ZSKT_X) ZSKT_K_COUNT };
+#undef ZSKT_X
+// the context's: the planar staging buffer (the source's bytes), the plane frames' records, the seal's stash; the handle's: the planar buffer of a read
+// (at most the scratch limit, or one piece above it), its tables (jobs, owners, status places), the status arrays of its passes
+enum ZskTypedArea { ZSKT_A_STAGING, ZSKT_A_RECORDS, ZSKT_A_STASH, ZSKT_A_PLANAR, ZSKT_A_TABLES, ZSKT_A_STATUS, ZSKT_A_COUNT };
+
+// what the open call's typed probe adds to a handle: elementSize 1 = a plain stream
+struct ZskTypedOpened : ZskOpened { uint32_t elementSize = 1, groupElements = 0; };
+
+// a workgroup per tile, eight waves a CU
+static inline uint32_t zsk_tile_grid(int numCU, uint64_t tiles, uint64_t lanes)
+{
+    const uint64_t w = (lanes + 63) / 64, want = tiles > w ? tiles : w, gm = (uint64_t)(numCU > 0 ? numCU : 1) * 8;
+    return (uint32_t)(want < 1 ? 1 : want < gm ? want : gm);
+}
+static inline uint64_t zsk_planes_tiles(uint64_t elements, uint32_t group) { return zsk_frame_count(elements, group) * ((group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE); }
+
+static inline int zsk_planes_check(bool pointers, uint64_t size, uint32_t k, uint32_t frameSize, std::string& err)
+{
+    if (!pointers) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: bad arguments");
+    if (!zsk_element_ok(k)) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: the element size must be 2, 4 or 8");
+    if (size % k) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: the size must be a multiple of the element size");
+    if (frameSize < 1 || frameSize > ZSK_MAX_CONTENT) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: frameSize must be 1 ... 2^30 elements");
+    return 0;
+}
+static inline int zsk_typed_compress_check(bool pointers, uint64_t srcSize, uint32_t frameSize, uint32_t k, int flags, std::string& err)
+{
+    if (!pointers || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "seekable typed compress: bad arguments");
+    if (int rc = zsk_planes_check(true, srcSize, k, frameSize, err)) return rc;
+    if (zsk_frame_count(srcSize / k, frameSize) * k > ZSK_MAX_PLANE_FRAMES) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "seekable typed compress: at most 2^27 - 1 plane frames");
+    return 0;
+}
+
+// The whole-buffer kernels on their own: interleaved -> planar (no records) and back
+template <class B> int zsk_planes_split(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst)
+{
+    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err)) return rc;
+    if (!size) return 0;
+    ZskPlanesArgs a; memset(&a, 0, sizeof a);
+    a.src = (const uint8_t*)d_src; a.dst = (uint8_t*)d_dst; a.elements = size / k; a.k = k; a.group = frameSize; a.nGroups = (uint32_t)zsk_frame_count(a.elements, frameSize);
+    b.launch_typed(ZSKT_K_PLANES_SPLIT, zsk_tile_grid(b.numCU, zsk_planes_tiles(a.elements, frameSize), 0), &a);
+    return b.check();
+}
+template <class B> int zsk_planes_join(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst)
+{
+    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err)) return rc;
+    if (!size) return 0;
+    ZskJoinArgs a; memset(&a, 0, sizeof a);
+    a.planar = (const uint8_t*)d_src; a.dst = (uint8_t*)d_dst; a.elements = size / k; a.k = k; a.group = frameSize; a.tiles = zsk_planes_tiles(a.elements, frameSize);
+    b.launch_typed(ZSKT_K_PLANES_JOIN, zsk_tile_grid(b.numCU, a.tiles, 0), &a);
+    return b.check();
+}
+
+// Typed compress: the split kernel writes the planar staging buffer and the plane frames' records; the records call compresses them as they are; the seal
+// puts the marker in. The records call is handed the capacity less the marker and its entry, so a stream that does not fit fails there (70) with nothing written
+template <class B> int zsk_typed_compress(B& b, bool ctx, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t k, int flags, void* d_dst, uint64_t dstCapacity,
+                                          uint64_t* d_streamSize, int32_t* d_status)
+{
+    if (k == 1) return zsk_compress(b, ctx, d_src, srcSize, frameSize, flags, d_dst, dstCapacity, d_streamSize, d_status);
+    if (int rc = zsk_typed_compress_check(ctx && d_streamSize && d_status && (!srcSize || d_src), srcSize, frameSize, k, flags, b.err)) return rc;
+    const int checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1 : 0;
+    const uint64_t elements = srcSize / k, nGroups = zsk_frame_count(elements, frameSize), n = nGroups * k;
+    uint8_t* staging = nullptr; uint8_t* records = nullptr; uint8_t* stash = nullptr;
+    if (srcSize) if (int rc = b.reserve_typed(ZSKT_A_STAGING, (size_t)srcSize, &staging)) return rc;
+    if (n) if (int rc = b.reserve_typed(ZSKT_A_RECORDS, (size_t)n * 16, &records)) return rc;
+    if (int rc = b.reserve_typed(ZSKT_A_STASH, (size_t)zsk_seal_stash_bytes(n, checksum), &stash)) return rc;
+    if (n) {
+        ZskPlanesArgs a; memset(&a, 0, sizeof a);
+        a.src = (const uint8_t*)d_src; a.dst = staging; a.elements = elements; a.k = k; a.group = frameSize; a.nGroups = (uint32_t)nGroups; a.records = (uint64_t*)records;
+        b.launch_typed(ZSKT_K_PLANES_SPLIT, zsk_tile_grid(b.numCU, zsk_planes_tiles(elements, frameSize), n), &a);
+        if (int rc = b.check()) return rc;
+    }
+    const uint64_t extra = ZSK_MARKER + zsk_entry_size(checksum);
+    if (int rc = zsk_compress_records(b, ctx, staging, srcSize, (const zhip_segment*)records, (size_t)n, srcSize, elements < frameSize ? elements : frameSize, flags,
+                                      d_dst, dstCapacity > extra ? dstCapacity - extra : 0, d_streamSize, d_status)) return rc;
+    ZskSealArgs s; memset(&s, 0, sizeof s);
+    s.dst = (uint8_t*)d_dst; s.dstCapacity = dstCapacity; s.streamSize = d_streamSize; s.outStatus = d_status; s.stash = stash;
+    s.n = (uint32_t)n; s.checksum = (uint32_t)checksum; s.elementSize = k; s.frameSize = frameSize;
+    const uint32_t grid = zsk_lane_grid(b.numCU, n * zsk_entry_size(checksum) / 16 + 1);
+    b.launch_typed(ZSKT_K_SEAL_STASH, grid, &s);
+    b.launch_typed(ZSKT_K_SEAL, grid, &s);
+    return b.check();
+}
+
+// Behind zsk_open: a last entry of (24, 0) is looked at -- the one extra copy, and only then. No tag: a plain stream. A tag and the shape it promises:
+// a typed stream. A tag and anything else (a version or an element size this reader does not know, frames that are no groups of planes): corrupt, at the
+// first frame that does not fit
+template <class B> int zsk_typed_probe(B& b, ZskTypedOpened* h, int* zerr, size_t* index)
+{
+    h->elementSize = 1; h->groupElements = 0;
+    const uint32_t n = h->lay.n;
+    if (!n || h->cOff[n] - h->cOff[n - 1] != ZSK_MARKER || h->dOff[n] != h->dOff[n - 1]) return 0;
+    uint8_t m[ZSK_MARKER];
+    if (b.copy(m, h->stream + h->cOff[n - 1], ZSK_MARKER, ZSK_COPY_TO_HOST) || b.wait()) return zsk_refuse(b.err, ZHIP_ERR_HIP, "seekable open: reading the last frame failed");
+    uint32_t k = 0, frameSize = 0;
+    const int kind = zsk_parse_marker(m, &k, &frameSize);
+    if (!kind) return 0;
+    const uint32_t bad = kind < 0 ? n - 1 : zsk_typed_shape(h->dOff.data(), n, k, frameSize);
+    if (bad != n) { *zerr = ZSK_ERR_CORRUPT; *index = bad; return ZHIP_ERR_ZSTD; }
+    h->elementSize = k; h->groupElements = frameSize;
+    return 0;
+}
+
+// the tables a typed read uploads: the join jobs of every pass, the user ranges' planar ranges, every planar range's place in the status area
+struct ZskTypedReadLayout { size_t oJobs, oOwner, oPairAt, tableBytes; };
+static inline ZskTypedReadLayout zsk_typed_read_layout(size_t J, size_t R, size_t Q)
+{
+    ZskTypedReadLayout l;
+    l.oJobs = 0; l.oOwner = zsk_up16(J * sizeof(ZskJoinJob)); l.oPairAt = l.oOwner + zsk_up16(R * 8); l.tableBytes = l.oPairAt + zsk_up16(Q * 4);
+    return l;
+}
+
+// R user ranges in element order: per pass of the plan the many-ranges call into the planar buffer and the join kernel; then the status reducer.
+// stats (where given) receives the sums over the passes' many-ranges calls, `passes` counting the typed passes
+template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h, const uint64_t* rg, size_t R, void* d_dst, uint64_t dstCapacity, int32_t* d_status,
+                                        zhip_seekable_gather_stats* stats, size_t* bad)
+{
+    if (h && h->elementSize == 1) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, "seekable typed ranges: the stream is a plain one (no byte planes)");
+    bool any = false;
+    if (int rc = zsk_ranges_check(ctx && h && d_status, rg, R, h ? h->contentSize : 0, d_dst, dstCapacity, bad, &any, b.err)) return rc;
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (!any) return b.zero(d_status, (2 + 2 * R) * sizeof(int32_t));
+
+    ZskTypedPlan plan;
+    zsk_typed_plan(h->dOff.data(), h->elementSize, h->groupElements, rg, R, h->scratchLimit, &plan);
+    const size_t J = plan.jobs.size(), Q = plan.planar.size() / 3, nPass = plan.passes.size();
+    const ZskTypedReadLayout l = zsk_typed_read_layout(J, R, Q);
+    std::vector<uint32_t> pairAt(Q);
+    size_t statusInts = 0;
+    for (const ZskTypedPass& p : plan.passes) { for (uint32_t q = p.q0; q < p.q1; q++) pairAt[q] = (uint32_t)(statusInts + 2 + 2 * (q - p.q0)); statusInts += 2 + 2 * (size_t)(p.q1 - p.q0); }
+    uint8_t* P = nullptr; uint8_t* t = nullptr; uint8_t* st = nullptr; uint8_t* pin = nullptr;
+    if (int rc = b.reserve_typed(ZSKT_A_PLANAR, (size_t)plan.pMax, &P)) return rc;
+    if (int rc = b.reserve_typed(ZSKT_A_TABLES, l.tableBytes, &t)) return rc;
+    if (int rc = b.reserve_typed(ZSKT_A_STATUS, statusInts * 4, &st)) return rc;
+    if (int rc = b.reserve(ZSK_A_PIN, l.tableBytes, &pin)) return rc;
+    memcpy(pin + l.oJobs, plan.jobs.data(), J * sizeof(ZskJoinJob));
+    memcpy(pin + l.oOwner, plan.owner.data(), R * 8);
+    memcpy(pin + l.oPairAt, pairAt.data(), Q * 4);
+    if (int rc = b.copy(t, pin, l.tableBytes, ZSK_COPY_FROM_PIN)) return rc;
+
+    size_t at = 0;
+    for (size_t p = 0; p < nPass; p++) {
+        const ZskTypedPass& ps = plan.passes[p];
+        zhip_seekable_gather_stats one; size_t inner = 0;
+        if (int rc = zsk_ranges(b, ctx, h, plan.planar.data() + 3 * (size_t)ps.q0, ps.q1 - ps.q0, P, ps.bytes, (int32_t*)st + at, &one, &inner)) return rc;
+        at += 2 + 2 * (size_t)(ps.q1 - ps.q0);
+        if (stats) { stats->items += one.items; stats->inPlace += one.inPlace; stats->scratchBytes += one.scratchBytes; stats->copyJobs += one.copyJobs; stats->passes++; }
+        ZskJoinArgs a; memset(&a, 0, sizeof a);
+        a.planar = P; a.dst = (uint8_t*)d_dst; a.jobs = (const ZskJoinJob*)(t + l.oJobs) + ps.job0; a.nJobs = ps.job1 - ps.job0; a.tiles = ps.tiles; a.k = h->elementSize; a.group = h->groupElements;
+        b.launch_typed(ZSKT_K_PLANES_JOIN, zsk_tile_grid(b.numCU, a.tiles, 0), &a);
+        if (int rc = b.check()) return rc;
+    }
+    ZskTypedStatusArgs s; memset(&s, 0, sizeof s);
+    s.owner = (const uint32_t*)(t + l.oOwner); s.pairAt = (const uint32_t*)(t + l.oPairAt); s.status = (const int32_t*)st; s.nRanges = (uint32_t)R; s.outStatus = d_status;
+    b.launch_typed(ZSKT_K_TYPED_STATUS, zsk_lane_grid(b.numCU, R), &s);
+    return b.check();
+}

@@ -134,15 +134,22 @@ class DeviceBatchContext:
         """waves of the entropy kernel resident on this device"""
         return int(self.L.zhip_ctx_entropy_grid(self.ctx))
 
-    def seekable_compress(self, src, frame_size=131072, checksum=False, stream=None):
+    def seekable_compress(self, src, frame_size=131072, checksum=False, stream=None, element_size=1):
         """src (a uint8 CUDA tensor) as ONE zstd seekable stream: frames of frame_size bytes of it, compressed as a batch with this context's
         parameters, back to back, then the seek table (checksum: with the low 32 bits of XXH64 of every frame's content). Returns a uint8 CUDA
         tensor of exactly the stream's size -- a view of a zhip_seekable_bound-sized allocation. Waits for the size. Any zstd decoder decompresses
-        the stream whole; SeekableStream reads ranges of it."""
+        the stream whole; SeekableStream reads ranges of it.
+        element_size 2, 4 or 8: a TYPED stream -- src holds elements of that many bytes (a tensor's bytes: t.view(torch.uint8)), frame_size counts the ELEMENTS
+        of one group, and every group becomes element_size frames, one per byte position of the elements ("byte planes": each gets entropy tables of its own,
+        8-20 % smaller streams for bf16 / fp16 / fp32 weights and integer ids). A marker frame behind the last plane makes the stream describe itself:
+        SeekableStream reads elements back; other zstd decoders see the planar bytes (zstandard_amd.seekable.planes_to_elements). Takes src.numel() more
+        bytes of context memory, kept between calls."""
         self._ensure_cparams()
         self._check(src, torch.uint8)
         s = stream if stream is not None else torch.cuda.current_stream()
         flags = _lib.SEEKABLE_CHECKSUM if checksum else 0
+        if element_size != 1:
+            return self._seekable_compress_typed(src, frame_size, element_size, flags, s)
         bound = self.L.zhip_seekable_bound(src.numel(), frame_size, flags)
         if not bound:
             raise ZstdError("seekable compress: frame_size must be 1 ... 2^30 and give at most 2^27 frames")
@@ -161,6 +168,52 @@ class DeviceBatchContext:
         if rc:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return dst[:int(size[0])]
+
+    def _seekable_compress_typed(self, src, frame_size, element_size, flags, s):
+        if element_size not in (2, 4, 8):
+            raise ZstdError("seekable compress: element_size must be 1, 2, 4 or 8")
+        if src.numel() % element_size:
+            raise ZstdError("seekable compress: %d bytes are no whole elements of %d" % (src.numel(), element_size))
+        bound = self.L.zhip_seekable_typed_bound(src.numel(), frame_size, element_size, flags) if 0 < frame_size <= 1 << 30 else 0
+        if not bound:
+            raise ZstdError("seekable compress: frame_size must be 1 ... 2^30 elements and give at most 2^27 - 1 plane frames")
+        with torch.cuda.stream(s):
+            dst = torch.empty(bound, dtype=torch.uint8, device=src.device)
+            size = torch.zeros(1, dtype=torch.int64, device=src.device)
+            status = torch.zeros(2, dtype=torch.int32, device=src.device)
+        rc = self.L.zhip_seekable_compress_typed_device(self.ctx, src.data_ptr() if src.numel() else None, src.numel(), frame_size, element_size, flags, dst.data_ptr(), bound,
+                                                        size.data_ptr(), status.data_ptr(), s.cuda_stream)
+        if rc:
+            raise ZstdError("seekable compress failed: %s" % _lib.last_error())
+        err = _lib.Error()
+        rc = self.L.zhip_ctx_sync(self.ctx, s.cuda_stream, status.data_ptr(), 1, C.byref(err))
+        if rc == _lib.ERR_ZSTD:
+            raise ZstdError("seekable compress: plane frame %d: %s" % (int(status[1]), _lib.error_name(err.zstdErr)))
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return dst[:int(size[0])]
+
+    def _planes(self, call, src, frame_size, element_size, out, stream):
+        assert src.is_cuda and src.is_contiguous(), "expected a contiguous CUDA tensor"
+        raw = src.view(torch.uint8).reshape(-1)
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if out is None:
+            with torch.cuda.stream(s):
+                out = torch.empty(raw.numel(), dtype=torch.uint8, device=src.device)
+        self._check(out, torch.uint8)
+        assert out.numel() >= raw.numel(), "out is shorter than the source"
+        if call(self.ctx, raw.data_ptr() if raw.numel() else None, raw.numel(), element_size, frame_size, out.data_ptr() if raw.numel() else None, s.cuda_stream):
+            raise ZstdError("planes: %s" % _lib.last_error())
+        return out[:raw.numel()]
+
+    def planes_split(self, src, frame_size, element_size=None, out=None, stream=None):
+        """the bytes of src (any contiguous CUDA tensor; element_size None: its dtype's) in the PLANAR order of a typed seekable stream, as a uint8 tensor: groups
+        of frame_size elements, group g's plane p -- byte p of every element -- at g * element_size * frame_size + p * (the group's elements). Asynchronous."""
+        return self._planes(self.L.zhip_planes_split_device, src, frame_size, src.element_size() if element_size is None else element_size, out, stream)
+
+    def planes_join(self, planar, frame_size, element_size, out=None, stream=None):
+        """planes_split's inverse: planar bytes -> the elements' bytes, as a uint8 tensor (view it as the dtype). Asynchronous."""
+        return self._planes(self.L.zhip_planes_join_device, planar, frame_size, element_size, out, stream)
 
     def _records_table(self, src, records, max_content_bytes, max_record_bytes, s, what="seekable compress"):
         """records as seekable_compress_records takes them -> (the (n, 2) int64 CUDA table, n, max_content_bytes, max_record_bytes)"""
@@ -316,15 +369,42 @@ class DeviceBatchContext:
         return self.L.zhip_kernel_name(direction).decode()
 
 
+def planes_split(src, frame_size, element_size=None, ctx=None, out=None, stream=None):
+    """DeviceBatchContext.planes_split on `ctx`, or on a context of its own (then it waits)"""
+    if ctx is not None:
+        return ctx.planes_split(src, frame_size, element_size, out, stream)
+    with_ctx = DeviceBatchContext()
+    try:
+        return with_ctx.planes_split(src, frame_size, element_size, out, stream)
+    finally:
+        with_ctx.close()
+
+
+def planes_join(planar, frame_size, element_size, ctx=None, out=None, stream=None):
+    """DeviceBatchContext.planes_join on `ctx`, or on a context of its own (then it waits)"""
+    if ctx is not None:
+        return ctx.planes_join(planar, frame_size, element_size, out, stream)
+    with_ctx = DeviceBatchContext()
+    try:
+        return with_ctx.planes_join(planar, frame_size, element_size, out, stream)
+    finally:
+        with_ctx.close()
+
+
 class SeekableStream:
     """Range reads of a zstd seekable stream resident in HBM (any writer's): ``read(offset, length)`` decodes only the frames that cover the range,
     ``read_ranges`` many ranges as one decode batch, ``read_records`` whole frames by index; ``frame_offsets`` is the table it opened.
 
+    A TYPED stream (DeviceBatchContext.seekable_compress with element_size 2, 4 or 8) is recognised by its marker: ``element_size`` and ``group_elements``
+    say so (1 and 0 for a plain stream), and ``read`` / ``read_ranges`` return ELEMENTS -- offsets and lengths count the tensor's bytes. ``read_records`` and
+    ``frame_offsets`` stay raw: they name the plane frames. The edit family raises ValueError on a typed stream (moving plane frames breaks the groups).
+    ``raw=True`` opens a typed stream as the plain stream it also is: every call then sees its planar content, the edit family included.
+
     ctx: the DeviceBatchContext that decodes (its dictionary, format and window limit apply); stream_tensor: the whole stream, a uint8 CUDA tensor,
     kept alive and unchanged while this object is open. Opening reads and checks the seek table (it waits); a damaged table raises ZstdError."""
 
-    def __init__(self, ctx, stream_tensor, stream=None, scratch_limit=None):
-        """scratch_limit: see set_scratch_limit"""
+    def __init__(self, ctx, stream_tensor, stream=None, scratch_limit=None, raw=False):
+        """scratch_limit: see set_scratch_limit; raw: see the class"""
         DeviceBatchContext._check(stream_tensor, torch.uint8)
         self.ctx, self.tensor, self.handle = ctx, stream_tensor, None
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -337,6 +417,9 @@ class SeekableStream:
         self.handle = h
         self.content_size, self.n_frames, self.has_checksums = int(info.contentSize), int(info.nFrames), bool(info.checksumFlag)
         self.max_frame_content = int(info.maxFrameContent)
+        typed = not raw and ctx.L.zhip_seekable_element_size(h) != 1
+        self.element_size = int(ctx.L.zhip_seekable_element_size(h)) if typed else 1
+        self.group_elements = int(ctx.L.zhip_seekable_group_elements(h)) if typed else 0
         self.last_gather_stats = None
         self._frame_offsets = None
         if scratch_limit is not None:
@@ -344,7 +427,8 @@ class SeekableStream:
 
     def set_scratch_limit(self, nbytes):
         """most device memory read_ranges may hold frames in that do not decode straight into their place (0: the default, 1 GiB). A call that needs more
-        runs in several passes; one frame larger than the limit is still held whole."""
+        runs in several passes; one frame larger than the limit is still held whole. On a typed stream it also bounds the planar buffer the elements are
+        put together from: ranges are taken in passes and cut at group boundaries, one group above the limit is still held whole."""
         if self.handle is None:
             raise ZstdError("the seekable stream is closed")
         if nbytes < 0:
@@ -360,6 +444,10 @@ class SeekableStream:
             length = self.content_size - offset
         if offset < 0 or length < 0 or offset + length > self.content_size:
             raise ZstdError("range %d + %d is outside the content (%d bytes)" % (offset, length, self.content_size))
+        if self.element_size != 1:                                          # the one-range case of the typed call
+            if out is not None:
+                assert out.numel() >= length, "out is shorter than the range"
+            return self.read_ranges([(offset, length)], out, None if out is None else [0], stream)[0]
         s = stream if stream is not None else torch.cuda.current_stream()
         with torch.cuda.stream(s):
             if out is None:
@@ -421,8 +509,8 @@ class SeekableStream:
         DeviceBatchContext._check(out, torch.uint8)
         L = self.ctx.L
         stats = _lib.SeekableGatherStats()
-        rc = L.zhip_seekable_decompress_ranges_device(self.ctx.ctx, self.handle, table.ctypes.data, n, out.data_ptr(), out.numel(), status.data_ptr(),
-                                                      C.byref(stats), s.cuda_stream)
+        call = L.zhip_seekable_decompress_ranges_device if self.element_size == 1 else L.zhip_seekable_decompress_typed_ranges_device
+        rc = call(self.ctx.ctx, self.handle, table.ctypes.data, n, out.data_ptr(), out.numel(), status.data_ptr(), C.byref(stats), s.cuda_stream)
         if rc:
             raise ZstdError("seekable read failed: %s" % _lib.last_error())
         self.last_gather_stats = {k: int(getattr(stats, k)) for k, _ in stats._fields_}
@@ -517,7 +605,13 @@ class SeekableStream:
         frame that ends beyond `out`)."""
         if self.handle is None:
             raise ZstdError("the seekable stream is closed")
+        self._plain_only("edit")
         return self.ctx._edit(self, picks, src, records, max_content_bytes, max_record_bytes, self.has_checksums, out, stream)
+
+    def _plain_only(self, what):
+        if self.element_size != 1:
+            raise ValueError("seekable %s: a typed stream's frames are byte planes in groups of %d -- moving them breaks the groups (open it with raw=True to edit its "
+                             "planar form)" % (what, self.element_size))
 
     @staticmethod
     def _count(records):
@@ -537,6 +631,7 @@ class SeekableStream:
         neither read nor written, the new frames start where the old table started; this object is closed (it describes bytes that no longer exist) and
         buffer[:new size] is returned: open it again to read. A failed append in place leaves the old stream as it was, and this object open."""
         import numpy as np
+        self._plain_only("append")
         picks = self._picks(np.arange(self.n_frames), self._count(records))
         if buffer is None:
             return self.edit(picks, src, records, max_content_bytes, max_record_bytes, None, stream)
@@ -550,6 +645,7 @@ class SeekableStream:
     def replace_records(self, indices, src, records, max_content_bytes=None, max_record_bytes=None, stream=None):
         """frame indices[j] gives way to record j of `records` (an index named twice keeps the later record); every other frame is kept"""
         import numpy as np
+        self._plain_only("replace")
         idx = np.asarray(indices if len(indices) else np.zeros(0, dtype=np.int64))
         if idx.ndim != 1 or idx.dtype.kind not in "iu" or len(idx) != self._count(records):
             raise ZstdError("seekable replace: one frame index per record")
@@ -564,6 +660,7 @@ class SeekableStream:
     def delete_records(self, indices, stream=None):
         """the stream without the frames named by `indices`"""
         import numpy as np
+        self._plain_only("delete")
         idx = np.asarray(indices if len(indices) else np.zeros(0, dtype=np.int64))
         if idx.ndim != 1 or idx.dtype.kind not in "iu":
             raise ZstdError("seekable delete: indices must be a sequence of frame indices")
@@ -577,6 +674,7 @@ class SeekableStream:
     def reorder(self, order, stream=None):
         """the frames named by `order`, in that order -- a permutation lays an epoch's sample order out contiguously; `order` may repeat or omit frames"""
         import numpy as np
+        self._plain_only("reorder")
         return self.edit(self._picks(np.asarray(order if len(order) else np.zeros(0, dtype=np.int64))), stream=stream)
 
     def close(self):

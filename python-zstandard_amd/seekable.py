@@ -2,7 +2,11 @@
 appends the seek table; ``decompress`` reads any byte range of such a stream by decoding only the frames that cover it, ``decompress_ranges`` many ranges as one batch. The streams are ordinary zstd:
 ``zstd -d`` and ``ZstdDecompressor`` decompress them whole (the table is a skippable frame). Built on ``device.DeviceBatchContext.seekable_compress`` and
 ``device.SeekableStream``; the data crosses the link once each way. ``compress_records`` / ``decompress_records`` do the same for a list of records of any
-sizes: one frame per record, read back by index; ``append_records`` / ``edit`` make a new stream out of an old one's frames and new records."""
+sizes: one frame per record, read back by index; ``append_records`` / ``edit`` make a new stream out of an old one's frames and new records.
+
+``compress(..., element_size=2 | 4 | 8)`` writes a TYPED stream for a tensor's bytes: groups of ``frame_size`` elements, one frame per byte position of the
+elements ("byte planes"), and a marker frame that says so. ``decompress`` / ``decompress_ranges`` recognise it and return the elements; any other zstd decoder
+returns the planar bytes, which ``planes_to_elements`` puts back in order (``elements_to_planes`` is its inverse) -- numpy on the host, no GPU."""
 import torch
 
 from .backend_hip import ZstdError
@@ -16,19 +20,47 @@ def _to_device(data):
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()
 
 
-def compress(data, level=3, frame_size=131072, checksum=False, match_finder="libzstd", **ctx_kw):
+def elements_to_planes(data, element_size, frame_size):
+    """bytes of elements -> the planar content of the typed stream ``compress(data, frame_size=frame_size, element_size=element_size)`` writes: per group of
+    frame_size elements, byte 0 of every element, then byte 1 of every element, ... Returns bytes."""
+    import numpy as np
+    a = np.frombuffer(bytes(data), dtype=np.uint8)
+    if element_size not in (2, 4, 8) or a.size % element_size or frame_size < 1:
+        raise ValueError("element_size must be 2, 4 or 8, the data whole elements and frame_size at least 1")
+    out, step = np.empty_like(a), frame_size * element_size
+    for at in range(0, a.size, step):
+        g = a[at:at + step]
+        out[at:at + g.size] = g.reshape(-1, element_size).T.reshape(-1)
+    return out.tobytes()
+
+
+def planes_to_elements(raw, element_size, frame_size):
+    """the planar content of a typed stream, as any zstd decoder returns it (``zstd -d``, ``SeekableStream(..., raw=True).read()``), -> the elements' bytes"""
+    import numpy as np
+    a = np.frombuffer(bytes(raw), dtype=np.uint8)
+    if element_size not in (2, 4, 8) or a.size % element_size or frame_size < 1:
+        raise ValueError("element_size must be 2, 4 or 8, the data whole elements and frame_size at least 1")
+    out, step = np.empty_like(a), frame_size * element_size
+    for at in range(0, a.size, step):
+        g = a[at:at + step]
+        out[at:at + g.size] = g.reshape(element_size, -1).T.reshape(-1)
+    return out.tobytes()
+
+
+def compress(data, level=3, frame_size=131072, checksum=False, match_finder="libzstd", element_size=1, **ctx_kw):
     """data -> a seekable stream (bytes). match_finder: "libzstd" (frames byte for byte libzstd's) or "wave" (DeviceBatchContext.set_match_finder: valid zstd,
-    not libzstd's bytes; frame_size at most 131 072). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
+    not libzstd's bytes; frame_size at most 131 072). element_size 2, 4 or 8: a typed stream -- data is elements of that many bytes, frame_size counts the
+    elements of a group (see the module). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
     ctx = DeviceBatchContext(level=level, match_finder=match_finder, **ctx_kw)
     try:
-        return ctx.seekable_compress(_to_device(data), frame_size=frame_size, checksum=checksum).cpu().numpy().tobytes()
+        return ctx.seekable_compress(_to_device(data), frame_size=frame_size, checksum=checksum, element_size=element_size).cpu().numpy().tobytes()
     finally:
         ctx.close()
 
 
 def decompress(data, offset=0, length=None, **ctx_kw):
-    """content bytes [offset, offset + length) of a seekable stream (length None: to the end). Raises ZstdError for a stream without a valid seek table,
-    a range outside the content, or a frame that fails."""
+    """content bytes [offset, offset + length) of a seekable stream (length None: to the end); of a typed stream, the elements' bytes. Raises ZstdError for
+    a stream without a valid seek table, a range outside the content, or a frame that fails."""
     if len(data) == 0:
         raise ZstdError("not a seekable stream: empty input")
     ctx = DeviceBatchContext(**ctx_kw)
@@ -43,7 +75,8 @@ def decompress(data, offset=0, length=None, **ctx_kw):
 
 
 def decompress_ranges(data, ranges, **ctx_kw):
-    """the content bytes of every (offset, length) of `ranges` as a list of bytes: ONE decode batch over the frames the ranges touch, each decoded once.
+    """the content bytes of every (offset, length) of `ranges` as a list of bytes: ONE decode batch over the frames the ranges touch, each decoded once
+    (of a typed stream: the elements' bytes, every plane frame a range's groups need).
     Raises ZstdError as ``decompress`` does; a failing frame's error names the lowest range that needs it."""
     if len(data) == 0:
         raise ZstdError("not a seekable stream: empty input")
