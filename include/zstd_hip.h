@@ -230,8 +230,24 @@ int zhip_compress_sequences_device(zhip_ctx*, const void* d_src, const zhip_segm
  *                        call return ZHIP_ERR_UNSUPPORTED with a zhip_last_error() text that names the finder. A source of several blocks gets d_status 40 at its own
  *                        index and its neighbours compress; so does a source the row of its own size class does not serve (level 4 at 16 384 bytes and below, a window
  *                        that does not cover the source). Slot rules (zhip_compress_bound, d_status 70) are unchanged.
+ *   ZHIP_FINDER_NONE     no match search at all, for NUMERIC TENSORS (float weights and activations, above all the byte planes of a typed seekable stream): one kernel
+ *                        per chunk (zhip_encode_none.hpp) in place of the match kernels AND the entropy kernel, one wave per source, the source itself read as the block's
+ *                        literals -- no sequence arena, no tables, no literal copy. Every frame is byte for byte what libzstd 1.5.7's ZSTD_compressSequences writes for
+ *                        that source with explicit block delimiters and a list that is only the delimiter (litLength = the source's size) under the context's level,
+ *                        parameters, frame flags and format -- which is also what zhip_compress_sequences_device writes for count 0: a literals section (Huffman, raw
+ *                        or RLE) and "0 sequences", or a raw block where that gains less than ZSTD_minGain. The level still governs what it governs behind the search:
+ *                        window descriptor, raw literals at negative levels (the whole block then comes out raw: allowed, and pointless), ZSTD_minGain, checksum,
+ *                        content size, magicless format. On float tensors such frames are the size of level 3's or up to 13 % smaller (the search finds only short,
+ *                        worthless matches there); on data with real repetition they lose badly -- 1.9 x level 3's size on int64 running sums, worse on text
+ *                        (DESIGN.md 4.2 has the table). Pick it per context for data known to be numeric; nothing chooses it automatically.
+ *                        Scope and refusals are the wave finder's: sources of one block (<= 131 072 bytes), no dictionary, a level or parameters whose row for
+ *                        16 385 ... 131 072-byte sources is fast or double-fast (levels <= 4, negative levels, explicit strategy 1 / 2). A context with a dictionary,
+ *                        or outside those levels, makes the compress call return ZHIP_ERR_UNSUPPORTED with a zhip_last_error() text that names the finder
+ *                        ("ZHIP_FINDER_NONE", match finder "none"). A source of several blocks gets d_status 40 at its own index and its neighbours compress; so does
+ *                        a source the row of its own size class does not serve (level 4 at 16 384 bytes and below, a window that does not cover the source). Slot
+ *                        rules (zhip_compress_bound, d_status 70) are unchanged.
  * An unknown value: ZHIP_ERR_UNSUPPORTED, the finder stays what it was. */
-enum { ZHIP_FINDER_LIBZSTD = 0, ZHIP_FINDER_WAVE = 1 };
+enum { ZHIP_FINDER_LIBZSTD = 0, ZHIP_FINDER_WAVE = 1, ZHIP_FINDER_NONE = 2 };
 int zhip_ctx_set_match_finder(zhip_ctx*, int finder);
 size_t zhip_ctx_entropy_grid(zhip_ctx*);    /* waves of the entropy kernel resident on the context's device: a batch above it gives every wave several frames (for tests) */
 int zhip_ctx_sync(zhip_ctx*, void* stream, const int32_t* d_status, size_t n, zhip_error* err);
@@ -431,7 +447,8 @@ int      zhip_seekable_decompress_typed_ranges_device(zhip_ctx*, zhip_seekable*,
  * 4 K3, 5 / 6 the lane-serial match kernel (the greedy strategy's zhip_encode_match_greedy_kernel where that runs in its place) and the entropy kernel, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,
  * 8 the flat match kernel -- the match stage of a chunk whichever of its forms ran: the double-fast search's and, since the fast strategy has a flat search of its own
  * (levels 1, 2 and negative levels without a dictionary, sources of one block), that one's; the LDS-source kernels of small batches too --, 9 "zhip_decode_pipeline_span": not a kernel, a chunk's decode pipeline from K1's start to K3's end (what the overlapping kernels cost together),
- * 10 the wave match kernel (ZHIP_FINDER_WAVE: once per chunk, with 5 and 8 at zero launches). */
+ * 10 the wave match kernel (ZHIP_FINDER_WAVE: once per chunk, with 5 and 8 at zero launches),
+ * 11 the literals-only kernel (ZHIP_FINDER_NONE: once per chunk, timed with the trailer kernel behind it, with 5, 6, 8 and 10 at zero launches). */
 const char* zhip_kernel_name(int k);
 int         zhip_ctx_kernel_time(zhip_ctx*, int direction, double* avgMs, uint64_t* launches);
 /* how many frames of the context's last zhip_decompress_batch_device call the phase-split kernels (K1 -> K2 -> K3) handed to the generic kernel: frames of several

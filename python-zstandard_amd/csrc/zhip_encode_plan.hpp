@@ -95,6 +95,7 @@ static inline uint32_t ze_entropy_grid(const ZePlanDevice& dev, size_t chunk)
 }
 // the slots and the chunk of the calls that run no match search of the library's: sequences from the caller (zhip_compress_sequences_device: full one-block slots whatever the
 // level's strategy; dictionary batches the dictionary shape) and the wave match finder (ZHIP_FINDER_WAVE; no dictionary). Either call halves the chunk where its arena does not fit.
+// (ZHIP_FINDER_NONE has no slots at all: ze_none_plan below.)
 struct ZeSlotPlan { uint32_t arenaStride = 0, arenaLit = 0, slotSrcMax = 0; size_t chunk = 0; };
 static inline ZeSlotPlan ze_sequences_plan(const ZePlanIn& in)
 {
@@ -111,6 +112,29 @@ static inline ZeSlotPlan ze_wave_plan(const ZePlanIn& in)
     s.arenaStride = (uint32_t)(ZE_ARENA_LIT + 512); s.arenaLit = ZE_ARENA_LIT;      // sequences only (mode 4): the slot needs no literal area
     s.chunk = in.n < 65536 ? in.n : 65536;
     if (in.knob.echunk && in.knob.echunk < s.chunk) s.chunk = in.knob.echunk;
+    return s;
+}
+// no match search (ZHIP_FINDER_NONE, zhip_encode_none.hpp): the one kernel reads the sources and writes frames and a ZeMeta each -- no arena, so no arena stride and nothing
+// to halve. What bounds a chunk is the context's meta buffer (16 bytes a source) and the 32-bit work counter: 65 536 sources, the chunk the default finder and the wave
+// finder already size that buffer for (1 MiB), so a context that alternates finders never grows it for this one; a launch more per 65 536 sources costs microseconds against
+// the milliseconds each takes.
+struct ZeNonePlan { size_t chunk = 0; uint32_t grid = 0; size_t metaBytes = 0; };
+// what makes the compress call as a whole refuse under ZHIP_FINDER_NONE (the zhip_last_error text, null: served), as under the wave finder: a dictionary, or a one-block row
+// (sources of 16 385 ... 131 072 bytes) that is not fast or double-fast. Where only the row of smaller sources is something else (level 4), those sources are refused one by one.
+static inline const char* ze_none_refusal(const ZeRows& rows, bool hasDict)
+{
+    if (hasDict) return "no match search (ZHIP_FINDER_NONE, match finder \"none\") does not take a dictionary";
+    if (rows.r[2][6] != 1 && rows.r[2][6] != 2)
+        return "no match search (ZHIP_FINDER_NONE, match finder \"none\") serves the levels whose one-block row is fast or double-fast (levels <= 4, negative levels, explicit strategy 1 / 2)";
+    return nullptr;
+}
+static inline ZeNonePlan ze_none_plan(const ZePlanIn& in)
+{
+    ZeNonePlan s;
+    s.chunk = in.n < 65536 ? in.n : 65536;
+    if (in.knob.echunk && in.knob.echunk < s.chunk) s.chunk = in.knob.echunk;
+    s.grid = ze_entropy_grid(in.dev, s.chunk);                                      // one wave per source, sources claimed from the chunk's counter: the entropy kernel's grid
+    s.metaBytes = s.chunk * sizeof(ZeMeta);
     return s;
 }
 

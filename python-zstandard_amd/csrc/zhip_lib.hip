@@ -18,6 +18,7 @@
 #include "zhip_decode_pipeline.hpp"
 #include "zhip_encode_kernel.hpp"
 #include "zhip_encode_wave.hpp"
+#include "zhip_encode_none.hpp"
 #include "zhip_cparams.hpp"
 #include "zhip_encode_plan.hpp"
 #include "zhip_decode_plan.hpp"
@@ -143,6 +144,12 @@ template <int H> __global__ __launch_bounds__(64) void zhip_encode_match_wave_ke
 {
     __shared__ uint32_t table[1u << H];
     ze_match_wave_body<H>(a, table);
+}
+// no match search (ZHIP_FINDER_NONE, zhip_encode_none.hpp): literals-only frames, one wave per source, launched once per chunk in place of BOTH the match and the entropy kernel
+ZH_GLOBAL __launch_bounds__(64) void zhip_encode_none_kernel(ZhipEncodeArgs a)
+{
+    __shared__ ZeLDS L;
+    ze_none_body(a, L);
 }
 #ifndef ZHIP_WAVE_HLOG
 #define ZHIP_WAVE_HLOG 12                  // table cells of the wave match finder, log2: 12 by the rate measurement (profiles/r11_wave_finder_rate.txt, DESIGN.md 4.2 -- the kernel's rate is its resident
@@ -356,7 +363,7 @@ struct DevBuf {
         p = nullptr; cap = 0;
     }
 };
-#define ZHIP_NTIMER 11
+#define ZHIP_NTIMER 12
 struct KTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // owned: destroyed after reading
     std::vector<std::pair<hipEvent_t, hipEvent_t>> shared;    // borrowed: another timer owns the events
@@ -423,7 +430,7 @@ struct zhip_ctx {
     unsigned long long* profDecode = nullptr;    // ZHIP_PROF phase-timer accumulators, owned by the context (one context == one caller)
     unsigned long long* profPipe = nullptr;
     unsigned long long* profEncode = nullptr;
-    KTimer timer[ZHIP_NTIMER];   // (10: the wave match kernel) 0 fused decode, 1 fused encode, 2 K1 literals, 3 K2 sequences, 4 K3 execution, 5 E1 match, 6 E2 entropy, 7 K1b Huffman streams, 8 the flat match kernel, 9 the decode pipeline of a chunk from K1's start to K3's end (K1b runs beside K2)
+    KTimer timer[ZHIP_NTIMER];   // (10: the wave match kernel, 11: the literals-only kernel of ZHIP_FINDER_NONE) 0 fused decode, 1 fused encode, 2 K1 literals, 3 K2 sequences, 4 K3 execution, 5 E1 match, 6 E2 entropy, 7 K1b Huffman streams, 8 the flat match kernel, 9 the decode pipeline of a chunk from K1's start to K3's end (K1b runs beside K2)
     size_t device_bytes() const
     {
         const DevBuf* all[] = {&pipeMeta, &pipeLit, &pipeCounters, &pipeFallback, &pipeFse, &pipeOrder, &pipeHuf, &pipeOrderLit, &pipeItemFrame, &pipeItemReps, &pipeFrameRecs, &pipeBases, &pipePre, &encWorkspace, &encMeta, &encArena,
@@ -525,7 +532,7 @@ extern "C" const char* zhip_kernel_name(int k)
     static const char* names[ZHIP_NTIMER] = {"zhip_decode_frames_kernel", "zhip_encode_frames_kernel", "zhip_decode_lit_kernel",
                                    "zhip_decode_seq_kernel", "zhip_decode_exec_kernel", "zhip_encode_match_kernel",
                                    "zhip_encode_entropy_kernel", "zhip_decode_huf_kernel", "zhip_encode_match_flat_kernel", "zhip_decode_pipeline_span",
-                                   "zhip_encode_match_wave_kernel"};
+                                   "zhip_encode_match_wave_kernel", "zhip_encode_none_kernel"};
     return k >= 0 && k < ZHIP_NTIMER ? names[k] : "";
 }
 extern "C" int zhip_ctx_kernel_time(zhip_ctx* c, int direction, double* avgMs, uint64_t* launches)
@@ -1035,12 +1042,19 @@ static ZePlanIn plan_inputs(const zhip_ctx* c, size_t n)
     in.knob = c->knob;
     return in;
 }
+// EX over the chunk where the frame kernel in front of it left the checksum trailers to it (ZhipEncodeArgs.xxLater): a lane per frame
+static void launch_trailer(const zhip_ctx* c, const ZhipEncodeArgs& a, size_t cnt, hipStream_t stream)
+{
+    if (!a.xxLater) return;
+    const size_t w = (cnt + 63) / 64, gm = (size_t)c->numCU * 8;
+    hipLaunchKernelGGL(zhip_encode_trailer_kernel, dim3((uint32_t)(w < gm ? w : gm)), dim3(64), 0, stream, a);
+}
 // E2 over the chunk, g2 waves, and EX behind it for checksummed frames (timed with E2)
 static void launch_entropy(const zhip_ctx* c, ZhipEncodeArgs& a, uint32_t g2, size_t cnt, hipStream_t stream)
 {
     a.xxLater = ZHIP_TRAILER_LATER && a.checksumFlag ? 1u : 0u;
     hipLaunchKernelGGL(zhip_encode_entropy_kernel, dim3(g2), dim3(64), 0, stream, a);
-    if (a.xxLater) { const size_t w = (cnt + 63) / 64, gm = (size_t)c->numCU * 8; hipLaunchKernelGGL(zhip_encode_trailer_kernel, dim3((uint32_t)(w < gm ? w : gm)), dim3(64), 0, stream, a); }      // EX
+    launch_trailer(c, a, cnt, stream);
     a.xxLater = 0;
 }
 // the arena of the calls that run no match search of the library's (ZeSlotPlan): no room for a whole chunk's slots: half as many sources per launch, down to 64, before the call fails
@@ -1058,7 +1072,7 @@ static int reserve_slots(zhip_ctx* c, const ZePlanDevice& dev, ZeSlotPlan& s, Zh
 }
 extern "C" int zhip_ctx_set_match_finder(zhip_ctx* c, int finder)
 {
-    if (!c || (finder != ZHIP_FINDER_LIBZSTD && finder != ZHIP_FINDER_WAVE)) { g_lastError = "zhip_ctx_set_match_finder: unknown match finder"; return ZHIP_ERR_UNSUPPORTED; }
+    if (!c || (finder != ZHIP_FINDER_LIBZSTD && finder != ZHIP_FINDER_WAVE && finder != ZHIP_FINDER_NONE)) { g_lastError = "zhip_ctx_set_match_finder: unknown match finder"; return ZHIP_ERR_UNSUPPORTED; }
     c->matchFinder = finder;
     return 0;
 }
@@ -1090,6 +1104,32 @@ static int compress_batch_wave(zhip_ctx* c, ZhipEncodeArgs& a, uint8_t* cbase, s
         launch_entropy(c, a, g2, cnt, stream);
         HIP_TRY(ev.record(3, stream));
         ev.give(c->timer[10], 0, 1); ev.give(c->timer[6], 2, 3);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+// zhip_compress_batch_device under ZHIP_FINDER_NONE: per chunk the literals-only kernel in place of the match kernels AND the entropy kernel, then the trailer kernel where
+// checksums are on. It reserves the chunk's ZeMeta records and nothing else -- no arena, no tables, no entropy workspace -- and touches none of the default finder's state
+// (flat tables and their launch numbers, the placement pick, the arenas), so a context may alternate finders between calls.
+static int compress_batch_none(zhip_ctx* c, ZhipEncodeArgs& a, uint8_t* cbase, size_t n, hipStream_t stream)
+{
+    if (const char* why = ze_none_refusal(a.rows, c->hasCDict)) { g_lastError = why; return ZHIP_ERR_UNSUPPORTED; }
+    const ZeNonePlan s = ze_none_plan(plan_inputs(c, n));
+    if (c->encMeta.reserve(s.metaBytes)) return g_reserveRc;
+    a.meta = (ZeMeta*)c->encMeta.p; a.workspace = nullptr;
+    for (size_t first = 0; first < n; first += s.chunk) {
+        const size_t cnt = n - first < s.chunk ? n - first : s.chunk;
+        a.first = (uint32_t)first; a.count = (uint32_t)cnt;
+        HIP_TRY(hipMemsetAsync(cbase + ZC_E1_WORK, 0, 8, stream));
+        ChunkEvents ev;      // the literals-only kernel + trailer: 0 .. 1
+        if (c->timing) HIP_TRY(ev.create(2));
+        HIP_TRY(ev.record(0, stream));
+        a.xxLater = ZHIP_TRAILER_LATER && a.checksumFlag ? 1u : 0u;
+        hipLaunchKernelGGL(zhip_encode_none_kernel, dim3(s.grid), dim3(64), 0, stream, a);
+        launch_trailer(c, a, cnt, stream);
+        a.xxLater = 0;
+        HIP_TRY(ev.record(1, stream));
+        ev.give(c->timer[11], 0, 1);
         HIP_TRY(hipGetLastError());
     }
     return 0;
@@ -1259,6 +1299,7 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
     HIP_TRY(hipMemsetAsync(cbase + ZC_E1_WORK, 0, 4, stream));
     ZhipEncodeArgs a; enc_args_init(c, a, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, cbase);
     if (c->matchFinder == ZHIP_FINDER_WAVE) return compress_batch_wave(c, a, cbase, n, stream);
+    if (c->matchFinder == ZHIP_FINDER_NONE) return compress_batch_none(c, a, cbase, n, stream);
     // the plan: which kernels, how many sources per launch, how much memory (zhip_encode_plan.hpp)
     ZePlanIn in = plan_inputs(c, n);
     ZePlan p = ze_encode_plan(in);

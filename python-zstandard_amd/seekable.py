@@ -49,7 +49,9 @@ def planes_to_elements(raw, element_size, frame_size):
 
 def compress(data, level=3, frame_size=131072, checksum=False, match_finder="libzstd", element_size=1, **ctx_kw):
     """data -> a seekable stream (bytes). match_finder: "libzstd" (frames byte for byte libzstd's) or "wave" (DeviceBatchContext.set_match_finder: valid zstd,
-    not libzstd's bytes; frame_size at most 131 072). element_size 2, 4 or 8: a typed stream -- data is elements of that many bytes, frame_size counts the
+    not libzstd's bytes; frame_size at most 131 072) or "none" (no match search: every frame is libzstd's literals-only frame of its content, for NUMERIC
+    TENSORS -- with element_size 2, 4 or 8 the fastest compress path, and streams the size of level 3's or up to 13 % smaller on float data; "on data with real
+    repetition they lose badly: the int64 sums here, and any text", 1.9 x on int64 running sums; frame_size at most 131 072 bytes of a plane). element_size 2, 4 or 8: a typed stream -- data is elements of that many bytes, frame_size counts the
     elements of a group (see the module). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
     ctx = DeviceBatchContext(level=level, match_finder=match_finder, **ctx_kw)
     try:
@@ -100,7 +102,7 @@ def decompress_ranges(data, ranges, **ctx_kw):
 
 def compress_records(records, level=3, checksum=False, match_finder="libzstd", **ctx_kw):
     """a list of bytes -> a seekable stream (bytes) with ONE frame per record, compressed as one batch; ``decompress_records`` reads records back by index.
-    match_finder: as in ``compress`` (records of at most 131 072 bytes under "wave"). ctx_kw: what DeviceBatchContext takes. Raises ZstdError."""
+    match_finder: as in ``compress`` (records of at most 131 072 bytes under "wave" and "none"; "none" is for records of numeric data, not text). ctx_kw: what DeviceBatchContext takes. Raises ZstdError."""
     raws = [bytes(r) for r in records]
     table, at = [], 0
     for r in raws:
@@ -157,12 +159,14 @@ def _edited(data, records, level, match_finder, ctx_kw, call):
 def edit(data, picks, records=None, level=3, match_finder="libzstd", **ctx_kw):
     """a seekable stream (bytes) and a pick list -> a new seekable stream (bytes), what is kept not recompressed: picks is a sequence of (0, i) -- frame i of
     `data`, its bytes and its table entry as they are -- and (1, j) -- records[j] (a list of bytes), compressed as in ``compress_records``. A frame or a record
-    may be picked any number of times; the table has checksums exactly when that of `data` has. Raises ZstdError."""
+    may be picked any number of times; the table has checksums exactly when that of `data` has. match_finder: as in ``compress_records``, for the records
+    compressed here (kept frames are not looked at). Raises ZstdError."""
     if records is None:
         return _edited(data, [], level, match_finder, ctx_kw, lambda st, src, table: st.edit(picks))
     return _edited(data, records, level, match_finder, ctx_kw, lambda st, src, table: st.edit(picks, src, table))
 
 
 def append_records(data, records, level=3, match_finder="libzstd", **ctx_kw):
-    """a seekable stream (bytes) with one more frame per record of `records` (a list of bytes) behind its own: ``edit`` with every frame kept. Raises ZstdError."""
+    """a seekable stream (bytes) with one more frame per record of `records` (a list of bytes) behind its own: ``edit`` with every frame kept
+    (match_finder: as in ``compress_records``). Raises ZstdError."""
     return _edited(data, records, level, match_finder, ctx_kw, lambda st, src, table: st.append_records(src, table))
