@@ -24,6 +24,7 @@
 #include "zhip_decode_plan.hpp"
 #include "zhip_seekable_calls.hpp"
 #include "zhip_seekable_typed_calls.hpp"
+#include "zhip_host_calls.hpp"
 
 #define ZHIP_LDS_BYTES (160u * 1024u)      // per CU on gfx950
 static_assert(sizeof(ZpSeqQLDS) <= ZHIP_LDS_BYTES && sizeof(ZpHufKernelLDS) <= ZHIP_LDS_BYTES, "a workgroup's LDS must fit a CU");
@@ -208,7 +209,7 @@ extern "C" int zhip_device_count(void)
     return n;
 }
 extern "C" int zhip_set_device(int d) { HIP_TRY(hipSetDevice(d)); return 0; }
-extern "C" size_t zhip_compress_bound(size_t n) { return n + (n >> 8) + (n < (128u << 10) ? (((128u << 10) - n) >> 11) : 0); }
+extern "C" size_t zhip_compress_bound(size_t n) { return host_compress_bound(n); }
 
 extern "C" const char* zhip_error_name(int code)
 {
@@ -236,86 +237,10 @@ extern "C" const char* zhip_error_name(int code)
     }
 }
 
-// ------------------------------------------------------------------------------------------ frame inspection (host)
-static inline uint32_t rd16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-static inline uint32_t rd24(const uint8_t* p) { return rd16(p) | ((uint32_t)p[2] << 16); }
-static inline uint32_t rd32(const uint8_t* p) { uint32_t v; memcpy(&v, p, 4); return v; }
-static inline uint64_t rd64(const uint8_t* p) { uint64_t v; memcpy(&v, p, 8); return v; }
-
-struct HostFrameHeader { uint64_t contentSize; uint32_t headerSize; uint32_t hasChecksum; uint32_t skippable, skipSize; };
-// RFC 8878 3.1.1.1; restates ZSTD_getFrameHeader_advanced (zstd.c:43668) for the fields the dispatcher needs.
-static int host_frame_header(HostFrameHeader* h, const uint8_t* src, size_t n, int format)
-{
-    const size_t mg = format == ZHIP_FORMAT_ZSTD1_MAGICLESS ? 0 : 4;
-    h->skippable = 0; h->skipSize = 0;
-    if (n < mg + 1) return -ZE_SRC_SIZE_WRONG;
-    if (mg && (rd32(src) & 0xFFFFFFF0u) == ZF_MAGIC_SKIPPABLE) {          // skippable frame: content size 0 (ZSTD_getFrameContentSize, zstd.c:43773)
-        if (n < 8) return -ZE_SRC_SIZE_WRONG;
-        h->skippable = 1; h->skipSize = rd32(src + 4); h->contentSize = 0; h->headerSize = 8; h->hasChecksum = 0;
-        return 0;
-    }
-    if (mg && rd32(src) != ZF_MAGIC) return -ZE_PREFIX_UNKNOWN;
-    src += mg; n -= mg;
-    uint32_t fhd = src[0], dictCode = fhd & 3, single = (fhd >> 5) & 1, fcsCode = fhd >> 6;
-    uint32_t dictBytes = dictCode == 3 ? 4 : dictCode, fcsBytes = fcsCode == 0 ? single : (1u << fcsCode);
-    uint32_t hs = 1 + (single ? 0 : 1) + dictBytes + fcsBytes;
-    if (fhd & 8) return -ZE_FRAMEPARAM_UNSUPPORTED;
-    if (n < hs) return -ZE_SRC_SIZE_WRONG;
-    const uint8_t* p = src + 1 + (single ? 0 : 1) + dictBytes;
-    h->contentSize = ZHIP_CONTENTSIZE_UNKNOWN;
-    if (fcsCode == 0) { if (single) h->contentSize = p[0]; }
-    else if (fcsCode == 1) h->contentSize = (uint64_t)rd16(p) + 256;
-    else if (fcsCode == 2) h->contentSize = rd32(p);
-    else h->contentSize = rd64(p);
-    h->headerSize = (uint32_t)mg + hs; h->hasChecksum = (fhd >> 2) & 1;
-    return 0;
-}
-// how many blocks a frame has (0: not a frame this walk can follow -- the kernels will say what is wrong with it). The host-buffer decompress call uses it to tell frames of
-// SEVERAL blocks from frames of one: libzstd's block splitter (levels 16 and up) cuts even a 128 KiB source into many, and those belong to the pipeline's several-block mode,
-// not -- one wave each -- to the generic kernel (round 6: 2 048 level-19 frames of 128 KiB took 44 ms there, 6 GB/s)
-static uint32_t host_count_blocks(const uint8_t* src, size_t n, int format)
-{
-    HostFrameHeader h;
-    if (host_frame_header(&h, src, n, format) < 0 || h.skippable) return 0;
-    size_t pos = h.headerSize; uint32_t nb = 0;
-    for (;;) {
-        if (pos + 3 > n) return 0;
-        const uint32_t bh = rd24(src + pos); pos += 3;
-        const uint32_t type = (bh >> 1) & 3, bs = bh >> 3;
-        if (type == 3) return 0;
-        const size_t body = type == 1 ? 1 : bs;
-        if (pos + body > n) return 0;
-        pos += body; nb++;
-        if (bh & 1) return nb;
-        if (nb > 65535) return 0;
-    }
-}
-extern "C" uint64_t zhip_frame_content_size_format(const void* src, size_t n, int format)
-{
-    HostFrameHeader h;
-    if (host_frame_header(&h, (const uint8_t*)src, n, format) < 0) return ZHIP_CONTENTSIZE_ERROR;
-    return h.contentSize;
-}
+// ------------------------------------------------------------------------------------------ frame inspection (host: zhip_host_calls.hpp)
+extern "C" uint64_t zhip_frame_content_size_format(const void* src, size_t n, int format) { return host_frame_content_size((const uint8_t*)src, n, format); }
 extern "C" uint64_t zhip_frame_content_size(const void* src, size_t n) { return zhip_frame_content_size_format(src, n, ZHIP_FORMAT_ZSTD1); }
-extern "C" int64_t zhip_find_frame_compressed_size_format(const void* srcv, size_t n, int format)
-{
-    const uint8_t* src = (const uint8_t*)srcv;
-    HostFrameHeader h; int e = host_frame_header(&h, src, n, format); if (e < 0) return e;
-    if (h.skippable) return (uint64_t)h.skipSize + 8 > n ? -ZE_SRC_SIZE_WRONG : (int64_t)h.skipSize + 8;      // readSkippableFrameSize (zstd.c:43795)
-    size_t pos = h.headerSize;
-    for (;;) {
-        if (pos + 3 > n) return -ZE_SRC_SIZE_WRONG;
-        uint32_t bh = rd24(src + pos); pos += 3;
-        uint32_t type = (bh >> 1) & 3, bs = bh >> 3;
-        if (type == 3) return -ZE_CORRUPTION;
-        size_t c = type == 1 ? 1 : bs;
-        if (pos + c > n) return -ZE_SRC_SIZE_WRONG;
-        pos += c;
-        if (bh & 1) break;
-    }
-    if (h.hasChecksum) { if (pos + 4 > n) return -ZE_SRC_SIZE_WRONG; pos += 4; }
-    return (int64_t)pos;
-}
+extern "C" int64_t zhip_find_frame_compressed_size_format(const void* src, size_t n, int format) { return host_frame_compressed_size((const uint8_t*)src, n, format); }
 extern "C" int64_t zhip_find_frame_compressed_size(const void* src, size_t n) { return zhip_find_frame_compressed_size_format(src, n, ZHIP_FORMAT_ZSTD1); }
 extern "C" void zhip_get_cparams(int level, uint64_t srcSizeHint, size_t dictSize, zhip_compression_parameters* out) { if (out) zh_get_cparams(level, srcSizeHint, dictSize, out); }
 
@@ -1588,25 +1513,6 @@ static int ensure_pinned(zhip_ctx* c, size_t n)          // small pinned area fo
     c->pinnedCap = want;
     return 0;
 }
-// items [lo, hi) -> stage, item i at offset segs[i].offset - segs[lo].offset. Big chunks are split over host threads by bytes.
-static void pack_items(uint8_t* stage, const zhip_item* items, const zhip_segment* segs, size_t lo, size_t hi, unsigned packThreads)
-{
-    const uint64_t base = segs[lo].offset, bytes = hi > lo ? segs[hi - 1].offset + segs[hi - 1].length - base : 0;
-    auto run = [&](size_t a, size_t b) { for (size_t i = a; i < b; i++) if (items[i].srcSize) memcpy(stage + (segs[i].offset - base), items[i].src, items[i].srcSize); };
-    unsigned nt = bytes >= ((uint64_t)32 << 20) ? (packThreads ? packThreads : ZHIP_PACK_THREADS) : 1;
-    if (nt <= 1 || hi - lo < 2 * nt) { run(lo, hi); return; }
-    std::vector<std::thread> th;
-    size_t a = lo;
-    for (unsigned t = 0; t < nt && a < hi; t++) {
-        const uint64_t target = base + bytes * (t + 1) / nt;
-        size_t b = a;
-        while (b < hi && (t + 1 == nt || segs[b].offset + segs[b].length <= target)) b++;
-        if (b == a) b = a + 1;
-        th.emplace_back(run, a, b);
-        a = b;
-    }
-    for (auto& t : th) t.join();
-}
 // one lazily created context per calling thread, destroyed when the thread exits; re-created when the thread switched devices
 struct TlsCtx { zhip_ctx* c = nullptr; ~TlsCtx() { if (c) zhip_ctx_destroy(c); } };
 static thread_local TlsCtx g_tls;
@@ -1662,145 +1568,153 @@ extern "C" void zhip_free_outbufs(zhip_outbuf* bufs, size_t n, int freePayload)
     free(bufs);
 }
 
-// chunk boundaries [cut[k], cut[k+1]) over n items: a chunk closes when its input or output bytes reach maxBytes or it holds maxItems
-// items. segs: [0,n) source, [n,2n) destination.
-// firstItems (0: like the others): a smaller first chunk shortens the pipeline's fill -- the time before the first kernel can start
-static std::vector<size_t> host_chunks(const zhip_segment* segs, size_t n, uint64_t maxBytes, size_t maxItems, size_t firstItems = 0)
-{
-    std::vector<size_t> cut(1, 0);
-    uint64_t in = 0, out = 0; size_t cnt = 0;
-    for (size_t i = 0; i < n; i++) {
-        in += segs[i].length; out += segs[n + i].length; cnt++;
-        const size_t lim = cut.size() == 1 && firstItems ? firstItems : maxItems;
-        if (in >= maxBytes || out >= maxBytes || cnt >= lim) { cut.push_back(i + 1); in = out = 0; cnt = 0; }
-    }
-    if (cut.back() != n) cut.push_back(n);
-    return cut;
-}
-// items [lo, hi) -> their place in the device source arena, in steps of <= ZHIP_STAGE_BYTES through the two pinned staging slots: the
-// packing of step s+1 (host threads) overlaps the H2D copy of step s. Every copy is only ENQUEUED on hpH2D; `done` is recorded behind
+// items [lo, hi) -> their place in the device source arena, in steps of <= ZHIP_STAGE_BYTES (host_upload_step) through the two pinned staging slots: the
+// packing of step s+1 (host threads, from ZHIP_PACK_BYTES on) overlaps the H2D copy of step s. Every copy is only ENQUEUED on hpH2D; `done` is recorded behind
 // the last one. A slot is reused once the copy that last read it has finished (its event).
 #define ZHIP_STAGE_BYTES ((uint64_t)512 << 20)
+#define ZHIP_PACK_BYTES ((uint64_t)32 << 20)
 static int upload_items(zhip_ctx* c, const zhip_item* items, const zhip_segment* segs, size_t lo, size_t hi, hipEvent_t done)
 {
-    size_t a = lo;
-    while (a < hi) {
-        size_t b = a; uint64_t bytes = 0;
-        while (b < hi && (b == a || bytes + segs[b].length <= ZHIP_STAGE_BYTES)) { bytes += segs[b].length; b++; }
+    for (size_t a = lo; a < hi;) {
+        const HostStep st = host_upload_step(segs, a, hi, ZHIP_STAGE_BYTES);
         const int slot = c->hpNextSlot; c->hpNextSlot ^= 1;
         if (hipEventSynchronize(c->hpStageFree[slot]) != hipSuccess) return ZHIP_ERR_HIP;
-        if (ensure_stage(c, slot, bytes + 16)) return ZHIP_ERR_HIP;
-        pack_items((uint8_t*)c->hpStage[slot], items, segs, a, b, c->knob.packThreads);
-        if (bytes && hipMemcpyAsync((uint8_t*)c->hSrc.p + segs[a].offset, c->hpStage[slot], bytes, hipMemcpyHostToDevice, c->hpH2D) != hipSuccess) return ZHIP_ERR_HIP;
+        if (ensure_stage(c, slot, st.bytes + 16)) return ZHIP_ERR_HIP;
+        pack_items((uint8_t*)c->hpStage[slot], items, segs, st.a, st.b, ZHIP_PACK_BYTES, c->knob.packThreads ? c->knob.packThreads : ZHIP_PACK_THREADS);
+        if (st.bytes && hipMemcpyAsync((uint8_t*)c->hSrc.p + segs[a].offset, c->hpStage[slot], st.bytes, hipMemcpyHostToDevice, c->hpH2D) != hipSuccess) return ZHIP_ERR_HIP;
         if (hipEventRecord(c->hpStageFree[slot], c->hpH2D) != hipSuccess) return ZHIP_ERR_HIP;
-        a = b;
+        a = st.b;
     }
     return hipEventRecord(done, c->hpH2D) == hipSuccess ? 0 : ZHIP_ERR_HIP;
 }
 static void empty_outbuf(zhip_outbuf* ob) { ob->data = malloc(1); ob->segs = (zhip_segment*)malloc(sizeof(zhip_segment)); ob->dataSize = 0; ob->nSegs = 0; }
 
-// ONE device (the calling thread's current one): the chunked three-stream pipeline
+// One host-buffer call on ONE device (the calling thread's current one): what the two directions share around their chunk loops. It owns the call's events and its
+// output array: however the call ends the events are destroyed, and the outputs freed unless finish() handed them to the caller. The plan -- segments, cuts, meta
+// layouts, verdicts -- is zhip_host_calls.hpp's.
+struct HostCall {
+    const bool compress;
+    zhip_ctx* c; zhip_error* err;
+    zhip_outbuf* ob = nullptr; size_t nOb = 0;      // one output per chunk (one empty one for no chunk)
+    hipEvent_t evUp = nullptr, evK = nullptr;       // behind a chunk's upload; decompress: behind its kernels
+    std::vector<hipEvent_t> evMeta;                 // compress: behind a chunk's sizes, status and total on their way back
+    HostCall(bool compress_, zhip_outbuf** out, size_t* nOut, zhip_error* err_) : compress(compress_), err(err_)
+    {
+        if (err) memset(err, 0, sizeof *err);
+        *out = nullptr; *nOut = 0;
+        c = tls_ctx();
+    }
+    ~HostCall() { release(); }
+    HostCall(const HostCall&) = delete;
+    void drop_events()
+    {
+        for (auto& e : evMeta) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        if (evUp) (void)hipEventDestroy(evUp);
+        if (evK) (void)hipEventDestroy(evK);
+        evUp = evK = nullptr;
+    }
+    void release() { drop_events(); if (ob) zhip_free_outbufs(ob, nOb, 1); ob = nullptr; }
+    int fail(int kind, size_t index = 0, int zerr = 0, uint64_t d0 = 0, uint64_t d1 = 0)
+    {
+        if (kind == ZHIP_ERR_HIP) hip_fail(hipGetLastError(), compress ? "host compress pipeline" : "host decompress pipeline");
+        (void)hipDeviceSynchronize();          // nothing of the call still runs when its events and its outputs go
+        release();
+        return set_err(err, kind, index, zerr, d0, d1);
+    }
+    // the prologue behind pass 1 and the cuts: streams, arenas (compress: the dense frames too), the meta areas of the direction's layout, an output per chunk, the
+    // events, and the segment table on the device
+    int begin(const std::vector<zhip_segment>& segs, size_t n, size_t nChunks, uint64_t srcTotal, uint64_t dstTotal, size_t dBytes, size_t hBytes)
+    {
+        if (host_pipe_init(c)) return set_err(err, ZHIP_ERR_HIP, 0, 0);
+        if (c->hSrc.reserve(srcTotal + 16) || c->hDst.reserve(dstTotal + 16) || (compress && c->hDense.reserve(dstTotal + 16)) ||
+            c->hSegs.reserve(2 * n * sizeof(zhip_segment) + 16) || c->hStatus.reserve(dBytes)) return set_err(err, g_reserveRc, 0, 0);
+        if (ensure_pinned(c, hBytes)) return set_err(err, ZHIP_ERR_HIP, 0, 0);
+        ob = (zhip_outbuf*)calloc(nChunks ? nChunks : 1, sizeof(zhip_outbuf));
+        if (!ob) return set_err(err, ZHIP_ERR_NO_MEMORY, 0, 0);
+        nOb = nChunks ? nChunks : 1;
+        if (compress) evMeta.assign(nChunks, nullptr);
+        if (hipEventCreateWithFlags(&evUp, hipEventDisableTiming) != hipSuccess || (!compress && hipEventCreateWithFlags(&evK, hipEventDisableTiming) != hipSuccess)) return fail(ZHIP_ERR_HIP);
+        if (hipMemcpyAsync(c->hSegs.p, segs.data(), 2 * n * sizeof(zhip_segment), hipMemcpyHostToDevice, c->hpH2D) != hipSuccess ||
+            hipStreamSynchronize(c->hpH2D) != hipSuccess) return fail(ZHIP_ERR_HIP);      // segs is pageable: wait before anything reads the table
+        return 0;
+    }
+    // the epilogue: everything has arrived ..
+    int drain() { return hipStreamSynchronize(c->hpD2H) != hipSuccess || hipStreamSynchronize(c->hpCompute) != hipSuccess ? fail(ZHIP_ERR_HIP) : 0; }
+    // .. and the outputs are the caller's
+    int finish(zhip_outbuf** out, size_t* nOut, size_t nChunks)
+    {
+        drop_events();
+        if (nChunks == 0) empty_outbuf(&ob[0]);
+        *out = ob; *nOut = nOb; ob = nullptr;
+        tls_trim(c);
+        return ZHIP_ERR_NONE;
+    }
+};
+
+// decompress: the chunked three-stream pipeline
 static int decompress_batch_one(const zhip_dparams* params, const zhip_item* items, size_t n, int requireSizes,
                                 zhip_outbuf** out, size_t* nOut, zhip_error* err)
 {
     const bool allowShort = (requireSizes & 2) != 0;   // dstSize is a capacity (one-shot decompress with max_output_size)
-    if (err) memset(err, 0, sizeof *err);
-    *out = nullptr; *nOut = 0;
-    zhip_ctx* c = tls_ctx();
+    HostCall call(false, out, nOut, err);
+    zhip_ctx* c = call.c;
     if (!c) return set_err(err, ZHIP_ERR_HIP, 0, 0);
-    // pass 1 (decompress_worker pass 1, decompressor.c:981-1014): every frame needs a known decompressed size
     std::vector<zhip_segment> segs(2 * n);           // [0,n) source, [n,2n) destination
     std::vector<uint32_t> nBlocks(n);                // blocks per frame (0: unknown), from the block headers (host_count_blocks)
     const int format = params ? params->format : ZHIP_FORMAT_ZSTD1;
     uint64_t srcTotal = 0, dstTotal = 0;
-    for (size_t i = 0; i < n; i++) {
-        uint64_t ds = items[i].dstSize;
-        if (ds == 0) {
-            uint64_t fcs = zhip_frame_content_size_format(items[i].src, items[i].srcSize, format);
-            if (fcs == ZHIP_CONTENTSIZE_ERROR || fcs == ZHIP_CONTENTSIZE_UNKNOWN) return set_err(err, ZHIP_ERR_UNKNOWN_SIZE, i, 0);
-            ds = fcs;
-        }
-        // the sizes come from untrusted frame headers: a claimed size that cannot be allocated is "out of memory" (what the reference's
-        // malloc of the destination reports, decompressor.c:1085-1090), never a wrapped sum
-        if (ds > ((uint64_t)1 << 46) || dstTotal + ds > ((uint64_t)1 << 46)) return set_err(err, ZHIP_ERR_NO_MEMORY, i, 0);
-        segs[i].offset = srcTotal; segs[i].length = items[i].srcSize; srcTotal += items[i].srcSize;
-        segs[n + i].offset = dstTotal; segs[n + i].length = ds; dstTotal += ds;
-        nBlocks[i] = host_count_blocks((const uint8_t*)items[i].src, items[i].srcSize, format);
-    }
+    const HostRefusal no = host_decompress_segments(items, n, format, segs.data(), nBlocks.data(), &srcTotal, &dstTotal);
+    if (no.kind) return set_err(err, no.kind, no.index, 0);
     int r = zhip_ctx_set_dformat(c, format, params ? params->maxWindowSize : 0);
     if (r) return set_err(err, r, 0, 0);
     r = zhip_ctx_set_ddict(c, params ? params->dict : nullptr, params ? params->dictSize : 0, params ? params->dictType : ZHIP_DICT_AUTO);
     if (r < 0) return set_err(err, ZHIP_ERR_ZSTD, 0, -r);
     if (r) return set_err(err, r, 0, 0);
-    if (host_pipe_init(c)) return set_err(err, ZHIP_ERR_HIP, 0, 0);
     // the kernels are several times faster than the link here: chunks of ~1 GiB of output keep all three streams busy
     // (a small FIRST chunk -- ZHIP_HCHUNK_D0 items, default 2 048 for batches above 8 192 -- starts the copy back, which is what the call waits for, a few ms after
     // the call instead of after a whole chunk's packing, upload and kernels)
     const std::vector<size_t> cut = host_chunks(segs.data(), n, (uint64_t)1 << 30, 32768, n > 8192 ? c->knob.hchunkD0 : 0);
     const size_t nChunks = cut.size() - 1;
-    if (c->hSrc.reserve(srcTotal + 16) || c->hDst.reserve(dstTotal + 16) || c->hSegs.reserve(2 * n * sizeof(zhip_segment) + 16) ||
-        c->hStatus.reserve(n * (sizeof(uint64_t) + sizeof(int32_t)) + 16)) return set_err(err, g_reserveRc, 0, 0);
-    if (ensure_pinned(c, n * (sizeof(uint64_t) + sizeof(int32_t)) + 16)) return set_err(err, ZHIP_ERR_HIP, 0, 0);
-    zhip_outbuf* ob = (zhip_outbuf*)calloc(nChunks ? nChunks : 1, sizeof(zhip_outbuf));
-    if (!ob) return set_err(err, ZHIP_ERR_NO_MEMORY, 0, 0);
-    hipEvent_t evUp = nullptr, evK = nullptr;
-    auto fail = [&](int kind, size_t index = 0, int zerr = 0, uint64_t d0 = 0, uint64_t d1 = 0) -> int {
-        if (kind == ZHIP_ERR_HIP) hip_fail(hipGetLastError(), "host decompress pipeline");
-        (void)hipDeviceSynchronize();
-        if (evUp) (void)hipEventDestroy(evUp);
-        if (evK) (void)hipEventDestroy(evK);
-        zhip_free_outbufs(ob, nChunks ? nChunks : 1, 1);
-        return set_err(err, kind, index, zerr, d0, d1);
-    };
-    if (hipEventCreateWithFlags(&evUp, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&evK, hipEventDisableTiming) != hipSuccess) return fail(ZHIP_ERR_HIP);
-    if (hipMemcpyAsync(c->hSegs.p, segs.data(), 2 * n * sizeof(zhip_segment), hipMemcpyHostToDevice, c->hpH2D) != hipSuccess ||
-        hipStreamSynchronize(c->hpH2D) != hipSuccess) return fail(ZHIP_ERR_HIP);      // segs is pageable: wait before anything reads the table
-    uint64_t* dSizes = (uint64_t*)c->hStatus.p;
-    int32_t* dStatus = (int32_t*)((uint8_t*)c->hStatus.p + n * sizeof(uint64_t));
-    uint64_t* hSizes = (uint64_t*)c->pinned;
-    int32_t* hStatus = (int32_t*)((uint8_t*)c->pinned + n * sizeof(uint64_t));
+    const HostDecompressLayout l = host_decompress_layout(n);
+    if (const int e = call.begin(segs, n, nChunks, srcTotal, dstTotal, l.dBytes, l.hBytes)) return e;
+    uint64_t* dSizes = (uint64_t*)((uint8_t*)c->hStatus.p + l.dSizes);
+    int32_t* dStatus = (int32_t*)((uint8_t*)c->hStatus.p + l.dStatus);
+    uint64_t* hSizes = (uint64_t*)((uint8_t*)c->pinned + l.hSizes);
+    int32_t* hStatus = (int32_t*)((uint8_t*)c->pinned + l.hStatus);
     const zhip_segment* dSegs = (const zhip_segment*)c->hSegs.p;
+    zhip_outbuf* ob = call.ob;
+    // payloads, sizes and statuses all go back on the third stream, and every item is judged once everything has arrived
     for (size_t k = 0; k < nChunks; k++) {
         const size_t lo = cut[k], hi = cut[k + 1], cnt = hi - lo;
         const uint64_t outBytes = segs[n + hi - 1].offset + segs[n + hi - 1].length - segs[n + lo].offset;
-        if (upload_items(c, items, segs.data(), lo, hi, evUp)) return fail(ZHIP_ERR_HIP);
-        if (hipStreamWaitEvent(c->hpCompute, evUp, 0) != hipSuccess) return fail(ZHIP_ERR_HIP);
+        if (upload_items(c, items, segs.data(), lo, hi, call.evUp)) return call.fail(ZHIP_ERR_HIP);
+        if (hipStreamWaitEvent(c->hpCompute, call.evUp, 0) != hipSuccess) return call.fail(ZHIP_ERR_HIP);
         ZdHints hint = zd_host_hint(&segs[n + lo].length, 2, nBlocks.data() + lo, cnt);      // (the frames' content sizes: the length of every destination segment)
         if (!hint.size) hint.size = c->itemHint;
         r = decompress_batch(c, hint, c->hSrc.p, dSegs + lo, cnt, c->hDst.p, dSegs + n + lo, dSizes + lo, dStatus + lo, c->hpCompute);
-        if (r) return fail(r);
-        if (hipEventRecord(evK, c->hpCompute) != hipSuccess || hipStreamWaitEvent(c->hpD2H, evK, 0) != hipSuccess) return fail(ZHIP_ERR_HIP);
+        if (r) return call.fail(r);
+        if (hipEventRecord(call.evK, c->hpCompute) != hipSuccess || hipStreamWaitEvent(c->hpD2H, call.evK, 0) != hipSuccess) return call.fail(ZHIP_ERR_HIP);
         // the chunk's output goes straight into its (pinned) result payload
         ob[k].data = pin_pool().take((size_t)outBytes);
         ob[k].segs = (zhip_segment*)malloc((cnt ? cnt : 1) * sizeof(zhip_segment));
-        if (!ob[k].data || !ob[k].segs) return fail(ZHIP_ERR_NO_MEMORY, lo);
+        if (!ob[k].data || !ob[k].segs) return call.fail(ZHIP_ERR_NO_MEMORY, lo);
         ob[k].dataSize = (size_t)outBytes; ob[k].nSegs = cnt;
         if ((outBytes && hipMemcpyAsync(ob[k].data, (uint8_t*)c->hDst.p + segs[n + lo].offset, outBytes, hipMemcpyDeviceToHost, c->hpD2H) != hipSuccess) ||
             hipMemcpyAsync(hSizes + lo, dSizes + lo, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, c->hpD2H) != hipSuccess ||
-            hipMemcpyAsync(hStatus + lo, dStatus + lo, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, c->hpD2H) != hipSuccess) return fail(ZHIP_ERR_HIP);
+            hipMemcpyAsync(hStatus + lo, dStatus + lo, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, c->hpD2H) != hipSuccess) return call.fail(ZHIP_ERR_HIP);
     }
-    if (hipStreamSynchronize(c->hpD2H) != hipSuccess || hipStreamSynchronize(c->hpCompute) != hipSuccess) return fail(ZHIP_ERR_HIP);
+    if (const int e = call.drain()) return e;
     for (size_t k = 0; k < nChunks; k++) {
-        const size_t lo = cut[k], hi = cut[k + 1];
-        const uint64_t base = segs[n + lo].offset;
-        for (size_t i = lo; i < hi; i++) {
-            if (hStatus[i]) return fail(ZHIP_ERR_ZSTD, i, hStatus[i]);
-            if (hSizes[i] != segs[n + i].length && !(allowShort && hSizes[i] < segs[n + i].length)) return fail(ZHIP_ERR_SIZE_MISMATCH, i, 0, hSizes[i], segs[n + i].length);
-            ob[k].segs[i - lo].offset = segs[n + i].offset - base; ob[k].segs[i - lo].length = hSizes[i];
-        }
+        const HostVerdict v = host_decompress_verdict(segs.data() + n, hSizes, hStatus, cut[k], cut[k + 1], allowShort, ob[k].segs);
+        if (v.kind) return call.fail(v.kind, v.index, v.zerr, v.d0, v.d1);
     }
-    (void)hipEventDestroy(evUp); (void)hipEventDestroy(evK);
-    if (nChunks == 0) empty_outbuf(&ob[0]);
-    *out = ob; *nOut = nChunks ? nChunks : 1;
-    tls_trim(c);
-    return ZHIP_ERR_NONE;
+    return call.finish(out, nOut, nChunks);
 }
 
 static int compress_batch_one(const zhip_cparams* params, const zhip_item* items, size_t n, zhip_outbuf** out, size_t* nOut, zhip_error* err)
 {
-    if (err) memset(err, 0, sizeof *err);
-    *out = nullptr; *nOut = 0;
-    zhip_ctx* c = tls_ctx();
+    HostCall call(true, out, nOut, err);
+    zhip_ctx* c = call.c;
     if (!c) return set_err(err, ZHIP_ERR_HIP, 0, 0);
     zhip_cparams defaults; memset(&defaults, 0, sizeof defaults);
     defaults.level = 3; defaults.contentSizeFlag = 1; defaults.dictIDFlag = 1;
@@ -1813,21 +1727,10 @@ static int compress_batch_one(const zhip_cparams* params, const zhip_item* items
         empty_outbuf(e); *out = e; *nOut = 1;
         return ZHIP_ERR_NONE;
     }
-    // like compress_worker (compressor.c:913-947) every item gets a ZSTD_compressBound-sized slot; the frames are compacted on the
-    // device, chunk by chunk, and only they travel back
     std::vector<zhip_segment> segs(2 * n);
     uint64_t srcTotal = 0, dstTotal = 0;
-    for (size_t i = 0; i < n; i++) {
-        if (items[i].srcSize >= (1ull << 31)) {
-            g_lastError = "inputs of 2 GiB and more are not implemented in the HIP backend";
-            return set_err(err, ZHIP_ERR_UNSUPPORTED, i, 0);
-        }
-        segs[i].offset = srcTotal; segs[i].length = items[i].srcSize; srcTotal += items[i].srcSize;
-        uint64_t b = zhip_compress_bound(items[i].srcSize);
-        b = (b + 15) & ~(uint64_t)15;
-        segs[n + i].offset = dstTotal; segs[n + i].length = b; dstTotal += b;
-    }
-    if (host_pipe_init(c)) return set_err(err, ZHIP_ERR_HIP, 0, 0);
+    const HostRefusal no = host_compress_segments(items, n, segs.data(), &srcTotal, &dstTotal);
+    if (no.kind) { g_lastError = no.text; return set_err(err, no.kind, no.index, 0); }
     // the match kernel is a per-frame latency chain (its time barely depends on the batch below ~16 K frames), so compress chunks are
     // large: two of them overlap one's upload with the other's kernels, more would only add chains end to end
     // (round 4 ran these chunks side by side on their own streams, each in its own part of the encode arenas -- +8 % at best and an unexplained 5 x
@@ -1837,55 +1740,40 @@ static int compress_batch_one(const zhip_cparams* params, const zhip_item* items
     const std::vector<size_t> cut = host_chunks(segs.data(), n, (uint64_t)4 << 30, c->knob.hchunkE, n > c->knob.hchunkE ? c->knob.hchunkE0 : 0);
     const size_t nChunks = cut.size() - 1;
     // device: sources, slots, dense frames, segment table, [sizes | offsets | chunk totals | status]
-    const size_t metaBytes = n * (2 * sizeof(uint64_t) + sizeof(int32_t)) + (nChunks + 1) * sizeof(uint64_t) + 32;
-    if (c->hSrc.reserve(srcTotal + 16) || c->hDst.reserve(dstTotal + 16) || c->hDense.reserve(dstTotal + 16) || c->hSegs.reserve(2 * n * sizeof(zhip_segment) + 16) ||
-        c->hStatus.reserve(metaBytes)) return set_err(err, g_reserveRc, 0, 0);
-    if (ensure_pinned(c, metaBytes)) return set_err(err, ZHIP_ERR_HIP, 0, 0);
-    zhip_outbuf* ob = (zhip_outbuf*)calloc(nChunks ? nChunks : 1, sizeof(zhip_outbuf));
-    if (!ob) return set_err(err, ZHIP_ERR_NO_MEMORY, 0, 0);
-    std::vector<hipEvent_t> evMeta(nChunks, nullptr);
-    hipEvent_t evUp = nullptr;
-    auto fail = [&](int kind, size_t index = 0, int zerr = 0) -> int {
-        if (kind == ZHIP_ERR_HIP) hip_fail(hipGetLastError(), "host compress pipeline");
-        (void)hipDeviceSynchronize();
-        for (auto e : evMeta) if (e) (void)hipEventDestroy(e);
-        if (evUp) (void)hipEventDestroy(evUp);
-        zhip_free_outbufs(ob, nChunks ? nChunks : 1, 1);
-        return set_err(err, kind, index, zerr);
-    };
-    if (hipEventCreateWithFlags(&evUp, hipEventDisableTiming) != hipSuccess) return fail(ZHIP_ERR_HIP);
-    if (hipMemcpyAsync(c->hSegs.p, segs.data(), 2 * n * sizeof(zhip_segment), hipMemcpyHostToDevice, c->hpH2D) != hipSuccess ||
-        hipStreamSynchronize(c->hpH2D) != hipSuccess) return fail(ZHIP_ERR_HIP);
-    uint64_t* dSizes = (uint64_t*)c->hStatus.p; uint64_t* dOffs = dSizes + n; uint64_t* dTotals = dOffs + n; int32_t* dStatus = (int32_t*)(dTotals + nChunks + 1);
-    uint64_t* hSizes = (uint64_t*)c->pinned; uint64_t* hTotals = hSizes + 2 * n; int32_t* hStatus = (int32_t*)(hTotals + nChunks + 1);
+    const HostCompressLayout l = host_compress_layout(n, nChunks);
+    if (const int e = call.begin(segs, n, nChunks, srcTotal, dstTotal, l.dBytes, l.hBytes)) return e;
+    uint8_t* dMeta = (uint8_t*)c->hStatus.p; uint8_t* hMeta = (uint8_t*)c->pinned;
+    uint64_t* dSizes = (uint64_t*)(dMeta + l.dSizes); uint64_t* dOffs = (uint64_t*)(dMeta + l.dOffs); uint64_t* dTotals = (uint64_t*)(dMeta + l.dTotals); int32_t* dStatus = (int32_t*)(dMeta + l.dStatus);
+    uint64_t* hSizes = (uint64_t*)(hMeta + l.hSizes); uint64_t* hTotals = (uint64_t*)(hMeta + l.hTotals); int32_t* hStatus = (int32_t*)(hMeta + l.hStatus);
     const zhip_segment* dSegs = (const zhip_segment*)c->hSegs.p;
+    zhip_outbuf* ob = call.ob;
     // the host learns a chunk's total one chunk behind: while chunk k is being packed / copied / compressed, chunk k-1's sizes have
     // arrived, its payload is allocated (exact size) and its frames travel back on the third stream
     auto collect = [&](size_t k) -> int {
         const size_t lo = cut[k], hi = cut[k + 1], cnt = hi - lo;
-        if (hipEventSynchronize(evMeta[k]) != hipSuccess) return fail(ZHIP_ERR_HIP);
-        (void)hipEventDestroy(evMeta[k]); evMeta[k] = nullptr;
-        for (size_t i = lo; i < hi; i++) if (hStatus[i]) return fail(ZHIP_ERR_ZSTD, i, hStatus[i]);
+        if (hipEventSynchronize(call.evMeta[k]) != hipSuccess) return call.fail(ZHIP_ERR_HIP);
+        (void)hipEventDestroy(call.evMeta[k]); call.evMeta[k] = nullptr;
+        const HostVerdict v = host_compress_verdict(hStatus, lo, hi);
+        if (v.kind) return call.fail(v.kind, v.index, v.zerr);
         const uint64_t total = hTotals[k];
         ob[k].data = pin_pool().take((size_t)total);
         ob[k].segs = (zhip_segment*)malloc((cnt ? cnt : 1) * sizeof(zhip_segment));
-        if (!ob[k].data || !ob[k].segs) return fail(ZHIP_ERR_NO_MEMORY, lo);
+        if (!ob[k].data || !ob[k].segs) return call.fail(ZHIP_ERR_NO_MEMORY, lo);
         ob[k].dataSize = (size_t)total; ob[k].nSegs = cnt;
-        uint64_t o = 0;
-        for (size_t i = lo; i < hi; i++) { ob[k].segs[i - lo].offset = o; ob[k].segs[i - lo].length = hSizes[i]; o += hSizes[i]; }
+        (void)host_compress_out_segments(hSizes, lo, hi, ob[k].segs);
         // the compaction finished before evMeta (same stream), so the copy needs no further dependency
-        if (total && hipMemcpyAsync(ob[k].data, (uint8_t*)c->hDense.p + segs[n + lo].offset, total, hipMemcpyDeviceToHost, c->hpD2H) != hipSuccess) return fail(ZHIP_ERR_HIP);
+        if (total && hipMemcpyAsync(ob[k].data, (uint8_t*)c->hDense.p + segs[n + lo].offset, total, hipMemcpyDeviceToHost, c->hpD2H) != hipSuccess) return call.fail(ZHIP_ERR_HIP);
         return 0;
     };
     for (size_t k = 0; k < nChunks; k++) {
         const size_t lo = cut[k], hi = cut[k + 1], cnt = hi - lo;
         hipStream_t sk = c->hpCompute;
-        if (upload_items(c, items, segs.data(), lo, hi, evUp)) return fail(ZHIP_ERR_HIP);
-        if (hipStreamWaitEvent(sk, evUp, 0) != hipSuccess) return fail(ZHIP_ERR_HIP);
+        if (upload_items(c, items, segs.data(), lo, hi, call.evUp)) return call.fail(ZHIP_ERR_HIP);
+        if (hipStreamWaitEvent(sk, call.evUp, 0) != hipSuccess) return call.fail(ZHIP_ERR_HIP);
         { size_t mx = 0; for (size_t i = lo; i < hi; i++) if (items[i].srcSize > mx) mx = items[i].srcSize; c->srcMaxHint = mx; }
         r = zhip_compress_batch_device(c, c->hSrc.p, dSegs + lo, cnt, c->hDst.p, dSegs + n + lo, dSizes + lo, dStatus + lo, sk);
         c->srcMaxHint = 0;
-        if (r) return fail(r);
+        if (r) return call.fail(r);
         hipLaunchKernelGGL(zhip_scan_sizes_kernel, dim3(1), dim3(1024), 0, sk, dSizes + lo, dStatus + lo, (uint32_t)cnt, dOffs + lo, dTotals + k);
         const uint32_t gridC = (uint32_t)(cnt < (size_t)c->numCU * 16 ? cnt : (size_t)c->numCU * 16);
         hipLaunchKernelGGL(zhip_compact_kernel, dim3(gridC ? gridC : 1), dim3(64), 0, sk, (const uint8_t*)c->hDst.p, dSegs + n + lo, dSizes + lo, dStatus + lo,
@@ -1895,16 +1783,12 @@ static int compress_batch_one(const zhip_cparams* params, const zhip_item* items
             hipMemcpyAsync(hSizes + lo, dSizes + lo, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, sk) != hipSuccess ||
             hipMemcpyAsync(hStatus + lo, dStatus + lo, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, sk) != hipSuccess ||
             hipMemcpyAsync(hTotals + k, dTotals + k, sizeof(uint64_t), hipMemcpyDeviceToHost, sk) != hipSuccess ||
-            hipEventCreateWithFlags(&evMeta[k], hipEventDisableTiming) != hipSuccess || hipEventRecord(evMeta[k], sk) != hipSuccess) return fail(ZHIP_ERR_HIP);
+            hipEventCreateWithFlags(&call.evMeta[k], hipEventDisableTiming) != hipSuccess || hipEventRecord(call.evMeta[k], sk) != hipSuccess) return call.fail(ZHIP_ERR_HIP);
         if (k >= 1) { const int e = collect(k - 1); if (e) return e; }
     }
     if (nChunks) { const int e = collect(nChunks - 1); if (e) return e; }
-    if (hipStreamSynchronize(c->hpD2H) != hipSuccess || hipStreamSynchronize(c->hpCompute) != hipSuccess) return fail(ZHIP_ERR_HIP);
-    (void)hipEventDestroy(evUp);
-    if (nChunks == 0) empty_outbuf(&ob[0]);
-    *out = ob; *nOut = nChunks ? nChunks : 1;
-    tls_trim(c);
-    return ZHIP_ERR_NONE;
+    if (const int e = call.drain()) return e;
+    return call.finish(out, nOut, nChunks);
 }
 
 
@@ -1917,25 +1801,8 @@ static int compress_batch_one(const zhip_cparams* params, const zhip_item* items
 // device. ZHIP_DEVICES=0,1,... selects the device slots (a device may be listed twice: two contexts on one GPU -- how the split is tested on a
 // one-GPU box); unset = every visible device, but never more devices than ZHIP_DEVICE_MIN_BYTES (default 256 MiB) of input each -- small batches stay on the
 // calling thread's current device, exactly as before.
-extern "C" size_t zhip_partition_by_bytes(const uint64_t* sizes, size_t n, size_t workers, size_t* bounds)
-{
-    // compressor.c:1127-1216: never more workers than items (:1151); walk the items, close a worker's run once its bytes reach total / workers; the
-    // last worker takes the rest. bounds[2w], bounds[2w+1] = [start, end) of worker w; returns the workers that got a run.
-    if (workers < 1) workers = 1;
-    if (n && workers > n) workers = n;
-    if (!n) return 0;
-    uint64_t total = 0;
-    for (size_t i = 0; i < n; i++) total += sizes[i];
-    const uint64_t per = total / workers;
-    size_t w = 0, start = 0; uint64_t acc = 0;
-    for (size_t i = 0; i < n; i++) {
-        acc += sizes[i];
-        if (w == workers - 1) continue;
-        if (acc >= per) { bounds[2 * w] = start; bounds[2 * w + 1] = i + 1; w++; start = i + 1; acc = 0; }
-    }
-    if (start < n) { bounds[2 * w] = start; bounds[2 * w + 1] = n; w++; }
-    return w;
-}
+// The rules -- the partition, the device list, the slot count, the merge -- are zhip_host_calls.hpp's; the threads and the contexts are here.
+extern "C" size_t zhip_partition_by_bytes(const uint64_t* sizes, size_t n, size_t workers, size_t* bounds) { return host_partition_by_bytes(sizes, n, workers, bounds); }
 
 namespace {
 struct DevJob { std::function<void()> fn; };
@@ -1970,13 +1837,7 @@ struct DevPool {
         if (hipGetDeviceCount(&count) != hipSuccess) { (void)hipGetLastError(); count = 0; }
         if (const char* e = getenv("ZHIP_DEVICES")) {
             explicitList = true;
-            for (const char* p = e; *p;) {
-                char* end = nullptr;
-                const long v = strtol(p, &end, 10);
-                if (end == p) break;
-                if (v >= 0 && v < count) slots.push_back((int)v);
-                p = *end == ',' ? end + 1 : end;
-            }
+            slots = host_parse_devices(e, count);
         } else for (int d = 0; d < count; d++) slots.push_back(d);
         workers.assign(slots.size(), nullptr);
         if (slots.size() > 1) g_pinPortable.store(true);       // payload blocks serve any device's copy engines from the first one on
@@ -1991,56 +1852,42 @@ struct DevPool {
     size_t slotsFor(size_t n, uint64_t bytes)
     {
         { std::lock_guard<std::mutex> l(mu); parse(); }
-        size_t d = slots.size();
-        if (!explicitList) {
-            if (d <= 1) return 0;
-            const uint64_t byBytes = minBytes ? bytes / minBytes : d;
-            if (byBytes < d) d = (size_t)byBytes;
-            if (d <= 1) return 0;
-        }
-        if (d > n) d = n;
-        return d;
+        return host_slots_for(slots.size(), explicitList, minBytes, n, bytes);
     }
 };
 DevPool& dev_pool() { static DevPool* p = new DevPool(); return *p; }
-
-struct DevResult { int rc = 0; zhip_error err; zhip_outbuf* out = nullptr; size_t nOut = 0; std::string text; bool done = false; };
 
 // runs fn(slot, lo, hi, &result) for every run of the partition on its device's thread; gathers the devices' buffers in order
 template <typename F>
 int fan_out(size_t d, const std::vector<uint64_t>& sizes, size_t n, F&& one, zhip_outbuf** out, size_t* nOut, zhip_error* err)
 {
     std::vector<size_t> bounds(2 * d);
-    const size_t used = zhip_partition_by_bytes(sizes.data(), n, d, bounds.data());
-    std::vector<DevResult> res(used);
+    const size_t used = host_partition_by_bytes(sizes.data(), n, d, bounds.data());
+    std::vector<HostRun> runs(used); std::vector<std::string> text(used);      // what every run's call returned, and its thread's zhip_last_error()
     std::mutex mu; std::condition_variable cv; size_t pending = used;
     for (size_t w = 0; w < used; w++) {
         const size_t lo = bounds[2 * w], hi = bounds[2 * w + 1];
         dev_pool().worker(w)->post([&, w, lo, hi] {
-            DevResult& r = res[w];
+            HostRun& r = runs[w];
+            r.lo = lo;
             memset(&r.err, 0, sizeof r.err);
             r.rc = one(lo, hi, &r.out, &r.nOut, &r.err);
-            if (r.rc) r.text = g_lastError;
+            if (r.rc) text[w] = g_lastError;
             if (w < 64 && g_tls.c) g_slotBytes[w].store(g_tls.c->device_bytes());
-            { std::lock_guard<std::mutex> l(mu); r.done = true; pending--; }
+            { std::lock_guard<std::mutex> l(mu); pending--; }
             cv.notify_one();
         });
     }
     { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return pending == 0; }); }
-    // the first failing item (the lowest index: runs are in item order), as the reference reports it (compressor.c:1225-1253)
-    for (size_t w = 0; w < used; w++) if (res[w].rc) {
-        for (size_t v = 0; v < used; v++) if (!res[v].rc) zhip_free_outbufs(res[v].out, res[v].nOut, 1);
-        if (err) { *err = res[w].err; err->index += bounds[2 * w]; }
-        g_lastError = res[w].text;
-        return res[w].rc;
+    const size_t bad = host_merge_failing(runs.data(), used, err);
+    if (bad < used) {
+        for (size_t v = 0; v < used; v++) if (!runs[v].rc) zhip_free_outbufs(runs[v].out, runs[v].nOut, 1);
+        g_lastError = text[bad];
+        return runs[bad].rc;
     }
-    size_t total = 0;
-    for (size_t w = 0; w < used; w++) total += res[w].nOut;
-    zhip_outbuf* all = (zhip_outbuf*)calloc(total ? total : 1, sizeof(zhip_outbuf));
-    if (!all) { for (size_t w = 0; w < used; w++) zhip_free_outbufs(res[w].out, res[w].nOut, 1); if (err) { memset(err, 0, sizeof *err); err->kind = ZHIP_ERR_NO_MEMORY; } return ZHIP_ERR_NO_MEMORY; }
-    size_t k = 0;
-    for (size_t w = 0; w < used; w++) { for (size_t j = 0; j < res[w].nOut; j++) all[k++] = res[w].out[j]; free(res[w].out); }
-    *out = all; *nOut = total;
+    zhip_outbuf* all = host_merge_concat(runs.data(), used, nOut);
+    if (!all) { for (size_t w = 0; w < used; w++) zhip_free_outbufs(runs[w].out, runs[w].nOut, 1); if (err) { memset(err, 0, sizeof *err); err->kind = ZHIP_ERR_NO_MEMORY; } return ZHIP_ERR_NO_MEMORY; }
+    *out = all;
     return ZHIP_ERR_NONE;
 }
 }

@@ -104,6 +104,7 @@ class RefZstd:
             ("ZSTD_isError", C.c_uint, [C.c_size_t]),
             ("ZSTD_getErrorName", C.c_char_p, [C.c_size_t]),
             ("ZSTD_getFrameContentSize", C.c_ulonglong, [C.c_void_p, C.c_size_t]),
+            ("ZSTD_findFrameCompressedSize", C.c_size_t, [C.c_void_p, C.c_size_t]),
             ("ZDICT_trainFromBuffer", C.c_size_t, [C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t), C.c_uint]),
             ("ZSTD_getCParams", _CParams, [C.c_int, C.c_ulonglong, C.c_size_t]),
             ("ZSTD_createCDict_advanced", C.c_void_p, [C.c_char_p, C.c_size_t, C.c_int, C.c_int, _CParams, _CMem]),
@@ -334,6 +335,11 @@ class RefZstd:
     def frame_content_size(self, frame):
         frame = bytes(frame)
         return self.lib.ZSTD_getFrameContentSize(frame, len(frame))
+
+    def find_frame_compressed_size(self, data):
+        """ZSTD_findFrameCompressedSize: the bytes of the first frame of `data`, or an error code as libzstd returns it (a size_t of minus the ZSTD_ErrorCode)"""
+        data = bytes(data)
+        return self.lib.ZSTD_findFrameCompressedSize(data, len(data))
 
     def train_dictionary(self, dict_size, samples):
         blob = b"".join(samples)
