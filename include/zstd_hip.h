@@ -442,6 +442,33 @@ int      zhip_seekable_decompress_typed_ranges_device(zhip_ctx*, zhip_seekable*,
                                                       void* d_dst, uint64_t dstCapacity, int32_t* d_status /* [2 + 2 * nRanges] */,
                                                       zhip_seekable_gather_stats* stats /* host, may be NULL */, void* stream);
 
+/* FILTERS of a typed stream: what is done to a group's elements before the plane split. ZHIP_FILTER_DELTA is for integer tensors whose
+ * neighbours are close -- offsets, sorted ids, timestamps, counters, running sums: each element's bit pattern is read as an unsigned little-endian integer of
+ * 8 * elementSize bits, and per group d[0] = x[0], d[i] = x[i] - x[i - 1] mod 2^(8 * elementSize); the plane frames hold the byte planes of d. Groups stay
+ * independent, so a group is still the unit of random access. Floats gain nothing from it. Everything else about a typed stream is unchanged: the frames are
+ * libzstd's frames of those planes, the table's checksums are those of the planar content, zstd -d and every plain reader see the filtered planar bytes.
+ * The marker keeps version 1; its word at +16 is elementSize | filter << 8, so an unfiltered stream is byte for byte what it was, and a reader from before
+ * the filters refuses a filtered stream as an element size it does not know. Any value but 0 or 1 in bits 8 .. 31 is a marker this reader does not
+ * understand: corruption_detected (20) at the marker frame.
+ *
+ * zhip_planes_split_filter_device / zhip_planes_join_filter_device: the transposition kernels with the filter fused in. Split subtracts on the words between
+ * its loads and its stores (no pass of its own over the source); join under ZHIP_FILTER_DELTA is the inclusive prefix sum of every group and runs as three
+ * launches -- tile sums, their exclusive prefix sums per group, join-scan-store -- with a uint64 per 1 024 elements of context memory, kept between calls.
+ * zhip_seekable_compress_typed_filter_device: zhip_seekable_compress_typed_device with the filter in the split and in the marker.
+ * With ZHIP_FILTER_NONE all three are the calls without a filter, byte for byte and launch for launch. ZHIP_ERR_UNSUPPORTED, with nothing queued and nothing
+ * written, beyond those calls': a filter that is neither, and a filter other than ZHIP_FILTER_NONE with elementSize 1. zhip_seekable_typed_bound holds for
+ * every filter (a filter changes no size bound).
+ * zhip_seekable_filter: the opened stream's filter (0 for a plain stream). zhip_seekable_decompress_typed_ranges_device returns the ELEMENTS of a filtered
+ * stream with no new argument: a group a range covers in part is fetched from its first element (its planes' ranges start at the planes' starts), the join
+ * sums over what is in front and stores the range only. The plane frames are decoded whole either way, so the decode costs what it did; the copy out of the
+ * decode scratch and the join grow by the elements in front of the range within its group. */
+enum { ZHIP_FILTER_NONE = 0, ZHIP_FILTER_DELTA = 1 };
+int      zhip_planes_split_filter_device(zhip_ctx*, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, uint32_t filter, void* d_dst, void* stream);
+int      zhip_planes_join_filter_device(zhip_ctx*, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, uint32_t filter, void* d_dst, void* stream);
+int      zhip_seekable_compress_typed_filter_device(zhip_ctx*, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, uint32_t filter, int flags,
+                                                    void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status /* [2] */, void* stream);
+uint32_t zhip_seekable_filter(const zhip_seekable*);
+
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,
  * 4 K3, 5 / 6 the lane-serial match kernel (the greedy strategy's zhip_encode_match_greedy_kernel where that runs in its place) and the entropy kernel, 7 K1b -- which runs BESIDE K2 on a side stream: timed from K2's end to its own end, what it adds to the step --,

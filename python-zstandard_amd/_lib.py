@@ -145,6 +145,10 @@ def lib():
         "zhip_seekable_typed_bound": (u64, [u64, C.c_uint32, C.c_uint32, C.c_int]),
         "zhip_seekable_compress_typed_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, C.c_int, vp, u64, vp, vp, vp]),
         "zhip_seekable_element_size": (C.c_uint32, [vp]),
+        "zhip_planes_split_filter_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
+        "zhip_planes_join_filter_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]),
+        "zhip_seekable_compress_typed_filter_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, vp, u64, vp, vp, vp]),
+        "zhip_seekable_filter": (C.c_uint32, [vp]),
         "zhip_seekable_group_elements": (C.c_uint32, [vp]),
         "zhip_seekable_decompress_typed_ranges_device": (C.c_int, [vp, vp, vp, sz, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
     }
@@ -172,6 +176,7 @@ EXPORTED_SYMBOLS = [
     "zhip_seekable_edit_bound", "zhip_seekable_edit_device",
     "zhip_planes_split_device", "zhip_planes_join_device", "zhip_seekable_typed_bound", "zhip_seekable_compress_typed_device",
     "zhip_seekable_element_size", "zhip_seekable_group_elements", "zhip_seekable_decompress_typed_ranges_device",
+    "zhip_planes_split_filter_device", "zhip_planes_join_filter_device", "zhip_seekable_compress_typed_filter_device", "zhip_seekable_filter",
 ]
 
 

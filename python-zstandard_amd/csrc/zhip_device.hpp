@@ -145,3 +145,34 @@ ZH_DEV uint32_t zh_scan_add(uint32_t v)
     return v;
 }
 #endif
+// the value of the lane below (lane 0: 0), all 64 lanes must call: one DPP move (wave_shr:1), no LDS crossbar trip as zh_shfl_up's ds_bpermute
+#ifndef ZHIP_EMU
+ZH_DEV uint32_t zh_lane_below(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); }
+#else
+ZH_DEV uint32_t zh_lane_below(uint32_t v) { const uint32_t r = zh_shfl_up(v, 1); return zh_lane() ? r : 0u; }
+#endif
+// the same over 64-bit values. Two zh_scan_add would not carry from the low halves into the high ones, so every step moves both halves with the step's DPP
+// control and adds in 64 bits. The emulator's form is here, beside it, over the 32-bit shuffle.
+#ifndef ZHIP_EMU
+template <int CTRL, int ROWS> ZH_DEV uint64_t zh_dpp_add64(uint64_t v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROWS, 0xf, false);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROWS, 0xf, false);
+    return v + (((uint64_t)hi << 32) | lo);
+}
+ZH_DEV uint64_t zh_scan_add64(uint64_t v)
+{
+    v = zh_dpp_add64<0x111, 0xf>(v); v = zh_dpp_add64<0x112, 0xf>(v); v = zh_dpp_add64<0x114, 0xf>(v); v = zh_dpp_add64<0x118, 0xf>(v);
+    v = zh_dpp_add64<0x142, 0xa>(v); v = zh_dpp_add64<0x143, 0xc>(v);
+    return v;
+}
+#else
+ZH_DEV uint64_t zh_scan_add64(uint64_t v)
+{
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t lo = zh_shfl_up((uint32_t)v, d), hi = zh_shfl_up((uint32_t)(v >> 32), d);
+        if (zh_lane() >= d) v += ((uint64_t)hi << 32) | lo;
+    }
+    return v;
+}
+#endif

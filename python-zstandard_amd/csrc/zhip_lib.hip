@@ -333,6 +333,7 @@ struct zhip_ctx {
     DevBuf hSrc, hDst, hSegs, hStatus, hDense;
     DevBuf skSlots, skMeta;            // seekable streams: the chunks' compressBound-sized slots; segments, sizes, statuses and the scan's cells
     std::vector<ZskPinSlot> skPins;    // the pick list of an edit without an opened stream travels through these
+    DevBuf skTileSums;                         // the delta join on its own (zhip_planes_join_filter_device): a uint64 per tile
     DevBuf skStaging, skRecords, skStash;      // typed seekable compress: the planar copy of the source (its bytes), the plane frames' records, the seal's stash
     void* pinned = nullptr; size_t pinnedCap = 0;
     bool hpReady = false; hipStream_t hpH2D = nullptr, hpCompute = nullptr, hpD2H = nullptr;     // host pipeline: copy-in, kernels, copy-out
@@ -440,7 +441,7 @@ extern "C" void zhip_ctx_destroy(zhip_ctx* c)
     c->scratch.release(); c->counter.release(); c->encWorkspace.release(); c->encMeta.release(); c->encArena.release(); c->encTables.release(); c->encBigList.release(); c->encBigWs.release(); c->encFlatTables.release(); c->encE1List.release(); c->encMbBlocks.release(); c->encMbCount.release(); c->encMbSeqs.release(); c->dictBlob.release(); c->dictEntropy.release(); c->dictTables.release();
     c->cdictBlob.release(); c->cdictEntropy.release(); c->cdictDigest.release(); c->cdictTables.release();
     c->hSrc.release(); c->hDst.release(); c->hSegs.release(); c->hStatus.release(); c->hDense.release();
-    c->skSlots.release(); c->skMeta.release(); c->skStaging.release(); c->skRecords.release(); c->skStash.release();
+    c->skSlots.release(); c->skMeta.release(); c->skStaging.release(); c->skRecords.release(); c->skStash.release(); c->skTileSums.release();
     for (ZskPinSlot& x : c->skPins) { if (x.p) (void)hipHostFree(x.p); (void)hipEventDestroy(x.done); }
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->profDecode) (void)hipFree(c->profDecode);
@@ -1940,6 +1941,7 @@ struct zhip_seekable : ZskTypedOpened {
     DevBuf gTables, gMeta, gScratch;
     std::vector<ZskPinSlot> slots;
     DevBuf tPlanar, tTables, tStatus;     // a typed read: the planar buffer the many-ranges call fills (at exactly its bytes), the jobs and owners, the passes' status arrays
+    DevBuf tTileSums;                     // a read of a delta-filtered stream: a uint64 per tile of its largest pass
 };
 
 // a pinned slot of at least `bytes` that no upload still reads: one whose event has completed (grown where too small), else a new one
@@ -2044,7 +2046,8 @@ struct ZskHipTypedBackend : ZskHipBackend {
             *base = (uint8_t*)s.p;
             return 0;
         }
-        DevBuf& d = area == ZSKT_A_STAGING ? c->skStaging : area == ZSKT_A_RECORDS ? c->skRecords : area == ZSKT_A_STASH ? c->skStash : area == ZSKT_A_TABLES ? h->tTables : h->tStatus;
+        DevBuf& d = area == ZSKT_A_STAGING ? c->skStaging : area == ZSKT_A_RECORDS ? c->skRecords : area == ZSKT_A_STASH ? c->skStash : area == ZSKT_A_TABLES ? h->tTables :
+                    area == ZSKT_A_TILESUMS ? (h ? h->tTileSums : c->skTileSums) : h->tStatus;
         if (d.reserve(bytes)) return g_reserveRc;
         *base = (uint8_t*)d.p;
         return 0;
@@ -2089,7 +2092,7 @@ extern "C" void zhip_seekable_close(zhip_seekable* h)
 {
     if (!h) return;
     h->prefix.release(); h->meta.release(); h->edge.release();
-    h->gTables.release(); h->gMeta.release(); h->gScratch.release(); h->tPlanar.release(); h->tTables.release(); h->tStatus.release();      // (hipFree waits for the device: no upload from a slot is in flight behind it)
+    h->gTables.release(); h->gMeta.release(); h->gScratch.release(); h->tPlanar.release(); h->tTables.release(); h->tStatus.release(); h->tTileSums.release();      // (hipFree waits for the device: no upload from a slot is in flight behind it)
     for (ZskPinSlot& s : h->slots) { if (s.p) (void)hipHostFree(s.p); (void)hipEventDestroy(s.done); }
     delete h;
 }
@@ -2184,6 +2187,16 @@ extern "C" int zhip_planes_join_device(zhip_ctx* c, const void* d_src, uint64_t 
     ZskHipTypedBackend b(c, nullptr, streamv);
     return zsk_planes_join(b, c != nullptr, d_src, size, elementSize, frameSize, d_dst);
 }
+extern "C" int zhip_planes_split_filter_device(zhip_ctx* c, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, uint32_t filter, void* d_dst, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_planes_split(b, c != nullptr, d_src, size, elementSize, frameSize, d_dst, filter);
+}
+extern "C" int zhip_planes_join_filter_device(zhip_ctx* c, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, uint32_t filter, void* d_dst, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_planes_join(b, c != nullptr, d_src, size, elementSize, frameSize, d_dst, filter);
+}
 extern "C" uint64_t zhip_seekable_typed_bound(uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, int flags)
 {
     if (flags & ~ZHIP_SEEKABLE_CHECKSUM) return 0;
@@ -2196,6 +2209,13 @@ extern "C" int zhip_seekable_compress_typed_device(zhip_ctx* c, const void* d_sr
     ZskHipTypedBackend b(c, nullptr, streamv);
     return zsk_typed_compress(b, c != nullptr, d_src, srcSize, frameSize, elementSize, flags, d_dst, dstCapacity, d_streamSize, d_status);
 }
+extern "C" int zhip_seekable_compress_typed_filter_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, uint32_t filter, int flags,
+                                                          void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_typed_compress(b, c != nullptr, d_src, srcSize, frameSize, elementSize, flags, d_dst, dstCapacity, d_streamSize, d_status, filter);
+}
+extern "C" uint32_t zhip_seekable_filter(const zhip_seekable* h) { return h ? h->filter : 0; }
 extern "C" uint32_t zhip_seekable_element_size(const zhip_seekable* h) { return h ? h->elementSize : 0; }
 extern "C" uint32_t zhip_seekable_group_elements(const zhip_seekable* h) { return h ? h->groupElements : 0; }
 extern "C" int zhip_seekable_decompress_typed_ranges_device(zhip_ctx* c, zhip_seekable* h, const zhip_seekable_range* ranges, size_t nRanges, void* d_dst, uint64_t dstCapacity,

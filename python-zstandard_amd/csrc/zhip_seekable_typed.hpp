@@ -3,9 +3,10 @@
 // becomes the k frames g * k + p, p = 0 .. k - 1, frame g * k + p holding byte p of every element of the group in element order. Behind the last plane frame
 // stands the MARKER, a skippable frame of 24 bytes with a seek-table entry of its own (Compressed_Size 24, Decompressed_Size 0):
 //
-//     0x184D2A5D | Frame_Size = 16 | 'Z' 'H' 'P' 'L' | version = 1 | element_size | frame_size          (all little-endian words)
+//     0x184D2A5D | Frame_Size = 16 | 'Z' 'H' 'P' 'L' | version = 1 | element_size | filter << 8 | frame_size          (all little-endian words)
 //
-// and the standard seek table comes last: the stream is an ordinary seekable stream whose content is the PLANAR bytes.
+// filter 0: the planes are those of the elements; filter 1 (delta): those of the differences of neighbouring elements within the group.
+// The standard seek table comes last: the stream is an ordinary seekable stream whose content is the PLANAR bytes.
 // What is here: the two transposition kernels (interleaved -> planar with the record table of the plane frames, planar -> interleaved driven by a job table),
 // the two kernels that seal a stream the records call has written, the status reducer of the typed read, and the host plan of that read. One-wave
 // workgroups written against zhip_device.hpp like zhip_seekable.hpp, so the same bodies run under the host wave emulator (tests/emu/emu_seekable_typed.cpp).
@@ -20,7 +21,12 @@
 #define ZSK_PLANE_TILE 1024u                 // elements of one group a workgroup takes per step: 16 per lane
 #define ZSK_MAX_PLANE_FRAMES (ZSK_MAX_FRAMES - 1)      // the marker is a frame of the table too
 
+// the marker's word at +16 is element_size | filter << 8: what was done to a group's elements before the plane split
+#define ZSK_FILTER_NONE 0u
+#define ZSK_FILTER_DELTA 1u                  // d[0] = x[0], d[i] = x[i] - x[i - 1] mod 2^(8k) on the elements' bit patterns as unsigned little-endian integers, per group
+
 ZSK_HD bool zsk_element_ok(uint32_t k) { return k == 2 || k == 4 || k == 8; }
+ZSK_HD bool zsk_filter_ok(uint32_t filter) { return filter == ZSK_FILTER_NONE || filter == ZSK_FILTER_DELTA; }
 ZSK_HD bool zsk_typed_args_ok(uint64_t srcSize, uint32_t frameSize, uint32_t k)
 {
     return zsk_element_ok(k) && srcSize % k == 0 && frameSize >= 1 && frameSize <= ZSK_MAX_CONTENT && zsk_frame_count(srcSize / k, frameSize) * k <= ZSK_MAX_PLANE_FRAMES;
@@ -31,12 +37,15 @@ ZSK_HD uint64_t zsk_typed_bound(uint64_t srcSize, uint32_t frameSize, uint32_t k
     if (!zsk_typed_args_ok(srcSize, frameSize, k)) return 0;
     return zsk_records_bound(srcSize, zsk_frame_count(srcSize / k, frameSize) * k, checksum) + ZSK_MARKER + zsk_entry_size(checksum);
 }
-// the 24 bytes a probe read where the last entry says (24, 0) -> 0: no marker (a plain stream), 1: a marker this reader understands, -1: a marker it does not
-static inline int zsk_parse_marker(const uint8_t* m, uint32_t* k, uint32_t* frameSize)
+// the 24 bytes a probe read where the last entry says (24, 0) -> 0: no marker (a plain stream), 1: a marker this reader understands, -1: a marker it does not.
+// The word at +16 holds the element size in bits 0 .. 7 and the filter above; a caller that takes no filter understands unfiltered streams only
+static inline int zsk_parse_marker(const uint8_t* m, uint32_t* k, uint32_t* frameSize, uint32_t* filter = nullptr)
 {
     if (zsk_rd32(m) != ZSK_PLANES_MAGIC || zsk_rd32(m + 4) != 16 || zsk_rd32(m + 8) != ZSK_PLANES_TAG) return 0;
-    *k = zsk_rd32(m + 16); *frameSize = zsk_rd32(m + 20);
-    return zsk_rd32(m + 12) == ZSK_PLANES_VERSION && zsk_element_ok(*k) && *frameSize >= 1 && *frameSize <= ZSK_MAX_CONTENT ? 1 : -1;
+    const uint32_t word = zsk_rd32(m + 16), f = word >> 8;
+    *k = word & 0xFFu; *frameSize = zsk_rd32(m + 20);
+    if (filter) *filter = f;
+    return zsk_rd32(m + 12) == ZSK_PLANES_VERSION && zsk_element_ok(*k) && (filter ? zsk_filter_ok(f) : f == ZSK_FILTER_NONE) && *frameSize >= 1 && *frameSize <= ZSK_MAX_CONTENT ? 1 : -1;
 }
 // the shape a marker promises, against the table's decompressed offsets D [n + 1] (the marker is frame n - 1): k frames of one size per group, that size
 // frameSize but for the last group's, which is 1 ... frameSize. Returns n, or the first frame that does not fit
@@ -75,11 +84,14 @@ ZH_DEV void zsk_words(zh_v16 v, uint32_t* w) { w[0] = (uint32_t)v.lo; w[1] = (ui
 ZH_DEV zh_v16 zsk_v16(const uint32_t* w) { zh_v16 v; v.lo = w[0] | ((uint64_t)w[1] << 32); v.hi = w[2] | ((uint64_t)w[3] << 32); return v; }
 
 // 16 elements at s -> 16 bytes to each of the K planes, plane p at d + p * plane: K loads and K stores of 16 bytes
-template <int K> ZH_DEV void zsk_split16(const uint8_t* s, uint8_t* d, uint64_t plane)
+// (the loads and the stores are functions of their own: the delta kernels work on the words between them)
+template <int K> ZH_DEV void zsk_load16(const uint8_t* s, uint32_t* w)
 {
-    uint32_t w[4 * K];
 #pragma unroll
     for (int j = 0; j < K; j++) zsk_words(zh_ld128(s + 16 * j), w + 4 * j);
+}
+template <int K> ZH_DEV void zsk_split16_store(const uint32_t* w, uint8_t* d, uint64_t plane)
+{
 #pragma unroll
     for (int p = 0; p < K; p++) {
         uint32_t o[4];
@@ -90,6 +102,12 @@ template <int K> ZH_DEV void zsk_split16(const uint8_t* s, uint8_t* d, uint64_t 
         }
         zh_st128(d + p * plane, zsk_v16(o));
     }
+}
+template <int K> ZH_DEV void zsk_split16(const uint8_t* s, uint8_t* d, uint64_t plane)
+{
+    uint32_t w[4 * K];
+    zsk_load16<K>(s, w);
+    zsk_split16_store<K>(w, d, plane);
 }
 // the mirror image: 16 bytes of each of the K planes (plane p at s + p * plane) -> 16 elements at d
 template <int K> ZH_DEV void zsk_join16(const uint8_t* s, uint64_t plane, uint8_t* d)
@@ -109,6 +127,23 @@ template <int K> ZH_DEV void zsk_join16(const uint8_t* s, uint64_t plane, uint8_
         zh_st128(d + 16 * j, zsk_v16(o));
     }
 }
+// the same with the 4 K words of the 16 elements kept in registers, and their store: the delta join sums between the two
+template <int K> ZH_DEV void zsk_join16_words(const uint8_t* s, uint64_t plane, uint32_t* o)
+{
+    uint32_t w[K][4];
+#pragma unroll
+    for (int p = 0; p < K; p++) zsk_words(zh_ld128(s + p * plane), w[p]);
+#pragma unroll
+    for (int W = 0; W < 4 * K; W++) {                  // the output word: bytes 4W .. 4W + 3 of the 16 elements
+        if (K == 2) o[W] = zsk_perm(w[1][W >> 1], w[0][W >> 1], W & 1 ? 0x07030602u : 0x05010400u);
+        else { const int per = K / 4, i = W / per, p0 = (W % per) * 4; o[W] = zsk_byte_of4(w[p0][i >> 2], w[p0 + 1][i >> 2], w[p0 + 2][i >> 2], w[p0 + 3][i >> 2], i & 3); }
+    }
+}
+template <int K> ZH_DEV void zsk_store16(const uint32_t* o, uint8_t* d)
+{
+#pragma unroll
+    for (int j = 0; j < K; j++) zh_st128(d + 16 * j, zsk_v16(o + 4 * j));
+}
 
 // ------------------------------------------------------------------------------------------------ split: interleaved -> planar, and the plane frames' records
 struct ZskPlanesArgs {
@@ -125,6 +160,14 @@ template <int K> ZH_DEV void zsk_split_lane(const uint8_t* s, uint8_t* d, uint32
     if (e - i0 >= 16) { zsk_split16<K>(s + (uint64_t)i0 * K, d + i0, e); return; }
     for (uint32_t i = i0; i < e; i++) for (uint32_t p = 0; p < K; p++) d[(uint64_t)p * e + i] = s[(uint64_t)i * K + p];
 }
+ZH_DEV void zsk_planes_records(const ZskPlanesArgs& a)
+{
+    if (!a.records) return;
+    for (uint64_t i = (uint64_t)zh_block() * 64 + zh_lane(); i < (uint64_t)a.nGroups * a.k; i += (uint64_t)zh_nblocks() * 64) {
+        const uint64_t g = i / a.k, e = zsk_group_len(a.elements, a.group, g);
+        a.records[2 * i] = g * a.group * a.k + (i % a.k) * e; a.records[2 * i + 1] = e;
+    }
+}
 // a workgroup per tile of ZSK_PLANE_TILE elements of one group (grid-stride over the tiles of all groups); a lane per plane frame writes its record
 ZH_DEV void zsk_planes_split_body(const ZskPlanesArgs& a)
 {
@@ -137,21 +180,93 @@ ZH_DEV void zsk_planes_split_body(const ZskPlanesArgs& a)
         else if (a.k == 4) zsk_split_lane<4>(a.src + at, a.dst + at, e, i0);
         else zsk_split_lane<8>(a.src + at, a.dst + at, e, i0);
     }
-    if (!a.records) return;
-    for (uint64_t i = (uint64_t)zh_block() * 64 + zh_lane(); i < (uint64_t)a.nGroups * a.k; i += (uint64_t)zh_nblocks() * 64) {
-        const uint64_t g = i / a.k, e = zsk_group_len(a.elements, a.group, g);
-        a.records[2 * i] = g * a.group * a.k + (i % a.k) * e; a.records[2 * i + 1] = e;
+    zsk_planes_records(a);
+}
+
+// ------------------------------------------------------------------------------------------------ split with the delta filter
+// The subtraction is done on the words between the split's loads and its stores: no pass of its own over the source. A lane needs the element in front of its
+// 16: lanes 1 .. 63 take it from the lane below with a DPP move (that lane's 16 are whole wherever this lane has any), lane 0 loads it, and the group's first element has 0 in front.
+#ifndef ZHIP_EMU
+typedef uint16_t zsk_u16x2 __attribute__((ext_vector_type(2)));
+ZH_DEV uint32_t zsk_sub16x2(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(zsk_u16x2, a) - __builtin_bit_cast(zsk_u16x2, b)); }      // v_pk_sub_u16
+ZH_DEV uint32_t zsk_add16x2(uint32_t a, uint32_t b) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(zsk_u16x2, a) + __builtin_bit_cast(zsk_u16x2, b)); }      // v_pk_add_u16
+#else
+ZH_DEV uint32_t zsk_sub16x2(uint32_t a, uint32_t b) { return ((a - b) & 0xFFFFu) | (((a >> 16) - (b >> 16)) << 16); }
+ZH_DEV uint32_t zsk_add16x2(uint32_t a, uint32_t b) { return ((a + b) & 0xFFFFu) | (((a >> 16) + (b >> 16)) << 16); }
+#endif
+template <int K> ZH_DEV uint64_t zsk_ld_element(const uint8_t* p) { if constexpr (K == 2) return zh_ld16(p); else if constexpr (K == 4) return zh_ld32(p); else return zh_ld64(p); }
+// w: the 4 K words of 16 elements, before: the words of the element in front of them (K = 2: in the high half of before[0]) -> the 16 differences, in place
+template <int K> ZH_DEV void zsk_delta16(uint32_t* w, const uint32_t* before)
+{
+    if constexpr (K == 2) {                        // a word is two elements: what stands in front of them is the pair one element down
+#pragma unroll
+        for (int j = 7; j >= 0; j--) w[j] = zsk_sub16x2(w[j], zh_alignbit(w[j], j ? w[j - 1] : before[0], 16));
+    } else if constexpr (K == 4) {
+#pragma unroll
+        for (int i = 15; i >= 0; i--) w[i] -= i ? w[i - 1] : before[0];
+    } else {
+#pragma unroll
+        for (int i = 15; i >= 0; i--) {
+            const uint64_t x = w[2 * i] | ((uint64_t)w[2 * i + 1] << 32), y = i ? w[2 * i - 2] | ((uint64_t)w[2 * i - 1] << 32) : before[0] | ((uint64_t)before[1] << 32), dl = x - y;
+            w[2 * i] = (uint32_t)dl; w[2 * i + 1] = (uint32_t)(dl >> 32);
+        }
     }
+}
+// a lane's share of a tile, as zsk_split_lane. EVERY lane of the wave calls (the lane shuffle); the group's last elements, fewer than 16: element by element
+template <int K> ZH_DEV void zsk_split_delta_lane(const uint8_t* s, uint8_t* d, uint32_t e, uint32_t i0)
+{
+    constexpr int B = K == 8 ? 2 : 1;              // the words of the element in front
+    const bool whole = i0 < e && e - i0 >= 16;
+    uint32_t w[4 * K], before[B];
+    // the tile's first element: the one in front is the last of the tile below, or nothing. Lane 0's load goes out WITH its 16 elements' loads: behind the
+    // shuffle it would be a second memory round trip per tile. (K = 2: the WORD that ends with that element -- lane 0's i0 is a multiple of the tile, so two
+    // elements stand in front of it -- since a 16-bit load is waited for where it is issued, which is that second round trip again)
+    const uint64_t x = !(whole && zh_lane() == 0 && i0) ? 0 : K == 2 ? zh_ld32(s + (uint64_t)(i0 - 2) * 2) : zsk_ld_element<K>(s + (uint64_t)(i0 - 1) * K);
+    if (whole) zsk_load16<K>(s + (uint64_t)i0 * K, w);
+#pragma unroll
+    for (int q = 0; q < B; q++) before[q] = zh_lane_below(whole ? w[4 * K - B + q] : 0u);
+    if (whole) {
+        if (zh_lane() == 0) {
+            before[0] = (uint32_t)x;
+            if constexpr (K == 8) before[1] = (uint32_t)(x >> 32);
+        }
+        zsk_delta16<K>(w, before);
+        zsk_split16_store<K>(w, d + i0, e);
+        return;
+    }
+    if (i0 >= e) return;
+    uint64_t y = i0 ? zsk_ld_element<K>(s + (uint64_t)(i0 - 1) * K) : 0;
+    for (uint32_t i = i0; i < e; i++) {
+        const uint64_t x = zsk_ld_element<K>(s + (uint64_t)i * K), dl = x - y;
+        for (uint32_t p = 0; p < K; p++) d[(uint64_t)p * e + i] = (uint8_t)(dl >> (8 * p));
+        y = x;
+    }
+}
+ZH_DEV void zsk_planes_split_delta_body(const ZskPlanesArgs& a)
+{
+    const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
+    const uint64_t tiles = (uint64_t)a.nGroups * tpg;
+    for (uint64_t t = zh_block(); t < tiles; t += zh_nblocks()) {
+        const uint64_t g = t / tpg, at = g * a.group * a.k;
+        const uint32_t e = zsk_group_len(a.elements, a.group, g), i0 = (uint32_t)(t % tpg) * ZSK_PLANE_TILE + zh_lane() * 16;
+        if (a.k == 2) zsk_split_delta_lane<2>(a.src + at, a.dst + at, e, i0);
+        else if (a.k == 4) zsk_split_delta_lane<4>(a.src + at, a.dst + at, e, i0);
+        else zsk_split_delta_lane<8>(a.src + at, a.dst + at, e, i0);
+    }
+    zsk_planes_records(a);
 }
 
 // ------------------------------------------------------------------------------------------------ join: planar -> interleaved, by jobs
 // A job: m elements whose planes lie at planar + p * m; output byte j in [h, m * k - t) -- byte j % k of element j / k -- goes to dst[j - h]. h, t < k trim
 // the first and the last element of a range that starts or ends inside one. Without a job table the jobs are the groups of a whole buffer.
-struct ZskJoinJob { uint64_t planar, m, dst, tilePrefix; uint32_t h, t; };      // planar, dst: offsets from the two bases; tilePrefix: the launch's tiles in front
+// Under the delta filter a job starts at its group's first element, and `skip` elements in front of the output feed the sums only: the output is byte j in
+// [skip * k + h, m * k - t), at dst[j - skip * k - h]. The plain join knows no skip (0 in all its jobs).
+struct ZskJoinJob { uint64_t planar, m, dst, tilePrefix; uint32_t h, t; uint64_t skip; };      // planar, dst: offsets from the two bases; tilePrefix: the launch's tiles in front
 struct ZskJoinArgs {
     const uint8_t* planar; uint8_t* dst;
     const ZskJoinJob* jobs; uint32_t nJobs; uint64_t tiles;
     uint32_t k, group; uint64_t elements;       // jobs NULL: the whole buffer, group g one job
+    uint64_t* tileSums;                         // the delta kernels': [tiles], a tile's sum, then the sum of the job's tiles in front of it (NULL: the plain join)
 };
 ZSK_HD uint64_t zsk_join_tiles(uint64_t m) { return (m + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE; }
 template <int K> ZH_DEV void zsk_join_lane(const uint8_t* s, uint8_t* d, uint64_t m, uint32_t h, uint32_t t, uint64_t i0)
@@ -161,6 +276,20 @@ template <int K> ZH_DEV void zsk_join_lane(const uint8_t* s, uint8_t* d, uint64_
     const uint64_t from = lo < h ? h : lo, to = hi > end ? end : hi;
     if (n == 16 && from == lo && to == hi) { zsk_join16<K>(s + i0, m, d + (lo - h)); return; }
     for (uint64_t j = from; j < to; j++) d[j - h] = s[(j % K) * m + j / K];      // a job's trimmed first / last element, its last elements, fewer than 16
+}
+// the job of the launch's tile t
+ZH_DEV ZskJoinJob zsk_join_job(const ZskJoinArgs& a, uint32_t tpg, uint64_t t)
+{
+    ZskJoinJob job;
+    if (a.jobs) {
+        uint32_t lo = 0, hi = a.nJobs;                                      // the last job whose tilePrefix <= t
+        while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.jobs[mid].tilePrefix <= t) lo = mid; else hi = mid; }
+        job = a.jobs[lo];
+    } else {
+        const uint64_t g = t / tpg;
+        job.planar = job.dst = g * a.group * a.k; job.m = zsk_group_len(a.elements, a.group, g); job.tilePrefix = g * tpg; job.h = job.t = 0; job.skip = 0;
+    }
+    return job;
 }
 ZH_DEV void zsk_planes_join_body(const ZskJoinArgs& a)
 {
@@ -182,13 +311,122 @@ ZH_DEV void zsk_planes_join_body(const ZskJoinArgs& a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ join with the delta filter: three launches
+// The inverse is the inclusive prefix sum of a job's elements mod 2^(8k), which crosses tiles. It crosses them at kernel boundaries only -- no workgroup waits
+// for another one inside a launch:
+//     zsk_delta_sums     a workgroup per tile joins the tile's planes in registers and stores the sum of its elements, tileSums[tile]
+//     zsk_delta_offsets  a wave per job turns its tiles' sums into their exclusive prefix sums, in place, 64 tiles a trip with a running carry
+//     zsk_planes_join_delta   a workgroup per tile joins again, sums a lane's 16 elements serially, adds the wave's exclusive sum of the lane totals and the
+//                        tile's offset, truncates to 8k bits and stores, trimmed as the plain join
+// All sums are 64 bits wide whatever k is: truncation commutes with addition. The planar bytes are read twice.
+template <int K> ZH_DEV uint64_t zsk_ld_planar(const uint8_t* s, uint64_t m, uint64_t i)
+{
+    uint64_t v = 0;
+#pragma unroll
+    for (int p = 0; p < K; p++) v |= (uint64_t)s[(uint64_t)p * m + i] << (8 * p);
+    return v;
+}
+// element i of the 4 K words of 16 elements
+template <int K> ZH_DEV uint64_t zsk_word_element(const uint32_t* o, int i)
+{
+    if constexpr (K == 2) return (o[i >> 1] >> (16 * (i & 1))) & 0xFFFFu; else if constexpr (K == 4) return o[i]; else return o[2 * i] | ((uint64_t)o[2 * i + 1] << 32);
+}
+// the sum of a lane's share of a tile: elements i0 .. i0 + 15 of a job of m; whole in registers, the job's last elements one by one
+template <int K> ZH_DEV uint64_t zsk_delta_lane_sum(const uint8_t* s, uint64_t m, uint64_t i0)
+{
+    uint64_t sum = 0;
+    if (i0 >= m) return 0;
+    if (m - i0 >= 16) {
+        uint32_t o[4 * K];
+        zsk_join16_words<K>(s + i0, m, o);
+#pragma unroll
+        for (int i = 0; i < 16; i++) sum += zsk_word_element<K>(o, i);
+        return sum;
+    }
+    for (uint64_t i = i0; i < m; i++) sum += zsk_ld_planar<K>(s, m, i);
+    return sum;
+}
+ZH_DEV void zsk_delta_sums_body(const ZskJoinArgs& a)
+{
+    const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
+    for (uint64_t t = zh_block(); t < a.tiles; t += zh_nblocks()) {
+        const ZskJoinJob job = zsk_join_job(a, tpg, t);
+        const uint64_t i0 = (t - job.tilePrefix) * ZSK_PLANE_TILE + zh_lane() * 16;
+        const uint8_t* const s = a.planar + job.planar;
+        const uint64_t sum = zh_scan_add64(a.k == 2 ? zsk_delta_lane_sum<2>(s, job.m, i0) : a.k == 4 ? zsk_delta_lane_sum<4>(s, job.m, i0) : zsk_delta_lane_sum<8>(s, job.m, i0));
+        if (zh_lane() == 63) a.tileSums[t] = sum;
+    }
+}
+ZH_DEV void zsk_delta_offsets_body(const ZskJoinArgs& a)
+{
+    const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE, nJobs = a.jobs ? a.nJobs : (uint32_t)zsk_frame_count(a.elements, a.group);
+    for (uint32_t j = zh_block(); j < nJobs; j += zh_nblocks()) {
+        const uint64_t first = a.jobs ? a.jobs[j].tilePrefix : (uint64_t)j * tpg, n = a.jobs ? zsk_join_tiles(a.jobs[j].m) : tpg;      // (a shorter last group has a group's tiles too, the empty ones summing to 0)
+        uint64_t carry = 0;
+        for (uint64_t at = 0; at < n; at += 64) {
+            const uint64_t i = at + zh_lane(), v = i < n ? a.tileSums[first + i] : 0, incl = zh_scan_add64(v);
+            if (i < n) a.tileSums[first + i] = carry + incl - v;
+            carry += zsk_shfl64(incl, 63);
+        }
+    }
+}
+// EVERY lane of the wave calls (the scan of the lane totals). offset: the sum of the job's elements in front of the tile
+template <int K> ZH_DEV void zsk_join_delta_lane(const uint8_t* s, uint8_t* d, const ZskJoinJob& job, uint64_t i0, uint64_t offset)
+{
+    const uint64_t m = job.m, n = i0 >= m ? 0 : m - i0 < 16 ? m - i0 : 16;
+    const uint64_t lo = i0 * K, hi = (i0 + n) * K, first = job.skip * K + job.h, end = m * K - job.t;
+    const uint64_t from = lo < first ? first : lo, to = hi > end ? end : hi;
+    uint32_t o[4 * K];
+    uint64_t total = 0;
+    if (n == 16) {                                 // the lane's inclusive sums, truncated, in the words' place
+        zsk_join16_words<K>(s + i0, m, o);
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+            total += zsk_word_element<K>(o, i);
+            if constexpr (K == 2) o[i >> 1] = i & 1 ? (o[i >> 1] & 0xFFFFu) | ((uint32_t)total << 16) : (o[i >> 1] & 0xFFFF0000u) | ((uint32_t)total & 0xFFFFu);
+            else if constexpr (K == 4) o[i] = (uint32_t)total;
+            else { o[2 * i] = (uint32_t)total; o[2 * i + 1] = (uint32_t)(total >> 32); }
+        }
+    } else for (uint64_t i = i0; i < i0 + n; i++) total += zsk_ld_planar<K>(s, m, i);
+    const uint64_t base = offset + zh_scan_add64(total) - total;      // what stands in front of the lane's first element
+    if (from >= to) return;
+    if (n == 16 && from == lo && to == hi) {
+#pragma unroll
+        for (int W = 0; W < 4 * K; W++) {
+            if constexpr (K == 2) o[W] = zsk_add16x2(o[W], ((uint32_t)base & 0xFFFFu) * 0x10001u);
+            else if constexpr (K == 4) o[W] += (uint32_t)base;
+            else if (!(W & 1)) { const uint64_t x = (o[W] | ((uint64_t)o[W + 1] << 32)) + base; o[W] = (uint32_t)x; o[W + 1] = (uint32_t)(x >> 32); }
+        }
+        zsk_store16<K>(o, d + (lo - first));
+        return;
+    }
+    uint64_t sum = base;                           // a job's trimmed first / last element, the lane the skip ends in, its last elements, fewer than 16
+    for (uint64_t i = i0; i < i0 + n; i++) {
+        sum += zsk_ld_planar<K>(s, m, i);
+        for (uint32_t p = 0; p < K; p++) { const uint64_t j = i * K + p; if (j >= from && j < to) d[j - first] = (uint8_t)(sum >> (8 * p)); }
+    }
+}
+ZH_DEV void zsk_planes_join_delta_body(const ZskJoinArgs& a)
+{
+    const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
+    for (uint64_t t = zh_block(); t < a.tiles; t += zh_nblocks()) {
+        const ZskJoinJob job = zsk_join_job(a, tpg, t);
+        const uint64_t tile = t - job.tilePrefix, i0 = tile * ZSK_PLANE_TILE + zh_lane() * 16;
+        if ((tile + 1) * ZSK_PLANE_TILE <= job.skip) continue;         // inside the skip: it fed the sums, it stores nothing
+        const uint64_t offset = a.tileSums[t];
+        if (a.k == 2) zsk_join_delta_lane<2>(a.planar + job.planar, a.dst + job.dst, job, i0, offset);
+        else if (a.k == 4) zsk_join_delta_lane<4>(a.planar + job.planar, a.dst + job.dst, job, i0, offset);
+        else zsk_join_delta_lane<8>(a.planar + job.planar, a.dst + job.dst, job, i0, offset);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ seal: the marker behind a stream the records call wrote
 // The records call leaves n plane frames, the table behind them and *streamSize (0: it failed, and so does the typed call). The marker goes where the table
 // starts and the table 24 bytes further on, one entry longer; the two overlap, so the first kernel keeps the stream size and the old entries aside.
 struct ZskSealArgs {
     uint8_t* dst; uint64_t dstCapacity; uint64_t* streamSize; int32_t* outStatus;
     uint8_t* stash;                             // 16 bytes (the records call's stream size) + the n entries
-    uint32_t n, checksum, elementSize, frameSize;
+    uint32_t n, checksum, elementSize, frameSize;      // elementSize: the marker's word at +16 as it is written, element size | filter << 8
 };
 #define ZSK_SEAL_HEAD 16u
 ZSK_HD uint64_t zsk_seal_stash_bytes(uint64_t n, int checksum) { return ZSK_SEAL_HEAD + n * zsk_entry_size(checksum); }
@@ -259,6 +497,10 @@ ZH_DEV void zsk_typed_status_body(const ZskTypedStatusArgs& a)
 // a group it covers whole is the group's k frames, contiguous in the planar content -- neighbouring whole groups are ONE planar range, and one join job each;
 // a group it covers in part is k planar ranges, elements lo .. hi - 1 of every plane, laid back to back in the planar buffer P -- one join job. P is filled
 // from 0 in every pass; a pass closes where the next piece would take P beyond the limit (a piece above the limit is alone in its pass).
+// Under the delta filter an element is the sum of everything in front of it in its group, so a group covered in part is fetched FROM ITS FIRST ELEMENT: its
+// planar ranges are elements 0 .. hi - 1 of every plane, and the job gets m = hi and skip = lo -- the tiles inside the skip feed the sums and store nothing.
+// The plane frames are decoded whole either way, so the decode costs what it did; what grows is the copy out of the decode scratch and the join, by the lo
+// elements in front. Whole groups, merged runs, passes and the limit work as without a filter, and with filter 0 the plan is that one field for field.
 struct ZskTypedPass { uint32_t q0, q1, job0, job1; uint64_t bytes, tiles; };
 struct ZskTypedPlan {
     std::vector<uint64_t> planar;               // [Q][3]: what the many-ranges call is handed, (offset, length, offset in P)
@@ -267,7 +509,7 @@ struct ZskTypedPlan {
     uint64_t pMax = 0;
 };
 // D = dOff of the opened stream; rg = [R][3], checked (zsk_gather_check); limit 0 = ZSK_SCRATCH_DEFAULT
-static inline void zsk_typed_plan(const uint64_t* D, uint32_t k, uint32_t group, const uint64_t* rg, size_t R, uint64_t limit, ZskTypedPlan* out)
+static inline void zsk_typed_plan(const uint64_t* D, uint32_t k, uint32_t group, const uint64_t* rg, size_t R, uint64_t limit, ZskTypedPlan* out, uint32_t filter = ZSK_FILTER_NONE)
 {
     if (!limit) limit = ZSK_SCRATCH_DEFAULT;
     *out = ZskTypedPlan();
@@ -288,19 +530,20 @@ static inline void zsk_typed_plan(const uint64_t* D, uint32_t k, uint32_t group,
             const uint64_t E0 = a / k, E1 = (a + len - 1) / k;
             for (uint64_t g = E0 / group; g <= E1 / group; g++) {
                 const uint64_t f = g * k, e = D[f + 1] - D[f], g0 = g * group;          // the group's first frame, its elements, its first element
-                const uint64_t lo = E0 > g0 ? E0 - g0 : 0, hi = E1 + 1 < g0 + e ? E1 + 1 - g0 : e, m = hi - lo;
+                const uint64_t lo = E0 > g0 ? E0 - g0 : 0, hi = E1 + 1 < g0 + e ? E1 + 1 - g0 : e;
+                const uint64_t skip = filter == ZSK_FILTER_DELTA && hi - lo != e ? lo : 0, m = hi - lo + skip, from = lo - skip;      // what is fetched: elements from .. hi - 1
                 if (used && used + m * k > limit) close();
                 ZskJoinJob job;
-                job.planar = used; job.m = m; job.h = g0 + lo == E0 ? (uint32_t)(a - E0 * k) : 0; job.t = g0 + hi == E1 + 1 ? (uint32_t)((E1 + 1) * k - (a + len)) : 0;
+                job.planar = used; job.m = m; job.skip = skip; job.h = g0 + lo == E0 ? (uint32_t)(a - E0 * k) : 0; job.t = g0 + hi == E1 + 1 ? (uint32_t)((E1 + 1) * k - (a + len)) : 0;
                 job.dst = to + ((g0 + lo) * k + job.h - a); job.tilePrefix = cur.tiles;
                 cur.tiles += zsk_join_tiles(m);
                 out->jobs.push_back(job);
-                if (m == e) {
+                if (hi - lo == e) {
                     if (merge) out->planar[out->planar.size() - 2] += e * k;
                     else { out->planar.push_back(D[f]); out->planar.push_back(e * k); out->planar.push_back(used); }
                     merge = true;
                 } else {
-                    for (uint32_t p = 0; p < k; p++) { out->planar.push_back(D[f + p] + lo); out->planar.push_back(m); out->planar.push_back(used + p * m); }
+                    for (uint32_t p = 0; p < k; p++) { out->planar.push_back(D[f + p] + from); out->planar.push_back(m); out->planar.push_back(used + p * m); }
                     merge = false;
                 }
                 used += m * k;
@@ -317,4 +560,8 @@ __global__ __launch_bounds__(64) void zhip_seekable_planes_join_kernel(ZskJoinAr
 __global__ __launch_bounds__(64) void zhip_seekable_seal_stash_kernel(ZskSealArgs a) { zsk_seal_stash_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_seal_kernel(ZskSealArgs a) { zsk_seal_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_typed_status_kernel(ZskTypedStatusArgs a) { zsk_typed_status_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_planes_split_delta_kernel(ZskPlanesArgs a) { zsk_planes_split_delta_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_delta_sums_kernel(ZskJoinArgs a) { zsk_delta_sums_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_delta_offsets_kernel(ZskJoinArgs a) { zsk_delta_offsets_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_planes_join_delta_kernel(ZskJoinArgs a) { zsk_planes_join_delta_body(a); }
 #endif

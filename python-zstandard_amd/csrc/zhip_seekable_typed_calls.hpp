@@ -12,16 +12,19 @@
 
 #define ZSKT_KERNELS(X) \
     X(PLANES_SPLIT, planes_split, ZskPlanesArgs) X(PLANES_JOIN, planes_join, ZskJoinArgs) X(SEAL_STASH, seal_stash, ZskSealArgs) X(SEAL, seal, ZskSealArgs) \
-    X(TYPED_STATUS, typed_status, ZskTypedStatusArgs)
+    X(TYPED_STATUS, typed_status, ZskTypedStatusArgs) \
+    X(PLANES_SPLIT_DELTA, planes_split_delta, ZskPlanesArgs) X(DELTA_SUMS, delta_sums, ZskJoinArgs) X(DELTA_OFFSETS, delta_offsets, ZskJoinArgs) \
+    X(PLANES_JOIN_DELTA, planes_join_delta, ZskJoinArgs)
 #define ZSKT_X(id, name, args) ZSKT_K_##id,
 enum ZskTypedKernel { ZSKT_KERNELS(ZSKT_X) ZSKT_K_COUNT };
 #undef ZSKT_X
 // the context's: the planar staging buffer (the source's bytes), the plane frames' records, the seal's stash; the handle's: the planar buffer of a read
-// (at most the scratch limit, or one piece above it), its tables (jobs, owners, status places), the status arrays of its passes
-enum ZskTypedArea { ZSKT_A_STAGING, ZSKT_A_RECORDS, ZSKT_A_STASH, ZSKT_A_PLANAR, ZSKT_A_TABLES, ZSKT_A_STATUS, ZSKT_A_COUNT };
+// (at most the scratch limit, or one piece above it), its tables (jobs, owners, status places), the status arrays of its passes. The delta join's tile sums,
+// 8 bytes a tile: the handle's for a read, the context's for the join on its own
+enum ZskTypedArea { ZSKT_A_STAGING, ZSKT_A_RECORDS, ZSKT_A_STASH, ZSKT_A_PLANAR, ZSKT_A_TABLES, ZSKT_A_STATUS, ZSKT_A_TILESUMS, ZSKT_A_COUNT };
 
-// what the open call's typed probe adds to a handle: elementSize 1 = a plain stream
-struct ZskTypedOpened : ZskOpened { uint32_t elementSize = 1, groupElements = 0; };
+// what the open call's typed probe adds to a handle: elementSize 1 = a plain stream; filter: ZSK_FILTER_* of the marker
+struct ZskTypedOpened : ZskOpened { uint32_t elementSize = 1, groupElements = 0, filter = ZSK_FILTER_NONE; };
 
 // a workgroup per tile, eight waves a CU
 static inline uint32_t zsk_tile_grid(int numCU, uint64_t tiles, uint64_t lanes)
@@ -31,49 +34,63 @@ static inline uint32_t zsk_tile_grid(int numCU, uint64_t tiles, uint64_t lanes)
 }
 static inline uint64_t zsk_planes_tiles(uint64_t elements, uint32_t group) { return zsk_frame_count(elements, group) * ((group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE); }
 
-static inline int zsk_planes_check(bool pointers, uint64_t size, uint32_t k, uint32_t frameSize, std::string& err)
+static inline int zsk_planes_check(bool pointers, uint64_t size, uint32_t k, uint32_t frameSize, std::string& err, uint32_t filter = ZSK_FILTER_NONE)
 {
     if (!pointers) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: bad arguments");
+    if (!zsk_filter_ok(filter)) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: the filter must be 0 (none) or 1 (delta)");
     if (!zsk_element_ok(k)) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: the element size must be 2, 4 or 8");
     if (size % k) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: the size must be a multiple of the element size");
     if (frameSize < 1 || frameSize > ZSK_MAX_CONTENT) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: frameSize must be 1 ... 2^30 elements");
     return 0;
 }
-static inline int zsk_typed_compress_check(bool pointers, uint64_t srcSize, uint32_t frameSize, uint32_t k, int flags, std::string& err)
+static inline int zsk_typed_compress_check(bool pointers, uint64_t srcSize, uint32_t frameSize, uint32_t k, int flags, std::string& err, uint32_t filter = ZSK_FILTER_NONE)
 {
     if (!pointers || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "seekable typed compress: bad arguments");
-    if (int rc = zsk_planes_check(true, srcSize, k, frameSize, err)) return rc;
+    if (int rc = zsk_planes_check(true, srcSize, k, frameSize, err, filter)) return rc;
     if (zsk_frame_count(srcSize / k, frameSize) * k > ZSK_MAX_PLANE_FRAMES) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "seekable typed compress: at most 2^27 - 1 plane frames");
     return 0;
 }
 
 // The whole-buffer kernels on their own: interleaved -> planar (no records) and back
-template <class B> int zsk_planes_split(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst)
+template <class B> int zsk_planes_split(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst, uint32_t filter = ZSK_FILTER_NONE)
 {
-    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err)) return rc;
+    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err, filter)) return rc;
     if (!size) return 0;
     ZskPlanesArgs a; memset(&a, 0, sizeof a);
     a.src = (const uint8_t*)d_src; a.dst = (uint8_t*)d_dst; a.elements = size / k; a.k = k; a.group = frameSize; a.nGroups = (uint32_t)zsk_frame_count(a.elements, frameSize);
-    b.launch_typed(ZSKT_K_PLANES_SPLIT, zsk_tile_grid(b.numCU, zsk_planes_tiles(a.elements, frameSize), 0), &a);
+    b.launch_typed(filter == ZSK_FILTER_DELTA ? ZSKT_K_PLANES_SPLIT_DELTA : ZSKT_K_PLANES_SPLIT, zsk_tile_grid(b.numCU, zsk_planes_tiles(a.elements, frameSize), 0), &a);
     return b.check();
 }
-template <class B> int zsk_planes_join(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst)
+// the join of the handle's filter: the plain kernel, or the delta filter's three launches over tileSums [a.tiles]
+template <class B> void zsk_launch_join(B& b, uint32_t filter, ZskJoinArgs& a, uint64_t nJobs, uint8_t* tileSums)
 {
-    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err)) return rc;
+    const uint32_t grid = zsk_tile_grid(b.numCU, a.tiles, 0);
+    if (filter != ZSK_FILTER_DELTA) { b.launch_typed(ZSKT_K_PLANES_JOIN, grid, &a); return; }
+    a.tileSums = (uint64_t*)tileSums;
+    b.launch_typed(ZSKT_K_DELTA_SUMS, grid, &a);
+    b.launch_typed(ZSKT_K_DELTA_OFFSETS, zsk_tile_grid(b.numCU, nJobs, 0), &a);
+    b.launch_typed(ZSKT_K_PLANES_JOIN_DELTA, grid, &a);
+}
+template <class B> int zsk_planes_join(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst, uint32_t filter = ZSK_FILTER_NONE)
+{
+    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err, filter)) return rc;
     if (!size) return 0;
     ZskJoinArgs a; memset(&a, 0, sizeof a);
     a.planar = (const uint8_t*)d_src; a.dst = (uint8_t*)d_dst; a.elements = size / k; a.k = k; a.group = frameSize; a.tiles = zsk_planes_tiles(a.elements, frameSize);
-    b.launch_typed(ZSKT_K_PLANES_JOIN, zsk_tile_grid(b.numCU, a.tiles, 0), &a);
+    uint8_t* sums = nullptr;
+    if (filter == ZSK_FILTER_DELTA) if (int rc = b.reserve_typed(ZSKT_A_TILESUMS, (size_t)a.tiles * 8, &sums)) return rc;
+    zsk_launch_join(b, filter, a, zsk_frame_count(a.elements, frameSize), sums);
     return b.check();
 }
 
 // Typed compress: the split kernel writes the planar staging buffer and the plane frames' records; the records call compresses them as they are; the seal
 // puts the marker in. The records call is handed the capacity less the marker and its entry, so a stream that does not fit fails there (70) with nothing written
 template <class B> int zsk_typed_compress(B& b, bool ctx, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t k, int flags, void* d_dst, uint64_t dstCapacity,
-                                          uint64_t* d_streamSize, int32_t* d_status)
+                                          uint64_t* d_streamSize, int32_t* d_status, uint32_t filter = ZSK_FILTER_NONE)
 {
+    if (k == 1 && filter != ZSK_FILTER_NONE) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, zsk_filter_ok(filter) ? "seekable typed compress: a filter needs an element size of 2, 4 or 8" : "seekable typed compress: the filter must be 0 (none) or 1 (delta)");
     if (k == 1) return zsk_compress(b, ctx, d_src, srcSize, frameSize, flags, d_dst, dstCapacity, d_streamSize, d_status);
-    if (int rc = zsk_typed_compress_check(ctx && d_streamSize && d_status && (!srcSize || d_src), srcSize, frameSize, k, flags, b.err)) return rc;
+    if (int rc = zsk_typed_compress_check(ctx && d_streamSize && d_status && (!srcSize || d_src), srcSize, frameSize, k, flags, b.err, filter)) return rc;
     const int checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1 : 0;
     const uint64_t elements = srcSize / k, nGroups = zsk_frame_count(elements, frameSize), n = nGroups * k;
     uint8_t* staging = nullptr; uint8_t* records = nullptr; uint8_t* stash = nullptr;
@@ -83,7 +100,7 @@ template <class B> int zsk_typed_compress(B& b, bool ctx, const void* d_src, uin
     if (n) {
         ZskPlanesArgs a; memset(&a, 0, sizeof a);
         a.src = (const uint8_t*)d_src; a.dst = staging; a.elements = elements; a.k = k; a.group = frameSize; a.nGroups = (uint32_t)nGroups; a.records = (uint64_t*)records;
-        b.launch_typed(ZSKT_K_PLANES_SPLIT, zsk_tile_grid(b.numCU, zsk_planes_tiles(elements, frameSize), n), &a);
+        b.launch_typed(filter == ZSK_FILTER_DELTA ? ZSKT_K_PLANES_SPLIT_DELTA : ZSKT_K_PLANES_SPLIT, zsk_tile_grid(b.numCU, zsk_planes_tiles(elements, frameSize), n), &a);
         if (int rc = b.check()) return rc;
     }
     const uint64_t extra = ZSK_MARKER + zsk_entry_size(checksum);
@@ -91,7 +108,7 @@ template <class B> int zsk_typed_compress(B& b, bool ctx, const void* d_src, uin
                                       d_dst, dstCapacity > extra ? dstCapacity - extra : 0, d_streamSize, d_status)) return rc;
     ZskSealArgs s; memset(&s, 0, sizeof s);
     s.dst = (uint8_t*)d_dst; s.dstCapacity = dstCapacity; s.streamSize = d_streamSize; s.outStatus = d_status; s.stash = stash;
-    s.n = (uint32_t)n; s.checksum = (uint32_t)checksum; s.elementSize = k; s.frameSize = frameSize;
+    s.n = (uint32_t)n; s.checksum = (uint32_t)checksum; s.elementSize = k | (filter << 8); s.frameSize = frameSize;
     const uint32_t grid = zsk_lane_grid(b.numCU, n * zsk_entry_size(checksum) / 16 + 1);
     b.launch_typed(ZSKT_K_SEAL_STASH, grid, &s);
     b.launch_typed(ZSKT_K_SEAL, grid, &s);
@@ -99,21 +116,21 @@ template <class B> int zsk_typed_compress(B& b, bool ctx, const void* d_src, uin
 }
 
 // Behind zsk_open: a last entry of (24, 0) is looked at -- the one extra copy, and only then. No tag: a plain stream. A tag and the shape it promises:
-// a typed stream. A tag and anything else (a version or an element size this reader does not know, frames that are no groups of planes): corrupt, at the
+// a typed stream. A tag and anything else (a version, an element size or a filter this reader does not know, frames that are no groups of planes): corrupt, at the
 // first frame that does not fit
 template <class B> int zsk_typed_probe(B& b, ZskTypedOpened* h, int* zerr, size_t* index)
 {
-    h->elementSize = 1; h->groupElements = 0;
+    h->elementSize = 1; h->groupElements = 0; h->filter = ZSK_FILTER_NONE;
     const uint32_t n = h->lay.n;
     if (!n || h->cOff[n] - h->cOff[n - 1] != ZSK_MARKER || h->dOff[n] != h->dOff[n - 1]) return 0;
     uint8_t m[ZSK_MARKER];
     if (b.copy(m, h->stream + h->cOff[n - 1], ZSK_MARKER, ZSK_COPY_TO_HOST) || b.wait()) return zsk_refuse(b.err, ZHIP_ERR_HIP, "seekable open: reading the last frame failed");
-    uint32_t k = 0, frameSize = 0;
-    const int kind = zsk_parse_marker(m, &k, &frameSize);
+    uint32_t k = 0, frameSize = 0, filter = 0;
+    const int kind = zsk_parse_marker(m, &k, &frameSize, &filter);
     if (!kind) return 0;
     const uint32_t bad = kind < 0 ? n - 1 : zsk_typed_shape(h->dOff.data(), n, k, frameSize);
     if (bad != n) { *zerr = ZSK_ERR_CORRUPT; *index = bad; return ZHIP_ERR_ZSTD; }
-    h->elementSize = k; h->groupElements = frameSize;
+    h->elementSize = k; h->groupElements = frameSize; h->filter = filter;
     return 0;
 }
 
@@ -126,7 +143,8 @@ static inline ZskTypedReadLayout zsk_typed_read_layout(size_t J, size_t R, size_
     return l;
 }
 
-// R user ranges in element order: per pass of the plan the many-ranges call into the planar buffer and the join kernel; then the status reducer.
+// R user ranges in element order: per pass of the plan the many-ranges call into the planar buffer and the join kernel (the handle's filter picks it: under
+// delta the three launches of zsk_launch_join); then the status reducer.
 // stats (where given) receives the sums over the passes' many-ranges calls, `passes` counting the typed passes
 template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h, const uint64_t* rg, size_t R, void* d_dst, uint64_t dstCapacity, int32_t* d_status,
                                         zhip_seekable_gather_stats* stats, size_t* bad)
@@ -138,7 +156,7 @@ template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h,
     if (!any) return b.zero(d_status, (2 + 2 * R) * sizeof(int32_t));
 
     ZskTypedPlan plan;
-    zsk_typed_plan(h->dOff.data(), h->elementSize, h->groupElements, rg, R, h->scratchLimit, &plan);
+    zsk_typed_plan(h->dOff.data(), h->elementSize, h->groupElements, rg, R, h->scratchLimit, &plan, h->filter);
     const size_t J = plan.jobs.size(), Q = plan.planar.size() / 3, nPass = plan.passes.size();
     const ZskTypedReadLayout l = zsk_typed_read_layout(J, R, Q);
     std::vector<uint32_t> pairAt(Q);
@@ -148,6 +166,12 @@ template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h,
     if (int rc = b.reserve_typed(ZSKT_A_PLANAR, (size_t)plan.pMax, &P)) return rc;
     if (int rc = b.reserve_typed(ZSKT_A_TABLES, l.tableBytes, &t)) return rc;
     if (int rc = b.reserve_typed(ZSKT_A_STATUS, statusInts * 4, &st)) return rc;
+    uint8_t* sums = nullptr;
+    if (h->filter == ZSK_FILTER_DELTA) {
+        uint64_t most = 0;
+        for (const ZskTypedPass& p : plan.passes) if (p.tiles > most) most = p.tiles;
+        if (int rc = b.reserve_typed(ZSKT_A_TILESUMS, (size_t)most * 8, &sums)) return rc;
+    }
     if (int rc = b.reserve(ZSK_A_PIN, l.tableBytes, &pin)) return rc;
     memcpy(pin + l.oJobs, plan.jobs.data(), J * sizeof(ZskJoinJob));
     memcpy(pin + l.oOwner, plan.owner.data(), R * 8);
@@ -163,7 +187,7 @@ template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h,
         if (stats) { stats->items += one.items; stats->inPlace += one.inPlace; stats->scratchBytes += one.scratchBytes; stats->copyJobs += one.copyJobs; stats->passes++; }
         ZskJoinArgs a; memset(&a, 0, sizeof a);
         a.planar = P; a.dst = (uint8_t*)d_dst; a.jobs = (const ZskJoinJob*)(t + l.oJobs) + ps.job0; a.nJobs = ps.job1 - ps.job0; a.tiles = ps.tiles; a.k = h->elementSize; a.group = h->groupElements;
-        b.launch_typed(ZSKT_K_PLANES_JOIN, zsk_tile_grid(b.numCU, a.tiles, 0), &a);
+        zsk_launch_join(b, h->filter, a, a.nJobs, sums);
         if (int rc = b.check()) return rc;
     }
     ZskTypedStatusArgs s; memset(&s, 0, sizeof s);

@@ -12,6 +12,15 @@ from . import _lib
 from .backend_hip import ZstdError
 
 
+def _filter_code(filter):
+    """the filter of a typed seekable stream, None or "delta" -> ZHIP_FILTER_NONE / ZHIP_FILTER_DELTA"""
+    if filter is None:
+        return 0
+    if filter == "delta":
+        return 1
+    raise ZstdError("filter must be None or \"delta\"")
+
+
 class DeviceBatchContext:
     """Owns the native context (scratch, dictionary tables, kernel timers) for one GPU / one stream."""
 
@@ -143,7 +152,7 @@ class DeviceBatchContext:
         """waves of the entropy kernel resident on this device"""
         return int(self.L.zhip_ctx_entropy_grid(self.ctx))
 
-    def seekable_compress(self, src, frame_size=131072, checksum=False, stream=None, element_size=1):
+    def seekable_compress(self, src, frame_size=131072, checksum=False, stream=None, element_size=1, filter=None):
         """src (a uint8 CUDA tensor) as ONE zstd seekable stream: frames of frame_size bytes of it, compressed as a batch with this context's
         parameters, back to back, then the seek table (checksum: with the low 32 bits of XXH64 of every frame's content). Returns a uint8 CUDA
         tensor of exactly the stream's size -- a view of a zhip_seekable_bound-sized allocation. Waits for the size. Any zstd decoder decompresses
@@ -152,13 +161,20 @@ class DeviceBatchContext:
         of one group, and every group becomes element_size frames, one per byte position of the elements ("byte planes": each gets entropy tables of its own,
         8-20 % smaller streams for bf16 / fp16 / fp32 weights and integer ids). A marker frame behind the last plane makes the stream describe itself:
         SeekableStream reads elements back; other zstd decoders see the planar bytes (zstandard_amd.seekable.planes_to_elements). Takes src.numel() more
-        bytes of context memory, kept between calls."""
+        bytes of context memory, kept between calls.
+        filter "delta" (typed streams only): for INTEGER tensors whose neighbours are close -- offsets, sorted ids, timestamps, counters, running sums. Per group
+        the planes are those of d[0] = x[0], d[i] = x[i] - x[i - 1] mod 2^(8 * element_size), the subtraction fused into the split kernel; 13-34 % smaller
+        streams on such data, nothing gained on floats. The marker names the filter: SeekableStream reads the elements back (``SeekableStream.filter``),
+        other decoders see the filtered planar bytes (planes_to_elements(..., filter="delta"))."""
         self._ensure_cparams()
         self._check(src, torch.uint8)
         s = stream if stream is not None else torch.cuda.current_stream()
         flags = _lib.SEEKABLE_CHECKSUM if checksum else 0
+        code = _filter_code(filter)
+        if code and element_size == 1:
+            raise ZstdError("seekable compress: a filter needs an element_size of 2, 4 or 8")
         if element_size != 1:
-            return self._seekable_compress_typed(src, frame_size, element_size, flags, s)
+            return self._seekable_compress_typed(src, frame_size, element_size, flags, s, code)
         bound = self.L.zhip_seekable_bound(src.numel(), frame_size, flags)
         if not bound:
             raise ZstdError("seekable compress: frame_size must be 1 ... 2^30 and give at most 2^27 frames")
@@ -178,7 +194,7 @@ class DeviceBatchContext:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return dst[:int(size[0])]
 
-    def _seekable_compress_typed(self, src, frame_size, element_size, flags, s):
+    def _seekable_compress_typed(self, src, frame_size, element_size, flags, s, filter_code=0):
         if element_size not in (2, 4, 8):
             raise ZstdError("seekable compress: element_size must be 1, 2, 4 or 8")
         if src.numel() % element_size:
@@ -190,8 +206,8 @@ class DeviceBatchContext:
             dst = torch.empty(bound, dtype=torch.uint8, device=src.device)
             size = torch.zeros(1, dtype=torch.int64, device=src.device)
             status = torch.zeros(2, dtype=torch.int32, device=src.device)
-        rc = self.L.zhip_seekable_compress_typed_device(self.ctx, src.data_ptr() if src.numel() else None, src.numel(), frame_size, element_size, flags, dst.data_ptr(), bound,
-                                                        size.data_ptr(), status.data_ptr(), s.cuda_stream)
+        rc = self.L.zhip_seekable_compress_typed_filter_device(self.ctx, src.data_ptr() if src.numel() else None, src.numel(), frame_size, element_size, filter_code, flags,
+                                                               dst.data_ptr(), bound, size.data_ptr(), status.data_ptr(), s.cuda_stream)
         if rc:
             raise ZstdError("seekable compress failed: %s" % _lib.last_error())
         err = _lib.Error()
@@ -202,7 +218,7 @@ class DeviceBatchContext:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return dst[:int(size[0])]
 
-    def _planes(self, call, src, frame_size, element_size, out, stream):
+    def _planes(self, call, src, frame_size, element_size, out, stream, filter=None):
         assert src.is_cuda and src.is_contiguous(), "expected a contiguous CUDA tensor"
         raw = src.view(torch.uint8).reshape(-1)
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -211,18 +227,20 @@ class DeviceBatchContext:
                 out = torch.empty(raw.numel(), dtype=torch.uint8, device=src.device)
         self._check(out, torch.uint8)
         assert out.numel() >= raw.numel(), "out is shorter than the source"
-        if call(self.ctx, raw.data_ptr() if raw.numel() else None, raw.numel(), element_size, frame_size, out.data_ptr() if raw.numel() else None, s.cuda_stream):
+        if call(self.ctx, raw.data_ptr() if raw.numel() else None, raw.numel(), element_size, frame_size, _filter_code(filter), out.data_ptr() if raw.numel() else None, s.cuda_stream):
             raise ZstdError("planes: %s" % _lib.last_error())
         return out[:raw.numel()]
 
-    def planes_split(self, src, frame_size, element_size=None, out=None, stream=None):
+    def planes_split(self, src, frame_size, element_size=None, out=None, stream=None, filter=None):
         """the bytes of src (any contiguous CUDA tensor; element_size None: its dtype's) in the PLANAR order of a typed seekable stream, as a uint8 tensor: groups
-        of frame_size elements, group g's plane p -- byte p of every element -- at g * element_size * frame_size + p * (the group's elements). Asynchronous."""
-        return self._planes(self.L.zhip_planes_split_device, src, frame_size, src.element_size() if element_size is None else element_size, out, stream)
+        of frame_size elements, group g's plane p -- byte p of every element -- at g * element_size * frame_size + p * (the group's elements). filter "delta": the planes of the
+        group's differences (seekable_compress), subtracted in the same kernel. Asynchronous."""
+        return self._planes(self.L.zhip_planes_split_filter_device, src, frame_size, src.element_size() if element_size is None else element_size, out, stream, filter)
 
-    def planes_join(self, planar, frame_size, element_size, out=None, stream=None):
-        """planes_split's inverse: planar bytes -> the elements' bytes, as a uint8 tensor (view it as the dtype). Asynchronous."""
-        return self._planes(self.L.zhip_planes_join_device, planar, frame_size, element_size, out, stream)
+    def planes_join(self, planar, frame_size, element_size, out=None, stream=None, filter=None):
+        """planes_split's inverse under the same filter: planar bytes -> the elements' bytes, as a uint8 tensor (view it as the dtype). Under "delta" the
+        prefix sum of every group, three launches and 8 bytes of context memory per 1 024 elements. Asynchronous."""
+        return self._planes(self.L.zhip_planes_join_filter_device, planar, frame_size, element_size, out, stream, filter)
 
     def _records_table(self, src, records, max_content_bytes, max_record_bytes, s, what="seekable compress"):
         """records as seekable_compress_records takes them -> (the (n, 2) int64 CUDA table, n, max_content_bytes, max_record_bytes)"""
@@ -378,24 +396,24 @@ class DeviceBatchContext:
         return self.L.zhip_kernel_name(direction).decode()
 
 
-def planes_split(src, frame_size, element_size=None, ctx=None, out=None, stream=None):
+def planes_split(src, frame_size, element_size=None, ctx=None, out=None, stream=None, filter=None):
     """DeviceBatchContext.planes_split on `ctx`, or on a context of its own (then it waits)"""
     if ctx is not None:
-        return ctx.planes_split(src, frame_size, element_size, out, stream)
+        return ctx.planes_split(src, frame_size, element_size, out, stream, filter)
     with_ctx = DeviceBatchContext()
     try:
-        return with_ctx.planes_split(src, frame_size, element_size, out, stream)
+        return with_ctx.planes_split(src, frame_size, element_size, out, stream, filter)
     finally:
         with_ctx.close()
 
 
-def planes_join(planar, frame_size, element_size, ctx=None, out=None, stream=None):
+def planes_join(planar, frame_size, element_size, ctx=None, out=None, stream=None, filter=None):
     """DeviceBatchContext.planes_join on `ctx`, or on a context of its own (then it waits)"""
     if ctx is not None:
-        return ctx.planes_join(planar, frame_size, element_size, out, stream)
+        return ctx.planes_join(planar, frame_size, element_size, out, stream, filter)
     with_ctx = DeviceBatchContext()
     try:
-        return with_ctx.planes_join(planar, frame_size, element_size, out, stream)
+        return with_ctx.planes_join(planar, frame_size, element_size, out, stream, filter)
     finally:
         with_ctx.close()
 
@@ -405,9 +423,10 @@ class SeekableStream:
     ``read_ranges`` many ranges as one decode batch, ``read_records`` whole frames by index; ``frame_offsets`` is the table it opened.
 
     A TYPED stream (DeviceBatchContext.seekable_compress with element_size 2, 4 or 8) is recognised by its marker: ``element_size`` and ``group_elements``
-    say so (1 and 0 for a plain stream), and ``read`` / ``read_ranges`` return ELEMENTS -- offsets and lengths count the tensor's bytes. ``read_records`` and
+    say so (1 and 0 for a plain stream), ``filter`` is None or "delta" (seekable_compress's), and ``read`` / ``read_ranges`` return ELEMENTS whatever the
+    filter -- offsets and lengths count the tensor's bytes; under "delta" a group read in part is summed from its first element. ``read_records`` and
     ``frame_offsets`` stay raw: they name the plane frames. The edit family raises ValueError on a typed stream (moving plane frames breaks the groups).
-    ``raw=True`` opens a typed stream as the plain stream it also is: every call then sees its planar content, the edit family included.
+    ``raw=True`` opens a typed stream as the plain stream it also is: every call then sees its planar content -- under a filter the filtered one --, the edit family included.
 
     ctx: the DeviceBatchContext that decodes (its dictionary, format and window limit apply); stream_tensor: the whole stream, a uint8 CUDA tensor,
     kept alive and unchanged while this object is open. Opening reads and checks the seek table (it waits); a damaged table raises ZstdError."""
@@ -429,6 +448,7 @@ class SeekableStream:
         typed = not raw and ctx.L.zhip_seekable_element_size(h) != 1
         self.element_size = int(ctx.L.zhip_seekable_element_size(h)) if typed else 1
         self.group_elements = int(ctx.L.zhip_seekable_group_elements(h)) if typed else 0
+        self.filter = "delta" if typed and ctx.L.zhip_seekable_filter(h) == 1 else None
         self.last_gather_stats = None
         self._frame_offsets = None
         if scratch_limit is not None:

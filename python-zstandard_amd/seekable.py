@@ -6,7 +6,11 @@ sizes: one frame per record, read back by index; ``append_records`` / ``edit`` m
 
 ``compress(..., element_size=2 | 4 | 8)`` writes a TYPED stream for a tensor's bytes: groups of ``frame_size`` elements, one frame per byte position of the
 elements ("byte planes"), and a marker frame that says so. ``decompress`` / ``decompress_ranges`` recognise it and return the elements; any other zstd decoder
-returns the planar bytes, which ``planes_to_elements`` puts back in order (``elements_to_planes`` is its inverse) -- numpy on the host, no GPU."""
+returns the planar bytes, which ``planes_to_elements`` puts back in order (``elements_to_planes`` is its inverse) -- numpy on the host, no GPU.
+
+``filter="delta"`` (with an element_size) is for INTEGER tensors whose neighbours are close -- offsets, sorted ids, timestamps, counters, running sums: per
+group the planes are those of the differences of neighbouring elements mod 2^(8 * element_size), 13-34 % smaller streams on such data (floats gain nothing).
+The marker names the filter, so the readers return the elements as before; ``elements_to_planes`` / ``planes_to_elements`` take the same ``filter``."""
 import torch
 
 from .backend_hip import ZstdError
@@ -20,42 +24,59 @@ def _to_device(data):
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()
 
 
-def elements_to_planes(data, element_size, frame_size):
-    """bytes of elements -> the planar content of the typed stream ``compress(data, frame_size=frame_size, element_size=element_size)`` writes: per group of
-    frame_size elements, byte 0 of every element, then byte 1 of every element, ... Returns bytes."""
+def _filter_code(filter):
+    if filter not in (None, "delta"):
+        raise ValueError("filter must be None or \"delta\"")
+    return 1 if filter == "delta" else 0
+
+
+def elements_to_planes(data, element_size, frame_size, filter=None):
+    """bytes of elements -> the planar content of the typed stream ``compress(data, frame_size=frame_size, element_size=element_size, filter=filter)`` writes:
+    per group of frame_size elements, byte 0 of every element, then byte 1 of every element, ... -- under filter="delta" of the group's differences
+    d[0] = x[0], d[i] = x[i] - x[i - 1] mod 2^(8 * element_size), the elements read as unsigned little-endian integers. Returns bytes."""
     import numpy as np
     a = np.frombuffer(bytes(data), dtype=np.uint8)
     if element_size not in (2, 4, 8) or a.size % element_size or frame_size < 1:
         raise ValueError("element_size must be 2, 4 or 8, the data whole elements and frame_size at least 1")
+    delta = _filter_code(filter)
     out, step = np.empty_like(a), frame_size * element_size
     for at in range(0, a.size, step):
         g = a[at:at + step]
+        if delta:
+            x = g.view("<u%d" % element_size)
+            g = np.diff(x, prepend=x.dtype.type(0)).view(np.uint8)
         out[at:at + g.size] = g.reshape(-1, element_size).T.reshape(-1)
     return out.tobytes()
 
 
-def planes_to_elements(raw, element_size, frame_size):
-    """the planar content of a typed stream, as any zstd decoder returns it (``zstd -d``, ``SeekableStream(..., raw=True).read()``), -> the elements' bytes"""
+def planes_to_elements(raw, element_size, frame_size, filter=None):
+    """the planar content of a typed stream, as any zstd decoder returns it (``zstd -d``, ``SeekableStream(..., raw=True).read()``), -> the elements' bytes
+    (filter: the stream's, ``SeekableStream.filter`` -- under "delta" every group's inclusive prefix sum mod 2^(8 * element_size))"""
     import numpy as np
     a = np.frombuffer(bytes(raw), dtype=np.uint8)
     if element_size not in (2, 4, 8) or a.size % element_size or frame_size < 1:
         raise ValueError("element_size must be 2, 4 or 8, the data whole elements and frame_size at least 1")
+    delta = _filter_code(filter)
     out, step = np.empty_like(a), frame_size * element_size
     for at in range(0, a.size, step):
         g = a[at:at + step]
-        out[at:at + g.size] = g.reshape(element_size, -1).T.reshape(-1)
+        e = np.ascontiguousarray(g.reshape(element_size, -1).T).reshape(-1)
+        if delta:
+            d = e.view("<u%d" % element_size)
+            e = np.cumsum(d, dtype=d.dtype).view(np.uint8)
+        out[at:at + g.size] = e
     return out.tobytes()
 
 
-def compress(data, level=3, frame_size=131072, checksum=False, match_finder="libzstd", element_size=1, **ctx_kw):
+def compress(data, level=3, frame_size=131072, checksum=False, match_finder="libzstd", element_size=1, filter=None, **ctx_kw):
     """data -> a seekable stream (bytes). match_finder: "libzstd" (frames byte for byte libzstd's) or "wave" (DeviceBatchContext.set_match_finder: valid zstd,
     not libzstd's bytes; frame_size at most 131 072) or "none" (no match search: every frame is libzstd's literals-only frame of its content, for NUMERIC
     TENSORS -- with element_size 2, 4 or 8 the fastest compress path, and streams the size of level 3's or up to 13 % smaller on float data; "on data with real
     repetition they lose badly: the int64 sums here, and any text", 1.9 x on int64 running sums; frame_size at most 131 072 bytes of a plane). element_size 2, 4 or 8: a typed stream -- data is elements of that many bytes, frame_size counts the
-    elements of a group (see the module). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
+    elements of a group (see the module); filter None or "delta": the filter of a typed stream (see the module; with element_size 1 a ZstdError). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
     ctx = DeviceBatchContext(level=level, match_finder=match_finder, **ctx_kw)
     try:
-        return ctx.seekable_compress(_to_device(data), frame_size=frame_size, checksum=checksum, element_size=element_size).cpu().numpy().tobytes()
+        return ctx.seekable_compress(_to_device(data), frame_size=frame_size, checksum=checksum, element_size=element_size, filter=filter).cpu().numpy().tobytes()
     finally:
         ctx.close()
 
