@@ -232,6 +232,9 @@ static int huf_read_table(huf_dtable* ht, const uint8_t* src, size_t srcSize)
         int hdr = zo_fse_read_ncount(norm, &maxS, &tl, src + 1, hb);
         if (hdr < 0) return hdr;
         if (tl > 6) return -ZO_E_TABLELOG_TOO_LARGE;
+        /* libzstd's work area for this decode is sized for log 6 and the weights 0 .. 11 (HUF_READ_STATS_WORKSPACE_SIZE); a distribution that needs more
+         * 4-byte units than that one -- log 6 naming weight 12, log 5 naming a symbol above 91 -- is refused with tableLog_tooLarge */
+        if ((1u << tl) + (2 * (maxS + 1) + (1u << tl) + 8 + 3) / 4 > 64 + 24) return -ZO_E_TABLELOG_TOO_LARGE;
         fse_dtable dt;
         int e = fse_build_dtable(&dt, norm, maxS, tl); if (e < 0) return e;
         bwd_bits b; e = bwd_init(&b, src + 1 + hdr, hb - (size_t)hdr); if (e < 0) return e;

@@ -352,6 +352,11 @@ ZH_DEV uint32_t zd_pb_peek(const ZdPBits& b, uint32_t n) { return (uint32_t)((b.
 ZH_DEV bool zd_pb_done(const ZdPBits& b) { return b.ptr == b.start && b.used == 64; }
 
 // ------------------------------------------------------------------------------------------ Huffman
+// The distribution of FSE-compressed weights: accuracy log at most 6, no symbol above weight 12 -- and not both limits at once: libzstd decodes the weights in a
+// work area sized for log 6 and the weights 0 .. 11 (HUF_READ_STATS_WORKSPACE_SIZE; its own encoder stops at 11) and refuses a distribution that needs more, which
+// is one of log 6 that names weight 12. We never accept what it refuses (tests/huffamilies.py, "FSE descriptions"). A distribution that NAMES a symbol above 12 is
+// refused whether a weight uses it or not: stricter than libzstd at accuracy log 5, and what keeps every FSE-decoded weight at 12 or below.
+ZH_DEV bool zd_weights_dist_ok(uint32_t tl, uint32_t maxS) { return tl <= 6 && maxS <= 12 && !(tl == 6 && maxS == 12); }
 // Reads a tree description into L.weights (all lanes call). Returns bytes used or -err; *pCount = #weights incl. last.
 // `pre` (K1 of the pipeline, round 6): K0's record of the frame -- when it holds the weights of the description at block offset `at`, they are copied and nothing is parsed
 ZH_DEVFN int zd_read_huf_weights(ZdLDS& L, const uint8_t* src, uint32_t srcSize, uint32_t* pCount, uint32_t* pLog, const ZpPre* pre = nullptr, uint32_t at = 0)
@@ -392,7 +397,7 @@ ZH_DEVFN int zd_read_huf_weights(ZdLDS& L, const uint8_t* src, uint32_t srcSize,
         }
         zh_sync();
         int r = (int)L.misc[0]; uint32_t maxS = L.misc[1], tl = L.misc[2];
-        if (r < 0 || tl > 6 || maxS > 12) return -ZE_CORRUPTION;
+        if (r < 0 || !zd_weights_dist_ok(tl, maxS)) return -ZE_CORRUPTION;
         if (zd_build_fse(L, L.u.b.wfse, maxS, tl, ZD_KIND_W) < 0) return -ZE_CORRUPTION;
         if (lane == 0) {
             ZdBits b; uint32_t cnt = 0; int bad = 0;
@@ -433,13 +438,13 @@ ZH_DEVFN int zd_read_huf_weights(ZdLDS& L, const uint8_t* src, uint32_t srcSize,
     uint32_t part = 0, ones = 0;
     for (uint32_t i = lane; i < n; i += 64) {
         uint32_t w = L.weights[i];
-        if (w > 12) part = 0x40000000u;
+        if (w > 12) part = 0x02000000u;                   // (a mark that 64 lanes cannot wrap: 64 x (2^25 + 4 x 2^11) < 2^32)
         else if (w) part += 1u << (w - 1);
         ones += (w == 1);
     }
     uint32_t total = zh_shfl(zh_scan_add(part), 63);
     uint32_t nOnes = zh_shfl(zh_scan_add(ones), 63);
-    if (total == 0 || total >= 0x40000000u) return -ZE_CORRUPTION;
+    if (total == 0 || total >= 0x02000000u) return -ZE_CORRUPTION;
     uint32_t log = (uint32_t)zh_highbit32(total) + 1;
     if (log > 12) return -ZE_CORRUPTION;
     uint32_t rest = (1u << log) - total;
@@ -586,6 +591,9 @@ ZH_DEVFN int zd_literals(ZdLDS& L, ZdState& st, const uint8_t* src, uint32_t src
         st.litPtr = lit; st.litSize = regen;
         return (int)(hdr + csize);
     }
+#ifdef ZHIP_EMU
+    if (type == 3 && defer && lane == 0) zd_stat[5]++;                                   // (test hook [5]: treeless blocks of the pipeline rebuilt from the weights in LDS)
+#endif
     int lg = zd_build_huf(L, st.hufCount);
     if (lg < 0) return -ZE_CORRUPTION;
     if (defer && (uint32_t)lg <= defer->maxLog) {
@@ -601,6 +609,9 @@ ZH_DEVFN int zd_literals(ZdLDS& L, ZdState& st, const uint8_t* src, uint32_t src
         return (int)(hdr + csize);
     }
     ZD_T(P, ZP_HUFTAB);
+#ifdef ZHIP_EMU
+    if (defer && lane == 0) zd_stat[4]++;                                                // (test hook [4]: Huffman streams decoded inside K1, the table too deep for K1b's slots)
+#endif
     bool ok = true;
     if (!four) {
         if (lane == 0) ok = zd_huf_stream(L.u.huf, (uint32_t)lg, p, left, lit, regen);

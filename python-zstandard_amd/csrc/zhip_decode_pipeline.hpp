@@ -374,7 +374,7 @@ ZH_DEV void zp_pre_weights(ZpPre& R, ZpPreLane& S, const uint8_t* desc, uint32_t
 {
     uint32_t maxS = 63, tl = 0;
     const int r = zd_read_ncount_to(S.wnorm, desc, desc + hb, &maxS, &tl);
-    if (r < 0 || tl > 6 || maxS > 12) return;
+    if (r < 0 || !zd_weights_dist_ok(tl, maxS)) return;
     const uint32_t size = 1u << tl, mask = size - 1, step = (size >> 1) + (size >> 3) + 3;
     uint32_t high = size - 1, total = 0;
     for (uint32_t q = 0; q <= maxS; q++) {
@@ -588,7 +588,12 @@ ZH_DEVFN void zp_lit_body(const ZhipPipeArgs& a, ZdLDS& L)
             if (de) {                                                       // a dictionary with entropy tables: they are the block's "previous" tables
                 st.hufCount = de->hufCount;
                 if (a.dictTables->hufLog <= ZP_HUF_LOGMAX) { df.prevTable = a.dictTables->huf; df.prevLog = a.dictTables->hufLog; }
-                else { zh_sync(); for (uint32_t k = lane; k < 256; k += 64) L.weights[k] = de->hufWeights[k]; zh_sync(); }
+                else {
+                    zh_sync(); for (uint32_t k = lane; k < 256; k += 64) L.weights[k] = de->hufWeights[k]; zh_sync();
+#ifdef ZHIP_EMU
+                    if (lane == 0) zd_stat[6]++;                            // (test hook [6]: frames that met a dictionary table too deep to share)
+#endif
+                }
             }
             err = zp_block_tables(a, L, st, df, src, pos, bs, blockMax, i, m, P, true, false);
             if (err == (int)ZP_RC_FALLBACK) { err = 0; fallback = true; break; }
@@ -688,6 +693,9 @@ ZH_DEVFN void zp_lit_mb_body(const ZhipPipeArgs& a, ZdLDS& L)
             if (de) {                                                       // the dictionary's tables are the first block's "previous" ones
                 st.hufCount = de->hufCount;
                 if (a.dictTables->hufLog <= ZP_HUF_LOGMAX) { prevTable = a.dictTables->huf; prevLog = a.dictTables->hufLog; }
+#ifdef ZHIP_EMU
+                else if (lane == 0) zd_stat[6]++;                           // (test hook [6], as in zp_lit_body)
+#endif
                 zh_sync();
                 for (uint32_t k = lane; k < 256; k += 64) L.weights[k] = de->hufWeights[k];
                 const uint32_t* T = a.dictTables->fse;

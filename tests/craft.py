@@ -286,6 +286,72 @@ def sequences_section(seqs, modes=(0, 0, 0), count_bytes=None):
     return head + w.finish()
 
 
+def ncount(norm, log):
+    """An FSE distribution as the format writes it (RFC 8878 4.1.1): the accuracy log, then every count in its variable width with the zero-run
+    flags, up to the symbol that completes the total (a list that stays below 2^log ends where it ends: the reader goes on into what follows)"""
+    w = _Bits()
+    w.add(log - 5, 4)
+    remaining, threshold, nb = (1 << log) + 1, 1 << log, log + 1
+    s = 0
+    while s < len(norm) and remaining > 1:
+        c = norm[s]; s += 1
+        v, mx = c + 1, 2 * threshold - 1 - remaining
+        assert 0 <= v <= remaining, "a count above what is left cannot be written"
+        if v < mx: w.add(v, nb - 1)
+        elif v < threshold: w.add(v, nb)
+        else: w.add(v + mx, nb)
+        remaining -= abs(c)
+        while 1 <= remaining < threshold: nb -= 1; threshold >>= 1
+        if c == 0 and remaining > 1 and s < len(norm):
+            run = 0
+            while s < len(norm) and norm[s] == 0: run += 1; s += 1
+            for _ in range(run // 3): w.add(3, 2)
+            w.add(run % 3, 2)
+    if w.n: w.out.append(w.acc)
+    return bytes(w.out)
+
+
+def fit_norm(ws, log):
+    """a normalised distribution over the weights in `ws` that totals 2^log: every weight present gets at least one cell, the most frequent one the rest"""
+    size, cnt = 1 << log, [0] * (max(ws) + 1)
+    for x in ws: cnt[x] += 1
+    norm = [max(1, c * size // len(ws)) if c else 0 for c in cnt]
+    top = max(range(len(cnt)), key=lambda i: cnt[i])
+    while sum(norm) > size:
+        big = max(range(len(norm)), key=lambda i: norm[i]); norm[big] -= 1
+    norm[top] += size - sum(norm)
+    if norm[top] == size:                                                       # one weight value alone: no state would read a bit and the stream never end
+        if len(norm) == 1: norm.append(0)
+        norm[top] -= 1; norm[1 if top == 0 else 0] = 1
+    assert all(n > 0 for n, c in zip(norm, cnt) if c) and sum(norm) == size
+    return norm
+
+
+def fse_weights(ws, log, norm, report=None):
+    """distribution + the two-state backward bit stream of the weights `ws`. The decoder gives weight 0, 2, 4 ... from its first state and 1, 3, 5 ...
+    from its second, and ends when a state update asks for more bits than are left: the weight just given and one more from the OTHER state are
+    the last two. So the stream holds the updates behind the weights 0 .. n - 3 and not one bit more, and the state that gives weight n - 2 is one
+    whose update reads at least one bit. Walked backwards: each weight takes the state of its symbol whose range holds the state two weights on."""
+    n = len(ws)
+    assert n >= 2
+    cells = _decode_table(norm, log)
+    by = {}
+    for x, c in enumerate(cells): by.setdefault(c[0], []).append(x)
+    st = [None] * n
+    st[n - 1] = by[ws[n - 1]][0]
+    st[n - 2] = next(x for x in by[ws[n - 2]] if cells[x][1] >= 1)
+    w = _Bits()
+    for i in range(n - 3, -1, -1):
+        succ = st[i + 2]
+        x = next(x for x in by[ws[i]] if cells[x][2] <= succ < cells[x][2] + (1 << cells[x][1]))
+        w.add(succ - cells[x][2], cells[x][1]); st[i] = x
+    w.add(st[1], log); w.add(st[0], log)
+    body = ncount(norm, log) + w.finish()
+    if report is not None:
+        report.update({"weights": n, "exit": 3 if n > 255 else 1 if n % 2 == 0 else 2, "bytes": len(body)})
+    return body
+
+
 class HufTable:
     """A canonical Huffman code of the format (RFC 8878 4.2.1) over the byte values in `data` (all <= 128, so the weights fit the direct form;
     at least two different values), code lengths capped at 11 bits. nbits[s] / code[s] per symbol; description() is the tree as direct weights."""
@@ -312,10 +378,43 @@ class HufTable:
                 if ws == w: self.nbits[s] = mb_ + 1 - w; self.code[s] = pos >> (w - 1); pos += 1 << (w - 1)
         assert pos == 1 << mb_
 
-    def description(self):
-        ws = self.weights[:-1]                                                  # the last symbol's weight is implied
-        ws = ws + [0] * (len(ws) & 1)
-        return bytes([127 + len(self.weights) - 1]) + bytes((ws[i] << 4) | ws[i + 1] for i in range(0, len(ws), 2))
+    @classmethod
+    def from_weights(cls, weights, valid=True):
+        """The canonical code of an explicit weight list: weights[s] for the symbols 0 .. len - 1 (any of 0 .. 255), zero = the symbol is absent, table log
+        1 .. 12. valid=True: the list is the whole alphabet -- its last weight is the one the format leaves implied and must be what completes the
+        sum to a power of two. valid=False: `weights` are the WRITTEN weights as they stand (nothing implied, nothing checked): a list to be
+        described, not to encode with."""
+        t = cls.__new__(cls)
+        t.weights = list(weights)
+        t.written = t.weights[:-1] if valid else t.weights
+        t.nbits, t.code, t.max_bits = {}, {}, None
+        if not valid: return t
+        assert 2 <= len(t.weights) <= 256 and t.weights[-1] > 0 and all(0 <= w <= 12 for w in t.weights)
+        total = sum(1 << (w - 1) for w in t.weights if w)
+        assert total & (total - 1) == 0 and total >= 2, "the weights do not complete to a power of two"
+        t.max_bits = mb_ = total.bit_length() - 1
+        assert any(t.written), "no weight in front of the implied one"        # (the reader takes the log from the written sum: always the list's own)
+        pos = 0
+        for w in range(1, mb_ + 1):
+            for s, ws in enumerate(t.weights):
+                if ws == w: t.nbits[s] = mb_ + 1 - w; t.code[s] = pos >> (w - 1); pos += 1 << (w - 1)
+        assert pos == 1 << mb_
+        return t
+
+    def description(self, form="direct", accuracy_log=6, norm=None, report=None):
+        """The tree description. form "direct": 4-bit weights (at most 128 of them). form "fse": the weights FSE-compressed (RFC 8878 4.2.1.2) on the
+        normalised distribution `norm` over the weights 0 .. len(norm) - 1 (-1 = "less than one"; default: one fitted to the list) at `accuracy_log`
+        (5 or 6); `report`, a dict, receives "weights" (how many the stream carries), "exit" (which of the decoder's ends it takes: 1 = the stream
+        runs out behind a weight of the first state, 2 = of the second, 3 = the list is too long and the decoder gives up first) and "bytes"."""
+        ws = getattr(self, "written", self.weights[:-1])                        # the last symbol's weight is implied
+        if form == "direct":
+            assert 1 <= len(ws) <= 128
+            pad = ws + [0] * (len(ws) & 1)
+            return bytes([127 + len(ws)]) + bytes((pad[i] << 4) | pad[i + 1] for i in range(0, len(pad), 2))
+        if norm is None: norm = fit_norm(ws, accuracy_log)
+        body = fse_weights(ws, accuracy_log, norm, report)
+        assert len(body) < 128, "an FSE description has at most 127 bytes (%d)" % len(body)
+        return bytes([len(body)]) + body
 
     def stream(self, data):
         w = _Bits()
@@ -323,9 +422,13 @@ class HufTable:
         return w.finish()
 
 
-def literals_section(lits, mode="raw", hdr=None, table=None):
+def literals_section(lits, mode="raw", hdr=None, table=None, desc=None, jump=None, mangle=None, claim=None, size_format=None):
     """The literals section of `lits`. mode: "raw" / "rle" (hdr = 1, 2 or 3 header bytes, default the shortest), "huf1" / "huf4" (Huffman with `table`
-    written in front, one or four streams) or "treeless1" / "treeless4" (the previous block's table, `table`, not written)."""
+    written in front, one or four streams) or "treeless1" / "treeless4" (the previous block's table, `table`, not written).
+    Huffman sections from explicit choices: desc = the description's bytes instead of table.description(); four streams of 6 literals and up (the
+    fourth stream is then empty: its end mark alone); jump = the three sizes of the jump table as written; mangle = a function from the list of
+    stream byte strings to the list to write; claim = the literal count the header states; size_format = 1 / 2 / 3 forces the 10- / 14- / 18-bit
+    sizes of the four-stream header."""
     n = len(lits)
     if mode in ("raw", "rle"):
         t = 0 if mode == "raw" else 1
@@ -336,18 +439,24 @@ def literals_section(lits, mode="raw", hdr=None, table=None):
         else: assert n < (1 << 20); h = ((n << 4) | (3 << 2) | t).to_bytes(3, "little")
         return h + (bytes(lits) if mode == "raw" else bytes(lits[:1]))
     t = 2 if mode.startswith("huf") else 3
-    body = table.description() if t == 2 else b""
+    body = (table.description() if desc is None else desc) if t == 2 else b""
+    said = n if claim is None else claim
     if mode.endswith("1"):
-        body += table.stream(lits)
-        assert n < 1024 and len(body) < 1024
-        return (t | (0 << 2) | (n << 4) | (len(body) << 14)).to_bytes(3, "little") + body
+        parts = [table.stream(lits)]
+        if mangle: parts = mangle(parts)
+        body += parts[0]
+        assert said < 1024 and len(body) < 1024
+        return (t | (0 << 2) | (said << 4) | (len(body) << 14)).to_bytes(3, "little") + body
     q = (n + 3) // 4
     parts = [table.stream(lits[i * q:(i + 1) * q]) for i in range(3)] + [table.stream(lits[3 * q:])]
-    assert n >= 3 * q + 1 and all(len(p) < 65536 for p in parts[:3])
-    body += b"".join(len(p).to_bytes(2, "little") for p in parts[:3]) + b"".join(parts)
+    assert n >= 3 * q and n >= 6 and all(len(p) < 65536 for p in parts[:3])
+    if mangle: parts = mangle(parts)
+    sizes = [len(p) for p in parts[:3]] if jump is None else list(jump)
+    body += b"".join(x.to_bytes(2, "little") for x in sizes) + b"".join(parts)
     for sf, bits, size in ((1, 10, 3), (2, 14, 4), (3, 18, 5)):
-        if n < (1 << bits) and len(body) < (1 << bits):
-            return (t | (sf << 2) | (n << 4) | (len(body) << (4 + bits))).to_bytes(size, "little") + body
+        if size_format not in (None, sf): continue
+        if said < (1 << bits) and len(body) < (1 << bits):
+            return (t | (sf << 2) | (said << 4) | (len(body) << (4 + bits))).to_bytes(size, "little") + body
     raise AssertionError("literals too large")
 
 
@@ -381,7 +490,8 @@ def frame_header(fcs=None, single_segment=False, window_log=17, dict_id=None, ch
 
 def write_frame(blocks, fcs="auto", content=None, checksum=None, **header):
     """A frame of `blocks`: ("seq", literals, seqs, options) / ("raw", data) / ("rle", byte, n). A "seq" block's options: lit = the literals mode
-    of literals_section (default "raw"), lit_hdr, modes, count_bytes; Huffman tables are built per block ("huf*") and inherited ("treeless*").
+    of literals_section (default "raw"), lit_hdr, modes, count_bytes; Huffman tables are built per block ("huf*") and inherited ("treeless*"), or
+    explicit: huf_table (a HufTable, e.g. from_weights), huf_desc (the description's bytes), jump, mangle, claim, size_format (literals_section).
     fcs "auto" declares len(content); checksum = the 32-bit trailer to write (the caller computes it: Oracle.xxh64(content) & 0xFFFFFFFF, or a
     wrong one); other keywords go to frame_header."""
     if fcs == "auto": fcs = len(content)
@@ -395,8 +505,9 @@ def write_frame(blocks, fcs="auto", content=None, checksum=None, **header):
             lits, seqs = bytes(b[1]), b[2]
             o = b[3] if len(b) > 3 else {}
             mode = o.get("lit", "raw")
-            if mode.startswith("huf"): table = HufTable(o.get("huf_from", lits))
-            body = literals_section(lits, mode, o.get("lit_hdr"), table) + sequences_section(seqs, o.get("modes", (0, 0, 0)), o.get("count_bytes"))
+            if "huf_table" in o: table = o["huf_table"]                        # (with a treeless mode: the table the block inherits, a dictionary's)
+            elif mode.startswith("huf"): table = HufTable(o.get("huf_from", lits))
+            body = literals_section(lits, mode, o.get("lit_hdr"), table, o.get("huf_desc"), o.get("jump"), o.get("mangle"), o.get("claim"), o.get("size_format")) + sequences_section(seqs, o.get("modes", (0, 0, 0)), o.get("count_bytes"))
             out.append(block(2, body, last))
     if checksum is not None: out.append((checksum & 0xFFFFFFFF).to_bytes(4, "little"))
     return b"".join(out)

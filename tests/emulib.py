@@ -47,13 +47,15 @@ class Emu:
         huf_count = struct.unpack_from("<I", blob.raw, 256)[0]
         return (blob if huf_count else None), dict_bytes[content_off:], dict_id
 
-    def decompress_batch(self, frames, sizes, n_blocks=2, dict_content=None, dict_id=0, dict_entropy=None):
+    def decompress_batch(self, frames, sizes, n_blocks=2, dict_content=None, dict_id=0, dict_entropy=None, pads=None):
         n = len(frames)
-        src = np.frombuffer(b"".join(frames) + b"\0" * 0, dtype=np.uint8).copy()
-        src_segs = np.zeros((n, 2), dtype=np.uint64)
-        o = 0
-        for i, f in enumerate(frames):
-            src_segs[i] = (o, len(f)); o += len(f)
+        if pads is None:
+            src = np.frombuffer(b"".join(frames) + b"\0" * 0, dtype=np.uint8).copy()
+            src_segs = np.zeros((n, 2), dtype=np.uint64)
+            o = 0
+            for i, f in enumerate(frames):
+                src_segs[i] = (o, len(f)); o += len(f)
+        else: src, src_segs = _padded_arena(frames, pads)
         dst_segs = np.zeros((n, 2), dtype=np.uint64)
         o = 0
         for i, s in enumerate(sizes):
@@ -110,13 +112,31 @@ def _emu_compress_batch(self, raws, level=3, flags=5, n_blocks=2, pipeline=False
 Emu.compress_batch = _emu_compress_batch
 
 
-def _emu_decompress_pipeline(self, frames, sizes, n_blocks=2, chunk=0):
-    n = len(frames)
-    src = np.frombuffer(b"".join(frames) + b"\0" * 16, dtype=np.uint8).copy()
-    src_segs = np.zeros((n, 2), dtype=np.uint64)
+def _padded_arena(frames, pads):
+    """frames with pads[i] filler bytes in front of frame i, in an arena whose first byte lies at a multiple of 64: (arena, segments). The offsets are
+    then absolute alignments, so a test can place a bit stream at a chosen offset mod 16."""
+    total = sum(pads) + sum(len(f) for f in frames)
+    raw = np.full(total + 16 + 64, 0x3C, dtype=np.uint8)
+    src = raw[(-raw.ctypes.data) % 64:][:total + 16]
+    assert src.ctypes.data % 64 == 0
+    segs = np.zeros((len(frames), 2), dtype=np.uint64)
     o = 0
     for i, f in enumerate(frames):
-        src_segs[i] = (o, len(f)); o += len(f)
+        o += pads[i]
+        src[o:o + len(f)] = np.frombuffer(f, dtype=np.uint8)
+        segs[i] = (o, len(f)); o += len(f)
+    return src, segs
+
+
+def _emu_decompress_pipeline(self, frames, sizes, n_blocks=2, chunk=0, pads=None):
+    n = len(frames)
+    if pads is None:
+        src = np.frombuffer(b"".join(frames) + b"\0" * 16, dtype=np.uint8).copy()
+        src_segs = np.zeros((n, 2), dtype=np.uint64)
+        o = 0
+        for i, f in enumerate(frames):
+            src_segs[i] = (o, len(f)); o += len(f)
+    else: src, src_segs = _padded_arena(frames, pads)
     dst_segs = np.zeros((n, 2), dtype=np.uint64)
     o = 0
     for i, s in enumerate(sizes):
