@@ -226,7 +226,7 @@ ZH_DEVFN int zd_build_fse(ZdLDS& L, uint32_t* table, uint32_t maxSym, uint32_t l
     bool low = (n == -1);
     uint64_t lowMask = zh_ballot(low);
     uint32_t nLow = (uint32_t)zh_popc64(lowMask);
-    uint32_t high = S - 1 - nLow;
+    const int high = (int)S - 1 - (int)nLow;     // -1 when every cell is a "less than one" symbol's (32 of them at log 5): the walk then places nothing
     if (low) L.u.b.symAt[S - 1 - (uint32_t)zh_popc64(lowMask & lt)] = (uint8_t)lane;
     uint32_t cnt = n > 0 ? (uint32_t)n : 0;
     uint32_t incl = zh_scan_add(cnt);
@@ -240,7 +240,7 @@ ZH_DEVFN int zd_build_fse(ZdLDS& L, uint32_t* table, uint32_t maxSym, uint32_t l
     for (uint32_t c = 0; c < S; c += 64) {
         uint32_t k = c + lane;
         uint32_t p = (k * step) & mask;
-        bool valid = (k < S) && (p <= high);
+        bool valid = (k < S) && ((int)p <= high);
         uint64_t m = zh_ballot(valid);
         if (valid) {
             uint32_t j = jbase + (uint32_t)zh_popc64(m & lt);

@@ -208,7 +208,8 @@ def encoding_variants():
 # ------------------------------------------------------------------------------------------------ frames from explicit sequences, at any size
 # A frame is DESCRIBED as a list of blocks -- ("seq", literals, [(ll, ml, offset value)], options), ("raw", data), ("rle", byte, n) -- which
 # tests/seqmodel.py executes in plain Python and write_frame() below turns into bytes. Nothing above this line changes (tests/golden/edge_frames.json
-# pins its bytes); the writer here has no size caps: 1/2/3-byte sequence counts, predefined or RLE mode per table, raw / RLE / Huffman literals
+# pins its bytes); the writer here has no size caps: 1/2/3-byte sequence counts, each table predefined, RLE, described (a distribution written in the block) or a
+# repeat of what an earlier block or a dictionary left, the last sequence's states and with them the initial states a choice, raw / RLE / Huffman literals
 # (one or four streams, direct weights, treeless), every frame-header form. The bit streams are built byte by byte, in linear time.
 class _Bits:
     """LSB-first bit writer; finish() appends the closing 1 bit. The format's decoders read such a stream from its end, so the fields are added in
@@ -251,9 +252,47 @@ def seq_codes(ll, ml, ofv):
     return (lc, ll - _LL_BASE[lc], _LL_BITS[lc]), (oc, ofv - (1 << oc), oc), (mc, ml - _ML_BASE[mc], _ML_BITS[mc])
 
 
-def sequences_section(seqs, modes=(0, 0, 0), count_bytes=None):
-    """count + modes byte + RLE symbols + bit stream for seqs = [(ll, ml, offset value)]; modes = (LL, OF, ML), each 0 (predefined) or 1 (RLE: every
-    sequence then has the same code in that table); count_bytes forces the 1-, 2- or 3-byte form of the count"""
+def fse_table(norm, log):
+    """(cells, log, {symbol: [states]}) of the table an FSE distribution describes (-1 = "less than one"), in the form sequences_section walks"""
+    cells = _decode_table(norm, log)
+    by = {}
+    for x, c in enumerate(cells): by.setdefault(c[0], []).append(x)
+    return cells, log, by
+
+
+def described(norm, log, desc=None, walk=None):
+    """mode 2 for one table of sequences_section's `modes`: the distribution `norm` at accuracy log `log` is written in the block (or `desc`, raw bytes, in
+    its place) and the states walk the table it describes -- or the table of `walk` = (norm, log), for a description the stream then does not follow. A
+    count of 0 is fine as long as no sequence uses that symbol."""
+    return {"mode": 2, "norm": list(norm), "log": log, "desc": desc, "walk": walk}
+
+
+def _state_walk(table, syms, last, first):
+    """the states of one table over `syms`, walked backwards: each symbol takes the state whose range holds its successor (in a table built from a
+    distribution there is exactly one). The last sequence's state is free: `last` = "first" (the lowest state of its symbol), "most" / "least" (the one
+    that reads the most / fewest bits when it is reached), or a state number; `first`, a state number, asks for the choice that makes the walk START there
+    (the stream's initial state). Returns (initial state, [(bits value, width)] behind every sequence but the last)."""
+    cells, _, by = table
+    cands = by[syms[-1]]
+    if isinstance(last, int): cands = [last]; assert cells[last][0] == syms[-1]
+    elif last == "most": cands = sorted(cands, key=lambda x: -cells[x][1])
+    elif last == "least": cands = sorted(cands, key=lambda x: cells[x][1])
+    for st in cands:
+        upd = [None] * (len(syms) - 1)
+        for i in range(len(syms) - 2, -1, -1):
+            succ = st
+            st = next(x for x in by[syms[i]] if cells[x][2] <= succ < cells[x][2] + (1 << cells[x][1]))
+            upd[i] = (succ - cells[st][2], cells[st][1])
+        if first is None or st == first: return st, upd
+    raise AssertionError("no choice of the last state starts the walk at state %r" % (first,))
+
+
+def sequences_section(seqs, modes=(0, 0, 0), count_bytes=None, inherit=None, last="first", first=(None, None, None), used=None):
+    """count + modes byte + RLE symbols / descriptions + bit stream for seqs = [(ll, ml, offset value)]; modes = (LL, OF, ML), each 0 (predefined), 1 (RLE:
+    every sequence then has the same code in that table), described(...) (mode 2: a distribution written in the block) or 3 (repeat: the table is
+    inherit[k], a fse_table() / _seq_table() value -- with nothing to inherit only the mode bits are written and the stream walks the predefined table);
+    count_bytes forces the 1-, 2- or 3-byte form of the count; last / first choose the states (_state_walk: one value, or one per table); `used`, a
+    list, receives the three tables the block leaves to a later "repeat"."""
     n = len(seqs)
     if count_bytes is None: count_bytes = 1 if n < 128 else 2 if n < 0x7F00 else 3
     if count_bytes == 1: assert n < 128; head = bytes([n])
@@ -261,28 +300,32 @@ def sequences_section(seqs, modes=(0, 0, 0), count_bytes=None):
     else: assert 0x7F00 <= n < 0x7F00 + 65536; head = b"\xff" + (n - 0x7F00).to_bytes(2, "little")
     if n == 0: return head
     codes = [seq_codes(*q) for q in seqs]
-    tabs = []
+    tabs, bits, body, left = [], [], b"", []
     for k in range(3):
-        if modes[k]:
+        m = modes[k]
+        if isinstance(m, dict):
+            bits.append(2); body += ncount(m["norm"], m["log"]) if m["desc"] is None else bytes(m["desc"])
+            left.append(fse_table(m["norm"], m["log"]) if 0 < sum(abs(c) for c in m["norm"]) == 1 << m["log"] else None)
+            tabs.append(fse_table(*m["walk"]) if m["walk"] else left[-1])
+        elif m == 3:
+            bits.append(3); left.append(inherit[k] if inherit else None); tabs.append(left[-1] or _seq_table(k))
+        elif m:
             assert all(c[k][0] == codes[0][k][0] for c in codes), "RLE mode needs one code for every sequence"
-            tabs.append(_seq_table(k, codes[0][k][0]))
-        else: tabs.append(_seq_table(k))
-    head += bytes([(modes[0] << 6) | (modes[1] << 4) | (modes[2] << 2)]) + bytes(codes[0][k][0] for k in range(3) if modes[k])
+            bits.append(1); body += bytes([codes[0][k][0]]); tabs.append(_seq_table(k, codes[0][k][0])); left.append(tabs[-1])
+        else: bits.append(0); tabs.append(_seq_table(k)); left.append(tabs[-1])
+    if used is not None: used[:] = left
+    head += bytes([(bits[0] << 6) | (bits[1] << 4) | (bits[2] << 2)]) + body
     # walk backwards: the last sequence takes any state of its symbols; each earlier one the state of its symbol whose range holds its successor.
     # Fields in reading order per sequence: OF, ML, LL extra bits, then (not after the last) LL, ML, OF state bits -- added here in reverse.
+    lasts = last if isinstance(last, (tuple, list)) else (last,) * 3
+    walks = [_state_walk(tabs[k], [c[k][0] for c in codes], lasts[k], first[k]) for k in range(3)]
     w = _Bits()
-    st = [tabs[k][2][codes[n - 1][k][0]][0] for k in range(3)]
     for i in range(n - 1, -1, -1):
         (_, lx, lb), (_, ox, ob), (_, mx, mb) = codes[i]
         if i < n - 1:
-            upd = []
-            for k in range(3):
-                cells = tabs[k][0]; succ = st[k]
-                x = next(x for x in tabs[k][2][codes[i][k][0]] if cells[x][2] <= succ < cells[x][2] + (1 << cells[x][1]))
-                upd.append((succ - cells[x][2], cells[x][1])); st[k] = x
-            w.add(*upd[1]); w.add(*upd[2]); w.add(*upd[0])
+            w.add(*walks[1][1][i]); w.add(*walks[2][1][i]); w.add(*walks[0][1][i])
         w.add(lx, lb); w.add(mx, mb); w.add(ox, ob)
-    w.add(st[2], tabs[2][1]); w.add(st[1], tabs[1][1]); w.add(st[0], tabs[0][1])
+    w.add(walks[2][0], tabs[2][1]); w.add(walks[1][0], tabs[1][1]); w.add(walks[0][0], tabs[0][1])
     return head + w.finish()
 
 
@@ -488,15 +531,17 @@ def frame_header(fcs=None, single_segment=False, window_log=17, dict_id=None, ch
     return b"\x28\xb5\x2f\xfd" + bytes([fhd]) + tail
 
 
-def write_frame(blocks, fcs="auto", content=None, checksum=None, **header):
+def write_frame(blocks, fcs="auto", content=None, checksum=None, dict_tables=None, **header):
     """A frame of `blocks`: ("seq", literals, seqs, options) / ("raw", data) / ("rle", byte, n). A "seq" block's options: lit = the literals mode
     of literals_section (default "raw"), lit_hdr, modes, count_bytes; Huffman tables are built per block ("huf*") and inherited ("treeless*"), or
     explicit: huf_table (a HufTable, e.g. from_weights), huf_desc (the description's bytes), jump, mangle, claim, size_format (literals_section).
     fcs "auto" declares len(content); checksum = the 32-bit trailer to write (the caller computes it: Oracle.xxh64(content) & 0xFFFFFFFF, or a
-    wrong one); other keywords go to frame_header."""
+    wrong one); other keywords go to frame_header. Sequence tables: a block's `modes` may hold described(...) and 3 (sequences_section); a "repeat"
+    inherits what the last block WITH sequences left, whatever its modes were, and the first such block what dict_tables gives (a dictionary's three
+    tables, or None: nothing to inherit); seq_last / seq_first choose the states (sequences_section's last / first); seq_mangle = a function from the sequences section's bytes to the bytes to write (a block cut short, a stream damaged)."""
     if fcs == "auto": fcs = len(content)
     out = [frame_header(fcs=fcs, checksum=checksum is not None, **header)]
-    table = None
+    table, seq_tabs = None, dict_tables
     for i, b in enumerate(blocks):
         last = i == len(blocks) - 1
         if b[0] == "raw": out.append(block(0, b[1], last))
@@ -507,7 +552,11 @@ def write_frame(blocks, fcs="auto", content=None, checksum=None, **header):
             mode = o.get("lit", "raw")
             if "huf_table" in o: table = o["huf_table"]                        # (with a treeless mode: the table the block inherits, a dictionary's)
             elif mode.startswith("huf"): table = HufTable(o.get("huf_from", lits))
-            body = literals_section(lits, mode, o.get("lit_hdr"), table, o.get("huf_desc"), o.get("jump"), o.get("mangle"), o.get("claim"), o.get("size_format")) + sequences_section(seqs, o.get("modes", (0, 0, 0)), o.get("count_bytes"))
+            left = []
+            sec = sequences_section(seqs, o.get("modes", (0, 0, 0)), o.get("count_bytes"), seq_tabs, o.get("seq_last", "first"), o.get("seq_first", (None, None, None)), left)
+            if seqs: seq_tabs = left
+            if "seq_mangle" in o: sec = o["seq_mangle"](sec)
+            body = literals_section(lits, mode, o.get("lit_hdr"), table, o.get("huf_desc"), o.get("jump"), o.get("mangle"), o.get("claim"), o.get("size_format")) + sec
             out.append(block(2, body, last))
     if checksum is not None: out.append((checksum & 0xFFFFFFFF).to_bytes(4, "little"))
     return b"".join(out)
