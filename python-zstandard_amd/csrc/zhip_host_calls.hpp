@@ -242,6 +242,24 @@ static inline uint64_t host_compress_out_segments(const uint64_t* sizes, size_t 
     return o;
 }
 
+// ------------------------------------------------------------------------------------------ what a context gives back after a call
+// a context keeps its device buffers between calls as long as they total at most `keep` bytes. Above that: release the largest trimmable buffer whose capacity is above 64 MiB
+// (of equals the earlier one), again and again, until the total fits or no such buffer is left. caps: every buffer of the context (all of them count towards the total),
+// trimmable: which of them may go. Returns the indices to release, in order
+static inline std::vector<size_t> host_trim_order(const size_t* caps, const bool* trimmable, size_t n, size_t keep)
+{
+    std::vector<size_t> cap(caps, caps + n), order;
+    size_t total = 0;
+    for (size_t i = 0; i < n; i++) total += cap[i];
+    while (total > keep) {
+        size_t big = n;
+        for (size_t i = 0; i < n; i++) if (trimmable[i] && cap[i] > ((size_t)64 << 20) && (big == n || cap[i] > cap[big])) big = i;
+        if (big == n) break;
+        order.push_back(big); total -= cap[big]; cap[big] = 0;
+    }
+    return order;
+}
+
 // ------------------------------------------------------------------------------------------ one call, every device: the decisions of the fan-out
 // compressor.c:1127-1216: never more workers than items (:1151); walk the items, close a worker's run once its bytes reach total / workers; the
 // last worker takes the rest. bounds[2w], bounds[2w+1] = [start, end) of worker w; returns the workers that got a run.

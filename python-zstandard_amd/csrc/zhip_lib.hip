@@ -25,6 +25,7 @@
 #include "zhip_seekable_calls.hpp"
 #include "zhip_seekable_typed_calls.hpp"
 #include "zhip_host_calls.hpp"
+#include "zhip_host_pool.hpp"
 
 #define ZHIP_LDS_BYTES (160u * 1024u)      // per CU on gfx950
 static_assert(sizeof(ZpSeqQLDS) <= ZHIP_LDS_BYTES && sizeof(ZpHufKernelLDS) <= ZHIP_LDS_BYTES, "a workgroup's LDS must fit a CU");
@@ -271,6 +272,10 @@ static thread_local int g_reserveRc = ZHIP_ERR_HIP;      // why the last failed 
 struct DevBuf {
     void* p = nullptr; size_t cap = 0;
     uint64_t gen = 0;            // which allocation this is, process-wide (a released buffer's address may come back with other contents: whoever remembers something ABOUT the contents remembers this too)
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }     // (the owner waits for the device first: zhip_ctx_destroy synchronises, and hipFree itself waits)
     int reserve(size_t n) {
         if (n <= cap) return 0;
         release();
@@ -282,9 +287,40 @@ struct DevBuf {
         static std::atomic<uint64_t> g_gen{0};
         cap = want; gen = ++g_gen; return 0;
     }
+    int reserve_exact(size_t bytes)      // at exactly its bytes, no head-room (areas as large as what a caller asked to read)
+    {
+        if (bytes <= cap) return 0;
+        release();
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) { p = nullptr; (void)hipGetLastError(); g_lastError = "out of device memory"; return ZHIP_ERR_NO_MEMORY; }
+        cap = bytes;
+        return 0;
+    }
     void release()
     {
         if (p) (void)hipFree(p);
+        p = nullptr; cap = 0;
+    }
+};
+// pinned host memory, owned: reserve(n, 3) keeps n / 8 of head-room (the staging slots), reserve(n, 2) n / 4 (the small meta area, the seekable calls' slots)
+struct PinBuf {
+    void* p = nullptr; size_t cap = 0;
+    PinBuf() = default;
+    PinBuf(const PinBuf&) = delete;
+    PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { release(); }
+    hipError_t reserve(size_t n, int headroomShift)
+    {
+        if (n <= cap) return hipSuccess;
+        release();
+        const size_t want = n + (n >> headroomShift) + 4096;
+        const hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);      // (write-combined / non-coherent staging: no difference, profiles/r05zb_*)
+        if (e != hipSuccess) p = nullptr; else cap = want;
+        return e;
+    }
+    void release()
+    {
+        if (p) (void)hipHostFree(p);
         p = nullptr; cap = 0;
     }
 };
@@ -296,7 +332,33 @@ struct KTimer {
 };
 
 // pinned memory a host table is uploaded from: written again only after the event behind its upload has completed (zsk_take_slot)
-struct ZskPinSlot { void* p; size_t cap; hipEvent_t done; };
+// (whoever owns slots waits for the device before they go: neither a slot's memory nor its event is in flight then)
+struct ZskPinSlot {
+    hipEvent_t done = nullptr; PinBuf pin;
+    ZskPinSlot() = default;
+    ZskPinSlot(const ZskPinSlot&) = delete;
+    ~ZskPinSlot() { if (done) (void)hipEventDestroy(done); }
+};
+
+// Every device buffer of a context, ONCE: X(member, trimmable). The members are declared from this list, device_bytes() sums it, tls_trim picks from it, and each
+// DevBuf releases itself when the context goes. trimmable = 1: a working area the host-buffer calls give back above the keep limit -- the 14 that tls_trim has
+// always named, in its order (ties go to the earlier one): pipeMeta pipeLit pipeFse pipeHuf pipeBases encArena encTables encFlatTables encWorkspace encBigWs scratch
+// hSrc hDst hDense. The rest is small or holds state a later call relies on (counters, dictionaries, lists).
+#define ZHIP_CTX_DEVBUFS(X) \
+    /* decode pipeline */ \
+    X(pipeMeta, 1) X(pipeLit, 1) X(pipeCounters, 0) X(pipeFallback, 0) X(pipeFse, 1) X(pipeOrder, 0) X(pipeHuf, 1) X(pipeOrderLit, 0) X(pipeItemFrame, 0) X(pipeItemReps, 0) \
+    X(pipeFrameRecs, 0) X(pipeBases, 1) X(pipePre, 0) \
+    /* encode */ \
+    X(encArena, 1) X(encTables, 1) X(encFlatTables, 1) X(encWorkspace, 1) X(encBigWs, 1) X(encMeta, 0) X(encBigList, 0) X(encE1List, 0) X(encMbBlocks, 0) X(encMbCount, 0) X(encMbSeqs, 0) \
+    X(scratch, 1) X(counter, 0) \
+    /* dictionary, compress side: raw bytes, parsed entropy section, digested form and its tagged tables; decode side */ \
+    X(cdictBlob, 0) X(cdictEntropy, 0) X(cdictDigest, 0) X(cdictTables, 0) X(dictBlob, 0) X(dictEntropy, 0) X(dictTables, 0) \
+    /* host-API staging */ \
+    X(hSrc, 1) X(hDst, 1) X(hDense, 1) X(hSegs, 0) X(hStatus, 0) \
+    /* seekable streams: the chunks' compressBound-sized slots; segments, sizes, statuses and the scan's cells; the delta join on its own (a uint64 per tile) */ \
+    X(skSlots, 0) X(skMeta, 0) X(skTileSums, 0) \
+    /* typed seekable compress: the planar copy of the source (its bytes), the plane frames' records, the seal's stash */ \
+    X(skStaging, 0) X(skRecords, 0) X(skStash, 0)
 
 struct zhip_ctx {
     int device = 0;
@@ -304,10 +366,11 @@ struct zhip_ctx {
     int decBlocksPerCU = 0;
     int encBlocksPerCU = 0;
     int k1PerCU = 0, k3PerCU = 0;
-    DevBuf pipeMeta, pipeLit, pipeCounters, pipeFallback, pipeFse, pipeOrder, pipeHuf, pipeOrderLit, pipeItemFrame, pipeItemReps, pipeFrameRecs, pipeBases, pipePre;
+#define ZHIP_X(name, trim) DevBuf name;
+    ZHIP_CTX_DEVBUFS(ZHIP_X)
+#undef ZHIP_X
     hipStream_t slotStream[ZHIP_NSLOT] = {};
     hipStream_t sideStream[ZHIP_NSLOT] = {};
-    DevBuf encWorkspace, encMeta, encArena, encTables, encBigList, encBigWs, encFlatTables, encE1List, encMbBlocks, encMbCount, encMbSeqs;
     int e1PerCU = 0, e2PerCU = 0;
     int matchFinder = ZHIP_FINDER_LIBZSTD;     // zhip_ctx_set_match_finder
     int wavePerCU[3] = {0, 0, 0};      // resident workgroups per CU of the wave match kernel at H = 12, 13, 14
@@ -315,9 +378,7 @@ struct zhip_ctx {
     size_t itemHint = 0;               // zhip_ctx_set_size_hint: what a device-API caller says about its items' uncompressed sizes (0 = nothing)
     zhip_cparams cparams = {3, 1, 0, 1, nullptr, 0, 0, 0, {0, 0, 0, 0, 0, 0, 0}};
     ZeRows rows = {};                  // cparams resolved per source-size class (zhip_cparams.hpp)
-    DevBuf scratch, counter;
-    // dictionary (compress side): raw bytes, parsed entropy section, digested form and its tagged tables
-    DevBuf cdictBlob, cdictEntropy, cdictDigest, cdictTables;
+    // dictionary (compress side)
     bool hasCDict = false; uint32_t cdictContentOffset = 0, cdictAttachMax = ZE_DICT_ATTACH_MAX; int cdictHlog = 0, cdictClog = 0, cdictStrat = 2;
     uint32_t cdictContentSize = 0;
     // launch numbers in the cells of the flat dictionary search's tables (ZhipEncodeArgs.tabEpoch): the last one used on the allocation at encEpochPtr, the index width and
@@ -325,19 +386,14 @@ struct zhip_ctx {
     uint32_t encEpoch = 0, encEpochShift = 0; void* encEpochPtr = nullptr; uint64_t encEpochKey = 0, encEpochGen = 0; size_t encEpochBytes = 0;      // (encEpochBytes: how much of the allocation has been zeroed -- a larger batch that still fits the allocation reaches slots that never were)
     uint64_t cdictKey = 0, ddictKey = 0;     // fingerprint of the dictionary currently digested (skip re-digesting per call)
     // dictionary (decode side)
-    DevBuf dictBlob, dictEntropy, dictTables;
     uint32_t dictSize = 0, dictID = 0, dictContentOffset = 0; bool dictHasEntropy = false;
     uint64_t maxWindowSize = (1ull << 27) + 1;
     int dformat = ZHIP_FORMAT_ZSTD1;
     // host-API staging
-    DevBuf hSrc, hDst, hSegs, hStatus, hDense;
-    DevBuf skSlots, skMeta;            // seekable streams: the chunks' compressBound-sized slots; segments, sizes, statuses and the scan's cells
-    std::vector<ZskPinSlot> skPins;    // the pick list of an edit without an opened stream travels through these
-    DevBuf skTileSums;                         // the delta join on its own (zhip_planes_join_filter_device): a uint64 per tile
-    DevBuf skStaging, skRecords, skStash;      // typed seekable compress: the planar copy of the source (its bytes), the plane frames' records, the seal's stash
-    void* pinned = nullptr; size_t pinnedCap = 0;
+    std::deque<ZskPinSlot> skPins;     // the pick list of an edit without an opened stream travels through these
+    PinBuf pinned;                     // small pinned area for per-item sizes / status / chunk totals coming back
     bool hpReady = false; hipStream_t hpH2D = nullptr, hpCompute = nullptr, hpD2H = nullptr;     // host pipeline: copy-in, kernels, copy-out
-    void* hpStage[2] = {nullptr, nullptr}; size_t hpStageCap[2] = {0, 0}; hipEvent_t hpStageFree[2] = {nullptr, nullptr}; int hpNextSlot = 0;
+    PinBuf hpStage[2]; hipEvent_t hpStageFree[2] = {nullptr, nullptr}; int hpNextSlot = 0;
     // bring-up / tuning knobs, read from the environment ONCE when the context is created (never in a launch path)
     struct Knobs : ZeEncodeKnobs, ZdDecodeKnobs {      // (the knobs the launch plans read: ZeEncodeKnobs, zhip_encode_plan.hpp; ZdDecodeKnobs, zhip_decode_plan.hpp)
         // bring-up aids
@@ -359,12 +415,23 @@ struct zhip_ctx {
     KTimer timer[ZHIP_NTIMER];   // (10: the wave match kernel, 11: the literals-only kernel of ZHIP_FINDER_NONE) 0 fused decode, 1 fused encode, 2 K1 literals, 3 K2 sequences, 4 K3 execution, 5 E1 match, 6 E2 entropy, 7 K1b Huffman streams, 8 the flat match kernel, 9 the decode pipeline of a chunk from K1's start to K3's end (K1b runs beside K2)
     size_t device_bytes() const
     {
-        const DevBuf* all[] = {&pipeMeta, &pipeLit, &pipeCounters, &pipeFallback, &pipeFse, &pipeOrder, &pipeHuf, &pipeOrderLit, &pipeItemFrame, &pipeItemReps, &pipeFrameRecs, &pipeBases, &pipePre, &encWorkspace, &encMeta, &encArena,
-                               &encTables, &encBigList, &encBigWs, &encFlatTables, &encE1List, &encMbBlocks, &encMbCount, &encMbSeqs, &scratch, &counter, &cdictBlob, &cdictEntropy, &cdictDigest, &cdictTables,
-                               &dictBlob, &dictEntropy, &dictTables, &hSrc, &hDst, &hSegs, &hStatus, &hDense, &skSlots, &skMeta};
         size_t n = 0;
-        for (const DevBuf* b : all) n += b->cap;
+#define ZHIP_X(name, trim) n += name.cap;
+        ZHIP_CTX_DEVBUFS(ZHIP_X)
+#undef ZHIP_X
         return n;
+    }
+    zhip_ctx() = default;
+    zhip_ctx(const zhip_ctx&) = delete;
+    // what no member owns by itself: streams, the staging slots' events, the phase-timer accumulators. zhip_ctx_destroy has synchronised the device before this runs, so
+    // neither these nor the buffers and pinned areas that release themselves after it are in flight
+    ~zhip_ctx()
+    {
+        for (hipStream_t s : slotStream) if (s) (void)hipStreamDestroy(s);
+        for (hipStream_t s : sideStream) if (s) (void)hipStreamDestroy(s);
+        for (hipStream_t s : {hpH2D, hpCompute, hpD2H}) if (s) (void)hipStreamDestroy(s);
+        for (hipEvent_t e : hpStageFree) if (e) (void)hipEventDestroy(e);
+        for (unsigned long long* q : {profDecode, profPipe, profEncode}) if (q) (void)hipFree(q);
     }
 };
 
@@ -435,22 +502,6 @@ extern "C" void zhip_ctx_destroy(zhip_ctx* c)
     (void)hipDeviceSynchronize();
     for (int i = 0; i < ZHIP_NTIMER; i++) drain_shared(c->timer[i]);
     for (int i = 0; i < ZHIP_NTIMER; i++) drain_timer(c->timer[i]);
-    for (int i = 0; i < ZHIP_NSLOT; i++) if (c->slotStream[i]) (void)hipStreamDestroy(c->slotStream[i]);
-    for (int i = 0; i < ZHIP_NSLOT; i++) if (c->sideStream[i]) (void)hipStreamDestroy(c->sideStream[i]);
-    c->pipeMeta.release(); c->pipeLit.release(); c->pipeCounters.release(); c->pipeFallback.release(); c->pipeFse.release(); c->pipeOrder.release(); c->pipeHuf.release(); c->pipeOrderLit.release(); c->pipeItemFrame.release(); c->pipeItemReps.release(); c->pipeFrameRecs.release(); c->pipeBases.release(); c->pipePre.release();
-    c->scratch.release(); c->counter.release(); c->encWorkspace.release(); c->encMeta.release(); c->encArena.release(); c->encTables.release(); c->encBigList.release(); c->encBigWs.release(); c->encFlatTables.release(); c->encE1List.release(); c->encMbBlocks.release(); c->encMbCount.release(); c->encMbSeqs.release(); c->dictBlob.release(); c->dictEntropy.release(); c->dictTables.release();
-    c->cdictBlob.release(); c->cdictEntropy.release(); c->cdictDigest.release(); c->cdictTables.release();
-    c->hSrc.release(); c->hDst.release(); c->hSegs.release(); c->hStatus.release(); c->hDense.release();
-    c->skSlots.release(); c->skMeta.release(); c->skStaging.release(); c->skRecords.release(); c->skStash.release(); c->skTileSums.release();
-    for (ZskPinSlot& x : c->skPins) { if (x.p) (void)hipHostFree(x.p); (void)hipEventDestroy(x.done); }
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    if (c->profDecode) (void)hipFree(c->profDecode);
-    if (c->profPipe) (void)hipFree(c->profPipe);
-    if (c->profEncode) (void)hipFree(c->profEncode);
-    for (int i = 0; i < 2; i++) { if (c->hpStage[i]) (void)hipHostFree(c->hpStage[i]); if (c->hpStageFree[i]) (void)hipEventDestroy(c->hpStageFree[i]); }
-    if (c->hpH2D) (void)hipStreamDestroy(c->hpH2D);
-    if (c->hpCompute) (void)hipStreamDestroy(c->hpCompute);
-    if (c->hpD2H) (void)hipStreamDestroy(c->hpD2H);
     delete c;
 }
 extern "C" const char* zhip_kernel_name(int k)
@@ -560,12 +611,12 @@ extern "C" int zhip_ctx_set_dformat(zhip_ctx* c, int format, uint64_t maxWindowS
 // bring-up probe: launches a 64-lane kernel exercising every wave primitive the codec uses; returns 0 when correct
 extern "C" int zhip_selftest(void)
 {
-    uint32_t* d = nullptr; uint32_t h[64];
-    HIP_TRY(hipMalloc((void**)&d, sizeof h));
+    DevBuf buf; uint32_t h[64];
+    if (buf.reserve(sizeof h)) return g_reserveRc;
+    uint32_t* d = (uint32_t*)buf.p;
     hipLaunchKernelGGL(zhip_selftest_kernel, dim3(1), dim3(64), 0, 0, d);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost));
-    (void)hipFree(d);
     for (uint32_t l = 0; l < 64; l++) if (h[l] != l * (l + 1) / 2 + 32 + 63 + 7) { g_lastError = "selftest mismatch"; return 1; }
     return 0;
 }
@@ -1101,8 +1152,7 @@ static int pick_table_placement(zhip_ctx* c, const ZePlan& p, ZhipEncodeArgs& a,
     uint8_t* const cbase = (uint8_t*)c->counter.p;
     uint8_t* const flatTables = a.flatTables;
     const size_t cnt0 = p.chunk, bytes = p.flatTablesBytes;
-    DevBuf cand;
-    struct PickGuard { DevBuf& b; ~PickGuard() { b.release(); } } pickGuard{cand};
+    DevBuf cand;      // (releases itself however the pick ends)
     ChunkEvents ev;
     if (ev.create(2) == hipSuccess) {
         const hipEvent_t e0 = ev.ev[0], e1 = ev.ev[1];
@@ -1132,7 +1182,8 @@ static int pick_table_placement(zhip_ctx* c, const ZePlan& p, ZhipEncodeArgs& a,
         // as the mean of each sixteenth of the allocation -- is a slow allocation slow everywhere?
         {   const uint32_t cap0 = pa.probeCap;
             const size_t nw = (cnt0 + 63) / 64;
-            unsigned long long* dClock = nullptr; HIP_TRY(hipMalloc((void**)&dClock, nw * 8));
+            DevBuf clockBuf; if (clockBuf.reserve(nw * 8)) return g_reserveRc;
+            unsigned long long* dClock = (unsigned long long*)clockBuf.p;
             std::vector<unsigned long long> hClock(nw);
             for (int k = 0; k < (ZHIP_PICK_STUDY > 1 ? ZHIP_PICK_STUDY : 8); k++) {            // (-DZHIP_PICK_STUDY=n, n > 1: n candidates, whole launches for the first eight only)
                 uint8_t* t = flatTables;
@@ -1149,7 +1200,6 @@ static int pick_table_placement(zhip_ctx* c, const ZePlan& p, ZhipEncodeArgs& a,
                 fprintf(stderr, "[zhip-pick-study] candidate %d %p whole %.1f ms, first 8 KiB %.1f; waves' ms by sixteenth of the allocation:%s (min %.2f max %.2f)\n", k, (void*)t, whole, probe, line, mn / 1e5, mx / 1e5);
                 if (k) cand.release();
             }
-            (void)hipFree(dClock);
         }
 #endif
         float best = 0;
@@ -1361,19 +1411,10 @@ extern "C" int zhip_ctx_sync(zhip_ctx* c, void* streamv, const int32_t* d_status
 //   (zhip_free_payload; the CPython extension's BufferWithSegments does that in its deallocator);
 // * compress: the compressBound-sized slots are compacted ON THE DEVICE (scan of the frame sizes + one wave per frame) so that only
 //   the frames cross the link, into a payload allocated once the chunk's total is known (the host learns it one chunk behind).
-#include <atomic>
-#include <condition_variable>
-#include <deque>
-#include <functional>
-#include <mutex>
-#include <thread>
-#include <unordered_map>
-
 #ifndef ZHIP_PACK_THREADS
 #define ZHIP_PACK_THREADS 8
 #endif
 #define ZHIP_HOST_CHUNK_ITEMS 32768u                  // most items of one pipeline chunk (the scan kernel's bound)
-#define ZHIP_PIN_MIN ((size_t)1 << 20)                // payloads below 1 MiB are plain malloc() (one-shot calls, small batches)
 // idle pinned bytes kept for reuse; beyond that blocks are unpinned on free. 24 GiB covers a full-size batch's payloads (pinning costs more than
 // the copy it speeds up); ZHIP_PIN_POOL_KEEP_MB (read once) lowers or raises it, 0 = keep nothing (no way to trim it before)
 static size_t pin_pool_keep()
@@ -1381,52 +1422,20 @@ static size_t pin_pool_keep()
     static const size_t keep = [] { const char* e = getenv("ZHIP_PIN_POOL_KEEP_MB"); return e ? (size_t)strtoull(e, nullptr, 10) << 20 : (size_t)24 << 30; }();
     return keep;
 }
-#define ZHIP_PIN_POOL_KEEP pin_pool_keep()
 
-static std::atomic<bool> g_pinPortable{false};      // set when the host-buffer calls have more than one device slot to fan out over (DevPool::parse)
-namespace {
-struct PinBlock { size_t cap; bool busy; };
-struct PinPool {
-    std::mutex mu;
-    std::unordered_map<void*, PinBlock> blocks;
-    size_t idle = 0;
-    void* take(size_t n)
-    {
-        if (n < ZHIP_PIN_MIN) return malloc(n ? n : 1);
-        {
-            std::lock_guard<std::mutex> g(mu);
-            void* best = nullptr; size_t bestCap = ~(size_t)0;
-            for (auto& kv : blocks) if (!kv.second.busy && kv.second.cap >= n && kv.second.cap < bestCap) { best = kv.first; bestCap = kv.second.cap; }
-            if (best && bestCap <= n + (n >> 1) + ((size_t)64 << 20)) { blocks[best].busy = true; idle -= bestCap; return best; }
-        }
-        void* p = nullptr;
-        const size_t cap = (n + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-        // (portable -- pinned for every device's copy engines -- only where the in-call fan-out can hand a block to another device: fan_out sets the flag)
-        if (hipHostMalloc(&p, cap, g_pinPortable.load() ? hipHostMallocPortable : hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return malloc(n); }     // pageable still works, slower
-        std::lock_guard<std::mutex> g(mu);
-        blocks[p] = PinBlock{cap, true};
-        return p;
-    }
-    void give(void* p)
-    {
-        if (!p) return;
-        std::vector<void*> drop;
-        {
-            std::lock_guard<std::mutex> g(mu);
-            auto it = blocks.find(p);
-            if (it == blocks.end()) { free(p); return; }
-            it->second.busy = false; idle += it->second.cap;
-            while (idle > ZHIP_PIN_POOL_KEEP) {                       // unpin the largest idle blocks first
-                void* big = nullptr; size_t bigCap = 0;
-                for (auto& kv : blocks) if (!kv.second.busy && kv.second.cap > bigCap) { big = kv.first; bigCap = kv.second.cap; }
-                if (!big) break;
-                idle -= bigCap; blocks.erase(big); drop.push_back(big);
-            }
-        }
-        for (void* q : drop) (void)hipHostFree(q);
-    }
-};
-PinPool& pin_pool() { static PinPool* pool = new PinPool(); return *pool; }      // leaked on purpose: payloads may outlive static destruction
+static std::atomic<bool> g_pinPortable{false};      // set when the host-buffer calls have more than one device slot to fan out over (dev_pool)
+// the process's payload pool (PinPool, zhip_host_pool.hpp) over hipHostMalloc / hipHostFree; leaked on purpose: payloads may outlive static destruction
+static PinPool& pin_pool()
+{
+    static PinPool* pool = new PinPool(
+        [](size_t cap) -> void* {
+            // (portable -- pinned for every device's copy engines -- only where the in-call fan-out can hand a block to another device: dev_pool sets the flag)
+            void* p = nullptr;
+            if (hipHostMalloc(&p, cap, g_pinPortable.load() ? hipHostMallocPortable : hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+            return p;
+        },
+        [](void* p) { (void)hipHostFree(p); }, pin_pool_keep());
+    return *pool;
 }
 
 extern "C" void zhip_free_payload(void* p) { pin_pool().give(p); }
@@ -1494,26 +1503,6 @@ static int host_pipe_init(zhip_ctx* c)
     c->hpReady = true;
     return 0;
 }
-static int ensure_stage(zhip_ctx* c, int slot, size_t n)
-{
-    if (n <= c->hpStageCap[slot]) return 0;
-    if (c->hpStage[slot]) (void)hipHostFree(c->hpStage[slot]);
-    c->hpStage[slot] = nullptr; c->hpStageCap[slot] = 0;
-    const size_t want = n + (n >> 3) + 4096;
-    HIP_TRY(hipHostMalloc(&c->hpStage[slot], want, hipHostMallocDefault));      // (write-combined / non-coherent staging: no difference, profiles/r05zb_*)
-    c->hpStageCap[slot] = want;
-    return 0;
-}
-static int ensure_pinned(zhip_ctx* c, size_t n)          // small pinned area for per-item sizes / status / chunk totals coming back
-{
-    if (n <= c->pinnedCap) return 0;
-    if (c->pinned) (void)hipHostFree(c->pinned);
-    c->pinned = nullptr; c->pinnedCap = 0;
-    size_t want = n + (n >> 2) + 4096;
-    HIP_TRY(hipHostMalloc(&c->pinned, want, hipHostMallocDefault));
-    c->pinnedCap = want;
-    return 0;
-}
 // one lazily created context per calling thread, destroyed when the thread exits; re-created when the thread switched devices
 struct TlsCtx { zhip_ctx* c = nullptr; ~TlsCtx() { if (c) zhip_ctx_destroy(c); } };
 static thread_local TlsCtx g_tls;
@@ -1545,16 +1534,18 @@ static size_t tls_keep_bytes()
     static const size_t keep = [] { const char* e = getenv("ZHIP_KEEP_GB"); return (e ? (size_t)strtoull(e, nullptr, 10) : (size_t)64) << 30; }();
     return keep;
 }
-static void tls_trim(zhip_ctx* c)
+static void tls_trim(zhip_ctx* c)      // (which buffers go, and in what order: host_trim_order over the context's one list, its 14 trimmable ones the candidates)
 {
-    DevBuf* bufs[] = { &c->pipeMeta, &c->pipeLit, &c->pipeFse, &c->pipeHuf, &c->pipeBases, &c->encArena, &c->encTables, &c->encFlatTables, &c->encWorkspace,
-                       &c->encBigWs, &c->scratch, &c->hSrc, &c->hDst, &c->hDense };
-    while (c->device_bytes() > tls_keep_bytes()) {
-        DevBuf* big = nullptr;
-        for (DevBuf* b : bufs) if (b->cap > ((size_t)64 << 20) && (!big || b->cap > big->cap)) big = b;
-        if (!big) break;
-        big->release();
-    }
+#define ZHIP_X(name, trim) &c->name,
+    DevBuf* const bufs[] = { ZHIP_CTX_DEVBUFS(ZHIP_X) };
+#undef ZHIP_X
+#define ZHIP_X(name, trim) trim != 0,
+    static const bool trimmable[] = { ZHIP_CTX_DEVBUFS(ZHIP_X) };
+#undef ZHIP_X
+    const size_t n = sizeof bufs / sizeof bufs[0];
+    size_t caps[n];
+    for (size_t i = 0; i < n; i++) caps[i] = bufs[i]->cap;
+    for (size_t i : host_trim_order(caps, trimmable, n, tls_keep_bytes())) bufs[i]->release();
 }
 static int set_err(zhip_error* err, int kind, size_t index, int zerr, uint64_t d0 = 0, uint64_t d1 = 0)
 {
@@ -1580,9 +1571,9 @@ static int upload_items(zhip_ctx* c, const zhip_item* items, const zhip_segment*
         const HostStep st = host_upload_step(segs, a, hi, ZHIP_STAGE_BYTES);
         const int slot = c->hpNextSlot; c->hpNextSlot ^= 1;
         if (hipEventSynchronize(c->hpStageFree[slot]) != hipSuccess) return ZHIP_ERR_HIP;
-        if (ensure_stage(c, slot, st.bytes + 16)) return ZHIP_ERR_HIP;
-        pack_items((uint8_t*)c->hpStage[slot], items, segs, st.a, st.b, ZHIP_PACK_BYTES, c->knob.packThreads ? c->knob.packThreads : ZHIP_PACK_THREADS);
-        if (st.bytes && hipMemcpyAsync((uint8_t*)c->hSrc.p + segs[a].offset, c->hpStage[slot], st.bytes, hipMemcpyHostToDevice, c->hpH2D) != hipSuccess) return ZHIP_ERR_HIP;
+        if (c->hpStage[slot].reserve(st.bytes + 16, 3) != hipSuccess) return ZHIP_ERR_HIP;
+        pack_items((uint8_t*)c->hpStage[slot].p, items, segs, st.a, st.b, ZHIP_PACK_BYTES, c->knob.packThreads ? c->knob.packThreads : ZHIP_PACK_THREADS);
+        if (st.bytes && hipMemcpyAsync((uint8_t*)c->hSrc.p + segs[a].offset, c->hpStage[slot].p, st.bytes, hipMemcpyHostToDevice, c->hpH2D) != hipSuccess) return ZHIP_ERR_HIP;
         if (hipEventRecord(c->hpStageFree[slot], c->hpH2D) != hipSuccess) return ZHIP_ERR_HIP;
         a = st.b;
     }
@@ -1629,7 +1620,7 @@ struct HostCall {
         if (host_pipe_init(c)) return set_err(err, ZHIP_ERR_HIP, 0, 0);
         if (c->hSrc.reserve(srcTotal + 16) || c->hDst.reserve(dstTotal + 16) || (compress && c->hDense.reserve(dstTotal + 16)) ||
             c->hSegs.reserve(2 * n * sizeof(zhip_segment) + 16) || c->hStatus.reserve(dBytes)) return set_err(err, g_reserveRc, 0, 0);
-        if (ensure_pinned(c, hBytes)) return set_err(err, ZHIP_ERR_HIP, 0, 0);
+        if (const hipError_t e = c->pinned.reserve(hBytes, 2)) return set_err(err, hip_fail(e, "hipHostMalloc"), 0, 0);
         ob = (zhip_outbuf*)calloc(nChunks ? nChunks : 1, sizeof(zhip_outbuf));
         if (!ob) return set_err(err, ZHIP_ERR_NO_MEMORY, 0, 0);
         nOb = nChunks ? nChunks : 1;
@@ -1680,8 +1671,8 @@ static int decompress_batch_one(const zhip_dparams* params, const zhip_item* ite
     if (const int e = call.begin(segs, n, nChunks, srcTotal, dstTotal, l.dBytes, l.hBytes)) return e;
     uint64_t* dSizes = (uint64_t*)((uint8_t*)c->hStatus.p + l.dSizes);
     int32_t* dStatus = (int32_t*)((uint8_t*)c->hStatus.p + l.dStatus);
-    uint64_t* hSizes = (uint64_t*)((uint8_t*)c->pinned + l.hSizes);
-    int32_t* hStatus = (int32_t*)((uint8_t*)c->pinned + l.hStatus);
+    uint64_t* hSizes = (uint64_t*)((uint8_t*)c->pinned.p + l.hSizes);
+    int32_t* hStatus = (int32_t*)((uint8_t*)c->pinned.p + l.hStatus);
     const zhip_segment* dSegs = (const zhip_segment*)c->hSegs.p;
     zhip_outbuf* ob = call.ob;
     // payloads, sizes and statuses all go back on the third stream, and every item is judged once everything has arrived
@@ -1743,7 +1734,7 @@ static int compress_batch_one(const zhip_cparams* params, const zhip_item* items
     // device: sources, slots, dense frames, segment table, [sizes | offsets | chunk totals | status]
     const HostCompressLayout l = host_compress_layout(n, nChunks);
     if (const int e = call.begin(segs, n, nChunks, srcTotal, dstTotal, l.dBytes, l.hBytes)) return e;
-    uint8_t* dMeta = (uint8_t*)c->hStatus.p; uint8_t* hMeta = (uint8_t*)c->pinned;
+    uint8_t* dMeta = (uint8_t*)c->hStatus.p; uint8_t* hMeta = (uint8_t*)c->pinned.p;
     uint64_t* dSizes = (uint64_t*)(dMeta + l.dSizes); uint64_t* dOffs = (uint64_t*)(dMeta + l.dOffs); uint64_t* dTotals = (uint64_t*)(dMeta + l.dTotals); int32_t* dStatus = (int32_t*)(dMeta + l.dStatus);
     uint64_t* hSizes = (uint64_t*)(hMeta + l.hSizes); uint64_t* hTotals = (uint64_t*)(hMeta + l.hTotals); int32_t* hStatus = (int32_t*)(hMeta + l.hStatus);
     const zhip_segment* dSegs = (const zhip_segment*)c->hSegs.p;
@@ -1805,98 +1796,38 @@ static int compress_batch_one(const zhip_cparams* params, const zhip_item* items
 // The rules -- the partition, the device list, the slot count, the merge -- are zhip_host_calls.hpp's; the threads and the contexts are here.
 extern "C" size_t zhip_partition_by_bytes(const uint64_t* sizes, size_t n, size_t workers, size_t* bounds) { return host_partition_by_bytes(sizes, n, workers, bounds); }
 
-namespace {
-struct DevJob { std::function<void()> fn; };
-struct DevWorker {
-    int device = 0;
-    std::mutex mu; std::condition_variable cv;
-    std::deque<std::function<void()>> q;
-    std::thread th;
-    void loop()
-    {
-        (void)hipSetDevice(device);
-        for (;;) {
-            std::function<void()> fn;
-            { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return !q.empty(); }); fn = std::move(q.front()); q.pop_front(); }
-            fn();
-        }
-    }
-    void post(std::function<void()> fn) { { std::lock_guard<std::mutex> l(mu); q.push_back(std::move(fn)); } cv.notify_one(); }
-};
-struct DevPool {
-    std::mutex mu;
-    bool parsed = false, explicitList = false;
-    std::vector<int> slots;                      // device ordinal of every slot
-    std::vector<DevWorker*> workers;             // created on first use, never destroyed (their contexts live as long as the process)
-    uint64_t minBytes = (uint64_t)256 << 20;
-    void parse()
-    {
-        if (parsed) return;
-        parsed = true;
-        if (const char* e = getenv("ZHIP_DEVICE_MIN_BYTES")) minBytes = strtoull(e, nullptr, 10);
+// the process's device slots (DevPool, zhip_host_pool.hpp): the environment and the device count are read once, on the first call that asks; leaked on purpose like its threads
+static DevPool& dev_pool()
+{
+    static DevPool* pool = [] {
+        DevPool* p = new DevPool([](int device) { (void)hipSetDevice(device); });
         int count = 0;
         if (hipGetDeviceCount(&count) != hipSuccess) { (void)hipGetLastError(); count = 0; }
-        if (const char* e = getenv("ZHIP_DEVICES")) {
-            explicitList = true;
-            slots = host_parse_devices(e, count);
-        } else for (int d = 0; d < count; d++) slots.push_back(d);
-        workers.assign(slots.size(), nullptr);
-        if (slots.size() > 1) g_pinPortable.store(true);       // payload blocks serve any device's copy engines from the first one on
-    }
-    DevWorker* worker(size_t slot)
-    {
-        std::lock_guard<std::mutex> l(mu);
-        if (!workers[slot]) { DevWorker* w = new DevWorker(); w->device = slots[slot]; w->th = std::thread([w] { w->loop(); }); w->th.detach(); workers[slot] = w; }
-        return workers[slot];
-    }
-    // device slots a batch of `n` items / `bytes` input bytes is cut over (0: the calling thread's current device, inline)
-    size_t slotsFor(size_t n, uint64_t bytes)
-    {
-        { std::lock_guard<std::mutex> l(mu); parse(); }
-        return host_slots_for(slots.size(), explicitList, minBytes, n, bytes);
-    }
-};
-DevPool& dev_pool() { static DevPool* p = new DevPool(); return *p; }
-
-// runs fn(slot, lo, hi, &result) for every run of the partition on its device's thread; gathers the devices' buffers in order
-template <typename F>
-int fan_out(size_t d, const std::vector<uint64_t>& sizes, size_t n, F&& one, zhip_outbuf** out, size_t* nOut, zhip_error* err)
-{
-    std::vector<size_t> bounds(2 * d);
-    const size_t used = host_partition_by_bytes(sizes.data(), n, d, bounds.data());
-    std::vector<HostRun> runs(used); std::vector<std::string> text(used);      // what every run's call returned, and its thread's zhip_last_error()
-    std::mutex mu; std::condition_variable cv; size_t pending = used;
-    for (size_t w = 0; w < used; w++) {
-        const size_t lo = bounds[2 * w], hi = bounds[2 * w + 1];
-        dev_pool().worker(w)->post([&, w, lo, hi] {
-            HostRun& r = runs[w];
-            r.lo = lo;
-            memset(&r.err, 0, sizeof r.err);
-            r.rc = one(lo, hi, &r.out, &r.nOut, &r.err);
-            if (r.rc) text[w] = g_lastError;
-            if (w < 64 && g_tls.c) g_slotBytes[w].store(g_tls.c->device_bytes());
-            { std::lock_guard<std::mutex> l(mu); pending--; }
-            cv.notify_one();
-        });
-    }
-    { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return pending == 0; }); }
-    const size_t bad = host_merge_failing(runs.data(), used, err);
-    if (bad < used) {
-        for (size_t v = 0; v < used; v++) if (!runs[v].rc) zhip_free_outbufs(runs[v].out, runs[v].nOut, 1);
-        g_lastError = text[bad];
-        return runs[bad].rc;
-    }
-    zhip_outbuf* all = host_merge_concat(runs.data(), used, nOut);
-    if (!all) { for (size_t w = 0; w < used; w++) zhip_free_outbufs(runs[w].out, runs[w].nOut, 1); if (err) { memset(err, 0, sizeof *err); err->kind = ZHIP_ERR_NO_MEMORY; } return ZHIP_ERR_NO_MEMORY; }
-    *out = all;
-    return ZHIP_ERR_NONE;
+        p->parse(count, getenv("ZHIP_DEVICES"), getenv("ZHIP_DEVICE_MIN_BYTES"));
+        if (p->slots.size() > 1) g_pinPortable.store(true);       // payload blocks serve any device's copy engines from the first one on
+        return p;
+    }();
+    return *pool;
 }
+// one call over d slots (host_fan_out). What stays here is what a slot's thread does after its run: it keeps its thread's error text for the merge and publishes what its
+// context holds for memory_size()
+template <typename F>
+static int fan_out(size_t d, const zhip_item* items, size_t n, F&& one, zhip_outbuf** out, size_t* nOut, zhip_error* err)
+{
+    if (err) memset(err, 0, sizeof *err);
+    *out = nullptr; *nOut = 0;
+    std::vector<uint64_t> sizes(n);
+    for (size_t i = 0; i < n; i++) sizes[i] = items[i].srcSize;
+    auto after = [](size_t w, int rc) {
+        if (w < 64 && g_tls.c) g_slotBytes[w].store(g_tls.c->device_bytes());
+        return rc ? g_lastError : std::string();
+    };
+    return host_fan_out(dev_pool(), d, sizes.data(), n, one, after, [](zhip_outbuf* b, size_t k) { zhip_free_outbufs(b, k, 1); }, out, nOut, err, &g_lastError);
 }
 
 extern "C" int zhip_batch_devices(int* devices, int cap)
 {
-    DevPool& p = dev_pool();
-    { std::lock_guard<std::mutex> l(p.mu); p.parse(); }
+    const DevPool& p = dev_pool();
     for (int i = 0; i < cap && i < (int)p.slots.size(); i++) devices[i] = p.slots[i];
     return (int)p.slots.size();
 }
@@ -1907,11 +1838,7 @@ extern "C" int zhip_compress_batch(const zhip_cparams* params, const zhip_item* 
     for (size_t i = 0; i < n; i++) bytes += items[i].srcSize;
     const size_t d = dev_pool().slotsFor(n, bytes);
     if (d == 0) return compress_batch_one(params, items, n, out, nOut, err);
-    if (err) memset(err, 0, sizeof *err);
-    *out = nullptr; *nOut = 0;
-    std::vector<uint64_t> sizes(n);
-    for (size_t i = 0; i < n; i++) sizes[i] = items[i].srcSize;
-    return fan_out(d, sizes, n, [&](size_t lo, size_t hi, zhip_outbuf** o, size_t* no, zhip_error* e) { return compress_batch_one(params, items + lo, hi - lo, o, no, e); }, out, nOut, err);
+    return fan_out(d, items, n, [=](size_t lo, size_t hi, zhip_outbuf** o, size_t* no, zhip_error* e) { return compress_batch_one(params, items + lo, hi - lo, o, no, e); }, out, nOut, err);
 }
 
 extern "C" int zhip_decompress_batch(const zhip_dparams* params, const zhip_item* items, size_t n, int requireSizes,
@@ -1922,11 +1849,7 @@ extern "C" int zhip_decompress_batch(const zhip_dparams* params, const zhip_item
     for (size_t i = 0; i < n; i++) { bytes += items[i].srcSize; outBytes += items[i].dstSize; }
     const size_t d = dev_pool().slotsFor(n, outBytes > bytes ? outBytes : bytes);
     if (d == 0) return decompress_batch_one(params, items, n, requireSizes, out, nOut, err);
-    if (err) memset(err, 0, sizeof *err);
-    *out = nullptr; *nOut = 0;
-    std::vector<uint64_t> sizes(n);
-    for (size_t i = 0; i < n; i++) sizes[i] = items[i].srcSize;
-    return fan_out(d, sizes, n, [&](size_t lo, size_t hi, zhip_outbuf** o, size_t* no, zhip_error* e) { return decompress_batch_one(params, items + lo, hi - lo, requireSizes, o, no, e); }, out, nOut, err);
+    return fan_out(d, items, n, [=](size_t lo, size_t hi, zhip_outbuf** o, size_t* no, zhip_error* e) { return decompress_batch_one(params, items + lo, hi - lo, requireSizes, o, no, e); }, out, nOut, err);
 }
 
 // ------------------------------------------------------------------------------------------ seekable streams (zhip_seekable.hpp)
@@ -1934,34 +1857,29 @@ extern "C" int zhip_decompress_batch(const zhip_dparams* params, const zhip_item
 // a range read is zhip_decompress_batch_device over the frames that cover it. Everything between the batch calls is the small kernels of zhip_seekable.hpp,
 // queued on the caller's stream: no call here waits on the host except where scratch grows, and zhip_seekable_open_device, which reads the table's shape.
 struct zhip_seekable : ZskTypedOpened {
+    // the pinned slots the many-ranges call's tables are uploaded from (a slot is written again only after the event behind its upload has completed). Declared first, so they
+    // go last: behind the device buffers, whose hipFree waits for the device like the synchronise in zhip_seekable_close
+    std::deque<ZskPinSlot> slots;
     DevBuf prefix;                       // the table's scans (ZskOpened::pre points into it)
     DevBuf meta, edge;                   // a range call's segments / sizes / statuses, and where its partly covered frames are decoded
-    // the many-ranges call: its plan's tables on the device, its item arrays and per-range words, its scratch frames; the pinned slots the tables are
-    // uploaded from (a slot is written again only after the event behind its upload has completed)
+    // the many-ranges call: its plan's tables on the device, its item arrays and per-range words, its scratch frames
     DevBuf gTables, gMeta, gScratch;
-    std::vector<ZskPinSlot> slots;
     DevBuf tPlanar, tTables, tStatus;     // a typed read: the planar buffer the many-ranges call fills (at exactly its bytes), the jobs and owners, the passes' status arrays
     DevBuf tTileSums;                     // a read of a delta-filtered stream: a uint64 per tile of its largest pass
 };
 
 // a pinned slot of at least `bytes` that no upload still reads: one whose event has completed (grown where too small), else a new one
-static int zsk_take_slot(std::vector<ZskPinSlot>& slots, size_t bytes, ZskPinSlot** out)
+static int zsk_take_slot(std::deque<ZskPinSlot>& slots, size_t bytes, ZskPinSlot** out)
 {
     ZskPinSlot* s = nullptr;
     for (ZskPinSlot& x : slots) if (hipEventQuery(x.done) == hipSuccess) { s = &x; break; }
     (void)hipGetLastError();                                               // (hipErrorNotReady of a slot still in flight is no failure)
     if (!s) {
-        ZskPinSlot x = {nullptr, 0, nullptr};
-        HIP_TRY(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
-        slots.push_back(x); s = &slots.back();
+        hipEvent_t done = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        slots.emplace_back(); s = &slots.back(); s->done = done;
     }
-    if (s->cap < bytes) {
-        if (s->p) { (void)hipHostFree(s->p); s->p = nullptr; s->cap = 0; }
-        const size_t want = bytes + (bytes >> 2) + 4096;
-        const hipError_t e = hipHostMalloc(&s->p, want, hipHostMallocDefault);
-        if (e != hipSuccess) { s->p = nullptr; (void)hipGetLastError(); g_lastError = "seekable: no pinned memory for the call's tables"; return ZHIP_ERR_NO_MEMORY; }
-        s->cap = want;
-    }
+    if (s->pin.reserve(bytes, 2) != hipSuccess) { (void)hipGetLastError(); g_lastError = "seekable: no pinned memory for the call's tables"; return ZHIP_ERR_NO_MEMORY; }
     *out = s;
     return 0;
 }
@@ -1976,18 +1894,12 @@ struct ZskHipBackend {
     {
         if (area == ZSK_A_PIN) {
             if (int rc = zsk_take_slot(h ? h->slots : c->skPins, bytes, &slot)) return rc;
-            *base = (uint8_t*)slot->p;
+            *base = (uint8_t*)slot->pin.p;
             return 0;
         }
         if (area == ZSK_A_G_SCRATCH) {      // at exactly its bytes
-            DevBuf& s = h->gScratch;
-            if (bytes > s.cap) {
-                s.release();
-                const hipError_t e = hipMalloc(&s.p, bytes);
-                if (e != hipSuccess) { s.p = nullptr; (void)hipGetLastError(); g_lastError = "out of device memory"; return ZHIP_ERR_NO_MEMORY; }
-                s.cap = bytes;
-            }
-            *base = (uint8_t*)s.p;
+            if (int rc = h->gScratch.reserve_exact(bytes)) return rc;
+            *base = (uint8_t*)h->gScratch.p;
             return 0;
         }
         DevBuf& d = area == ZSK_A_SK_META ? c->skMeta : area == ZSK_A_SK_SLOTS ? c->skSlots : area == ZSK_A_PREFIX ? h->prefix : area == ZSK_A_META ? h->meta : area == ZSK_A_EDGE ? h->edge :
@@ -2036,14 +1948,8 @@ struct ZskHipTypedBackend : ZskHipBackend {
     int reserve_typed(ZskTypedArea area, size_t bytes, uint8_t** base)
     {
         if (area == ZSKT_A_PLANAR) {        // at exactly its bytes, as the many-ranges scratch
-            DevBuf& s = h->tPlanar;
-            if (bytes > s.cap) {
-                s.release();
-                const hipError_t e = hipMalloc(&s.p, bytes);
-                if (e != hipSuccess) { s.p = nullptr; (void)hipGetLastError(); g_lastError = "out of device memory"; return ZHIP_ERR_NO_MEMORY; }
-                s.cap = bytes;
-            }
-            *base = (uint8_t*)s.p;
+            if (int rc = h->tPlanar.reserve_exact(bytes)) return rc;
+            *base = (uint8_t*)h->tPlanar.p;
             return 0;
         }
         DevBuf& d = area == ZSKT_A_STAGING ? c->skStaging : area == ZSKT_A_RECORDS ? c->skRecords : area == ZSKT_A_STASH ? c->skStash : area == ZSKT_A_TABLES ? h->tTables :
@@ -2091,9 +1997,7 @@ extern "C" int zhip_seekable_compress_records_device(zhip_ctx* c, const void* d_
 extern "C" void zhip_seekable_close(zhip_seekable* h)
 {
     if (!h) return;
-    h->prefix.release(); h->meta.release(); h->edge.release();
-    h->gTables.release(); h->gMeta.release(); h->gScratch.release(); h->tPlanar.release(); h->tTables.release(); h->tStatus.release(); h->tTileSums.release();      // (hipFree waits for the device: no upload from a slot is in flight behind it)
-    for (ZskPinSlot& s : h->slots) { if (s.p) (void)hipHostFree(s.p); (void)hipEventDestroy(s.done); }
+    (void)hipDeviceSynchronize();      // no upload from a slot, no kernel over a buffer is in flight when the handle's members release themselves
     delete h;
 }
 

@@ -1,7 +1,9 @@
 // tests/emu/emu_host_calls.cpp -- the plan of the host-buffer batch calls (python-zstandard_amd/csrc/zhip_host_calls.hpp) behind flat C entries.
 // Test infrastructure only (tests/test_emu_host_calls.py); part of libzhip_emu.so. The plan is plain host code: nothing is emulated here.
+// The pool, the device slots and the fan-out (python-zstandard_amd/csrc/zhip_host_pool.hpp) run over the stubs of host_pool_stubs.hpp.
 // The entries up to emu_hc_merge are the ones tests/golden/host_calls.json was recorded through, from a library that held the parent commit's lines behind them.
 #include "../../python-zstandard_amd/csrc/zhip_host_calls.hpp"
+#include "host_pool_stubs.hpp"
 #include <stdio.h>
 
 static std::vector<zhip_segment> table(const uint64_t* inLen, const uint64_t* outLen, size_t n)      // [0,n) source, [n,2n) destination, both back to back
@@ -140,4 +142,78 @@ extern "C" void emu_hc_compress_verdict(const uint64_t* sizes, const int32_t* st
     out[0] = (uint64_t)v.kind; out[1] = v.index; out[2] = (uint64_t)(int64_t)v.zerr; out[3] = v.d0; out[4] = v.d1;
     out[5] = v.kind ? 0 : host_compress_out_segments(sizes, (size_t)lo, (size_t)hi, o.data());
     if (!v.kind) for (size_t i = 0; i < hi - lo; i++) { segs[2 * i] = o[i].offset; segs[2 * i + 1] = o[i].length; }
+}
+
+// ---- what a context gives back (host_trim_order): out = the indices to release, in order; returns how many
+extern "C" uint64_t emu_hc_trim_order(const uint64_t* caps, const uint8_t* trimmable, uint64_t n, uint64_t keep, uint64_t* out)
+{
+    std::vector<size_t> c(caps, caps + n);
+    std::unique_ptr<bool[]> t(new bool[n ? n : 1]);
+    for (size_t i = 0; i < n; i++) t[i] = trimmable[i] != 0;
+    const std::vector<size_t> order = host_trim_order(c.data(), t.get(), (size_t)n, (size_t)keep);
+    for (size_t i = 0; i < order.size(); i++) out[i] = order[i];
+    return order.size();
+}
+
+// ---- the payload pool over a counting allocator. ops: (kind, arg) pairs -- 0 take(arg bytes), 1 give(what op number arg took), 2 give(a malloc(arg) the pool never saw),
+// 3 the allocator refuses from here on (arg 1) or serves again (0). res, four words per op: take -> which distinct pointer this is (the op number that first returned it, while it
+// lived), 1 if it came from the allocator in this op, the capacity the allocator was asked for; every op -> [3] the pool's idle bytes afterwards.
+// tail: allocator calls, unpin calls, unknown frees, blocks still pinned; freedCaps: the capacities unpinned, in order (at most cap of them)
+extern "C" void emu_hc_pool_script(uint64_t keep, const uint64_t* ops, uint64_t nOps, uint64_t* res, uint64_t* tail, uint64_t* freedCaps, uint64_t cap)
+{
+    CountingPin pin;
+    std::unique_ptr<PinPool> pool(pin.pool((size_t)keep));
+    std::vector<void*> got((size_t)nOps, nullptr);
+    std::unordered_map<void*, uint64_t> firstOp;
+    for (size_t k = 0; k < nOps; k++) {
+        const uint64_t kind = ops[2 * k], arg = ops[2 * k + 1];
+        uint64_t* r = res + 4 * k;
+        r[0] = r[1] = r[2] = 0;
+        if (kind == 0) {
+            const size_t before = pin.allocated.size();
+            void* p = got[k] = pool->take((size_t)arg);
+            if (!firstOp.count(p)) firstOp[p] = k;
+            r[0] = firstOp[p]; r[1] = pin.allocated.size() - before; r[2] = r[1] ? pin.allocated.back() : 0;
+        } else if (kind == 1) {
+            void* p = got[(size_t)arg]; got[(size_t)arg] = nullptr;
+            const bool pooled = pin.live.count(p) != 0;
+            pool->give(p);
+            if (!pooled || !pin.live.count(p)) firstOp.erase(p);      // freed: the address may come back as another block
+        } else if (kind == 2) pool->give(malloc((size_t)arg));
+        else pin.refuse = arg != 0;
+        r[3] = pool->idle;
+    }
+    for (void* p : got) if (p) pool->give(p);      // (whatever the script left out: nothing leaks from the entry itself)
+    tail[0] = pin.allocated.size(); tail[1] = pin.freed.size(); tail[2] = (uint64_t)pin.unknownFrees; tail[3] = pin.live.size();
+    for (size_t i = 0; i < pin.freed.size() && i < cap; i++) freedCaps[i] = pin.freed[i];
+    for (auto& kv : pin.live) free(kv.first);
+}
+
+// ---- DevPool::parse: out = explicit list, minBytes, then the slots' devices; returns the slots
+extern "C" int emu_hc_pool_parse(int count, const char* devices, const char* minBytes, uint64_t* out, int cap)
+{
+    DevPool p([](int) {});
+    p.parse(count, devices, minBytes);
+    out[0] = p.explicitList; out[1] = p.minBytes;
+    for (size_t i = 0; i < p.slots.size() && (int)i < cap; i++) out[2 + i] = (uint64_t)p.slots[i];
+    return (int)p.slots.size();
+}
+
+// ---- host_fan_out over d of the eight stub slots, the items' modes as StubCall reads them. out: rc, err.kind, err.index, err.zstdErr, outputs, runs, runs with lo == hi,
+// after() calls, buffers the fan-out freed, buffers still alive, worker threads bound so far, 1 if every worker bound its slot's device first; order: the outputs' item indices
+extern "C" void emu_hc_fan_out(const uint64_t* sizes, const uint8_t* mode, uint64_t n, uint64_t d, uint64_t* out, uint64_t* order, char* text, uint64_t textCap)
+{
+    static StubDevices* dev = new StubDevices();      // persistent like the library's: its threads never end
+    StubCall call; call.mode = mode;
+    StubCall::current() = &call;
+    zhip_error err; std::string t; std::vector<uint64_t> ord;
+    const int rc = call.call(dev->pool, (size_t)d, sizes, (size_t)n, &err, &t, &ord);
+    out[0] = (uint64_t)rc; out[1] = (uint64_t)err.kind; out[2] = err.index; out[3] = (uint64_t)(int64_t)err.zstdErr; out[4] = ord.size(); out[5] = (uint64_t)call.runs; out[6] = (uint64_t)call.emptyRuns;
+    out[7] = (uint64_t)call.afters; out[8] = (uint64_t)call.freedBufs; out[9] = (uint64_t)call.liveBufs;
+    {   std::lock_guard<std::mutex> g(dev->mu);
+        out[10] = dev->bound.size(); out[11] = 1;
+        for (size_t w = 0; w < dev->pool.workers.size(); w++) if (dev->pool.workers[w]) { bool seen = false; for (int b : dev->bound) seen |= b == 10 + (int)w; if (!seen) out[11] = 0; }
+    }
+    for (size_t i = 0; i < ord.size(); i++) order[i] = ord[i];
+    snprintf(text, (size_t)textCap, "%s", t.c_str());
 }

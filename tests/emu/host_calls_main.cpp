@@ -2,8 +2,11 @@
 // (tests/emu/build_host_calls.sh; nothing is loaded into python). For a few dozen item lists it runs what a host-buffer call runs between its HIP calls, with every buffer a
 // heap block of EXACTLY the bytes the plan gives: pass 1 -> cuts -> upload steps -> pack_items into a block of the step's bytes (three threads: the threshold is lowered) -> the
 // step copied into a "device" block of srcTotal bytes, every item's bytes then checked at segs[i].offset; both meta layouts carved out of blocks of their reserved bytes, every
-// array written at its full length; the verdicts over those arrays. Exits 0 and prints the case count; any other exit is a finding.
+// array written at its full length; the verdicts over those arrays. Then the payload pool, the trim order and the fan-out of zhip_host_pool.hpp over the stubs of
+// host_pool_stubs.hpp: every block, every output and every run's state a heap object of its own, every one of them freed by the end (LeakSanitizer counts).
+// Exits 0 and prints the case count; any other exit is a finding.
 #include "../../python-zstandard_amd/csrc/zhip_host_calls.hpp"
+#include "host_pool_stubs.hpp"
 #include <stdio.h>
 
 #define CHECK(x) do { if (!(x)) { fprintf(stderr, "case %d: %s failed (line %d)\n", g_case, #x, __LINE__); exit(1); } } while (0)
@@ -110,6 +113,56 @@ static void run_case(const std::vector<size_t>& sizes, uint64_t stageBytes, uint
     for (size_t i = 0; i < n; i++) delete src[i];
 }
 
+// the pool under keep limits from nothing to everything, a foreign pointer, a refused allocation; every block is unpinned exactly once by the end
+static void run_pool(size_t keep)
+{
+    g_case++;
+    const size_t M = (size_t)1 << 20;
+    CountingPin pin; pin.exact = true;
+    PinPool* pool = pin.pool(keep);
+    auto touch = [](void* p, size_t n) { if (n) { ((volatile uint8_t*)p)[0] = 1; ((volatile uint8_t*)p)[n - 1] = 2; } };      // a payload of n bytes holds n bytes
+    std::vector<void*> held;
+    const size_t want[] = {0, 1, ZHIP_PIN_MIN - 1, ZHIP_PIN_MIN, 3 * M, 70 * M, 4 * M, 100 * M, 5 * M + 1, 64 * M};
+    for (int round = 0; round < 6; round++) {
+        for (size_t n : want) { void* p = pool->take(n); CHECK(p != nullptr); touch(p, n); held.push_back(p); }
+        for (size_t k = round % 3; k < held.size(); k += 2) { pool->give(held[k]); held[k] = nullptr; CHECK(pool->idle <= keep); }
+        if (round == 2) { pin.refuse = true; void* p = pool->take(300 * M); CHECK(p != nullptr); touch(p, 300 * M); pool->give(p); pin.refuse = false; }      // no idle block holds it, none can be pinned: pageable, at its bytes
+        pool->give(malloc(100));
+    }
+    for (void* p : held) pool->give(p);
+    CHECK(pool->idle <= keep && pin.unknownFrees == 0 && pin.allocated.size() == pin.freed.size() + pin.live.size());
+    for (auto& kv : pool->blocks) { CHECK(!kv.second.busy); pin.unpin(kv.first); }      // what the limit let the pool keep
+    CHECK(pin.live.empty() && pin.allocated.size() == pin.freed.size());
+    delete pool;
+}
+static void run_trim()
+{
+    g_case++;
+    const size_t F = (size_t)64 << 20;
+    Exact<size_t> caps(5); Exact<bool> flags(5);
+    const size_t c[5] = {F + 1, 3 * F, F, 3 * F, 10 * F}; const bool t[5] = {true, true, true, true, false};
+    for (int i = 0; i < 5; i++) { caps.p[i] = c[i]; flags.p[i] = t[i]; }
+    CHECK(host_trim_order(caps.p, flags.p, 5, 0) == (std::vector<size_t>{1, 3, 0}));
+    CHECK(host_trim_order(caps.p, flags.p, 5, 15 * F + 1).size() == 1 && host_trim_order(caps.p, flags.p, 5, 18 * F + 1).empty() && host_trim_order(caps.p, flags.p, 0, 0).empty());
+}
+// the fan-out over 1 .. 8 slots: clean runs, failing runs and runs that throw; nothing a run or the merge allocated is left behind
+static void run_fan_out(StubDevices& dev)
+{
+    const std::vector<std::vector<uint64_t>> lists = {{1}, {0, 0, 0}, {5, 5}, {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13}, {100, 1, 1, 1, 1, 1, 1, 1, 1}};
+    for (const auto& sizes : lists) for (size_t d = 1; d <= 8; d++) for (int mode = 0; mode <= 3; mode++) for (size_t bad : {(size_t)0, sizes.size() / 2, sizes.size() - 1}) {
+        g_case++;
+        Exact<uint64_t> sz(sizes.size()); Exact<uint8_t> md(sizes.size());
+        for (size_t i = 0; i < sizes.size(); i++) { sz.p[i] = sizes[i]; md.p[i] = i == bad || (mode && i == sizes.size() - 1) ? (uint8_t)mode : 0; }
+        StubCall call; call.mode = md.p;
+        StubCall::current() = &call;
+        zhip_error err; std::string text; std::vector<uint64_t> order;
+        const int rc = call.call(dev.pool, d, sz.p, sizes.size(), &err, &text, &order);
+        CHECK(call.emptyRuns == 0 && call.liveBufs == 0 && call.runs == call.afters);
+        if (mode == 0) { CHECK(rc == 0 && order.size() == sizes.size()); for (size_t i = 0; i < order.size(); i++) CHECK(order[i] == i); }
+        else CHECK(rc == (mode == 1 ? ZHIP_ERR_ZSTD : mode == 2 ? ZHIP_ERR_NO_MEMORY : ZHIP_ERR_HIP) && err.kind == rc && order.empty() && !text.empty());
+    }
+}
+
 int main()
 {
     const uint64_t stage = 1000;          // an upload step, in place of 512 MiB
@@ -126,6 +179,13 @@ int main()
     for (const auto& v : lists) {
         run_case(v, stage, (uint64_t)1 << 30, 32768, 0); cases++;          // one chunk
         run_case(v, stage, 1500, 5, 2); cases++;                          // several chunks, a smaller first one
+    }
+    for (size_t keep : {(size_t)0, (size_t)10 << 20, (size_t)200 << 20, (size_t)24 << 30}) { run_pool(keep); cases++; }
+    run_trim(); cases++;
+    {   static StubDevices* dev = new StubDevices();      // (its threads never end: kept reachable, as the library keeps its own)
+        const int before = g_case;
+        run_fan_out(*dev);
+        cases += g_case - before;
     }
     printf("ok: %d cases\n", cases);
     return 0;
