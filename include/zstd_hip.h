@@ -214,7 +214,7 @@ int zhip_compress_sequences_device(zhip_ctx*, const void* d_src, const zhip_segm
                                    void* d_dst, const zhip_segment* d_dstSegs,
                                    uint64_t* d_outSizes, int32_t* d_status, void* stream, uint32_t flags);
 /* Which match finder zhip_compress_batch_device runs -- and with it zhip_seekable_compress_device and zhip_seekable_compress_records_device, which call it. Host state
- * only, never waits; the default is ZHIP_FINDER_LIBZSTD. Not read by zhip_compress_sequences_device or by the host-buffer API (zhip_compress_batch), whose contract is
+ * only, never waits (the call itself does under ZHIP_FINDER_AUTO: below); the default is ZHIP_FINDER_LIBZSTD. Not read by zhip_compress_sequences_device or by the host-buffer API (zhip_compress_batch), whose contract is
  * libzstd's bytes.
  *   ZHIP_FINDER_LIBZSTD  the searches that keep libzstd's table contents: frames byte for byte libzstd's.
  *   ZHIP_FINDER_WAVE     one wave per source, a hash table of positions in LDS, 64 positions probed per trip (zhip_encode_wave.hpp), launched once per chunk in place of
@@ -246,9 +246,28 @@ int zhip_compress_sequences_device(zhip_ctx*, const void* d_src, const zhip_segm
  *                        ("ZHIP_FINDER_NONE", match finder "none"). A source of several blocks gets d_status 40 at its own index and its neighbours compress; so does
  *                        a source the row of its own size class does not serve (level 4 at 16 384 bytes and below, a window that does not cover the source). Slot
  *                        rules (zhip_compress_bound, d_status 70) are unchanged.
- * An unknown value: ZHIP_ERR_UNSUPPORTED, the finder stays what it was. */
-enum { ZHIP_FINDER_LIBZSTD = 0, ZHIP_FINDER_WAVE = 1, ZHIP_FINDER_NONE = 2 };
+ *   ZHIP_FINDER_AUTO     ZHIP_FINDER_NONE or ZHIP_FINDER_LIBZSTD, chosen PER SOURCE: the right finder is a property of a frame, not of a tensor (of one int64 tensor's eight
+ *                        byte planes some want the search by two orders of magnitude and some are smaller and 20-30 x cheaper without it). A classify kernel
+ *                        (zhip_encode_auto.hpp, zhip_classify_batch_device below) reads a bounded sample of every source -- at most 14 KiB of a 128 KiB one -- and decides
+ *                        from the sample's byte histogram and from what the matches it finds there would save over their bytes as literals; the batch is split in
+ *                        device memory by that decision and the two parts run through the two finders' code as it is. Every frame is byte for byte what
+ *                        ZHIP_FINDER_NONE or ZHIP_FINDER_LIBZSTD writes for that source -- libzstd's bytes for a well-defined libzstd call either way -- with d_status
+ *                        and d_outSizes at the source's own index. The decision is a pure function of the source's bytes: not of the level, the batch, the launch
+ *                        shape or the device. A source above one block or below 64 bytes goes to the search unsampled; a tie goes to the literals-only frame.
+ *                        UNLIKE THE OTHER FINDERS THE CALL WAITS ONCE ON THE STREAM, for the two parts' sizes (8 bytes): the launch arguments of the existing kernels
+ *                        carry their count by value. It is therefore not capturable into a graph. A part that is empty launches nothing.
+ *                        Scope and refusals of the CALL are ZHIP_FINDER_NONE's (either part may be its kernel's): no dictionary, a level whose one-block row is fast or
+ *                        double-fast, else ZHIP_ERR_UNSUPPORTED with a zhip_last_error() text that names the finder ("ZHIP_FINDER_AUTO", match finder "auto").
+ *                        Per source they are the chosen finder's: a source of several blocks goes to the search, which serves it. DESIGN.md 4.2 has the rule, its
+ *                        constants and what it costs against the better choice per frame.
+ * An unknown value (3 among them): ZHIP_ERR_UNSUPPORTED, the finder stays what it was. */
+enum { ZHIP_FINDER_LIBZSTD = 0, ZHIP_FINDER_WAVE = 1, ZHIP_FINDER_NONE = 2, ZHIP_FINDER_AUTO = 4 };
 int zhip_ctx_set_match_finder(zhip_ctx*, int finder);
+/* ZHIP_FINDER_AUTO's decision on its own, for a caller who routes frames itself: d_choice[i] = 0 (the search) or 1 (literals only) for source i of the batch, and, where
+ * d_stats is not null, d_stats[4 i ...] = the integers it was made from -- sampled window bytes, their order-0 cost and the matches' credit in 1/256 bit, sampled positions
+ * with a candidate of 4 bytes or more (all 0 for a source that was not sampled). Asynchronous and stream-ordered, no host wait except while scratch grows; reads the
+ * sources only. A null d_choice or d_srcSegs: ZHIP_ERR_UNSUPPORTED, nothing queued. Does not read the context's level, finder or dictionary. */
+int zhip_classify_batch_device(zhip_ctx*, const void* d_src, const zhip_segment* d_srcSegs, size_t n, uint8_t* d_choice, uint32_t* d_stats /* may be null */, void* stream);
 size_t zhip_ctx_entropy_grid(zhip_ctx*);    /* waves of the entropy kernel resident on the context's device: a batch above it gives every wave several frames (for tests) */
 int zhip_ctx_sync(zhip_ctx*, void* stream, const int32_t* d_status, size_t n, zhip_error* err);
 /* The compress direction writes every frame into a zhip_compress_bound-sized slot; what is handed on (a BufferWithSegments, a payload
@@ -475,7 +494,9 @@ uint32_t zhip_seekable_filter(const zhip_seekable*);
  * 8 the flat match kernel -- the match stage of a chunk whichever of its forms ran: the double-fast search's and, since the fast strategy has a flat search of its own
  * (levels 1, 2 and negative levels without a dictionary, sources of one block), that one's; the LDS-source kernels of small batches too --, 9 "zhip_decode_pipeline_span": not a kernel, a chunk's decode pipeline from K1's start to K3's end (what the overlapping kernels cost together),
  * 10 the wave match kernel (ZHIP_FINDER_WAVE: once per chunk, with 5 and 8 at zero launches),
- * 11 the literals-only kernel (ZHIP_FINDER_NONE: once per chunk, timed with the trailer kernel behind it, with 5, 6, 8 and 10 at zero launches). */
+ * 11 the literals-only kernel (ZHIP_FINDER_NONE: once per chunk, timed with the trailer kernel behind it, with 5, 6, 8 and 10 at zero launches),
+ * 12 the classify kernel (ZHIP_FINDER_AUTO and zhip_classify_batch_device: once per chunk of 65 536 sources; under ZHIP_FINDER_AUTO the two parts' kernels count in their own
+ * directions, so a batch that is all one kind shows zero launches of the other kind). */
 const char* zhip_kernel_name(int k);
 int         zhip_ctx_kernel_time(zhip_ctx*, int direction, double* avgMs, uint64_t* launches);
 /* how many frames of the context's last zhip_decompress_batch_device call the phase-split kernels (K1 -> K2 -> K3) handed to the generic kernel: frames of several

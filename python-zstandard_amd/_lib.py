@@ -119,6 +119,7 @@ def lib():
         "zhip_compress_sequences_device": (C.c_int, [vp, vp, vp, sz, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]),
         "zhip_ctx_entropy_grid": (sz, [vp]),
         "zhip_ctx_set_match_finder": (C.c_int, [vp, C.c_int]),
+        "zhip_classify_batch_device": (C.c_int, [vp, vp, vp, sz, vp, vp, vp]),
         "zhip_ctx_sync": (C.c_int, [vp, vp, vp, sz, C.POINTER(Error)]),
         "zhip_compact_device": (C.c_int, [vp, vp, vp, vp, vp, sz, vp, vp]),
         "zhip_ctx_set_size_hint": (None, [vp, u64]),
@@ -172,7 +173,7 @@ EXPORTED_SYMBOLS = [
     "zhip_seekable_frame_count", "zhip_seekable_bound", "zhip_seekable_compress_device", "zhip_seekable_open_device", "zhip_seekable_close",
     "zhip_seekable_decompress_device", "zhip_seekable_decompress_ranges_device", "zhip_seekable_set_scratch_limit",
     "zhip_seekable_records_bound", "zhip_seekable_compress_records_device", "zhip_seekable_frame_offsets", "zhip_seekable_decompress_frames_device",
-    "zhip_compress_sequences_device", "zhip_ctx_entropy_grid", "zhip_ctx_set_match_finder",
+    "zhip_compress_sequences_device", "zhip_ctx_entropy_grid", "zhip_ctx_set_match_finder", "zhip_classify_batch_device",
     "zhip_seekable_edit_bound", "zhip_seekable_edit_device",
     "zhip_planes_split_device", "zhip_planes_join_device", "zhip_seekable_typed_bound", "zhip_seekable_compress_typed_device",
     "zhip_seekable_element_size", "zhip_seekable_group_elements", "zhip_seekable_decompress_typed_ranges_device",

@@ -21,6 +21,7 @@
 #include "zhip_encode_none.hpp"
 #include "zhip_cparams.hpp"
 #include "zhip_encode_plan.hpp"
+#include "zhip_encode_auto.hpp"
 #include "zhip_decode_plan.hpp"
 #include "zhip_seekable_calls.hpp"
 #include "zhip_seekable_typed_calls.hpp"
@@ -153,6 +154,15 @@ ZH_GLOBAL __launch_bounds__(64) void zhip_encode_none_kernel(ZhipEncodeArgs a)
     __shared__ ZeLDS L;
     ze_none_body(a, L);
 }
+// the match finder chosen per source (ZHIP_FINDER_AUTO, zhip_encode_auto.hpp): the classifier, one wave per source, and the three small kernels of the split
+ZH_GLOBAL __launch_bounds__(64) void zhip_encode_classify_kernel(ZhipClassifyArgs a)
+{
+    __shared__ ZaLDS L;
+    ze_classify_body(a, L);
+}
+ZH_GLOBAL __launch_bounds__(64) void zhip_encode_auto_partition_kernel(ZhipSplitArgs a) { ze_auto_partition_body(a); }
+ZH_GLOBAL __launch_bounds__(64) void zhip_encode_auto_gather_kernel(ZhipSplitArgs a) { ze_auto_gather_body(a); }
+ZH_GLOBAL __launch_bounds__(64) void zhip_encode_auto_scatter_kernel(ZhipSplitArgs a) { ze_auto_scatter_body(a); }
 #ifndef ZHIP_WAVE_HLOG
 #define ZHIP_WAVE_HLOG 12                  // table cells of the wave match finder, log2: 12 by the rate measurement (profiles/r11_wave_finder_rate.txt, DESIGN.md 4.2 -- the kernel's rate is its resident
                                            // waves, which LDS bounds: 16 384 x 128 KiB 77 / 140 / 174 ms at 12 / 13 / 14). ZHIP_WAVE_HLOG in the environment overrides it FOR THAT MEASUREMENT ONLY
@@ -324,7 +334,7 @@ struct PinBuf {
         p = nullptr; cap = 0;
     }
 };
-#define ZHIP_NTIMER 12
+#define ZHIP_NTIMER 13
 struct KTimer {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;   // owned: destroyed after reading
     std::vector<std::pair<hipEvent_t, hipEvent_t>> shared;    // borrowed: another timer owns the events
@@ -349,7 +359,7 @@ struct ZskPinSlot {
     X(pipeMeta, 1) X(pipeLit, 1) X(pipeCounters, 0) X(pipeFallback, 0) X(pipeFse, 1) X(pipeOrder, 0) X(pipeHuf, 1) X(pipeOrderLit, 0) X(pipeItemFrame, 0) X(pipeItemReps, 0) \
     X(pipeFrameRecs, 0) X(pipeBases, 1) X(pipePre, 0) \
     /* encode */ \
-    X(encArena, 1) X(encTables, 1) X(encFlatTables, 1) X(encWorkspace, 1) X(encBigWs, 1) X(encMeta, 0) X(encBigList, 0) X(encE1List, 0) X(encMbBlocks, 0) X(encMbCount, 0) X(encMbSeqs, 0) \
+    X(encArena, 1) X(encTables, 1) X(encFlatTables, 1) X(encWorkspace, 1) X(encBigWs, 1) X(encMeta, 0) X(encBigList, 0) X(encE1List, 0) X(encMbBlocks, 0) X(encMbCount, 0) X(encMbSeqs, 0) X(encAuto, 0) \
     X(scratch, 1) X(counter, 0) \
     /* dictionary, compress side: raw bytes, parsed entropy section, digested form and its tagged tables; decode side */ \
     X(cdictBlob, 0) X(cdictEntropy, 0) X(cdictDigest, 0) X(cdictTables, 0) X(dictBlob, 0) X(dictEntropy, 0) X(dictTables, 0) \
@@ -373,6 +383,7 @@ struct zhip_ctx {
     hipStream_t sideStream[ZHIP_NSLOT] = {};
     int e1PerCU = 0, e2PerCU = 0;
     int matchFinder = ZHIP_FINDER_LIBZSTD;     // zhip_ctx_set_match_finder
+    int classifyPerCU = 0;             // resident workgroups per CU of the classify kernel (ZHIP_FINDER_AUTO)
     int wavePerCU[3] = {0, 0, 0};      // resident workgroups per CU of the wave match kernel at H = 12, 13, 14
     size_t srcMaxHint = 0;             // largest source of the batch being launched when the caller knows it (host-buffer API), else 0
     size_t itemHint = 0;               // zhip_ctx_set_size_hint: what a device-API caller says about its items' uncompressed sizes (0 = nothing)
@@ -412,7 +423,7 @@ struct zhip_ctx {
     unsigned long long* profDecode = nullptr;    // ZHIP_PROF phase-timer accumulators, owned by the context (one context == one caller)
     unsigned long long* profPipe = nullptr;
     unsigned long long* profEncode = nullptr;
-    KTimer timer[ZHIP_NTIMER];   // (10: the wave match kernel, 11: the literals-only kernel of ZHIP_FINDER_NONE) 0 fused decode, 1 fused encode, 2 K1 literals, 3 K2 sequences, 4 K3 execution, 5 E1 match, 6 E2 entropy, 7 K1b Huffman streams, 8 the flat match kernel, 9 the decode pipeline of a chunk from K1's start to K3's end (K1b runs beside K2)
+    KTimer timer[ZHIP_NTIMER];   // (10: the wave match kernel, 11: the literals-only kernel of ZHIP_FINDER_NONE, 12: the classify kernel of ZHIP_FINDER_AUTO) 0 fused decode, 1 fused encode, 2 K1 literals, 3 K2 sequences, 4 K3 execution, 5 E1 match, 6 E2 entropy, 7 K1b Huffman streams, 8 the flat match kernel, 9 the decode pipeline of a chunk from K1's start to K3's end (K1b runs beside K2)
     size_t device_bytes() const
     {
         size_t n = 0;
@@ -476,6 +487,8 @@ extern "C" zhip_ctx* zhip_ctx_create(void)
     c->wavePerCU[1] = nb;
     nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_encode_match_wave_kernel<14>, 64, 0) != hipSuccess || nb < 1) nb = 2;
     c->wavePerCU[2] = nb;
+    nb = 0; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, zhip_encode_classify_kernel, 64, 0) != hipSuccess || nb < 1) nb = 8;
+    c->classifyPerCU = nb;
     return c;
 }
 static void drain_shared(KTimer& t)
@@ -509,7 +522,7 @@ extern "C" const char* zhip_kernel_name(int k)
     static const char* names[ZHIP_NTIMER] = {"zhip_decode_frames_kernel", "zhip_encode_frames_kernel", "zhip_decode_lit_kernel",
                                    "zhip_decode_seq_kernel", "zhip_decode_exec_kernel", "zhip_encode_match_kernel",
                                    "zhip_encode_entropy_kernel", "zhip_decode_huf_kernel", "zhip_encode_match_flat_kernel", "zhip_decode_pipeline_span",
-                                   "zhip_encode_match_wave_kernel", "zhip_encode_none_kernel"};
+                                   "zhip_encode_match_wave_kernel", "zhip_encode_none_kernel", "zhip_encode_classify_kernel"};
     return k >= 0 && k < ZHIP_NTIMER ? names[k] : "";
 }
 extern "C" int zhip_ctx_kernel_time(zhip_ctx* c, int direction, double* avgMs, uint64_t* launches)
@@ -1049,7 +1062,7 @@ static int reserve_slots(zhip_ctx* c, const ZePlanDevice& dev, ZeSlotPlan& s, Zh
 }
 extern "C" int zhip_ctx_set_match_finder(zhip_ctx* c, int finder)
 {
-    if (!c || (finder != ZHIP_FINDER_LIBZSTD && finder != ZHIP_FINDER_WAVE && finder != ZHIP_FINDER_NONE)) { g_lastError = "zhip_ctx_set_match_finder: unknown match finder"; return ZHIP_ERR_UNSUPPORTED; }
+    if (!c || (finder != ZHIP_FINDER_LIBZSTD && finder != ZHIP_FINDER_WAVE && finder != ZHIP_FINDER_NONE && finder != ZHIP_FINDER_AUTO)) { g_lastError = "zhip_ctx_set_match_finder: unknown match finder"; return ZHIP_ERR_UNSUPPORTED; }
     c->matchFinder = finder;
     return 0;
 }
@@ -1262,20 +1275,24 @@ static void launch_big_list(const zhip_ctx* c, const ZePlan& p, const ZhipEncode
     b.frameList = a.bigList; b.listCount = a.bigCount;
     hipLaunchKernelGGL(zhip_encode_frames_kernel, dim3(p.gBig), dim3(64), 0, stream, b);
 }
-extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
-                                          void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
-                                          int32_t* d_status, void* streamv)
+static int compress_batch_auto(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n, void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
+                               int32_t* d_status, hipStream_t stream);
+// zhip_compress_batch_device under match finder `finder` (the context's, or one of the two that ZHIP_FINDER_AUTO hands its parts to)
+static int compress_batch_with(zhip_ctx* c, int finder, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
+                               void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
+                               int32_t* d_status, void* streamv)
 {
     if (!c) return ZHIP_ERR_UNSUPPORTED;
     if (n == 0) return 0;
     if (n > 0x7FFFFFFFu) { g_lastError = "too many frames in one launch"; return ZHIP_ERR_UNSUPPORTED; }
     hipStream_t stream = (hipStream_t)streamv;
+    if (finder == ZHIP_FINDER_AUTO) return compress_batch_auto(c, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, stream);
     if (c->counter.reserve(64 * 8)) return g_reserveRc;
     uint8_t* const cbase = (uint8_t*)c->counter.p;
     HIP_TRY(hipMemsetAsync(cbase + ZC_E1_WORK, 0, 4, stream));
     ZhipEncodeArgs a; enc_args_init(c, a, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, cbase);
-    if (c->matchFinder == ZHIP_FINDER_WAVE) return compress_batch_wave(c, a, cbase, n, stream);
-    if (c->matchFinder == ZHIP_FINDER_NONE) return compress_batch_none(c, a, cbase, n, stream);
+    if (finder == ZHIP_FINDER_WAVE) return compress_batch_wave(c, a, cbase, n, stream);
+    if (finder == ZHIP_FINDER_NONE) return compress_batch_none(c, a, cbase, n, stream);
     // the plan: which kernels, how many sources per launch, how much memory (zhip_encode_plan.hpp)
     ZePlanIn in = plan_inputs(c, n);
     ZePlan p = ze_encode_plan(in);
@@ -1343,6 +1360,78 @@ extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const 
         launch_big_list(c, p, a, stream);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+extern "C" int zhip_compress_batch_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n,
+                                          void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
+                                          int32_t* d_status, void* streamv)
+{
+    if (!c) return ZHIP_ERR_UNSUPPORTED;
+    return compress_batch_with(c, c->matchFinder, d_src, d_srcSegs, n, d_dst, d_dstSegs, d_outSizes, d_status, streamv);
+}
+
+// ---- ZHIP_FINDER_AUTO (zhip_encode_auto.hpp)
+// the classify kernel over a batch, in launches of the plan's chunk: choice bytes (and statistics) at the sources' own indices. The work counter is the first cell of the
+// context's encAuto buffer, which the caller has reserved.
+static int launch_classify(zhip_ctx* c, const ZeAutoPlan& s, const void* d_src, const zhip_segment* d_srcSegs, size_t n, uint8_t* d_choice, uint32_t* d_stats, hipStream_t stream)
+{
+    ZhipClassifyArgs k; k.src = (const uint8_t*)d_src; k.srcSegs = (const uint64_t*)d_srcSegs; k.choice = d_choice; k.stats = d_stats; k.counter = (uint32_t*)c->encAuto.p;
+    for (size_t first = 0; first < n; first += s.chunk) {
+        const size_t cnt = n - first < s.chunk ? n - first : s.chunk;
+        k.first = (uint32_t)first; k.count = (uint32_t)cnt;
+        HIP_TRY(hipMemsetAsync(k.counter, 0, 4, stream));
+        ChunkEvents ev;
+        if (c->timing) HIP_TRY(ev.create(2));
+        HIP_TRY(ev.record(0, stream));
+        hipLaunchKernelGGL(zhip_encode_classify_kernel, dim3((uint32_t)(cnt < s.grid ? cnt : s.grid)), dim3(64), 0, stream, k);
+        HIP_TRY(ev.record(1, stream));
+        ev.give(c->timer[12], 0, 1);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+extern "C" int zhip_classify_batch_device(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n, uint8_t* d_choice, uint32_t* d_stats, void* streamv)
+{
+    if (!c) return ZHIP_ERR_UNSUPPORTED;
+    if (n == 0) return 0;
+    if (!d_choice || !d_srcSegs) { g_lastError = "zhip_classify_batch_device: null choice or segment pointer"; return ZHIP_ERR_UNSUPPORTED; }
+    if (n > 0x7FFFFFFFu) { g_lastError = "too many frames in one launch"; return ZHIP_ERR_UNSUPPORTED; }
+    ZePlanIn in = plan_inputs(c, n); in.n = 0;                    // (no split: the counter's cell only)
+    ZeAutoPlan s = ze_auto_plan(in, c->classifyPerCU);
+    if (c->encAuto.reserve(s.bytes)) return g_reserveRc;
+    in.n = n; s = ze_auto_plan(in, c->classifyPerCU);
+    return launch_classify(c, s, d_src, d_srcSegs, n, d_choice, d_stats, (hipStream_t)streamv);
+}
+// zhip_compress_batch_device under ZHIP_FINDER_AUTO: classify, partition the indices, gather the segment tables, run the two parts through the default finder and the
+// literals-only finder as they are -- on the gathered tables and into gathered sizes and statuses -- and scatter those back to the sources' own indices. The two paths'
+// launch arguments carry the count by value, so the call WAITS ONCE on the stream, for the two counts (8 bytes); a part that is empty launches nothing.
+static int compress_batch_auto(zhip_ctx* c, const void* d_src, const zhip_segment* d_srcSegs, size_t n, void* d_dst, const zhip_segment* d_dstSegs, uint64_t* d_outSizes,
+                               int32_t* d_status, hipStream_t stream)
+{
+    if (const char* why = ze_auto_refusal(c->rows, c->hasCDict)) { g_lastError = why; return ZHIP_ERR_UNSUPPORTED; }
+    const ZeAutoPlan s = ze_auto_plan(plan_inputs(c, n), c->classifyPerCU);
+    if (c->encAuto.reserve(s.bytes)) return g_reserveRc;
+    uint8_t* const base = (uint8_t*)c->encAuto.p;
+    ZhipSplitArgs k; memset(&k, 0, sizeof k);
+    k.choice = base + s.offChoice; k.n = (uint32_t)n; k.perm = (uint32_t*)(base + s.offPerm); k.counts = (uint32_t*)(base + 4);
+    k.srcSegs = (const uint64_t*)d_srcSegs; k.dstSegs = (const uint64_t*)d_dstSegs; k.gSrcSegs = (uint64_t*)(base + s.offSrcSegs); k.gDstSegs = (uint64_t*)(base + s.offDstSegs);
+    k.outSizes = d_outSizes; k.status = d_status; k.gOutSizes = (const uint64_t*)(base + s.offOutSizes); k.gStatus = (const int32_t*)(base + s.offStatus);
+    if (int rc = launch_classify(c, s, d_src, d_srcSegs, n, base + s.offChoice, nullptr, stream)) return rc;
+    hipLaunchKernelGGL(zhip_encode_auto_partition_kernel, dim3(1), dim3(64), 0, stream, k);
+    hipLaunchKernelGGL(zhip_encode_auto_gather_kernel, dim3(s.gridMove), dim3(64), 0, stream, k);
+    HIP_TRY(hipGetLastError());
+    uint32_t counts[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(counts, k.counts, sizeof counts, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));                                  // the one host wait
+    if ((size_t)counts[0] + counts[1] != n) { g_lastError = "match finder \"auto\": the split does not cover the batch"; return ZHIP_ERR_HIP; }
+    const size_t n0 = counts[0], n1 = counts[1];
+    if (n0) if (int rc = compress_batch_with(c, ZHIP_FINDER_LIBZSTD, d_src, (const zhip_segment*)k.gSrcSegs, n0, d_dst, (const zhip_segment*)k.gDstSegs,
+                                             (uint64_t*)k.gOutSizes, (int32_t*)k.gStatus, stream)) return rc;
+    if (n1) if (int rc = compress_batch_with(c, ZHIP_FINDER_NONE, d_src, (const zhip_segment*)(k.gSrcSegs + 2 * n0), n1, d_dst, (const zhip_segment*)(k.gDstSegs + 2 * n0),
+                                             (uint64_t*)k.gOutSizes + n0, (int32_t*)k.gStatus + n0, stream)) return rc;
+    hipLaunchKernelGGL(zhip_encode_auto_scatter_kernel, dim3(s.gridMove), dim3(64), 0, stream, k);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

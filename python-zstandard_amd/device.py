@@ -28,8 +28,8 @@ class DeviceBatchContext:
                  format=0, max_window_size=0, match_finder="libzstd", **cparams):
         """dict_data: a ZstdCompressionDict (or bytes) used by both directions; level / write_* / cparams (window_log, hash_log,
         chain_log, min_match, target_length, strategy): what ZstdCompressor takes; format / max_window_size: what ZstdDecompressor takes.
-        match_finder: "libzstd" (the default: frames byte for byte libzstd's), "wave" or "none" (no search: literals-only frames, for numeric tensors) -- see
-        set_match_finder."""
+        match_finder: "libzstd" (the default: frames byte for byte libzstd's), "wave", "none" (no search: literals-only frames, for numeric tensors) or "auto" ("none" or "libzstd",
+        chosen per source) -- see set_match_finder."""
         self.ctx = None
         if match_finder not in self.MATCH_FINDERS:                      # (before anything native exists)
             raise ZstdError("match_finder must be one of %s" % ", ".join(repr(k) for k in self.MATCH_FINDERS))
@@ -73,7 +73,7 @@ class DeviceBatchContext:
         kernel; untold, such items are served one wave each by a token grid of the generic kernels (correct, slow)"""
         self.L.zhip_ctx_set_size_hint(self.ctx, int(max_item_bytes))
 
-    MATCH_FINDERS = {"libzstd": 0, "wave": 1, "none": 2}
+    MATCH_FINDERS = {"libzstd": 0, "wave": 1, "none": 2, "auto": 4}
 
     def set_match_finder(self, match_finder):
         """the match finder of the coming compress / seekable_compress / seekable_compress_records calls (compress_sequences has none). "libzstd": the searches
@@ -87,7 +87,12 @@ class DeviceBatchContext:
         (the search finds only short, worthless matches there) and no search is paid for. The caveat: "On data with real repetition they lose badly: the int64 sums
         here [1.9 x level 3's size], and any text" -- nothing picks the finder for you. Scope and refusals as for "wave": sources of one block, no dictionary, levels
         whose one-block row is fast or double-fast; a dictionary or level 5 raises ZstdError naming "none" from the compress call, a source of several blocks gets
-        status 40 at its own index. Host state only."""
+        status 40 at its own index.
+        "auto": "none" or "libzstd", chosen PER SOURCE by a classify kernel from a bounded sample of the source (``classify`` shows its decisions): the planes of one
+        typed stream want different finders, and so do the records of a mixed stream. Every frame is byte for byte what "none" or "libzstd" writes for that source,
+        with status and size at the source's own index; the choice depends on the source's bytes alone. A source above one block or below 64 bytes goes to the
+        search. Unlike the other finders the compress call waits once on its stream (for the two parts' sizes). A dictionary or level 5 raises ZstdError naming
+        "auto" from the compress call. Host state only."""
         if match_finder not in self.MATCH_FINDERS:
             raise ZstdError("match_finder must be one of %s" % ", ".join(repr(k) for k in self.MATCH_FINDERS))
         if self.L.zhip_ctx_set_match_finder(self.ctx, self.MATCH_FINDERS[match_finder]):
@@ -132,6 +137,21 @@ class DeviceBatchContext:
                                                s.cuda_stream)
         if rc:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+
+    def classify(self, src, src_segs, stats=False, stream=None):
+        """match_finder="auto"'s decision for every source of a batch, without compressing anything: a uint8 CUDA tensor [n], 0 = the search ("libzstd"),
+        1 = literals only ("none"); with stats=True also an int32 tensor [n, 4] of the integers it was made from -- sampled window bytes, their order-0 cost and
+        the matches' credit in 1/256 bit, sampled positions with a candidate of 4 bytes or more (zeros for a source that was not sampled: above one block, below
+        64 bytes). Asynchronous; reads the context's level, finder and dictionary not at all."""
+        self._check(src, torch.uint8); self._check(src_segs, torch.int64)
+        n = src_segs.shape[0]
+        choice = torch.zeros(n, dtype=torch.uint8, device=src.device)
+        st = torch.zeros((n, 4), dtype=torch.int32, device=src.device) if stats else None
+        s = stream if stream is not None else torch.cuda.current_stream()
+        rc = self.L.zhip_classify_batch_device(self.ctx, src.data_ptr(), src_segs.data_ptr(), n, choice.data_ptr(), st.data_ptr() if stats else None, s.cuda_stream)
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return (choice, st) if stats else choice
 
     def compress_sequences(self, src, src_segs, seqs, seq_segs, dst, dst_segs, out_sizes, status, copy_literals=False, stream=None):
         """compress() from the caller's sequences instead of a match search (an external match finder; tests of the entropy stage). seqs: int64 CUDA tensor of

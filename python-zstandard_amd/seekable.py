@@ -72,7 +72,7 @@ def compress(data, level=3, frame_size=131072, checksum=False, match_finder="lib
     """data -> a seekable stream (bytes). match_finder: "libzstd" (frames byte for byte libzstd's) or "wave" (DeviceBatchContext.set_match_finder: valid zstd,
     not libzstd's bytes; frame_size at most 131 072) or "none" (no match search: every frame is libzstd's literals-only frame of its content, for NUMERIC
     TENSORS -- with element_size 2, 4 or 8 the fastest compress path, and streams the size of level 3's or up to 13 % smaller on float data; "on data with real
-    repetition they lose badly: the int64 sums here, and any text", 1.9 x on int64 running sums; frame_size at most 131 072 bytes of a plane). element_size 2, 4 or 8: a typed stream -- data is elements of that many bytes, frame_size counts the
+    repetition they lose badly: the int64 sums here, and any text", 1.9 x on int64 running sums; frame_size at most 131 072 bytes of a plane) or "auto" ("none" or "libzstd" chosen per frame by a classify kernel -- per PLANE frame of a typed stream, whose planes want different finders: every frame is byte for byte one of the two; any frame_size, a frame above 131 072 bytes goes to the search). element_size 2, 4 or 8: a typed stream -- data is elements of that many bytes, frame_size counts the
     elements of a group (see the module); filter None or "delta": the filter of a typed stream (see the module; with element_size 1 a ZstdError). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
     ctx = DeviceBatchContext(level=level, match_finder=match_finder, **ctx_kw)
     try:
@@ -123,7 +123,7 @@ def decompress_ranges(data, ranges, **ctx_kw):
 
 def compress_records(records, level=3, checksum=False, match_finder="libzstd", **ctx_kw):
     """a list of bytes -> a seekable stream (bytes) with ONE frame per record, compressed as one batch; ``decompress_records`` reads records back by index.
-    match_finder: as in ``compress`` (records of at most 131 072 bytes under "wave" and "none"; "none" is for records of numeric data, not text). ctx_kw: what DeviceBatchContext takes. Raises ZstdError."""
+    match_finder: as in ``compress`` (records of at most 131 072 bytes under "wave" and "none"; "none" is for records of numeric data, not text; "auto" chooses between "none" and "libzstd" per record). ctx_kw: what DeviceBatchContext takes. Raises ZstdError."""
     raws = [bytes(r) for r in records]
     table, at = [], 0
     for r in raws:
