@@ -467,7 +467,7 @@ int      zhip_seekable_decompress_typed_ranges_device(zhip_ctx*, zhip_seekable*,
  * independent, so a group is still the unit of random access. Floats gain nothing from it. Everything else about a typed stream is unchanged: the frames are
  * libzstd's frames of those planes, the table's checksums are those of the planar content, zstd -d and every plain reader see the filtered planar bytes.
  * The marker keeps version 1; its word at +16 is elementSize | filter << 8, so an unfiltered stream is byte for byte what it was, and a reader from before
- * the filters refuses a filtered stream as an element size it does not know. Any value but 0 or 1 in bits 8 .. 31 is a marker this reader does not
+ * the filters refuses a filtered stream as an element size it does not know. Any value but 0, 1 or 4 (ZHIP_FILTER_XOR_BASE, below) in bits 8 .. 31 is a marker this reader does not
  * understand: corruption_detected (20) at the marker frame.
  *
  * zhip_planes_split_filter_device / zhip_planes_join_filter_device: the transposition kernels with the filter fused in. Split subtracts on the words between
@@ -487,6 +487,35 @@ int      zhip_planes_join_filter_device(zhip_ctx*, const void* d_src, uint64_t s
 int      zhip_seekable_compress_typed_filter_device(zhip_ctx*, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, uint32_t filter, int flags,
                                                     void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status /* [2] */, void* stream);
 uint32_t zhip_seekable_filter(const zhip_seekable*);
+
+/* ZHIP_FILTER_XOR_BASE: the filter for VERSIONS of one tensor -- checkpoint after checkpoint, a fine-tune beside its base model, an optimizer
+ * state some steps later. The caller holds a BASE of the source's size in device memory (the previous checkpoint), and the plane frames hold the byte planes
+ * of x[i] ^ b[i]: the elements' bit patterns XORed bytewise, so nothing depends on the byte order within an element, there are no carries, and a byte needs
+ * its base byte and nothing else -- a range that starts inside a group is fetched from where it starts (no elements in front, unlike delta). Versions differ
+ * in the low mantissa bits and almost nowhere else: the high planes become runs of zeros, the low planes stay noise (what ZHIP_FINDER_AUTO sorts per frame).
+ * The frames are libzstd's frames of those planes, the table's checksums those of the filtered planar content, zstd -d and every plain reader
+ * (zhip_seekable_decompress_device, _ranges_, _frames_, zhip_seekable_edit_device) see the filtered planar bytes. The marker keeps version 1, its word at
+ * +16 is elementSize | 4 << 8. Filter values 2 and 3 are none and stay refused everywhere.
+ *
+ * THE STREAM DOES NOT NAME ITS BASE. Reading it with another tensor of the right size returns wrong elements with status 0; keeping stream and base together
+ * is the caller's business (a fingerprint of the base is not part of the format). A reader XORs once: chains of versions are the caller's to follow.
+ *
+ * zhip_planes_split_base_device / zhip_planes_join_base_device: the transposition kernels with the XOR fused in, one kernel each way; d_base is `size` bytes.
+ * zhip_seekable_compress_typed_base_device: zhip_seekable_compress_typed_device with the XOR in the split and filter 4 in the marker; d_base is srcSize bytes.
+ * zhip_seekable_decompress_typed_ranges_base_device: zhip_seekable_decompress_typed_ranges_device for a filter-4 handle -- the same plan, passes and scratch
+ * limit, the base XORed in by the join; d_base is baseSize bytes, the stream's content size, of which only the bytes at the content offsets the ranges cover
+ * are read. ZHIP_ERR_UNSUPPORTED, with nothing queued and nothing written, beyond the calls' own refusals: a NULL base; elementSize 1; a baseSize other than
+ * the stream's content size; a base that shares a byte with the output (d_dst over size / dstCapacity / dstCapacity bytes); the read with a base on a handle
+ * whose filter is not 4; and zhip_seekable_decompress_typed_ranges_device (no base) on a filter-4 handle. The three *_filter_device calls refuse filter 4 as
+ * they refuse 2: they have no base to take. */
+enum { ZHIP_FILTER_XOR_BASE = 4 };
+int      zhip_planes_split_base_device(zhip_ctx*, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, const void* d_base, void* d_dst, void* stream);
+int      zhip_planes_join_base_device(zhip_ctx*, const void* d_planar, uint64_t size, uint32_t elementSize, uint32_t frameSize, const void* d_base, void* d_dst, void* stream);
+int      zhip_seekable_compress_typed_base_device(zhip_ctx*, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, const void* d_base, int flags,
+                                                  void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status /* [2] */, void* stream);
+int      zhip_seekable_decompress_typed_ranges_base_device(zhip_ctx*, zhip_seekable*, const void* d_base, uint64_t baseSize, const zhip_seekable_range* ranges, size_t nRanges,
+                                                           void* d_out, uint64_t outCapacity, int32_t* d_status /* [2 + 2 * nRanges] */,
+                                                           zhip_seekable_gather_stats* stats /* host, may be NULL */, void* stream);
 
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,

@@ -152,6 +152,10 @@ def lib():
         "zhip_seekable_filter": (C.c_uint32, [vp]),
         "zhip_seekable_group_elements": (C.c_uint32, [vp]),
         "zhip_seekable_decompress_typed_ranges_device": (C.c_int, [vp, vp, vp, sz, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
+        "zhip_planes_split_base_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "zhip_planes_join_base_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "zhip_seekable_compress_typed_base_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, vp, C.c_int, vp, u64, vp, vp, vp]),
+        "zhip_seekable_decompress_typed_ranges_base_device": (C.c_int, [vp, vp, vp, u64, vp, sz, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
     }
     for name, (res, args) in protos.items():
         f = getattr(L, name)
@@ -178,6 +182,7 @@ EXPORTED_SYMBOLS = [
     "zhip_planes_split_device", "zhip_planes_join_device", "zhip_seekable_typed_bound", "zhip_seekable_compress_typed_device",
     "zhip_seekable_element_size", "zhip_seekable_group_elements", "zhip_seekable_decompress_typed_ranges_device",
     "zhip_planes_split_filter_device", "zhip_planes_join_filter_device", "zhip_seekable_compress_typed_filter_device", "zhip_seekable_filter",
+    "zhip_planes_split_base_device", "zhip_planes_join_base_device", "zhip_seekable_compress_typed_base_device", "zhip_seekable_decompress_typed_ranges_base_device",
 ]
 
 

@@ -2208,6 +2208,30 @@ extern "C" int zhip_seekable_compress_typed_filter_device(zhip_ctx* c, const voi
     ZskHipTypedBackend b(c, nullptr, streamv);
     return zsk_typed_compress(b, c != nullptr, d_src, srcSize, frameSize, elementSize, flags, d_dst, dstCapacity, d_streamSize, d_status, filter);
 }
+// the xor-with-base filter (ZHIP_FILTER_XOR_BASE): the calls that take the base
+extern "C" int zhip_planes_split_base_device(zhip_ctx* c, const void* d_src, uint64_t size, uint32_t elementSize, uint32_t frameSize, const void* d_base, void* d_dst, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_planes_split_base(b, c != nullptr, d_src, size, elementSize, frameSize, d_base, d_dst);
+}
+extern "C" int zhip_planes_join_base_device(zhip_ctx* c, const void* d_planar, uint64_t size, uint32_t elementSize, uint32_t frameSize, const void* d_base, void* d_dst, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_planes_join_base(b, c != nullptr, d_planar, size, elementSize, frameSize, d_base, d_dst);
+}
+extern "C" int zhip_seekable_compress_typed_base_device(zhip_ctx* c, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t elementSize, const void* d_base, int flags,
+                                                        void* d_dst, uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_typed_compress_base(b, c != nullptr, d_src, srcSize, frameSize, elementSize, d_base, flags, d_dst, dstCapacity, d_streamSize, d_status);
+}
+extern "C" int zhip_seekable_decompress_typed_ranges_base_device(zhip_ctx* c, zhip_seekable* h, const void* d_base, uint64_t baseSize, const zhip_seekable_range* ranges, size_t nRanges,
+                                                                 void* d_dst, uint64_t dstCapacity, int32_t* d_status, zhip_seekable_gather_stats* stats, void* streamv)
+{
+    ZskHipTypedBackend b(c, h, streamv);
+    size_t bad = 0;
+    return zsk_typed_ranges_base(b, c != nullptr, h, d_base, baseSize, (const uint64_t*)ranges, nRanges, d_dst, dstCapacity, d_status, stats, &bad);
+}
 extern "C" uint32_t zhip_seekable_filter(const zhip_seekable* h) { return h ? h->filter : 0; }
 extern "C" uint32_t zhip_seekable_element_size(const zhip_seekable* h) { return h ? h->elementSize : 0; }
 extern "C" uint32_t zhip_seekable_group_elements(const zhip_seekable* h) { return h ? h->groupElements : 0; }

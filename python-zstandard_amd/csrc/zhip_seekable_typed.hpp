@@ -5,7 +5,9 @@
 //
 //     0x184D2A5D | Frame_Size = 16 | 'Z' 'H' 'P' 'L' | version = 1 | element_size | filter << 8 | frame_size          (all little-endian words)
 //
-// filter 0: the planes are those of the elements; filter 1 (delta): those of the differences of neighbouring elements within the group.
+// filter 0: the planes are those of the elements; filter 1 (delta): those of the differences of neighbouring elements within the group;
+// filter 4 (xor with a base): those of x[i] ^ b[i], b a BASE tensor of the same size that the caller holds -- the previous checkpoint. The stream
+// does NOT name its base: reading it with another base returns wrong elements with status 0.
 // The standard seek table comes last: the stream is an ordinary seekable stream whose content is the PLANAR bytes.
 // What is here: the two transposition kernels (interleaved -> planar with the record table of the plane frames, planar -> interleaved driven by a job table),
 // the two kernels that seal a stream the records call has written, the status reducer of the typed read, and the host plan of that read. One-wave
@@ -24,9 +26,10 @@
 // the marker's word at +16 is element_size | filter << 8: what was done to a group's elements before the plane split
 #define ZSK_FILTER_NONE 0u
 #define ZSK_FILTER_DELTA 1u                  // d[0] = x[0], d[i] = x[i] - x[i - 1] mod 2^(8k) on the elements' bit patterns as unsigned little-endian integers, per group
+#define ZSK_FILTER_XOR_BASE 4u               // d[i] = x[i] ^ b[i] bytewise, b the caller's base at the same content offset (2 and 3 are no filters: refused everywhere)
 
 ZSK_HD bool zsk_element_ok(uint32_t k) { return k == 2 || k == 4 || k == 8; }
-ZSK_HD bool zsk_filter_ok(uint32_t filter) { return filter == ZSK_FILTER_NONE || filter == ZSK_FILTER_DELTA; }
+ZSK_HD bool zsk_filter_ok(uint32_t filter) { return filter == ZSK_FILTER_NONE || filter == ZSK_FILTER_DELTA || filter == ZSK_FILTER_XOR_BASE; }
 ZSK_HD bool zsk_typed_args_ok(uint64_t srcSize, uint32_t frameSize, uint32_t k)
 {
     return zsk_element_ok(k) && srcSize % k == 0 && frameSize >= 1 && frameSize <= ZSK_MAX_CONTENT && zsk_frame_count(srcSize / k, frameSize) * k <= ZSK_MAX_PLANE_FRAMES;
@@ -256,6 +259,40 @@ ZH_DEV void zsk_planes_split_delta_body(const ZskPlanesArgs& a)
     zsk_planes_records(a);
 }
 
+// ------------------------------------------------------------------------------------------------ split with the xor-with-base filter
+// The XOR is done on the words between the split's loads and its stores, as the delta filter's subtraction: no pass of its own over the source. The base's 16
+// elements stand at the source's offset, so a lane issues its 2 K loads of 16 bytes -- K of the source, K of the base -- back to back and waits once: a base
+// load behind the first XOR would be a second memory round trip per tile. Bytewise, so no carries, no neighbours, no shuffle: a lane beyond the group's end returns.
+struct ZskPlanesXorArgs { ZskPlanesArgs p; const uint8_t* base; };      // base: `elements` elements of k bytes, as src (ZskPlanesArgs keeps its layout)
+template <int K> ZH_DEV void zsk_split_xor_lane(const uint8_t* s, const uint8_t* b, uint8_t* d, uint32_t e, uint32_t i0)
+{
+    if (i0 >= e) return;
+    if (e - i0 >= 16) {
+        uint32_t w[4 * K], x[4 * K];
+        zsk_load16<K>(s + (uint64_t)i0 * K, w);
+        zsk_load16<K>(b + (uint64_t)i0 * K, x);
+#pragma unroll
+        for (int j = 0; j < 4 * K; j++) w[j] ^= x[j];
+        zsk_split16_store<K>(w, d + i0, e);
+        return;
+    }
+    for (uint32_t i = i0; i < e; i++) for (uint32_t p = 0; p < K; p++) d[(uint64_t)p * e + i] = s[(uint64_t)i * K + p] ^ b[(uint64_t)i * K + p];
+}
+ZH_DEV void zsk_planes_split_xor_body(const ZskPlanesXorArgs& x)
+{
+    const ZskPlanesArgs& a = x.p;
+    const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
+    const uint64_t tiles = (uint64_t)a.nGroups * tpg;
+    for (uint64_t t = zh_block(); t < tiles; t += zh_nblocks()) {
+        const uint64_t g = t / tpg, at = g * a.group * a.k;
+        const uint32_t e = zsk_group_len(a.elements, a.group, g), i0 = (uint32_t)(t % tpg) * ZSK_PLANE_TILE + zh_lane() * 16;
+        if (a.k == 2) zsk_split_xor_lane<2>(a.src + at, x.base + at, a.dst + at, e, i0);
+        else if (a.k == 4) zsk_split_xor_lane<4>(a.src + at, x.base + at, a.dst + at, e, i0);
+        else zsk_split_xor_lane<8>(a.src + at, x.base + at, a.dst + at, e, i0);
+    }
+    zsk_planes_records(a);
+}
+
 // ------------------------------------------------------------------------------------------------ join: planar -> interleaved, by jobs
 // A job: m elements whose planes lie at planar + p * m; output byte j in [h, m * k - t) -- byte j % k of element j / k -- goes to dst[j - h]. h, t < k trim
 // the first and the last element of a range that starts or ends inside one. Without a job table the jobs are the groups of a whole buffer.
@@ -420,6 +457,49 @@ ZH_DEV void zsk_planes_join_delta_body(const ZskJoinArgs& a)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ join with the xor-with-base filter: one launch
+// The plain join on the same jobs, tiles and grids, with the base's bytes XORed in between the join's words and their store. The base's bytes stand at the
+// job's place in the CONTENT -- (g0 + lo) * k for a range's job, g * group * k for a whole buffer's group -- which `dst` does not give (a range's destination
+// is the caller's): content[j], parallel to jobs[j], carries it (ZskJoinJob keeps its layout). Byte j of a job is XORed with base[content + j], the trimmed
+// first and last element and the tails byte by byte at the same offsets; nothing of the base outside the bytes that are stored is read.
+struct ZskJoinXorArgs { ZskJoinArgs j; const uint8_t* base; const uint64_t* content; };      // content [j.nJobs] (jobs NULL: not read)
+template <int K> ZH_DEV void zsk_join_xor_lane(const uint8_t* s, const uint8_t* b, uint8_t* d, uint64_t m, uint32_t h, uint32_t t, uint64_t i0)
+{
+    if (i0 >= m) return;
+    const uint64_t n = m - i0 < 16 ? m - i0 : 16, lo = i0 * K, hi = (i0 + n) * K, end = m * K - t;
+    const uint64_t from = lo < h ? h : lo, to = hi > end ? end : hi;
+    if (n == 16 && from == lo && to == hi) {
+        uint32_t o[4 * K], x[4 * K];
+        zsk_load16<K>(b + lo, x);                      // the base's loads go out with the planes': one wait for both
+        zsk_join16_words<K>(s + i0, m, o);
+#pragma unroll
+        for (int j = 0; j < 4 * K; j++) o[j] ^= x[j];
+        zsk_store16<K>(o, d + (lo - h));
+        return;
+    }
+    for (uint64_t j = from; j < to; j++) d[j - h] = s[(j % K) * m + j / K] ^ b[j];
+}
+ZH_DEV void zsk_planes_join_xor_body(const ZskJoinXorArgs& x)
+{
+    const ZskJoinArgs& a = x.j;
+    const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
+    for (uint64_t t = zh_block(); t < a.tiles; t += zh_nblocks()) {
+        ZskJoinJob job; uint64_t content;
+        if (a.jobs) {
+            uint32_t lo = 0, hi = a.nJobs;                                  // the last job whose tilePrefix <= t
+            while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.jobs[mid].tilePrefix <= t) lo = mid; else hi = mid; }
+            job = a.jobs[lo]; content = x.content[lo];
+        } else {
+            const uint64_t g = t / tpg;
+            job.planar = job.dst = content = g * a.group * a.k; job.m = zsk_group_len(a.elements, a.group, g); job.tilePrefix = g * tpg; job.h = job.t = 0;
+        }
+        const uint64_t i0 = (t - job.tilePrefix) * ZSK_PLANE_TILE + zh_lane() * 16;
+        if (a.k == 2) zsk_join_xor_lane<2>(a.planar + job.planar, x.base + content, a.dst + job.dst, job.m, job.h, job.t, i0);
+        else if (a.k == 4) zsk_join_xor_lane<4>(a.planar + job.planar, x.base + content, a.dst + job.dst, job.m, job.h, job.t, i0);
+        else zsk_join_xor_lane<8>(a.planar + job.planar, x.base + content, a.dst + job.dst, job.m, job.h, job.t, i0);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ seal: the marker behind a stream the records call wrote
 // The records call leaves n plane frames, the table behind them and *streamSize (0: it failed, and so does the typed call). The marker goes where the table
 // starts and the table 24 bytes further on, one entry longer; the two overlap, so the first kernel keeps the stream size and the old entries aside.
@@ -501,11 +581,14 @@ ZH_DEV void zsk_typed_status_body(const ZskTypedStatusArgs& a)
 // planar ranges are elements 0 .. hi - 1 of every plane, and the job gets m = hi and skip = lo -- the tiles inside the skip feed the sums and store nothing.
 // The plane frames are decoded whole either way, so the decode costs what it did; what grows is the copy out of the decode scratch and the join, by the lo
 // elements in front. Whole groups, merged runs, passes and the limit work as without a filter, and with filter 0 the plan is that one field for field.
+// Under the xor-with-base filter the plan is the unfiltered one (no skip: a byte needs its base byte and nothing in front), and `content` gets, per job, the
+// content offset of the job's first element -- where its base bytes stand. With filter 0 or 1 `content` stays empty.
 struct ZskTypedPass { uint32_t q0, q1, job0, job1; uint64_t bytes, tiles; };
 struct ZskTypedPlan {
     std::vector<uint64_t> planar;               // [Q][3]: what the many-ranges call is handed, (offset, length, offset in P)
     std::vector<ZskJoinJob> jobs; std::vector<ZskTypedPass> passes;
     std::vector<uint32_t> owner;                // [R][2]
+    std::vector<uint64_t> content;              // [J] under ZSK_FILTER_XOR_BASE, else empty
     uint64_t pMax = 0;
 };
 // D = dOff of the opened stream; rg = [R][3], checked (zsk_gather_check); limit 0 = ZSK_SCRATCH_DEFAULT
@@ -538,6 +621,7 @@ static inline void zsk_typed_plan(const uint64_t* D, uint32_t k, uint32_t group,
                 job.dst = to + ((g0 + lo) * k + job.h - a); job.tilePrefix = cur.tiles;
                 cur.tiles += zsk_join_tiles(m);
                 out->jobs.push_back(job);
+                if (filter == ZSK_FILTER_XOR_BASE) out->content.push_back((g0 + lo) * k);
                 if (hi - lo == e) {
                     if (merge) out->planar[out->planar.size() - 2] += e * k;
                     else { out->planar.push_back(D[f]); out->planar.push_back(e * k); out->planar.push_back(used); }
@@ -564,4 +648,6 @@ __global__ __launch_bounds__(64) void zhip_seekable_planes_split_delta_kernel(Zs
 __global__ __launch_bounds__(64) void zhip_seekable_delta_sums_kernel(ZskJoinArgs a) { zsk_delta_sums_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_delta_offsets_kernel(ZskJoinArgs a) { zsk_delta_offsets_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_planes_join_delta_kernel(ZskJoinArgs a) { zsk_planes_join_delta_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_planes_split_xor_kernel(ZskPlanesXorArgs a) { zsk_planes_split_xor_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_planes_join_xor_kernel(ZskJoinXorArgs a) { zsk_planes_join_xor_body(a); }
 #endif

@@ -14,7 +14,8 @@
     X(PLANES_SPLIT, planes_split, ZskPlanesArgs) X(PLANES_JOIN, planes_join, ZskJoinArgs) X(SEAL_STASH, seal_stash, ZskSealArgs) X(SEAL, seal, ZskSealArgs) \
     X(TYPED_STATUS, typed_status, ZskTypedStatusArgs) \
     X(PLANES_SPLIT_DELTA, planes_split_delta, ZskPlanesArgs) X(DELTA_SUMS, delta_sums, ZskJoinArgs) X(DELTA_OFFSETS, delta_offsets, ZskJoinArgs) \
-    X(PLANES_JOIN_DELTA, planes_join_delta, ZskJoinArgs)
+    X(PLANES_JOIN_DELTA, planes_join_delta, ZskJoinArgs) \
+    X(PLANES_SPLIT_XOR, planes_split_xor, ZskPlanesXorArgs) X(PLANES_JOIN_XOR, planes_join_xor, ZskJoinXorArgs)
 #define ZSKT_X(id, name, args) ZSKT_K_##id,
 enum ZskTypedKernel { ZSKT_KERNELS(ZSKT_X) ZSKT_K_COUNT };
 #undef ZSKT_X
@@ -34,32 +35,59 @@ static inline uint32_t zsk_tile_grid(int numCU, uint64_t tiles, uint64_t lanes)
 }
 static inline uint64_t zsk_planes_tiles(uint64_t elements, uint32_t group) { return zsk_frame_count(elements, group) * ((group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE); }
 
-static inline int zsk_planes_check(bool pointers, uint64_t size, uint32_t k, uint32_t frameSize, std::string& err, uint32_t filter = ZSK_FILTER_NONE)
+// base: the call has one (the *_base_ calls: filter 4 and nothing else goes through them)
+static inline int zsk_planes_check(bool pointers, uint64_t size, uint32_t k, uint32_t frameSize, std::string& err, uint32_t filter = ZSK_FILTER_NONE, bool base = false)
 {
     if (!pointers) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: bad arguments");
-    if (!zsk_filter_ok(filter)) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: the filter must be 0 (none) or 1 (delta)");
+    if (!zsk_filter_ok(filter) || (filter == ZSK_FILTER_XOR_BASE) != base)
+        return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: the filter must be 0 (none) or 1 (delta); 4 (xor with a base) takes its base through the calls with a base");
     if (!zsk_element_ok(k)) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: the element size must be 2, 4 or 8");
     if (size % k) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: the size must be a multiple of the element size");
     if (frameSize < 1 || frameSize > ZSK_MAX_CONTENT) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "planes: frameSize must be 1 ... 2^30 elements");
     return 0;
 }
-static inline int zsk_typed_compress_check(bool pointers, uint64_t srcSize, uint32_t frameSize, uint32_t k, int flags, std::string& err, uint32_t filter = ZSK_FILTER_NONE)
+static inline int zsk_typed_compress_check(bool pointers, uint64_t srcSize, uint32_t frameSize, uint32_t k, int flags, std::string& err, uint32_t filter = ZSK_FILTER_NONE, bool base = false)
 {
     if (!pointers || (flags & ~ZHIP_SEEKABLE_CHECKSUM)) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "seekable typed compress: bad arguments");
-    if (int rc = zsk_planes_check(true, srcSize, k, frameSize, err, filter)) return rc;
+    if (int rc = zsk_planes_check(true, srcSize, k, frameSize, err, filter, base)) return rc;
     if (zsk_frame_count(srcSize / k, frameSize) * k > ZSK_MAX_PLANE_FRAMES) return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, "seekable typed compress: at most 2^27 - 1 plane frames");
     return 0;
 }
 
-// The whole-buffer kernels on their own: interleaved -> planar (no records) and back
-template <class B> int zsk_planes_split(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst, uint32_t filter = ZSK_FILTER_NONE)
+// what the calls with a base refuse on top: no base, an element size of 1, a base that shares bytes with the output (the output would change the base under
+// the lanes that still have to read it). `bytes` of base, `outBytes` at d_out
+static inline bool zsk_overlap(const void* a, uint64_t an, const void* b, uint64_t bn)
 {
-    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err, filter)) return rc;
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return an && bn && x < y + bn && y < x + an;
+}
+static inline int zsk_base_check(const char* what, const void* d_base, uint64_t bytes, uint32_t k, const void* d_out, uint64_t outBytes, std::string& err)
+{
+    char buf[200];
+    if (!d_base) { snprintf(buf, sizeof buf, "%s: the base is NULL", what); return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, buf); }
+    if (k == 1) { snprintf(buf, sizeof buf, "%s: a base needs an element size of 2, 4 or 8", what); return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, buf); }
+    if (zsk_overlap(d_base, bytes, d_out, outBytes)) { snprintf(buf, sizeof buf, "%s: the base overlaps the output", what); return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, buf); }
+    return 0;
+}
+
+// The whole-buffer kernels on their own: interleaved -> planar (no records) and back. d_base: the *_base_ calls' (filter ZSK_FILTER_XOR_BASE), `size` bytes
+template <class B> int zsk_planes_split(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst, uint32_t filter = ZSK_FILTER_NONE, const void* d_base = nullptr)
+{
+    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err, filter, d_base != nullptr)) return rc;
     if (!size) return 0;
-    ZskPlanesArgs a; memset(&a, 0, sizeof a);
+    ZskPlanesXorArgs x; memset(&x, 0, sizeof x);
+    ZskPlanesArgs& a = x.p;
     a.src = (const uint8_t*)d_src; a.dst = (uint8_t*)d_dst; a.elements = size / k; a.k = k; a.group = frameSize; a.nGroups = (uint32_t)zsk_frame_count(a.elements, frameSize);
-    b.launch_typed(filter == ZSK_FILTER_DELTA ? ZSKT_K_PLANES_SPLIT_DELTA : ZSKT_K_PLANES_SPLIT, zsk_tile_grid(b.numCU, zsk_planes_tiles(a.elements, frameSize), 0), &a);
+    x.base = (const uint8_t*)d_base;
+    const uint32_t grid = zsk_tile_grid(b.numCU, zsk_planes_tiles(a.elements, frameSize), 0);
+    if (filter == ZSK_FILTER_XOR_BASE) b.launch_typed(ZSKT_K_PLANES_SPLIT_XOR, grid, &x);
+    else b.launch_typed(filter == ZSK_FILTER_DELTA ? ZSKT_K_PLANES_SPLIT_DELTA : ZSKT_K_PLANES_SPLIT, grid, &a);
     return b.check();
+}
+template <class B> int zsk_planes_split_base(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, const void* d_base, void* d_dst)
+{
+    if (int rc = zsk_base_check("planes split", d_base, size, k, d_dst, size, b.err)) return rc;
+    return zsk_planes_split(b, ctx, d_src, size, k, frameSize, d_dst, ZSK_FILTER_XOR_BASE, d_base);
 }
 // the join of the handle's filter: the plain kernel, or the delta filter's three launches over tileSums [a.tiles]
 template <class B> void zsk_launch_join(B& b, uint32_t filter, ZskJoinArgs& a, uint64_t nJobs, uint8_t* tileSums)
@@ -71,26 +99,40 @@ template <class B> void zsk_launch_join(B& b, uint32_t filter, ZskJoinArgs& a, u
     b.launch_typed(ZSKT_K_DELTA_OFFSETS, zsk_tile_grid(b.numCU, nJobs, 0), &a);
     b.launch_typed(ZSKT_K_PLANES_JOIN_DELTA, grid, &a);
 }
-template <class B> int zsk_planes_join(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst, uint32_t filter = ZSK_FILTER_NONE)
+// the xor-with-base join: the plain join's grid, one launch. content: the jobs' content offsets on the device (NULL with a.jobs NULL)
+template <class B> void zsk_launch_join_xor(B& b, const ZskJoinArgs& a, const void* d_base, const uint8_t* content)
 {
-    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err, filter)) return rc;
+    ZskJoinXorArgs x; memset(&x, 0, sizeof x);
+    x.j = a; x.base = (const uint8_t*)d_base; x.content = (const uint64_t*)content;
+    b.launch_typed(ZSKT_K_PLANES_JOIN_XOR, zsk_tile_grid(b.numCU, a.tiles, 0), &x);
+}
+template <class B> int zsk_planes_join(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst, uint32_t filter = ZSK_FILTER_NONE, const void* d_base = nullptr)
+{
+    if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err, filter, d_base != nullptr)) return rc;
     if (!size) return 0;
     ZskJoinArgs a; memset(&a, 0, sizeof a);
     a.planar = (const uint8_t*)d_src; a.dst = (uint8_t*)d_dst; a.elements = size / k; a.k = k; a.group = frameSize; a.tiles = zsk_planes_tiles(a.elements, frameSize);
+    if (filter == ZSK_FILTER_XOR_BASE) { zsk_launch_join_xor(b, a, d_base, nullptr); return b.check(); }
     uint8_t* sums = nullptr;
     if (filter == ZSK_FILTER_DELTA) if (int rc = b.reserve_typed(ZSKT_A_TILESUMS, (size_t)a.tiles * 8, &sums)) return rc;
     zsk_launch_join(b, filter, a, zsk_frame_count(a.elements, frameSize), sums);
     return b.check();
 }
 
+template <class B> int zsk_planes_join_base(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, const void* d_base, void* d_dst)
+{
+    if (int rc = zsk_base_check("planes join", d_base, size, k, d_dst, size, b.err)) return rc;
+    return zsk_planes_join(b, ctx, d_src, size, k, frameSize, d_dst, ZSK_FILTER_XOR_BASE, d_base);
+}
+
 // Typed compress: the split kernel writes the planar staging buffer and the plane frames' records; the records call compresses them as they are; the seal
 // puts the marker in. The records call is handed the capacity less the marker and its entry, so a stream that does not fit fails there (70) with nothing written
 template <class B> int zsk_typed_compress(B& b, bool ctx, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t k, int flags, void* d_dst, uint64_t dstCapacity,
-                                          uint64_t* d_streamSize, int32_t* d_status, uint32_t filter = ZSK_FILTER_NONE)
+                                          uint64_t* d_streamSize, int32_t* d_status, uint32_t filter = ZSK_FILTER_NONE, const void* d_base = nullptr)
 {
-    if (k == 1 && filter != ZSK_FILTER_NONE) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, zsk_filter_ok(filter) ? "seekable typed compress: a filter needs an element size of 2, 4 or 8" : "seekable typed compress: the filter must be 0 (none) or 1 (delta)");
+    if (k == 1 && filter != ZSK_FILTER_NONE) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, zsk_filter_ok(filter) && filter != ZSK_FILTER_XOR_BASE ? "seekable typed compress: a filter needs an element size of 2, 4 or 8" : "seekable typed compress: the filter must be 0 (none) or 1 (delta)");
     if (k == 1) return zsk_compress(b, ctx, d_src, srcSize, frameSize, flags, d_dst, dstCapacity, d_streamSize, d_status);
-    if (int rc = zsk_typed_compress_check(ctx && d_streamSize && d_status && (!srcSize || d_src), srcSize, frameSize, k, flags, b.err, filter)) return rc;
+    if (int rc = zsk_typed_compress_check(ctx && d_streamSize && d_status && (!srcSize || d_src), srcSize, frameSize, k, flags, b.err, filter, d_base != nullptr)) return rc;
     const int checksum = flags & ZHIP_SEEKABLE_CHECKSUM ? 1 : 0;
     const uint64_t elements = srcSize / k, nGroups = zsk_frame_count(elements, frameSize), n = nGroups * k;
     uint8_t* staging = nullptr; uint8_t* records = nullptr; uint8_t* stash = nullptr;
@@ -98,9 +140,13 @@ template <class B> int zsk_typed_compress(B& b, bool ctx, const void* d_src, uin
     if (n) if (int rc = b.reserve_typed(ZSKT_A_RECORDS, (size_t)n * 16, &records)) return rc;
     if (int rc = b.reserve_typed(ZSKT_A_STASH, (size_t)zsk_seal_stash_bytes(n, checksum), &stash)) return rc;
     if (n) {
-        ZskPlanesArgs a; memset(&a, 0, sizeof a);
+        ZskPlanesXorArgs x; memset(&x, 0, sizeof x);
+        ZskPlanesArgs& a = x.p;
         a.src = (const uint8_t*)d_src; a.dst = staging; a.elements = elements; a.k = k; a.group = frameSize; a.nGroups = (uint32_t)nGroups; a.records = (uint64_t*)records;
-        b.launch_typed(filter == ZSK_FILTER_DELTA ? ZSKT_K_PLANES_SPLIT_DELTA : ZSKT_K_PLANES_SPLIT, zsk_tile_grid(b.numCU, zsk_planes_tiles(elements, frameSize), n), &a);
+        x.base = (const uint8_t*)d_base;
+        const uint32_t grid = zsk_tile_grid(b.numCU, zsk_planes_tiles(elements, frameSize), n);
+        if (filter == ZSK_FILTER_XOR_BASE) b.launch_typed(ZSKT_K_PLANES_SPLIT_XOR, grid, &x);
+        else b.launch_typed(filter == ZSK_FILTER_DELTA ? ZSKT_K_PLANES_SPLIT_DELTA : ZSKT_K_PLANES_SPLIT, grid, &a);
         if (int rc = b.check()) return rc;
     }
     const uint64_t extra = ZSK_MARKER + zsk_entry_size(checksum);
@@ -113,6 +159,14 @@ template <class B> int zsk_typed_compress(B& b, bool ctx, const void* d_src, uin
     b.launch_typed(ZSKT_K_SEAL_STASH, grid, &s);
     b.launch_typed(ZSKT_K_SEAL, grid, &s);
     return b.check();
+}
+
+// the same with the xor-with-base filter: the base is srcSize bytes and may not share a byte with the output
+template <class B> int zsk_typed_compress_base(B& b, bool ctx, const void* d_src, uint64_t srcSize, uint32_t frameSize, uint32_t k, const void* d_base, int flags, void* d_dst,
+                                               uint64_t dstCapacity, uint64_t* d_streamSize, int32_t* d_status)
+{
+    if (int rc = zsk_base_check("seekable typed compress", d_base, srcSize, k, d_dst, dstCapacity, b.err)) return rc;
+    return zsk_typed_compress(b, ctx, d_src, srcSize, frameSize, k, flags, d_dst, dstCapacity, d_streamSize, d_status, ZSK_FILTER_XOR_BASE, d_base);
 }
 
 // Behind zsk_open: a last entry of (24, 0) is looked at -- the one extra copy, and only then. No tag: a plain stream. A tag and the shape it promises:
@@ -135,21 +189,25 @@ template <class B> int zsk_typed_probe(B& b, ZskTypedOpened* h, int* zerr, size_
 }
 
 // the tables a typed read uploads: the join jobs of every pass, the user ranges' planar ranges, every planar range's place in the status area
-struct ZskTypedReadLayout { size_t oJobs, oOwner, oPairAt, tableBytes; };
-static inline ZskTypedReadLayout zsk_typed_read_layout(size_t J, size_t R, size_t Q)
+// (C: the jobs' content offsets, the xor-with-base join's, J of them or none -- behind the rest, so that without them the layout is what it was)
+struct ZskTypedReadLayout { size_t oJobs, oOwner, oPairAt, oContent, tableBytes; };
+static inline ZskTypedReadLayout zsk_typed_read_layout(size_t J, size_t R, size_t Q, size_t C = 0)
 {
     ZskTypedReadLayout l;
-    l.oJobs = 0; l.oOwner = zsk_up16(J * sizeof(ZskJoinJob)); l.oPairAt = l.oOwner + zsk_up16(R * 8); l.tableBytes = l.oPairAt + zsk_up16(Q * 4);
+    l.oJobs = 0; l.oOwner = zsk_up16(J * sizeof(ZskJoinJob)); l.oPairAt = l.oOwner + zsk_up16(R * 8); l.oContent = l.oPairAt + zsk_up16(Q * 4); l.tableBytes = l.oContent + zsk_up16(C * 8);
     return l;
 }
 
 // R user ranges in element order: per pass of the plan the many-ranges call into the planar buffer and the join kernel (the handle's filter picks it: under
 // delta the three launches of zsk_launch_join); then the status reducer.
-// stats (where given) receives the sums over the passes' many-ranges calls, `passes` counting the typed passes
+// stats (where given) receives the sums over the passes' many-ranges calls, `passes` counting the typed passes.
+// d_base: zsk_typed_ranges_base's, the base of an xor-with-base stream (checked there); such a stream is not read without one
 template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h, const uint64_t* rg, size_t R, void* d_dst, uint64_t dstCapacity, int32_t* d_status,
-                                        zhip_seekable_gather_stats* stats, size_t* bad)
+                                        zhip_seekable_gather_stats* stats, size_t* bad, const void* d_base = nullptr)
 {
     if (h && h->elementSize == 1) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, "seekable typed ranges: the stream is a plain one (no byte planes)");
+    if (h && h->filter == ZSK_FILTER_XOR_BASE && !d_base)
+        return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, "seekable typed ranges: the stream's filter is xor with a base -- its elements need the base (the typed ranges call with a base)");
     bool any = false;
     if (int rc = zsk_ranges_check(ctx && h && d_status, rg, R, h ? h->contentSize : 0, d_dst, dstCapacity, bad, &any, b.err)) return rc;
     if (stats) memset(stats, 0, sizeof *stats);
@@ -158,7 +216,7 @@ template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h,
     ZskTypedPlan plan;
     zsk_typed_plan(h->dOff.data(), h->elementSize, h->groupElements, rg, R, h->scratchLimit, &plan, h->filter);
     const size_t J = plan.jobs.size(), Q = plan.planar.size() / 3, nPass = plan.passes.size();
-    const ZskTypedReadLayout l = zsk_typed_read_layout(J, R, Q);
+    const ZskTypedReadLayout l = zsk_typed_read_layout(J, R, Q, plan.content.size());
     std::vector<uint32_t> pairAt(Q);
     size_t statusInts = 0;
     for (const ZskTypedPass& p : plan.passes) { for (uint32_t q = p.q0; q < p.q1; q++) pairAt[q] = (uint32_t)(statusInts + 2 + 2 * (q - p.q0)); statusInts += 2 + 2 * (size_t)(p.q1 - p.q0); }
@@ -176,6 +234,7 @@ template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h,
     memcpy(pin + l.oJobs, plan.jobs.data(), J * sizeof(ZskJoinJob));
     memcpy(pin + l.oOwner, plan.owner.data(), R * 8);
     memcpy(pin + l.oPairAt, pairAt.data(), Q * 4);
+    memcpy(pin + l.oContent, plan.content.data(), plan.content.size() * 8);
     if (int rc = b.copy(t, pin, l.tableBytes, ZSK_COPY_FROM_PIN)) return rc;
 
     size_t at = 0;
@@ -187,11 +246,25 @@ template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h,
         if (stats) { stats->items += one.items; stats->inPlace += one.inPlace; stats->scratchBytes += one.scratchBytes; stats->copyJobs += one.copyJobs; stats->passes++; }
         ZskJoinArgs a; memset(&a, 0, sizeof a);
         a.planar = P; a.dst = (uint8_t*)d_dst; a.jobs = (const ZskJoinJob*)(t + l.oJobs) + ps.job0; a.nJobs = ps.job1 - ps.job0; a.tiles = ps.tiles; a.k = h->elementSize; a.group = h->groupElements;
-        zsk_launch_join(b, h->filter, a, a.nJobs, sums);
+        if (h->filter == ZSK_FILTER_XOR_BASE) zsk_launch_join_xor(b, a, d_base, t + l.oContent + 8 * (size_t)ps.job0);
+        else zsk_launch_join(b, h->filter, a, a.nJobs, sums);
         if (int rc = b.check()) return rc;
     }
     ZskTypedStatusArgs s; memset(&s, 0, sizeof s);
     s.owner = (const uint32_t*)(t + l.oOwner); s.pairAt = (const uint32_t*)(t + l.oPairAt); s.status = (const int32_t*)st; s.nRanges = (uint32_t)R; s.outStatus = d_status;
     b.launch_typed(ZSKT_K_TYPED_STATUS, zsk_lane_grid(b.numCU, R), &s);
     return b.check();
+}
+
+// The typed read of an xor-with-base stream: the base is the stream's element content, baseSize bytes of it, and shares no byte with the output. The stream
+// does not name its base: another tensor of the right size gives wrong elements with status 0
+template <class B> int zsk_typed_ranges_base(B& b, bool ctx, const ZskTypedOpened* h, const void* d_base, uint64_t baseSize, const uint64_t* rg, size_t R, void* d_dst, uint64_t dstCapacity,
+                                             int32_t* d_status, zhip_seekable_gather_stats* stats, size_t* bad)
+{
+    if (!ctx || !h) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, "seekable typed ranges: bad arguments");
+    if (h->elementSize == 1) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, "seekable typed ranges: the stream is a plain one (no byte planes)");
+    if (h->filter != ZSK_FILTER_XOR_BASE) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, "seekable typed ranges: the stream's filter is not xor with a base -- it is read without one");
+    if (baseSize != h->contentSize && d_base) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, "seekable typed ranges: the base must have the size of the stream's content");
+    if (int rc = zsk_base_check("seekable typed ranges", d_base, baseSize, h->elementSize, d_dst, dstCapacity, b.err)) return rc;
+    return zsk_typed_ranges(b, ctx, h, rg, R, d_dst, dstCapacity, d_status, stats, bad, d_base);
 }

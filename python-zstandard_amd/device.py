@@ -21,6 +21,27 @@ def _filter_code(filter):
     raise ZstdError("filter must be None or \"delta\"")
 
 
+def _base_filter(filter, base):
+    """filter and base of a typed call -> True where the call is the xor-with-base one: ``base=`` alone selects it, "xor_base" is its name"""
+    if base is None:
+        if filter == "xor_base":
+            raise ZstdError("filter \"xor_base\" needs base=, the tensor to XOR with")
+        return False
+    if filter not in (None, "xor_base"):
+        raise ZstdError("a base goes with filter \"xor_base\" (or no filter argument), not with %r" % (filter,))
+    return True
+
+
+def _base_bytes(base, like, nbytes, what):
+    """base as the uint8 view the calls take: a contiguous CUDA tensor on like's device, nbytes long"""
+    if not (isinstance(base, torch.Tensor) and base.is_cuda and base.is_contiguous() and base.device == like.device):
+        raise ZstdError("%s: base must be a contiguous CUDA tensor on the source's device" % what)
+    raw = base.view(torch.uint8).reshape(-1)
+    if raw.numel() != nbytes:
+        raise ZstdError("%s: the base has %d bytes, the tensor %d" % (what, raw.numel(), nbytes))
+    return raw
+
+
 class DeviceBatchContext:
     """Owns the native context (scratch, dictionary tables, kernel timers) for one GPU / one stream."""
 
@@ -172,7 +193,7 @@ class DeviceBatchContext:
         """waves of the entropy kernel resident on this device"""
         return int(self.L.zhip_ctx_entropy_grid(self.ctx))
 
-    def seekable_compress(self, src, frame_size=131072, checksum=False, stream=None, element_size=1, filter=None):
+    def seekable_compress(self, src, frame_size=131072, checksum=False, stream=None, element_size=1, filter=None, base=None):
         """src (a uint8 CUDA tensor) as ONE zstd seekable stream: frames of frame_size bytes of it, compressed as a batch with this context's
         parameters, back to back, then the seek table (checksum: with the low 32 bits of XXH64 of every frame's content). Returns a uint8 CUDA
         tensor of exactly the stream's size -- a view of a zhip_seekable_bound-sized allocation. Waits for the size. Any zstd decoder decompresses
@@ -185,16 +206,23 @@ class DeviceBatchContext:
         filter "delta" (typed streams only): for INTEGER tensors whose neighbours are close -- offsets, sorted ids, timestamps, counters, running sums. Per group
         the planes are those of d[0] = x[0], d[i] = x[i] - x[i - 1] mod 2^(8 * element_size), the subtraction fused into the split kernel; 13-34 % smaller
         streams on such data, nothing gained on floats. The marker names the filter: SeekableStream reads the elements back (``SeekableStream.filter``),
-        other decoders see the filtered planar bytes (planes_to_elements(..., filter="delta"))."""
+        other decoders see the filtered planar bytes (planes_to_elements(..., filter="delta")).
+        base (typed streams only; ``base=`` alone selects the filter, whose name is "xor_base"): for VERSIONS of one tensor -- the next checkpoint, a fine-tune
+        beside its base model, an optimizer state some steps later. base is a contiguous CUDA tensor of src's size, the earlier version, already in HBM; the
+        planes are those of src XOR base, bytewise, fused into the split kernel. Versions differ in the low mantissa bits and almost nowhere else, so the high
+        planes become runs of zeros: bf16 streams 2-12 x smaller than the unfiltered typed stream, fp32 1.3-1.8 x (README). THE STREAM DOES NOT NAME ITS BASE:
+        SeekableStream(..., base=) reads the elements back, and with another base of the right size it returns wrong elements and no error. Other decoders see
+        the filtered planar bytes (planes_to_elements(..., base=)). A base with filter="delta", or "xor_base" without a base, raises ZstdError."""
         self._ensure_cparams()
         self._check(src, torch.uint8)
         s = stream if stream is not None else torch.cuda.current_stream()
         flags = _lib.SEEKABLE_CHECKSUM if checksum else 0
-        code = _filter_code(filter)
-        if code and element_size == 1:
+        with_base = _base_filter(filter, base)
+        code = 0 if with_base else _filter_code(filter)
+        if (code or with_base) and element_size == 1:
             raise ZstdError("seekable compress: a filter needs an element_size of 2, 4 or 8")
         if element_size != 1:
-            return self._seekable_compress_typed(src, frame_size, element_size, flags, s, code)
+            return self._seekable_compress_typed(src, frame_size, element_size, flags, s, code, base if with_base else None)
         bound = self.L.zhip_seekable_bound(src.numel(), frame_size, flags)
         if not bound:
             raise ZstdError("seekable compress: frame_size must be 1 ... 2^30 and give at most 2^27 frames")
@@ -214,7 +242,7 @@ class DeviceBatchContext:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return dst[:int(size[0])]
 
-    def _seekable_compress_typed(self, src, frame_size, element_size, flags, s, filter_code=0):
+    def _seekable_compress_typed(self, src, frame_size, element_size, flags, s, filter_code=0, base=None):
         if element_size not in (2, 4, 8):
             raise ZstdError("seekable compress: element_size must be 1, 2, 4 or 8")
         if src.numel() % element_size:
@@ -222,12 +250,18 @@ class DeviceBatchContext:
         bound = self.L.zhip_seekable_typed_bound(src.numel(), frame_size, element_size, flags) if 0 < frame_size <= 1 << 30 else 0
         if not bound:
             raise ZstdError("seekable compress: frame_size must be 1 ... 2^30 elements and give at most 2^27 - 1 plane frames")
+        if base is not None:
+            base = _base_bytes(base, src, src.numel(), "seekable compress")
         with torch.cuda.stream(s):
             dst = torch.empty(bound, dtype=torch.uint8, device=src.device)
             size = torch.zeros(1, dtype=torch.int64, device=src.device)
             status = torch.zeros(2, dtype=torch.int32, device=src.device)
-        rc = self.L.zhip_seekable_compress_typed_filter_device(self.ctx, src.data_ptr() if src.numel() else None, src.numel(), frame_size, element_size, filter_code, flags,
-                                                               dst.data_ptr(), bound, size.data_ptr(), status.data_ptr(), s.cuda_stream)
+        if base is not None:
+            rc = self.L.zhip_seekable_compress_typed_base_device(self.ctx, src.data_ptr() if src.numel() else None, src.numel(), frame_size, element_size, base.data_ptr(), flags,
+                                                                 dst.data_ptr(), bound, size.data_ptr(), status.data_ptr(), s.cuda_stream)
+        else:
+            rc = self.L.zhip_seekable_compress_typed_filter_device(self.ctx, src.data_ptr() if src.numel() else None, src.numel(), frame_size, element_size, filter_code, flags,
+                                                                   dst.data_ptr(), bound, size.data_ptr(), status.data_ptr(), s.cuda_stream)
         if rc:
             raise ZstdError("seekable compress failed: %s" % _lib.last_error())
         err = _lib.Error()
@@ -238,29 +272,39 @@ class DeviceBatchContext:
             raise ZstdError("HIP backend failure: %s" % _lib.last_error())
         return dst[:int(size[0])]
 
-    def _planes(self, call, src, frame_size, element_size, out, stream, filter=None):
+    def _planes(self, call, src, frame_size, element_size, out, stream, filter=None, base=None):
         assert src.is_cuda and src.is_contiguous(), "expected a contiguous CUDA tensor"
         raw = src.view(torch.uint8).reshape(-1)
+        with_base = _base_filter(filter, base)
+        if with_base:
+            base = _base_bytes(base, src, raw.numel(), "planes")
         s = stream if stream is not None else torch.cuda.current_stream()
         if out is None:
             with torch.cuda.stream(s):
                 out = torch.empty(raw.numel(), dtype=torch.uint8, device=src.device)
         self._check(out, torch.uint8)
         assert out.numel() >= raw.numel(), "out is shorter than the source"
-        if call(self.ctx, raw.data_ptr() if raw.numel() else None, raw.numel(), element_size, frame_size, _filter_code(filter), out.data_ptr() if raw.numel() else None, s.cuda_stream):
+        if with_base:
+            call = self.L.zhip_planes_split_base_device if call is self.L.zhip_planes_split_filter_device else self.L.zhip_planes_join_base_device
+            rc = call(self.ctx, raw.data_ptr() if raw.numel() else None, raw.numel(), element_size, frame_size, base.data_ptr(), out.data_ptr() if raw.numel() else None, s.cuda_stream)
+        else:
+            rc = call(self.ctx, raw.data_ptr() if raw.numel() else None, raw.numel(), element_size, frame_size, _filter_code(filter), out.data_ptr() if raw.numel() else None, s.cuda_stream)
+        if rc:
             raise ZstdError("planes: %s" % _lib.last_error())
         return out[:raw.numel()]
 
-    def planes_split(self, src, frame_size, element_size=None, out=None, stream=None, filter=None):
+    def planes_split(self, src, frame_size, element_size=None, out=None, stream=None, filter=None, base=None):
         """the bytes of src (any contiguous CUDA tensor; element_size None: its dtype's) in the PLANAR order of a typed seekable stream, as a uint8 tensor: groups
         of frame_size elements, group g's plane p -- byte p of every element -- at g * element_size * frame_size + p * (the group's elements). filter "delta": the planes of the
-        group's differences (seekable_compress), subtracted in the same kernel. Asynchronous."""
-        return self._planes(self.L.zhip_planes_split_filter_device, src, frame_size, src.element_size() if element_size is None else element_size, out, stream, filter)
+        group's differences (seekable_compress), subtracted in the same kernel. base (a contiguous CUDA tensor of src's size; selects filter "xor_base"): the
+        planes of src XOR base, in one kernel; base and out must not overlap. Asynchronous."""
+        return self._planes(self.L.zhip_planes_split_filter_device, src, frame_size, src.element_size() if element_size is None else element_size, out, stream, filter, base)
 
-    def planes_join(self, planar, frame_size, element_size, out=None, stream=None, filter=None):
+    def planes_join(self, planar, frame_size, element_size, out=None, stream=None, filter=None, base=None):
         """planes_split's inverse under the same filter: planar bytes -> the elements' bytes, as a uint8 tensor (view it as the dtype). Under "delta" the
-        prefix sum of every group, three launches and 8 bytes of context memory per 1 024 elements. Asynchronous."""
-        return self._planes(self.L.zhip_planes_join_filter_device, planar, frame_size, element_size, out, stream, filter)
+        prefix sum of every group, three launches and 8 bytes of context memory per 1 024 elements. With base (the tensor the split was given -- another one
+        gives wrong elements, no error): the joined bytes XOR base, in one kernel. Asynchronous."""
+        return self._planes(self.L.zhip_planes_join_filter_device, planar, frame_size, element_size, out, stream, filter, base)
 
     def _records_table(self, src, records, max_content_bytes, max_record_bytes, s, what="seekable compress"):
         """records as seekable_compress_records takes them -> (the (n, 2) int64 CUDA table, n, max_content_bytes, max_record_bytes)"""
@@ -416,24 +460,24 @@ class DeviceBatchContext:
         return self.L.zhip_kernel_name(direction).decode()
 
 
-def planes_split(src, frame_size, element_size=None, ctx=None, out=None, stream=None, filter=None):
+def planes_split(src, frame_size, element_size=None, ctx=None, out=None, stream=None, filter=None, base=None):
     """DeviceBatchContext.planes_split on `ctx`, or on a context of its own (then it waits)"""
     if ctx is not None:
-        return ctx.planes_split(src, frame_size, element_size, out, stream, filter)
+        return ctx.planes_split(src, frame_size, element_size, out, stream, filter, base)
     with_ctx = DeviceBatchContext()
     try:
-        return with_ctx.planes_split(src, frame_size, element_size, out, stream, filter)
+        return with_ctx.planes_split(src, frame_size, element_size, out, stream, filter, base)
     finally:
         with_ctx.close()
 
 
-def planes_join(planar, frame_size, element_size, ctx=None, out=None, stream=None, filter=None):
+def planes_join(planar, frame_size, element_size, ctx=None, out=None, stream=None, filter=None, base=None):
     """DeviceBatchContext.planes_join on `ctx`, or on a context of its own (then it waits)"""
     if ctx is not None:
-        return ctx.planes_join(planar, frame_size, element_size, out, stream, filter)
+        return ctx.planes_join(planar, frame_size, element_size, out, stream, filter, base)
     with_ctx = DeviceBatchContext()
     try:
-        return with_ctx.planes_join(planar, frame_size, element_size, out, stream, filter)
+        return with_ctx.planes_join(planar, frame_size, element_size, out, stream, filter, base)
     finally:
         with_ctx.close()
 
@@ -447,12 +491,16 @@ class SeekableStream:
     filter -- offsets and lengths count the tensor's bytes; under "delta" a group read in part is summed from its first element. ``read_records`` and
     ``frame_offsets`` stay raw: they name the plane frames. The edit family raises ValueError on a typed stream (moving plane frames breaks the groups).
     ``raw=True`` opens a typed stream as the plain stream it also is: every call then sees its planar content -- under a filter the filtered one --, the edit family included.
+    A stream written with ``seekable_compress(..., base=)`` has ``filter == "xor_base"``: ``read`` / ``read_ranges`` return elements when ``base=`` -- the
+    tensor it was compressed against, kept alive and unchanged while this object is open -- was given, and raise ZstdError when not (``raw=True`` needs none).
+    THE STREAM DOES NOT NAME ITS BASE: with another tensor of the right size the reads return wrong elements and no error. Only the base's bytes at the
+    offsets a read covers are read; the base must not overlap a read's `out`.
 
     ctx: the DeviceBatchContext that decodes (its dictionary, format and window limit apply); stream_tensor: the whole stream, a uint8 CUDA tensor,
     kept alive and unchanged while this object is open. Opening reads and checks the seek table (it waits); a damaged table raises ZstdError."""
 
-    def __init__(self, ctx, stream_tensor, stream=None, scratch_limit=None, raw=False):
-        """scratch_limit: see set_scratch_limit; raw: see the class"""
+    def __init__(self, ctx, stream_tensor, stream=None, scratch_limit=None, raw=False, base=None):
+        """scratch_limit: see set_scratch_limit; raw, base: see the class"""
         DeviceBatchContext._check(stream_tensor, torch.uint8)
         self.ctx, self.tensor, self.handle = ctx, stream_tensor, None
         s = stream if stream is not None else torch.cuda.current_stream()
@@ -468,7 +516,17 @@ class SeekableStream:
         typed = not raw and ctx.L.zhip_seekable_element_size(h) != 1
         self.element_size = int(ctx.L.zhip_seekable_element_size(h)) if typed else 1
         self.group_elements = int(ctx.L.zhip_seekable_group_elements(h)) if typed else 0
-        self.filter = "delta" if typed and ctx.L.zhip_seekable_filter(h) == 1 else None
+        self.filter = {1: "delta", 4: "xor_base"}.get(int(ctx.L.zhip_seekable_filter(h))) if typed else None
+        self.base = None
+        if base is not None and self.filter == "xor_base":
+            try:
+                self.base = _base_bytes(base, stream_tensor, self.content_size, "seekable stream")
+            except ZstdError:
+                self.close()
+                raise
+        elif base is not None and not raw:
+            self.close()
+            raise ZstdError("seekable stream: base= goes with a stream written against a base (filter \"xor_base\"), this one's filter is %r" % (self.filter,))
         self.last_gather_stats = None
         self._frame_offsets = None
         if scratch_limit is not None:
@@ -558,8 +616,14 @@ class SeekableStream:
         DeviceBatchContext._check(out, torch.uint8)
         L = self.ctx.L
         stats = _lib.SeekableGatherStats()
-        call = L.zhip_seekable_decompress_ranges_device if self.element_size == 1 else L.zhip_seekable_decompress_typed_ranges_device
-        rc = call(self.ctx.ctx, self.handle, table.ctypes.data, n, out.data_ptr(), out.numel(), status.data_ptr(), C.byref(stats), s.cuda_stream)
+        if self.filter == "xor_base":
+            if self.base is None:
+                raise ZstdError("seekable read: the stream was written against a base (filter \"xor_base\") -- open it with base= to read elements, or raw=True for its planar bytes")
+            rc = L.zhip_seekable_decompress_typed_ranges_base_device(self.ctx.ctx, self.handle, self.base.data_ptr(), self.base.numel(), table.ctypes.data, n, out.data_ptr(), out.numel(),
+                                                                     status.data_ptr(), C.byref(stats), s.cuda_stream)
+        else:
+            call = L.zhip_seekable_decompress_ranges_device if self.element_size == 1 else L.zhip_seekable_decompress_typed_ranges_device
+            rc = call(self.ctx.ctx, self.handle, table.ctypes.data, n, out.data_ptr(), out.numel(), status.data_ptr(), C.byref(stats), s.cuda_stream)
         if rc:
             raise ZstdError("seekable read failed: %s" % _lib.last_error())
         self.last_gather_stats = {k: int(getattr(stats, k)) for k, _ in stats._fields_}

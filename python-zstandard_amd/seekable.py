@@ -10,7 +10,13 @@ returns the planar bytes, which ``planes_to_elements`` puts back in order (``ele
 
 ``filter="delta"`` (with an element_size) is for INTEGER tensors whose neighbours are close -- offsets, sorted ids, timestamps, counters, running sums: per
 group the planes are those of the differences of neighbouring elements mod 2^(8 * element_size), 13-34 % smaller streams on such data (floats gain nothing).
-The marker names the filter, so the readers return the elements as before; ``elements_to_planes`` / ``planes_to_elements`` take the same ``filter``."""
+The marker names the filter, so the readers return the elements as before; ``elements_to_planes`` / ``planes_to_elements`` take the same ``filter``.
+
+``base=`` (bytes of the data's size, with an element_size; the filter's name is "xor_base") is for VERSIONS of one tensor -- the next checkpoint, a fine-tune
+beside its base model: the planes are those of data XOR base, bytewise, and since versions differ in the low mantissa bits and almost nowhere else the high
+planes become runs of zeros (bf16 streams 2-12 x smaller than without, fp32 1.3-1.8 x). THE STREAM DOES NOT NAME ITS BASE: ``decompress`` and
+``decompress_ranges`` need the same ``base=`` (without one they raise ZstdError), and with other bytes of the right size they return wrong elements and no
+error. ``elements_to_planes`` / ``planes_to_elements`` take ``base=`` too."""
 import torch
 
 from .backend_hip import ZstdError
@@ -24,21 +30,40 @@ def _to_device(data):
     return torch.frombuffer(bytearray(raw), dtype=torch.uint8).cuda()
 
 
-def _filter_code(filter):
+def _filter_code(filter, base=None):
+    """0: none, 1: delta, 4: xor with `base` (base= alone selects it, "xor_base" is its name)"""
+    if base is not None:
+        if filter not in (None, "xor_base"):
+            raise ValueError("a base goes with filter \"xor_base\" (or no filter argument)")
+        return 4
+    if filter == "xor_base":
+        raise ValueError("filter \"xor_base\" needs base=")
     if filter not in (None, "delta"):
         raise ValueError("filter must be None or \"delta\"")
     return 1 if filter == "delta" else 0
 
 
-def elements_to_planes(data, element_size, frame_size, filter=None):
+def _xor_base(a, base):
+    import numpy as np
+    b = np.frombuffer(bytes(base), dtype=np.uint8)
+    if b.size != a.size:
+        raise ValueError("the base has %d bytes, the data %d" % (b.size, a.size))
+    return a ^ b
+
+
+def elements_to_planes(data, element_size, frame_size, filter=None, base=None):
     """bytes of elements -> the planar content of the typed stream ``compress(data, frame_size=frame_size, element_size=element_size, filter=filter)`` writes:
     per group of frame_size elements, byte 0 of every element, then byte 1 of every element, ... -- under filter="delta" of the group's differences
-    d[0] = x[0], d[i] = x[i] - x[i - 1] mod 2^(8 * element_size), the elements read as unsigned little-endian integers. Returns bytes."""
+    d[0] = x[0], d[i] = x[i] - x[i - 1] mod 2^(8 * element_size), the elements read as unsigned little-endian integers; with base (bytes of data's size; the
+    filter "xor_base") of data XOR base. Returns bytes."""
     import numpy as np
     a = np.frombuffer(bytes(data), dtype=np.uint8)
     if element_size not in (2, 4, 8) or a.size % element_size or frame_size < 1:
         raise ValueError("element_size must be 2, 4 or 8, the data whole elements and frame_size at least 1")
-    delta = _filter_code(filter)
+    code = _filter_code(filter, base)
+    delta = code == 1
+    if code == 4:
+        a = _xor_base(a, base)
     out, step = np.empty_like(a), frame_size * element_size
     for at in range(0, a.size, step):
         g = a[at:at + step]
@@ -49,14 +74,16 @@ def elements_to_planes(data, element_size, frame_size, filter=None):
     return out.tobytes()
 
 
-def planes_to_elements(raw, element_size, frame_size, filter=None):
+def planes_to_elements(raw, element_size, frame_size, filter=None, base=None):
     """the planar content of a typed stream, as any zstd decoder returns it (``zstd -d``, ``SeekableStream(..., raw=True).read()``), -> the elements' bytes
-    (filter: the stream's, ``SeekableStream.filter`` -- under "delta" every group's inclusive prefix sum mod 2^(8 * element_size))"""
+    (filter: the stream's, ``SeekableStream.filter`` -- under "delta" every group's inclusive prefix sum mod 2^(8 * element_size); a stream whose filter is
+    "xor_base" needs base=, the bytes it was compressed against -- other bytes of that size give wrong elements and no error)"""
     import numpy as np
     a = np.frombuffer(bytes(raw), dtype=np.uint8)
     if element_size not in (2, 4, 8) or a.size % element_size or frame_size < 1:
         raise ValueError("element_size must be 2, 4 or 8, the data whole elements and frame_size at least 1")
-    delta = _filter_code(filter)
+    code = _filter_code(filter, base)
+    delta = code == 1
     out, step = np.empty_like(a), frame_size * element_size
     for at in range(0, a.size, step):
         g = a[at:at + step]
@@ -65,30 +92,36 @@ def planes_to_elements(raw, element_size, frame_size, filter=None):
             d = e.view("<u%d" % element_size)
             e = np.cumsum(d, dtype=d.dtype).view(np.uint8)
         out[at:at + g.size] = e
+    if code == 4:
+        out = _xor_base(out, base)
     return out.tobytes()
 
 
-def compress(data, level=3, frame_size=131072, checksum=False, match_finder="libzstd", element_size=1, filter=None, **ctx_kw):
+def compress(data, level=3, frame_size=131072, checksum=False, match_finder="libzstd", element_size=1, filter=None, base=None, **ctx_kw):
     """data -> a seekable stream (bytes). match_finder: "libzstd" (frames byte for byte libzstd's) or "wave" (DeviceBatchContext.set_match_finder: valid zstd,
     not libzstd's bytes; frame_size at most 131 072) or "none" (no match search: every frame is libzstd's literals-only frame of its content, for NUMERIC
     TENSORS -- with element_size 2, 4 or 8 the fastest compress path, and streams the size of level 3's or up to 13 % smaller on float data; "on data with real
     repetition they lose badly: the int64 sums here, and any text", 1.9 x on int64 running sums; frame_size at most 131 072 bytes of a plane) or "auto" ("none" or "libzstd" chosen per frame by a classify kernel -- per PLANE frame of a typed stream, whose planes want different finders: every frame is byte for byte one of the two; any frame_size, a frame above 131 072 bytes goes to the search). element_size 2, 4 or 8: a typed stream -- data is elements of that many bytes, frame_size counts the
-    elements of a group (see the module); filter None or "delta": the filter of a typed stream (see the module; with element_size 1 a ZstdError). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
+    elements of a group (see the module); filter None or "delta": the filter of a typed stream (see the module; with element_size 1 a ZstdError); base: bytes of data's size, an earlier version of the tensor -- the planes are those of data XOR base (see the module: the readers need the same base, the stream does not name it). ctx_kw: what DeviceBatchContext takes (dict_data, write_checksum, window_log, ...). Raises ZstdError."""
     ctx = DeviceBatchContext(level=level, match_finder=match_finder, **ctx_kw)
     try:
-        return ctx.seekable_compress(_to_device(data), frame_size=frame_size, checksum=checksum, element_size=element_size, filter=filter).cpu().numpy().tobytes()
+        if base is not None and len(base) != len(data):
+            raise ZstdError("seekable compress: the base has %d bytes, the data %d" % (len(base), len(data)))
+        return ctx.seekable_compress(_to_device(data), frame_size=frame_size, checksum=checksum, element_size=element_size, filter=filter,
+                                     base=None if base is None else _to_device(base)).cpu().numpy().tobytes()
     finally:
         ctx.close()
 
 
-def decompress(data, offset=0, length=None, **ctx_kw):
-    """content bytes [offset, offset + length) of a seekable stream (length None: to the end); of a typed stream, the elements' bytes. Raises ZstdError for
-    a stream without a valid seek table, a range outside the content, or a frame that fails."""
+def decompress(data, offset=0, length=None, base=None, **ctx_kw):
+    """content bytes [offset, offset + length) of a seekable stream (length None: to the end); of a typed stream, the elements' bytes. base: the bytes a
+    stream written with ``compress(..., base=)`` was compressed against (the whole base, whatever the range; other bytes of that size give wrong elements and
+    no error). Raises ZstdError for a stream without a valid seek table, a range outside the content, a frame that fails, or such a stream without its base."""
     if len(data) == 0:
         raise ZstdError("not a seekable stream: empty input")
     ctx = DeviceBatchContext(**ctx_kw)
     try:
-        st = SeekableStream(ctx, _to_device(data))
+        st = SeekableStream(ctx, _to_device(data), base=None if base is None else _to_device(base))
         try:
             return st.read(offset, length).cpu().numpy().tobytes()
         finally:
@@ -97,15 +130,15 @@ def decompress(data, offset=0, length=None, **ctx_kw):
         ctx.close()
 
 
-def decompress_ranges(data, ranges, **ctx_kw):
+def decompress_ranges(data, ranges, base=None, **ctx_kw):
     """the content bytes of every (offset, length) of `ranges` as a list of bytes: ONE decode batch over the frames the ranges touch, each decoded once
     (of a typed stream: the elements' bytes, every plane frame a range's groups need).
-    Raises ZstdError as ``decompress`` does; a failing frame's error names the lowest range that needs it."""
+    base: as in ``decompress``. Raises ZstdError as ``decompress`` does; a failing frame's error names the lowest range that needs it."""
     if len(data) == 0:
         raise ZstdError("not a seekable stream: empty input")
     ctx = DeviceBatchContext(**ctx_kw)
     try:
-        st = SeekableStream(ctx, _to_device(data))
+        st = SeekableStream(ctx, _to_device(data), base=None if base is None else _to_device(base))
         try:
             views = st.read_ranges(ranges)
             if not views:
