@@ -498,7 +498,8 @@ uint32_t zhip_seekable_filter(const zhip_seekable*);
  * +16 is elementSize | 4 << 8. Filter values 2 and 3 are none and stay refused everywhere.
  *
  * THE STREAM DOES NOT NAME ITS BASE. Reading it with another tensor of the right size returns wrong elements with status 0; keeping stream and base together
- * is the caller's business (a fingerprint of the base is not part of the format). A reader XORs once: chains of versions are the caller's to follow.
+ * is the caller's business (a fingerprint of the base is not part of the format). The calls here XOR once; a chain of versions is read by
+ * zhip_seekable_decompress_typed_ranges_chain_device below.
  *
  * zhip_planes_split_base_device / zhip_planes_join_base_device: the transposition kernels with the XOR fused in, one kernel each way; d_base is `size` bytes.
  * zhip_seekable_compress_typed_base_device: zhip_seekable_compress_typed_device with the XOR in the split and filter 4 in the marker; d_base is srcSize bytes.
@@ -516,6 +517,35 @@ int      zhip_seekable_compress_typed_base_device(zhip_ctx*, const void* d_src, 
 int      zhip_seekable_decompress_typed_ranges_base_device(zhip_ctx*, zhip_seekable*, const void* d_base, uint64_t baseSize, const zhip_seekable_range* ranges, size_t nRanges,
                                                            void* d_out, uint64_t outCapacity, int32_t* d_status /* [2 + 2 * nRanges] */,
                                                            zhip_seekable_gather_stats* stats /* host, may be NULL */, void* stream);
+
+/* CHAINS of xor-with-base streams. A store of versions v0, v1, ... of one tensor writes every version against its PREDECESSOR (the smaller the
+ * step, the smaller the stream): v0 as a full unfiltered typed stream, v(i) as zhip_seekable_compress_typed_base_device(v(i), base = v(i-1)). Elements of
+ * version n are then v0 ^ d1 ^ ... ^ dn. zhip_seekable_decompress_typed_ranges_chain_device reads ranges of them in one call from links = [full, d1, ..., dn]
+ * with d_base NULL, or from links = [d1, ..., dn] and d_base = v0 (baseSize its bytes, the content size): ONE plan from link 0's table and scratch limit, per
+ * pass one many-ranges call per link -- only the frames the ranges touch are decoded, into that link's own planar scratch -- and ONE join kernel that XORs all
+ * links' planar words, transposes once, XORs the base and writes the output. Nothing intermediate is written. Traffic per element byte: nLinks planar reads,
+ * a base read where there is one, one write (following the chain by hand: 3 per link). Scratch: every link holds at most link 0's scratch limit of planar
+ * bytes (or one piece above it), the chain at most nLinks times that. nLinks == 1 returns byte for byte what the single-stream calls return.
+ * d_status [2 + 2 * nRanges] has the layout and meaning of zhip_seekable_decompress_typed_ranges_device's. A range fails if any link's frames under it
+ * failed; where several links fail, the EARLIEST link in chain order is reported, the frame index being the index in THAT link's frame table.
+ * d_link [1 + nRanges] (may be NULL): [0] the link behind d_status[0 .. 1], [1 + r] the link whose frame failed range r, -1 where none did. A failed range's
+ * bytes are unspecified, every other range is exact. stats sums over all links' many-ranges calls, `passes` counting the typed passes once.
+ * ZHIP_ERR_UNSUPPORTED, nothing queued, nothing written, the message naming the link: nLinks 0 or above 16; a NULL link; a handle that appears twice (its
+ * planar scratch would be shared); a plain link (element size 1); links that differ in element size, group elements or content size; link 0 with the delta
+ * filter; a later link whose filter is not 4; link 0 with filter 4 and no base; link 0 unfiltered WITH a base; a baseSize other than the content size; a base
+ * that shares a byte with the output; and the ranges' own refusals. The handles are used by the call: as with every call on a handle, one call at a time.
+ * NO LINK NAMES ITS BASE OR ITS PREDECESSOR: a chain in the wrong order, or with a link of another tensor of the same shape, returns wrong elements with
+ * status 0. (XOR commutes, so the order of the links behind a correct start does not matter; leaving one out or taking a foreign one does.)
+ * zhip_planes_join_chain_device: the join kernel on its own over nLinks whole planar buffers of `size` bytes (zhip_planes_split_*'s layout), d_base NULL or
+ * `size` bytes that share none with d_dst. */
+enum { ZHIP_CHAIN_MAX = 16 };
+int      zhip_planes_join_chain_device(zhip_ctx*, const void* const* d_planar /* host array [nLinks] of device pointers */, size_t nLinks, uint64_t size, uint32_t elementSize,
+                                       uint32_t frameSize, const void* d_base /* may be NULL */, void* d_dst, void* stream);
+int      zhip_seekable_decompress_typed_ranges_chain_device(zhip_ctx*, zhip_seekable* const* links /* host array, oldest first */, size_t nLinks,
+                                                            const void* d_base /* NULL iff link 0 is unfiltered */, uint64_t baseSize,
+                                                            const zhip_seekable_range* ranges, size_t nRanges, void* d_out, uint64_t outCapacity,
+                                                            int32_t* d_status /* [2 + 2 * nRanges] */, int32_t* d_link /* [1 + nRanges], may be NULL */,
+                                                            zhip_seekable_gather_stats* stats /* host, may be NULL */, void* stream);
 
 /* name of a kernel as it appears in rocprofv3 traces ("" past the last one), and its average duration (ms) over the launches since the last call, measured with HIP events
  * on the stream it is launched on (for bench.py's roofline). k: 0 / 1 the generic decode / encode kernels, 2 K1 (with K0 and the bin pass in front of / behind it), 3 K2,

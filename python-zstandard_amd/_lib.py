@@ -156,6 +156,8 @@ def lib():
         "zhip_planes_join_base_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, vp, vp, vp]),
         "zhip_seekable_compress_typed_base_device": (C.c_int, [vp, vp, u64, C.c_uint32, C.c_uint32, vp, C.c_int, vp, u64, vp, vp, vp]),
         "zhip_seekable_decompress_typed_ranges_base_device": (C.c_int, [vp, vp, vp, u64, vp, sz, vp, u64, vp, C.POINTER(SeekableGatherStats), vp]),
+        "zhip_planes_join_chain_device": (C.c_int, [vp, vp, sz, u64, C.c_uint32, C.c_uint32, vp, vp, vp]),
+        "zhip_seekable_decompress_typed_ranges_chain_device": (C.c_int, [vp, vp, sz, vp, u64, vp, sz, vp, u64, vp, vp, C.POINTER(SeekableGatherStats), vp]),
     }
     for name, (res, args) in protos.items():
         f = getattr(L, name)
@@ -183,6 +185,7 @@ EXPORTED_SYMBOLS = [
     "zhip_seekable_element_size", "zhip_seekable_group_elements", "zhip_seekable_decompress_typed_ranges_device",
     "zhip_planes_split_filter_device", "zhip_planes_join_filter_device", "zhip_seekable_compress_typed_filter_device", "zhip_seekable_filter",
     "zhip_planes_split_base_device", "zhip_planes_join_base_device", "zhip_seekable_compress_typed_base_device", "zhip_seekable_decompress_typed_ranges_base_device",
+    "zhip_planes_join_chain_device", "zhip_seekable_decompress_typed_ranges_chain_device",
 ]
 
 

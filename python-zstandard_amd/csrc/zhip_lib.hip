@@ -2242,3 +2242,27 @@ extern "C" int zhip_seekable_decompress_typed_ranges_device(zhip_ctx* c, zhip_se
     size_t bad = 0;
     return zsk_typed_ranges(b, c != nullptr, h, (const uint64_t*)ranges, nRanges, d_dst, dstCapacity, d_status, stats, &bad);
 }
+// chains of xor-with-base links: the chain join on its own, and the typed read through [full stream or base, delta 1, ..., delta n]
+extern "C" int zhip_planes_join_chain_device(zhip_ctx* c, const void* const* d_planar, size_t nLinks, uint64_t size, uint32_t elementSize, uint32_t frameSize, const void* d_base,
+                                             void* d_dst, void* streamv)
+{
+    ZskHipTypedBackend b(c, nullptr, streamv);
+    return zsk_planes_join_chain(b, c != nullptr, d_planar, nLinks, size, elementSize, frameSize, d_base, d_dst);
+}
+extern "C" int zhip_seekable_decompress_typed_ranges_chain_device(zhip_ctx* c, zhip_seekable* const* links, size_t nLinks, const void* d_base, uint64_t baseSize,
+                                                                  const zhip_seekable_range* ranges, size_t nRanges, void* d_dst, uint64_t dstCapacity, int32_t* d_status, int32_t* d_link,
+                                                                  zhip_seekable_gather_stats* stats, void* streamv)
+{
+    // a backend per link, over that link's handle: its many-ranges call, its planar and status areas (the sequence checks the chain before it touches one)
+    std::vector<ZskHipTypedBackend> backends;
+    std::vector<ZskHipTypedBackend*> bs;
+    std::vector<const ZskTypedOpened*> hs;
+    if (links && nLinks <= ZSK_CHAIN_MAX) {
+        backends.reserve(nLinks);
+        for (size_t i = 0; i < nLinks; i++) { backends.emplace_back(c, links[i], streamv); hs.push_back(links[i]); }
+        for (size_t i = 0; i < nLinks; i++) bs.push_back(&backends[i]);
+    }
+    size_t bad = 0;
+    return zsk_typed_ranges_chain(bs.data(), g_lastError, c != nullptr, links ? hs.data() : nullptr, nLinks, d_base, baseSize, (const uint64_t*)ranges, nRanges, d_dst, dstCapacity, d_status,
+                                  d_link, stats, &bad);
+}

@@ -500,6 +500,91 @@ ZH_DEV void zsk_planes_join_xor_body(const ZskJoinXorArgs& x)
     }
 }
 
+// ------------------------------------------------------------------------------------------------ join through a chain of xor-with-base links: one launch
+// Version n of a tensor written as [full stream or base, v1 ^ v0, ..., vn ^ v(n-1)]: every link's planar buffer has the SAME layout -- the same
+// jobs, job.planar offsets and tiles, one plan made once -- so byte j of a job is planar[0][..] ^ ... ^ planar[nLinks - 1][..], joined, ^ base[content + j]
+// where there is a base. XOR is bytewise and commutes with the transposition: the links' PLANAR 16-byte words are XORed and transposed ONCE, K loads and 4 K
+// XORs per link and 16 elements. The link loop's trip count is a run-time value (the pointers are read from the kernel's arguments by a wave-uniform index);
+// it takes two links a trip, their 2 K loads issued before the first XOR, and the base's and link 0's loads stand in front of the loop. The trimmed first and
+// last element and the tails go byte by byte; nothing of the base or of a planar buffer outside the stored bytes is read.
+#define ZSK_CHAIN_MAX 16u
+struct ZskJoinChainArgs { ZskJoinArgs j; const uint8_t* planar[ZSK_CHAIN_MAX]; uint32_t nLinks; const uint8_t* base; const uint64_t* content; };      // j.planar is not read; base NULL: none, content not read
+// zsk_join16_words in its two halves: the K planes' words as they lie (plane p's four at w + 4 p), and their transposition into the 16 elements' words
+template <int K> ZH_DEV void zsk_planar_load16(const uint8_t* s, uint64_t plane, uint32_t* w)
+{
+#pragma unroll
+    for (int p = 0; p < K; p++) zsk_words(zh_ld128(s + p * plane), w + 4 * p);
+}
+template <int K> ZH_DEV void zsk_planar_words(const uint32_t* w, uint32_t* o)
+{
+#pragma unroll
+    for (int W = 0; W < 4 * K; W++) {                  // the output word: bytes 4W .. 4W + 3 of the 16 elements
+        if (K == 2) o[W] = zsk_perm(w[4 + (W >> 1)], w[W >> 1], W & 1 ? 0x07030602u : 0x05010400u);
+        else { const int per = K / 4, i = W / per, p0 = (W % per) * 4; o[W] = zsk_byte_of4(w[4 * p0 + (i >> 2)], w[4 * (p0 + 1) + (i >> 2)], w[4 * (p0 + 2) + (i >> 2)], w[4 * (p0 + 3) + (i >> 2)], i & 3); }
+    }
+}
+// at: the job's offset in every planar buffer; b: the base at the job's content offset, or NULL
+template <int K> ZH_DEV void zsk_join_chain_lane(const ZskJoinChainArgs& x, uint64_t at, const uint8_t* b, uint8_t* d, uint64_t m, uint32_t h, uint32_t t, uint64_t i0)
+{
+    if (i0 >= m) return;
+    const uint64_t n = m - i0 < 16 ? m - i0 : 16, lo = i0 * K, hi = (i0 + n) * K, end = m * K - t;
+    const uint64_t from = lo < h ? h : lo, to = hi > end ? end : hi;
+    const uint32_t links = x.nLinks;
+    if (n == 16 && from == lo && to == hi) {
+        uint32_t w[4 * K], o[4 * K], xb[4 * K];
+        if (b) zsk_load16<K>(b + lo, xb);              // the base's loads go out with link 0's: one wait for both
+        zsk_planar_load16<K>(x.planar[0] + at + i0, m, w);
+        uint32_t i = 1;
+        for (; i + 1 < links; i += 2) {
+            uint32_t u[4 * K], v[4 * K];
+            zsk_planar_load16<K>(x.planar[i] + at + i0, m, u);
+            zsk_planar_load16<K>(x.planar[i + 1] + at + i0, m, v);
+#pragma unroll
+            for (int j = 0; j < 4 * K; j++) w[j] ^= u[j] ^ v[j];
+        }
+        if (i < links) {
+            uint32_t u[4 * K];
+            zsk_planar_load16<K>(x.planar[i] + at + i0, m, u);
+#pragma unroll
+            for (int j = 0; j < 4 * K; j++) w[j] ^= u[j];
+        }
+        zsk_planar_words<K>(w, o);
+        if (b) {
+#pragma unroll
+            for (int j = 0; j < 4 * K; j++) o[j] ^= xb[j];
+        }
+        zsk_store16<K>(o, d + (lo - h));
+        return;
+    }
+    for (uint64_t j = from; j < to; j++) {             // a job's trimmed first / last element, its last elements, fewer than 16
+        uint8_t v = b ? b[j] : 0;
+        for (uint32_t i = 0; i < links; i++) v ^= x.planar[i][at + (j % K) * m + j / K];
+        d[j - h] = v;
+    }
+}
+ZH_DEV void zsk_planes_join_chain_body(const ZskJoinChainArgs& x)
+{
+    const ZskJoinArgs& a = x.j;
+    const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
+    for (uint64_t t = zh_block(); t < a.tiles; t += zh_nblocks()) {
+        ZskJoinJob job; uint64_t content = 0;
+        if (a.jobs) {
+            uint32_t lo = 0, hi = a.nJobs;                                  // the last job whose tilePrefix <= t
+            while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.jobs[mid].tilePrefix <= t) lo = mid; else hi = mid; }
+            job = a.jobs[lo];
+            if (x.base) content = x.content[lo];
+        } else {
+            const uint64_t g = t / tpg;
+            job.planar = job.dst = content = g * a.group * a.k; job.m = zsk_group_len(a.elements, a.group, g); job.tilePrefix = g * tpg; job.h = job.t = 0;
+        }
+        const uint64_t i0 = (t - job.tilePrefix) * ZSK_PLANE_TILE + zh_lane() * 16;
+        const uint8_t* const b = x.base ? x.base + content : nullptr;
+        if (a.k == 2) zsk_join_chain_lane<2>(x, job.planar, b, a.dst + job.dst, job.m, job.h, job.t, i0);
+        else if (a.k == 4) zsk_join_chain_lane<4>(x, job.planar, b, a.dst + job.dst, job.m, job.h, job.t, i0);
+        else zsk_join_chain_lane<8>(x, job.planar, b, a.dst + job.dst, job.m, job.h, job.t, i0);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ seal: the marker behind a stream the records call wrote
 // The records call leaves n plane frames, the table behind them and *streamSize (0: it failed, and so does the typed call). The marker goes where the table
 // starts and the table 24 bytes further on, one entry longer; the two overlap, so the first kernel keeps the stream size and the old entries aside.
@@ -571,6 +656,36 @@ ZH_DEV void zsk_typed_status_body(const ZskTypedStatusArgs& a)
     for (uint32_t r = zh_lane(); r < a.nRanges; r += 64) if (first == ZSK_NONE && zsk_typed_first_bad(a, r) != ~0u) first = r;
     first = zsk_wave_min64(first);
     if (zh_lane() == 0) { a.outStatus[0] = first != ZSK_NONE ? a.status[a.pairAt[zsk_typed_first_bad(a, first)]] : 0; a.outStatus[1] = first != ZSK_NONE ? (int32_t)first : 0; }
+}
+
+// The same over a chain's links: every link ran the same planar ranges into a status area of its own, laid out alike (status[i] + pairAt[q]). A user range
+// fails if any link's frames under it failed; where several links fail, the EARLIEST link in chain order is reported, with its first failing planar range's
+// pair -- the frame index is that link's own. outLink [1 + R] (NULL: not wanted): the link reported, -1 where none failed; [0] goes with the overall pair
+struct ZskTypedStatusChainArgs { ZskTypedStatusArgs s; const int32_t* status[ZSK_CHAIN_MAX]; uint32_t nLinks; int32_t* outLink; };      // s.status is not read
+ZH_DEV bool zsk_typed_chain_first_bad(const ZskTypedStatusChainArgs& c, uint64_t r, uint32_t* link, uint32_t* q)
+{
+    for (uint32_t i = 0; i < c.nLinks; i++)
+        for (uint32_t p = c.s.owner[2 * r]; p < c.s.owner[2 * r + 1]; p++) if (c.status[i][c.s.pairAt[p]]) { *link = i; *q = p; return true; }
+    return false;
+}
+ZH_DEV void zsk_typed_status_chain_body(const ZskTypedStatusChainArgs& c)
+{
+    const ZskTypedStatusArgs& a = c.s;
+    uint32_t link = 0, q = 0;
+    for (uint64_t r = (uint64_t)zh_block() * 64 + zh_lane(); r < a.nRanges; r += (uint64_t)zh_nblocks() * 64) {
+        const bool bad = zsk_typed_chain_first_bad(c, r, &link, &q);
+        a.outStatus[2 + 2 * r] = bad ? c.status[link][a.pairAt[q]] : 0; a.outStatus[3 + 2 * r] = bad ? c.status[link][a.pairAt[q] + 1] : 0;
+        if (c.outLink) c.outLink[1 + r] = bad ? (int32_t)link : -1;
+    }
+    if (zh_block() != 0) return;
+    uint64_t first = ZSK_NONE;
+    for (uint32_t r = zh_lane(); r < a.nRanges; r += 64) if (first == ZSK_NONE && zsk_typed_chain_first_bad(c, r, &link, &q)) first = r;
+    first = zsk_wave_min64(first);
+    if (zh_lane() == 0) {
+        const bool bad = first != ZSK_NONE && zsk_typed_chain_first_bad(c, first, &link, &q);
+        a.outStatus[0] = bad ? c.status[link][a.pairAt[q]] : 0; a.outStatus[1] = bad ? (int32_t)first : 0;
+        if (c.outLink) c.outLink[0] = bad ? (int32_t)link : -1;
+    }
 }
 
 // The plan. A user range covers elements E0 .. E1 (rounded out to whole elements; h and t bytes of the first and the last are not its own). Group by group:
@@ -650,4 +765,6 @@ __global__ __launch_bounds__(64) void zhip_seekable_delta_offsets_kernel(ZskJoin
 __global__ __launch_bounds__(64) void zhip_seekable_planes_join_delta_kernel(ZskJoinArgs a) { zsk_planes_join_delta_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_planes_split_xor_kernel(ZskPlanesXorArgs a) { zsk_planes_split_xor_body(a); }
 __global__ __launch_bounds__(64) void zhip_seekable_planes_join_xor_kernel(ZskJoinXorArgs a) { zsk_planes_join_xor_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_planes_join_chain_kernel(ZskJoinChainArgs a) { zsk_planes_join_chain_body(a); }
+__global__ __launch_bounds__(64) void zhip_seekable_typed_status_chain_kernel(ZskTypedStatusChainArgs a) { zsk_typed_status_chain_body(a); }
 #endif

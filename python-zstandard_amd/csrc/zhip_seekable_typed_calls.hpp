@@ -15,7 +15,8 @@
     X(TYPED_STATUS, typed_status, ZskTypedStatusArgs) \
     X(PLANES_SPLIT_DELTA, planes_split_delta, ZskPlanesArgs) X(DELTA_SUMS, delta_sums, ZskJoinArgs) X(DELTA_OFFSETS, delta_offsets, ZskJoinArgs) \
     X(PLANES_JOIN_DELTA, planes_join_delta, ZskJoinArgs) \
-    X(PLANES_SPLIT_XOR, planes_split_xor, ZskPlanesXorArgs) X(PLANES_JOIN_XOR, planes_join_xor, ZskJoinXorArgs)
+    X(PLANES_SPLIT_XOR, planes_split_xor, ZskPlanesXorArgs) X(PLANES_JOIN_XOR, planes_join_xor, ZskJoinXorArgs) \
+    X(PLANES_JOIN_CHAIN, planes_join_chain, ZskJoinChainArgs) X(TYPED_STATUS_CHAIN, typed_status_chain, ZskTypedStatusChainArgs)
 #define ZSKT_X(id, name, args) ZSKT_K_##id,
 enum ZskTypedKernel { ZSKT_KERNELS(ZSKT_X) ZSKT_K_COUNT };
 #undef ZSKT_X
@@ -267,4 +268,128 @@ template <class B> int zsk_typed_ranges_base(B& b, bool ctx, const ZskTypedOpene
     if (baseSize != h->contentSize && d_base) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, "seekable typed ranges: the base must have the size of the stream's content");
     if (int rc = zsk_base_check("seekable typed ranges", d_base, baseSize, h->elementSize, d_dst, dstCapacity, b.err)) return rc;
     return zsk_typed_ranges(b, ctx, h, rg, R, d_dst, dstCapacity, d_status, stats, bad, d_base);
+}
+
+// ------------------------------------------------------------------------------------------------ chains of xor-with-base links
+// Version n of a tensor as [a full unfiltered stream, delta 1, ..., delta n], or as [delta 1, ..., delta n] and a base tensor, every delta an xor-with-base
+// stream written against its predecessor. No link names its base or its predecessor: a chain in the wrong order, or with a link of another tensor of the
+// same shape, reads back wrong elements with status 0. The message of a refusal names the link.
+static inline int zsk_chain_refuse(std::string& err, const char* what, size_t link, const char* why)
+{
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: link %zu %s", what, link, why);
+    return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, buf);
+}
+static inline int zsk_chain_count_check(const char* what, bool pointers, size_t nLinks, std::string& err)
+{
+    char buf[160];
+    if (nLinks < 1 || nLinks > ZSK_CHAIN_MAX) { snprintf(buf, sizeof buf, "%s: a chain has 1 ... %u links, not %zu", what, ZSK_CHAIN_MAX, nLinks); return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, buf); }
+    if (!pointers) { snprintf(buf, sizeof buf, "%s: bad arguments", what); return zsk_refuse(err, ZHIP_ERR_UNSUPPORTED, buf); }
+    return 0;
+}
+
+// The chain join on its own: nLinks whole planar buffers of `size` bytes with the layout of zsk_planes_split's, XORed, joined and XORed with the base where
+// one is given (d_base may be NULL) -- one launch on the plain join's grid
+template <class B> int zsk_planes_join_chain(B& b, bool ctx, const void* const* d_planar, size_t nLinks, uint64_t size, uint32_t k, uint32_t frameSize, const void* d_base, void* d_dst)
+{
+    if (int rc = zsk_chain_count_check("planes join chain", ctx && d_planar, nLinks, b.err)) return rc;
+    for (size_t i = 0; i < nLinks; i++) if (size && !d_planar[i]) return zsk_chain_refuse(b.err, "planes join chain", i, "is NULL");
+    if (int rc = zsk_planes_check(!size || d_dst, size, k, frameSize, b.err)) return rc;
+    if (d_base && zsk_overlap(d_base, size, d_dst, size)) return zsk_refuse(b.err, ZHIP_ERR_UNSUPPORTED, "planes join chain: the base overlaps the output");
+    if (!size) return 0;
+    ZskJoinChainArgs x; memset(&x, 0, sizeof x);
+    ZskJoinArgs& a = x.j;
+    a.planar = (const uint8_t*)d_planar[0]; a.dst = (uint8_t*)d_dst; a.elements = size / k; a.k = k; a.group = frameSize; a.tiles = zsk_planes_tiles(a.elements, frameSize);
+    for (size_t i = 0; i < nLinks; i++) x.planar[i] = (const uint8_t*)d_planar[i];
+    x.nLinks = (uint32_t)nLinks; x.base = (const uint8_t*)d_base;
+    b.launch_typed(ZSKT_K_PLANES_JOIN_CHAIN, zsk_tile_grid(b.numCU, a.tiles, 0), &x);
+    return b.check();
+}
+
+// what a chain read refuses before anything is queued or written (the ranges' own refusals follow in the call)
+static inline int zsk_chain_check(bool ctx, const ZskTypedOpened* const* links, size_t nLinks, const void* d_base, uint64_t baseSize, const void* d_dst, uint64_t dstCapacity, std::string& err)
+{
+    const char* const what = "seekable chain";
+    if (int rc = zsk_chain_count_check(what, ctx && links, nLinks, err)) return rc;
+    for (size_t i = 0; i < nLinks; i++) {
+        if (!links[i]) return zsk_chain_refuse(err, what, i, "is NULL");
+        for (size_t j = 0; j < i; j++) if (links[j] == links[i]) return zsk_chain_refuse(err, what, i, "is a handle that stands in the chain already (a link's planar buffer is its handle's)");
+        if (links[i]->elementSize == 1) return zsk_chain_refuse(err, what, i, "is a plain stream (no byte planes)");
+        if (links[i]->elementSize != links[0]->elementSize || links[i]->groupElements != links[0]->groupElements || links[i]->contentSize != links[0]->contentSize)
+            return zsk_chain_refuse(err, what, i, "differs from link 0 in element size, group elements or content size");
+        if (i == 0 && links[i]->filter == ZSK_FILTER_DELTA) return zsk_chain_refuse(err, what, i, "has the delta filter (a chain starts with an unfiltered stream, or with an xor-with-base stream and its base)");
+        if (i > 0 && links[i]->filter != ZSK_FILTER_XOR_BASE) return zsk_chain_refuse(err, what, i, "is not an xor-with-base stream (every link behind the first is one)");
+    }
+    if (links[0]->filter == ZSK_FILTER_XOR_BASE && !d_base) return zsk_chain_refuse(err, what, 0, "is an xor-with-base stream: the chain needs its base");
+    if (links[0]->filter == ZSK_FILTER_NONE && d_base) return zsk_chain_refuse(err, what, 0, "is an unfiltered stream: the chain takes no base");
+    if (d_base && baseSize != links[0]->contentSize) return zsk_chain_refuse(err, what, 0, "has another content size than the base");
+    if (d_base && zsk_overlap(d_base, baseSize, d_dst, dstCapacity)) return zsk_chain_refuse(err, what, 0, "has a base that overlaps the output");
+    return 0;
+}
+
+// R user ranges of version nLinks - 1 (or nLinks, with a base) in one call. bs[i] is the backend over link i's handle: the many-ranges call of link i runs on
+// it, unchanged, into THAT handle's planar area and a status area of its own; bs[0] also holds the call's tables and launches the join and the reducer.
+// ONE plan, from link 0's offsets and scratch limit (all links of a chain have one decompressed layout); per pass nLinks many-ranges calls and one chain join;
+// then the status reducer over all links' status areas. Every link holds at most the limit of planar scratch (or one piece above it), the chain nLinks times
+// that. stats sums over all links' many-ranges calls, `passes` counting the typed passes once. d_link [1 + R] may be NULL.
+template <class B> int zsk_typed_ranges_chain(B* const* bs, std::string& err, bool ctx, const ZskTypedOpened* const* links, size_t nLinks, const void* d_base, uint64_t baseSize,
+                                              const uint64_t* rg, size_t R, void* d_dst, uint64_t dstCapacity, int32_t* d_status, int32_t* d_link, zhip_seekable_gather_stats* stats, size_t* bad)
+{
+    if (int rc = zsk_chain_check(ctx && bs, links, nLinks, d_base, baseSize, d_dst, dstCapacity, err)) return rc;
+    const ZskTypedOpened* const h = links[0];
+    bool any = false;
+    if (int rc = zsk_ranges_check(d_status != nullptr, rg, R, h->contentSize, d_dst, dstCapacity, bad, &any, err)) return rc;
+    B& b = *bs[0];
+    if (stats) memset(stats, 0, sizeof *stats);
+    ZskTypedStatusChainArgs s; memset(&s, 0, sizeof s);
+    s.s.nRanges = (uint32_t)R; s.s.outStatus = d_status; s.outLink = d_link;
+    if (!any) {                                    // nothing to read: zeros, and no link anywhere (the reducer over no links writes exactly that)
+        if (!d_link) return b.zero(d_status, (2 + 2 * R) * sizeof(int32_t));
+        b.launch_typed(ZSKT_K_TYPED_STATUS_CHAIN, zsk_lane_grid(b.numCU, R), &s);
+        return b.check();
+    }
+
+    ZskTypedPlan plan;
+    zsk_typed_plan(h->dOff.data(), h->elementSize, h->groupElements, rg, R, h->scratchLimit, &plan, d_base ? ZSK_FILTER_XOR_BASE : ZSK_FILTER_NONE);
+    const size_t J = plan.jobs.size(), Q = plan.planar.size() / 3, nPass = plan.passes.size();
+    const ZskTypedReadLayout l = zsk_typed_read_layout(J, R, Q, plan.content.size());
+    std::vector<uint32_t> pairAt(Q);
+    size_t statusInts = 0;
+    for (const ZskTypedPass& p : plan.passes) { for (uint32_t q = p.q0; q < p.q1; q++) pairAt[q] = (uint32_t)(statusInts + 2 + 2 * (q - p.q0)); statusInts += 2 + 2 * (size_t)(p.q1 - p.q0); }
+    uint8_t* P[ZSK_CHAIN_MAX]; uint8_t* st[ZSK_CHAIN_MAX]; uint8_t* t = nullptr; uint8_t* pin = nullptr;
+    for (size_t i = 0; i < nLinks; i++) {
+        if (int rc = bs[i]->reserve_typed(ZSKT_A_PLANAR, (size_t)plan.pMax, &P[i])) return rc;
+        if (int rc = bs[i]->reserve_typed(ZSKT_A_STATUS, statusInts * 4, &st[i])) return rc;
+    }
+    if (int rc = b.reserve_typed(ZSKT_A_TABLES, l.tableBytes, &t)) return rc;
+    if (int rc = b.reserve(ZSK_A_PIN, l.tableBytes, &pin)) return rc;
+    memcpy(pin + l.oJobs, plan.jobs.data(), J * sizeof(ZskJoinJob));
+    memcpy(pin + l.oOwner, plan.owner.data(), R * 8);
+    memcpy(pin + l.oPairAt, pairAt.data(), Q * 4);
+    memcpy(pin + l.oContent, plan.content.data(), plan.content.size() * 8);
+    if (int rc = b.copy(t, pin, l.tableBytes, ZSK_COPY_FROM_PIN)) return rc;
+
+    size_t at = 0;
+    for (size_t p = 0; p < nPass; p++) {
+        const ZskTypedPass& ps = plan.passes[p];
+        for (size_t i = 0; i < nLinks; i++) {
+            zhip_seekable_gather_stats one; size_t inner = 0;
+            if (int rc = zsk_ranges(*bs[i], ctx, links[i], plan.planar.data() + 3 * (size_t)ps.q0, ps.q1 - ps.q0, P[i], ps.bytes, (int32_t*)st[i] + at, &one, &inner)) return rc;
+            if (stats) { stats->items += one.items; stats->inPlace += one.inPlace; stats->scratchBytes += one.scratchBytes; stats->copyJobs += one.copyJobs; }
+        }
+        at += 2 + 2 * (size_t)(ps.q1 - ps.q0);
+        if (stats) stats->passes++;
+        ZskJoinChainArgs x; memset(&x, 0, sizeof x);
+        ZskJoinArgs& a = x.j;
+        a.planar = P[0]; a.dst = (uint8_t*)d_dst; a.jobs = (const ZskJoinJob*)(t + l.oJobs) + ps.job0; a.nJobs = ps.job1 - ps.job0; a.tiles = ps.tiles; a.k = h->elementSize; a.group = h->groupElements;
+        for (size_t i = 0; i < nLinks; i++) x.planar[i] = P[i];
+        x.nLinks = (uint32_t)nLinks; x.base = (const uint8_t*)d_base; x.content = d_base ? (const uint64_t*)(t + l.oContent) + ps.job0 : nullptr;
+        b.launch_typed(ZSKT_K_PLANES_JOIN_CHAIN, zsk_tile_grid(b.numCU, a.tiles, 0), &x);
+        if (int rc = b.check()) return rc;
+    }
+    s.s.owner = (const uint32_t*)(t + l.oOwner); s.s.pairAt = (const uint32_t*)(t + l.oPairAt);
+    for (size_t i = 0; i < nLinks; i++) s.status[i] = (const int32_t*)st[i];
+    s.nLinks = (uint32_t)nLinks;
+    b.launch_typed(ZSKT_K_TYPED_STATUS_CHAIN, zsk_lane_grid(b.numCU, R), &s);
+    return b.check();
 }

@@ -306,6 +306,36 @@ class DeviceBatchContext:
         gives wrong elements, no error): the joined bytes XOR base, in one kernel. Asynchronous."""
         return self._planes(self.L.zhip_planes_join_filter_device, planar, frame_size, element_size, out, stream, filter, base)
 
+    def planes_join_chain(self, planars, frame_size, element_size, out=None, stream=None, base=None):
+        """1 ... 16 planar buffers of ONE layout (planes_split's, the same size, frame_size and element_size) -> the elements' bytes of their bytewise XOR,
+        XORed with base where one is given, as a uint8 tensor: what a chain of versions stored against their predecessors reads back as (SeekableChain), in
+        one kernel -- the planar words are XORed and transposed once. base and out must not overlap. Asynchronous."""
+        planars = list(planars)
+        if not 1 <= len(planars) <= 16:
+            raise ZstdError("planes join chain: a chain has 1 ... 16 links, not %d" % len(planars))
+        raws = []
+        for i, p in enumerate(planars):
+            if not (isinstance(p, torch.Tensor) and p.is_cuda and p.is_contiguous() and p.device == planars[0].device):
+                raise ZstdError("planes join chain: link %d is no contiguous CUDA tensor on link 0's device" % i)
+            raws.append(p.view(torch.uint8).reshape(-1))
+            if raws[i].numel() != raws[0].numel():
+                raise ZstdError("planes join chain: link %d has %d bytes, link 0 %d" % (i, raws[i].numel(), raws[0].numel()))
+        nbytes = raws[0].numel()
+        if base is not None:
+            base = _base_bytes(base, planars[0], nbytes, "planes join chain")
+        s = stream if stream is not None else torch.cuda.current_stream()
+        if out is None:
+            with torch.cuda.stream(s):
+                out = torch.empty(nbytes, dtype=torch.uint8, device=planars[0].device)
+        self._check(out, torch.uint8)
+        assert out.numel() >= nbytes, "out is shorter than the planar buffers"
+        ptrs = (C.c_void_p * len(raws))(*[r.data_ptr() if nbytes else None for r in raws])
+        rc = self.L.zhip_planes_join_chain_device(self.ctx, ptrs, len(raws), nbytes, element_size, frame_size, base.data_ptr() if base is not None and nbytes else None,
+                                                  out.data_ptr() if nbytes else None, s.cuda_stream)
+        if rc:
+            raise ZstdError("planes: %s" % _lib.last_error())
+        return out[:nbytes]
+
     def _records_table(self, src, records, max_content_bytes, max_record_bytes, s, what="seekable compress"):
         """records as seekable_compress_records takes them -> (the (n, 2) int64 CUDA table, n, max_content_bytes, max_record_bytes)"""
         import numpy as np
@@ -482,6 +512,48 @@ def planes_join(planar, frame_size, element_size, ctx=None, out=None, stream=Non
         with_ctx.close()
 
 
+def planes_join_chain(planars, frame_size, element_size, ctx=None, out=None, stream=None, base=None):
+    """DeviceBatchContext.planes_join_chain on `ctx`, or on a context of its own (then it waits)"""
+    if ctx is not None:
+        return ctx.planes_join_chain(planars, frame_size, element_size, out, stream, base)
+    with_ctx = DeviceBatchContext()
+    try:
+        return with_ctx.planes_join_chain(planars, frame_size, element_size, out, stream, base)
+    finally:
+        with_ctx.close()
+
+
+def _ranges_table(ranges, out, out_offsets):
+    """the (offset, length) ranges of a read_ranges call -> (the [R][3] table the library takes, R, the lengths, the bytes `out` needs)"""
+    import numpy as np
+    try:
+        r = np.asarray(ranges if len(ranges) else np.zeros((0, 2), dtype=np.int64))
+    except Exception:
+        raise ZstdError("ranges must be a sequence of (offset, length)")
+    if r.ndim != 2 or r.shape[1] != 2 or r.dtype.kind not in "iu":
+        raise ZstdError("ranges must be a sequence of (offset, length) or an integer array of shape (R, 2)")
+    n = r.shape[0]
+    if n and (r.astype(object) < 0).any():
+        raise ZstdError("ranges must not be negative")
+    table = np.zeros((max(n, 1), 3), dtype=np.uint64)
+    table[:n, :2] = r
+    lengths = [int(x) for x in table[:n, 1]]
+    if out_offsets is None:
+        at = 0
+        for k, ln in enumerate(lengths):
+            table[k, 2] = at; at += ln
+        need = at
+    else:
+        if out is None:
+            raise ZstdError("out_offsets needs out")
+        offs = [int(x) for x in out_offsets]
+        if len(offs) != n or any(x < 0 for x in offs):
+            raise ZstdError("out_offsets must hold one non-negative offset per range")
+        table[:n, 2] = np.array(offs, dtype=np.uint64) if n else 0
+        need = max([o + ln for o, ln in zip(offs, lengths)] + [0])
+    return table, n, lengths, need
+
+
 class SeekableStream:
     """Range reads of a zstd seekable stream resident in HBM (any writer's): ``read(offset, length)`` decodes only the frames that cover the range,
     ``read_ranges`` many ranges as one decode batch, ``read_records`` whole frames by index; ``frame_offsets`` is the table it opened.
@@ -582,32 +654,7 @@ class SeekableStream:
         counts (items, inPlace, scratchBytes, copyJobs, passes)."""
         if self.handle is None:
             raise ZstdError("the seekable stream is closed")
-        import numpy as np
-        try:
-            r = np.asarray(ranges if len(ranges) else np.zeros((0, 2), dtype=np.int64))
-        except Exception:
-            raise ZstdError("ranges must be a sequence of (offset, length)")
-        if r.ndim != 2 or r.shape[1] != 2 or r.dtype.kind not in "iu":
-            raise ZstdError("ranges must be a sequence of (offset, length) or an integer array of shape (R, 2)")
-        n = r.shape[0]
-        if n and (r.astype(object) < 0).any():
-            raise ZstdError("ranges must not be negative")
-        table = np.zeros((max(n, 1), 3), dtype=np.uint64)
-        table[:n, :2] = r
-        lengths = [int(x) for x in table[:n, 1]]
-        if out_offsets is None:
-            at = 0
-            for k, ln in enumerate(lengths):
-                table[k, 2] = at; at += ln
-            need = at
-        else:
-            if out is None:
-                raise ZstdError("out_offsets needs out")
-            offs = [int(x) for x in out_offsets]
-            if len(offs) != n or any(x < 0 for x in offs):
-                raise ZstdError("out_offsets must hold one non-negative offset per range")
-            table[:n, 2] = np.array(offs, dtype=np.uint64) if n else 0
-            need = max([o + ln for o, ln in zip(offs, lengths)] + [0])
+        table, n, lengths, need = _ranges_table(ranges, out, out_offsets)
         s = stream if stream is not None else torch.cuda.current_stream()
         with torch.cuda.stream(s):
             if out is None:
@@ -806,3 +853,110 @@ class SeekableStream:
             self.close()
         except Exception:
             pass
+
+
+class SeekableChain:
+    """Reads of version n of a tensor through a CHAIN of typed seekable streams, each version written against its PREDECESSOR
+    (``seekable_compress(v[i], element_size=k, base=v[i - 1])``): ``links`` are ``[full, d1, ..., dn]`` -- v0 as an unfiltered typed stream, then the deltas,
+    oldest first -- or ``[d1, ..., dn]`` with ``base=v0``, 1 ... 16 of them, stream tensors (opened here, closed by ``close``) or open SeekableStreams (the
+    caller's; they stay usable on their own between the chain's calls). ``read`` / ``read_ranges`` have SeekableStream's semantics and return types and
+    give the elements of the LAST version: per link only the frames the ranges touch are decoded, and ONE kernel XORs all links' planes, transposes once and
+    XORs the base -- no version in between is materialised. A frame that fails raises ZstdError naming the range, the link and the frame in that link's
+    table; where several links fail under a range, the earliest link. ``last_gather_stats`` sums over the links, ``passes`` counted once.
+
+    NO LINK NAMES ITS BASE OR ITS PREDECESSOR: links in the wrong order behind a wrong start, a link of another tensor, or another base return wrong
+    elements and no error. Device memory: every link holds at most the scratch limit (see set_scratch_limit) of planar bytes, the chain that many times
+    its links. The base, the streams and the open links stay alive and unchanged while the chain is open; the base must not overlap a read's `out`."""
+
+    def __init__(self, ctx, links, base=None, scratch_limit=None, stream=None):
+        self.ctx, self.links, self._own, self.base = ctx, [], [], None
+        try:
+            for i, link in enumerate(links):
+                if isinstance(link, SeekableStream):
+                    if link.handle is None:
+                        raise ZstdError("seekable chain: link %d is closed" % i)
+                    if link.ctx is not ctx:
+                        raise ZstdError("seekable chain: link %d was opened on another context" % i)
+                else:
+                    link = SeekableStream(ctx, link, stream=stream)
+                    self._own.append(link)
+                self.links.append(link)
+            if not 1 <= len(self.links) <= 16:
+                raise ZstdError("seekable chain: a chain has 1 ... 16 links, not %d" % len(self.links))
+            L, first = ctx.L, self.links[0]
+            self.element_size = int(L.zhip_seekable_element_size(first.handle))
+            self.group_elements = int(L.zhip_seekable_group_elements(first.handle))
+            self.content_size = first.content_size
+            if base is not None:
+                self.base = _base_bytes(base, first.tensor, self.content_size, "seekable chain")
+            self.last_gather_stats, self._scratch_limit = None, scratch_limit
+            if scratch_limit is not None:
+                self.set_scratch_limit(scratch_limit)
+            # the library's own verdict on the chain, now rather than at the first read: a call over no ranges decodes nothing
+            self.read_ranges([], stream=stream)
+        except Exception:
+            self.close()
+            raise
+
+    def set_scratch_limit(self, nbytes):
+        """SeekableStream.set_scratch_limit on EVERY link (the chain's plan is made with link 0's, and every link holds at most that much)"""
+        for link in self.links:
+            link.set_scratch_limit(nbytes)
+        self._scratch_limit = nbytes
+
+    def extended(self, stream_tensor_or_link):
+        """a NEW chain with one more link behind this one's (the next version's delta); this chain stays open, and the links it opened stay its own"""
+        return SeekableChain(self.ctx, self.links + [stream_tensor_or_link], base=self.base, scratch_limit=self._scratch_limit)
+
+    def read(self, offset=0, length=None, out=None, stream=None):
+        """the last version's bytes [offset, offset + length) (length None: to the end) as a uint8 CUDA tensor -- `out`, where given, else a new one"""
+        if length is None:
+            length = self.content_size - offset
+        if offset < 0 or length < 0 or offset + length > self.content_size:
+            raise ZstdError("range %d + %d is outside the content (%d bytes)" % (offset, length, self.content_size))
+        if out is not None:
+            assert out.numel() >= length, "out is shorter than the range"
+        return self.read_ranges([(offset, length)], out, None if out is None else [0], stream)[0]
+
+    def read_ranges(self, ranges, out=None, out_offsets=None, stream=None):
+        """SeekableStream.read_ranges on the last version: a list of views, one per range. Waits for the status"""
+        if any(link.handle is None for link in self.links) or not self.links:
+            raise ZstdError("the seekable chain is closed")
+        table, n, lengths, need = _ranges_table(ranges, out, out_offsets)
+        device = self.links[0].tensor.device
+        s = stream if stream is not None else torch.cuda.current_stream()
+        with torch.cuda.stream(s):
+            if out is None:
+                out = torch.empty(need, dtype=torch.uint8, device=device)
+            status = torch.zeros(2 + 2 * n, dtype=torch.int32, device=device)
+            which = torch.zeros(1 + n, dtype=torch.int32, device=device)
+        DeviceBatchContext._check(out, torch.uint8)
+        L = self.ctx.L
+        stats = _lib.SeekableGatherStats()
+        handles = (C.c_void_p * len(self.links))(*[link.handle.value for link in self.links])
+        rc = L.zhip_seekable_decompress_typed_ranges_chain_device(self.ctx.ctx, handles, len(self.links), None if self.base is None else self.base.data_ptr(),
+                                                                  0 if self.base is None else self.base.numel(), table.ctypes.data, n, out.data_ptr(), out.numel(),
+                                                                  status.data_ptr(), which.data_ptr(), C.byref(stats), s.cuda_stream)
+        if rc:
+            raise ZstdError("seekable chain read failed: %s" % _lib.last_error())
+        self.last_gather_stats = {k: int(getattr(stats, k)) for k, _ in stats._fields_}
+        err = _lib.Error()
+        rc = L.zhip_ctx_sync(self.ctx.ctx, s.cuda_stream, status.data_ptr(), 1, C.byref(err))
+        if rc == _lib.ERR_ZSTD:
+            bad = int(status[1])
+            raise ZstdError("seekable chain read: range %d: link %d: frame %d: %s" % (bad, int(which[1 + bad]), int(status[3 + 2 * bad]), _lib.error_name(err.zstdErr)))
+        if rc:
+            raise ZstdError("HIP backend failure: %s" % _lib.last_error())
+        return [out[int(table[k, 2]):int(table[k, 2]) + lengths[k]] for k in range(n)]
+
+    def close(self):
+        """closes the links this chain opened; the caller's SeekableStreams stay open"""
+        for link in self._own:
+            link.close()
+        self._own, self.links = [], []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

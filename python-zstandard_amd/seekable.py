@@ -16,11 +16,15 @@ The marker names the filter, so the readers return the elements as before; ``ele
 beside its base model: the planes are those of data XOR base, bytewise, and since versions differ in the low mantissa bits and almost nowhere else the high
 planes become runs of zeros (bf16 streams 2-12 x smaller than without, fp32 1.3-1.8 x). THE STREAM DOES NOT NAME ITS BASE: ``decompress`` and
 ``decompress_ranges`` need the same ``base=`` (without one they raise ZstdError), and with other bytes of the right size they return wrong elements and no
-error. ``elements_to_planes`` / ``planes_to_elements`` take ``base=`` too."""
+error. ``elements_to_planes`` / ``planes_to_elements`` take ``base=`` too.
+
+``decompress_chain`` / ``decompress_ranges_chain`` read the LAST version through a chain of such streams, every version compressed against its predecessor:
+``[compress(v0, element_size=k), compress(v1, element_size=k, base=v0), compress(v2, element_size=k, base=v1), ...]``, or the deltas alone with ``base=v0``
+(``device.SeekableChain``: per link only the frames the ranges touch are decoded, one kernel XORs all links). No stream names its predecessor either."""
 import torch
 
 from .backend_hip import ZstdError
-from .device import DeviceBatchContext, SeekableStream
+from .device import DeviceBatchContext, SeekableChain, SeekableStream
 
 
 def _to_device(data):
@@ -152,6 +156,43 @@ def decompress_ranges(data, ranges, base=None, **ctx_kw):
             st.close()
     finally:
         ctx.close()
+
+
+def _with_chain(streams, base, ctx_kw, call):
+    streams = list(streams)
+    if any(len(s) == 0 for s in streams):
+        raise ZstdError("not a seekable stream: empty input")
+    ctx = DeviceBatchContext(**ctx_kw)
+    try:
+        chain = SeekableChain(ctx, [_to_device(s) for s in streams], base=None if base is None else _to_device(base))
+        try:
+            return call(chain)
+        finally:
+            chain.close()
+    finally:
+        ctx.close()
+
+
+def decompress_chain(streams, offset=0, length=None, base=None, **ctx_kw):
+    """bytes [offset, offset + length) (length None: to the end) of the LAST version of a tensor stored as a chain of typed streams, oldest first: an
+    unfiltered typed stream of the first version and then every version ``compress(..., base=)``-ed against its predecessor -- or those alone, with base= the
+    bytes of the first version. 1 ... 16 streams. No stream names its predecessor: another order behind a wrong start, a foreign stream or another base
+    give wrong elements and no error. Raises ZstdError as ``decompress`` does; a refusal or a failing frame names the link."""
+    return _with_chain(streams, base, ctx_kw, lambda chain: chain.read(offset, length).cpu().numpy().tobytes())
+
+
+def decompress_ranges_chain(streams, ranges, base=None, **ctx_kw):
+    """``decompress_ranges`` through a chain (``decompress_chain``): the last version's bytes of every (offset, length), as a list of bytes"""
+    def call(chain):
+        views = chain.read_ranges(ranges)
+        if not views:
+            return []
+        host = torch.cat(views).cpu().numpy().tobytes()
+        out, at = [], 0
+        for v in views:
+            out.append(host[at:at + v.numel()]); at += v.numel()
+        return out
+    return _with_chain(streams, base, ctx_kw, call)
 
 
 def compress_records(records, level=3, checksum=False, match_finder="libzstd", **ctx_kw):
