@@ -10,9 +10,12 @@
 // does NOT name its base: reading it with another base returns wrong elements with status 0.
 // The standard seek table comes last: the stream is an ordinary seekable stream whose content is the PLANAR bytes.
 // What is here: the two transposition kernels (interleaved -> planar with the record table of the plane frames, planar -> interleaved driven by a job table),
-// the two kernels that seal a stream the records call has written, the status reducer of the typed read, and the host plan of that read. One-wave
+// their forms under the delta and xor filters and through a chain of links, the two kernels that seal a stream the records call has written, the status reducers
+// of the typed reads, and the host plan of a read. Every filter has kernels of its own, instantiated from ONE split tile loop (zsk_split_tiles), ONE job lookup
+// (zsk_join_job) and ONE transposition (zsk_planar_word) -- DESIGN.md 9.9 says which source forms keep the kernels' registers and which do not. One-wave
 // workgroups written against zhip_device.hpp like zhip_seekable.hpp, so the same bodies run under the host wave emulator (tests/emu/emu_seekable_typed.cpp).
 #pragma once
+#include <type_traits>
 #include "zhip_seekable.hpp"
 
 #define ZSK_PLANES_MAGIC 0x184D2A5Du
@@ -112,40 +115,47 @@ template <int K> ZH_DEV void zsk_split16(const uint8_t* s, uint8_t* d, uint64_t 
     zsk_load16<K>(s, w);
     zsk_split16_store<K>(w, d, plane);
 }
-// the mirror image: 16 bytes of each of the K planes (plane p at s + p * plane) -> 16 elements at d
-template <int K> ZH_DEV void zsk_join16(const uint8_t* s, uint64_t plane, uint8_t* d)
+// the mirror image: 16 bytes of each of the K planes (plane p at s + p * plane) -> 16 elements. In three steps: the K planes' words as they lie (plane p's
+// four at w + 4 p), their transposition into the 4 K words of the 16 elements, and the store -- the filters work on the words between the steps
+template <int K> ZH_DEV void zsk_planar_load16(const uint8_t* s, uint64_t plane, uint32_t* w)
 {
-    uint32_t w[K][4];
 #pragma unroll
-    for (int p = 0; p < K; p++) zsk_words(zh_ld128(s + p * plane), w[p]);
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-        uint32_t o[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int W = 4 * j + q;                   // the output word: bytes 4W .. 4W + 3 of the 16 elements
-            if (K == 2) o[q] = zsk_perm(w[1][W >> 1], w[0][W >> 1], W & 1 ? 0x07030602u : 0x05010400u);
-            else { const int per = K / 4, i = W / per, p0 = (W % per) * 4; o[q] = zsk_byte_of4(w[p0][i >> 2], w[p0 + 1][i >> 2], w[p0 + 2][i >> 2], w[p0 + 3][i >> 2], i & 3); }
-        }
-        zh_st128(d + 16 * j, zsk_v16(o));
-    }
+    for (int p = 0; p < K; p++) zsk_words(zh_ld128(s + p * plane), w + 4 * p);
 }
-// the same with the 4 K words of the 16 elements kept in registers, and their store: the delta join sums between the two
-template <int K> ZH_DEV void zsk_join16_words(const uint8_t* s, uint64_t plane, uint32_t* o)
+// output word W, bytes 4W .. 4W + 3 of the 16 elements: THE transposition, written once
+template <int K> ZH_DEV uint32_t zsk_planar_word(const uint32_t* w, int W)
 {
-    uint32_t w[K][4];
+    if constexpr (K == 2) return zsk_perm(w[4 + (W >> 1)], w[W >> 1], W & 1 ? 0x07030602u : 0x05010400u);
+    else { const int per = K / 4, i = W / per, p0 = (W % per) * 4, at = 4 * p0 + (i >> 2); return zsk_byte_of4(w[at], w[at + 4], w[at + 8], w[at + 12], i & 3); }
+}
+template <int K> ZH_DEV void zsk_planar_words(const uint32_t* w, uint32_t* o)
+{
 #pragma unroll
-    for (int p = 0; p < K; p++) zsk_words(zh_ld128(s + p * plane), w[p]);
-#pragma unroll
-    for (int W = 0; W < 4 * K; W++) {                  // the output word: bytes 4W .. 4W + 3 of the 16 elements
-        if (K == 2) o[W] = zsk_perm(w[1][W >> 1], w[0][W >> 1], W & 1 ? 0x07030602u : 0x05010400u);
-        else { const int per = K / 4, i = W / per, p0 = (W % per) * 4; o[W] = zsk_byte_of4(w[p0][i >> 2], w[p0 + 1][i >> 2], w[p0 + 2][i >> 2], w[p0 + 3][i >> 2], i & 3); }
-    }
+    for (int W = 0; W < 4 * K; W++) o[W] = zsk_planar_word<K>(w, W);
 }
 template <int K> ZH_DEV void zsk_store16(const uint32_t* o, uint8_t* d)
 {
 #pragma unroll
     for (int j = 0; j < K; j++) zh_st128(d + 16 * j, zsk_v16(o + 4 * j));
+}
+template <int K> ZH_DEV void zsk_join16_words(const uint8_t* s, uint64_t plane, uint32_t* o)
+{
+    uint32_t w[4 * K];
+    zsk_planar_load16<K>(s, plane, w);
+    zsk_planar_words<K>(w, o);
+}
+// the plain join's: 16 bytes go out as soon as their four words stand (all 4 K words first would cost it 24 VGPRs: DESIGN.md 9.9)
+template <int K> ZH_DEV void zsk_join16(const uint8_t* s, uint64_t plane, uint8_t* d)
+{
+    uint32_t w[4 * K];
+    zsk_planar_load16<K>(s, plane, w);
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        uint32_t o[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) o[q] = zsk_planar_word<K>(w, 4 * j + q);
+        zh_st128(d + 16 * j, zsk_v16(o));
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ split: interleaved -> planar, and the plane frames' records
@@ -171,19 +181,25 @@ ZH_DEV void zsk_planes_records(const ZskPlanesArgs& a)
         a.records[2 * i] = g * a.group * a.k + (i % a.k) * e; a.records[2 * i + 1] = e;
     }
 }
-// a workgroup per tile of ZSK_PLANE_TILE elements of one group (grid-stride over the tiles of all groups); a lane per plane frame writes its record
-ZH_DEV void zsk_planes_split_body(const ZskPlanesArgs& a)
+// THE split tile loop, of all three split kernels: a workgroup per tile of ZSK_PLANE_TILE elements of one group (grid-stride over the tiles of all groups),
+// lane(K, at, e, i0) on every lane of the wave -- K the element size as a type, at the group's byte offset in the source, the base and the planes, e its
+// elements, i0 the lane's first one; no lane leaves in front of it (the delta lane shuffles). Then a lane per plane frame writes its record
+template <class F> ZH_DEV void zsk_split_tiles(const ZskPlanesArgs& a, F lane)
 {
     const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
     const uint64_t tiles = (uint64_t)a.nGroups * tpg;
     for (uint64_t t = zh_block(); t < tiles; t += zh_nblocks()) {
         const uint64_t g = t / tpg, at = g * a.group * a.k;
         const uint32_t e = zsk_group_len(a.elements, a.group, g), i0 = (uint32_t)(t % tpg) * ZSK_PLANE_TILE + zh_lane() * 16;
-        if (a.k == 2) zsk_split_lane<2>(a.src + at, a.dst + at, e, i0);
-        else if (a.k == 4) zsk_split_lane<4>(a.src + at, a.dst + at, e, i0);
-        else zsk_split_lane<8>(a.src + at, a.dst + at, e, i0);
+        if (a.k == 2) lane(std::integral_constant<int, 2>(), at, e, i0);
+        else if (a.k == 4) lane(std::integral_constant<int, 4>(), at, e, i0);
+        else lane(std::integral_constant<int, 8>(), at, e, i0);
     }
     zsk_planes_records(a);
+}
+ZH_DEV void zsk_planes_split_body(const ZskPlanesArgs& a)
+{
+    zsk_split_tiles(a, [&](auto K, uint64_t at, uint32_t e, uint32_t i0) { zsk_split_lane<K()>(a.src + at, a.dst + at, e, i0); });
 }
 
 // ------------------------------------------------------------------------------------------------ split with the delta filter
@@ -247,16 +263,7 @@ template <int K> ZH_DEV void zsk_split_delta_lane(const uint8_t* s, uint8_t* d, 
 }
 ZH_DEV void zsk_planes_split_delta_body(const ZskPlanesArgs& a)
 {
-    const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
-    const uint64_t tiles = (uint64_t)a.nGroups * tpg;
-    for (uint64_t t = zh_block(); t < tiles; t += zh_nblocks()) {
-        const uint64_t g = t / tpg, at = g * a.group * a.k;
-        const uint32_t e = zsk_group_len(a.elements, a.group, g), i0 = (uint32_t)(t % tpg) * ZSK_PLANE_TILE + zh_lane() * 16;
-        if (a.k == 2) zsk_split_delta_lane<2>(a.src + at, a.dst + at, e, i0);
-        else if (a.k == 4) zsk_split_delta_lane<4>(a.src + at, a.dst + at, e, i0);
-        else zsk_split_delta_lane<8>(a.src + at, a.dst + at, e, i0);
-    }
-    zsk_planes_records(a);
+    zsk_split_tiles(a, [&](auto K, uint64_t at, uint32_t e, uint32_t i0) { zsk_split_delta_lane<K()>(a.src + at, a.dst + at, e, i0); });
 }
 
 // ------------------------------------------------------------------------------------------------ split with the xor-with-base filter
@@ -281,16 +288,7 @@ template <int K> ZH_DEV void zsk_split_xor_lane(const uint8_t* s, const uint8_t*
 ZH_DEV void zsk_planes_split_xor_body(const ZskPlanesXorArgs& x)
 {
     const ZskPlanesArgs& a = x.p;
-    const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
-    const uint64_t tiles = (uint64_t)a.nGroups * tpg;
-    for (uint64_t t = zh_block(); t < tiles; t += zh_nblocks()) {
-        const uint64_t g = t / tpg, at = g * a.group * a.k;
-        const uint32_t e = zsk_group_len(a.elements, a.group, g), i0 = (uint32_t)(t % tpg) * ZSK_PLANE_TILE + zh_lane() * 16;
-        if (a.k == 2) zsk_split_xor_lane<2>(a.src + at, x.base + at, a.dst + at, e, i0);
-        else if (a.k == 4) zsk_split_xor_lane<4>(a.src + at, x.base + at, a.dst + at, e, i0);
-        else zsk_split_xor_lane<8>(a.src + at, x.base + at, a.dst + at, e, i0);
-    }
-    zsk_planes_records(a);
+    zsk_split_tiles(a, [&](auto K, uint64_t at, uint32_t e, uint32_t i0) { zsk_split_xor_lane<K()>(a.src + at, x.base + at, a.dst + at, e, i0); });
 }
 
 // ------------------------------------------------------------------------------------------------ join: planar -> interleaved, by jobs
@@ -314,33 +312,28 @@ template <int K> ZH_DEV void zsk_join_lane(const uint8_t* s, uint8_t* d, uint64_
     if (n == 16 && from == lo && to == hi) { zsk_join16<K>(s + i0, m, d + (lo - h)); return; }
     for (uint64_t j = from; j < to; j++) d[j - h] = s[(j % K) * m + j / K];      // a job's trimmed first / last element, its last elements, fewer than 16
 }
-// the job of the launch's tile t
-ZH_DEV ZskJoinJob zsk_join_job(const ZskJoinArgs& a, uint32_t tpg, uint64_t t)
+// THE job lookup, of every join kernel: the job of the launch's tile t. content(j) is called with the job's index where there is a job table -- what stands
+// parallel to the jobs (the xor joins' content offsets) is fetched there; of a whole buffer's group it is job.planar
+template <class C> ZH_DEV ZskJoinJob zsk_join_job(const ZskJoinArgs& a, uint32_t tpg, uint64_t t, C content)
 {
     ZskJoinJob job;
     if (a.jobs) {
         uint32_t lo = 0, hi = a.nJobs;                                      // the last job whose tilePrefix <= t
         while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.jobs[mid].tilePrefix <= t) lo = mid; else hi = mid; }
         job = a.jobs[lo];
+        content(lo);
     } else {
         const uint64_t g = t / tpg;
         job.planar = job.dst = g * a.group * a.k; job.m = zsk_group_len(a.elements, a.group, g); job.tilePrefix = g * tpg; job.h = job.t = 0; job.skip = 0;
     }
     return job;
 }
+ZH_DEV ZskJoinJob zsk_join_job(const ZskJoinArgs& a, uint32_t tpg, uint64_t t) { return zsk_join_job(a, tpg, t, [](uint32_t) {}); }
 ZH_DEV void zsk_planes_join_body(const ZskJoinArgs& a)
 {
     const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
     for (uint64_t t = zh_block(); t < a.tiles; t += zh_nblocks()) {
-        ZskJoinJob job;
-        if (a.jobs) {
-            uint32_t lo = 0, hi = a.nJobs;                                  // the last job whose tilePrefix <= t
-            while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.jobs[mid].tilePrefix <= t) lo = mid; else hi = mid; }
-            job = a.jobs[lo];
-        } else {
-            const uint64_t g = t / tpg;
-            job.planar = job.dst = g * a.group * a.k; job.m = zsk_group_len(a.elements, a.group, g); job.tilePrefix = g * tpg; job.h = job.t = 0;
-        }
+        const ZskJoinJob job = zsk_join_job(a, tpg, t);
         const uint64_t i0 = (t - job.tilePrefix) * ZSK_PLANE_TILE + zh_lane() * 16;
         if (a.k == 2) zsk_join_lane<2>(a.planar + job.planar, a.dst + job.dst, job.m, job.h, job.t, i0);
         else if (a.k == 4) zsk_join_lane<4>(a.planar + job.planar, a.dst + job.dst, job.m, job.h, job.t, i0);
@@ -484,15 +477,9 @@ ZH_DEV void zsk_planes_join_xor_body(const ZskJoinXorArgs& x)
     const ZskJoinArgs& a = x.j;
     const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
     for (uint64_t t = zh_block(); t < a.tiles; t += zh_nblocks()) {
-        ZskJoinJob job; uint64_t content;
-        if (a.jobs) {
-            uint32_t lo = 0, hi = a.nJobs;                                  // the last job whose tilePrefix <= t
-            while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.jobs[mid].tilePrefix <= t) lo = mid; else hi = mid; }
-            job = a.jobs[lo]; content = x.content[lo];
-        } else {
-            const uint64_t g = t / tpg;
-            job.planar = job.dst = content = g * a.group * a.k; job.m = zsk_group_len(a.elements, a.group, g); job.tilePrefix = g * tpg; job.h = job.t = 0;
-        }
+        uint64_t content;
+        const ZskJoinJob job = zsk_join_job(a, tpg, t, [&](uint32_t j) { content = x.content[j]; });
+        if (!a.jobs) content = job.planar;
         const uint64_t i0 = (t - job.tilePrefix) * ZSK_PLANE_TILE + zh_lane() * 16;
         if (a.k == 2) zsk_join_xor_lane<2>(a.planar + job.planar, x.base + content, a.dst + job.dst, job.m, job.h, job.t, i0);
         else if (a.k == 4) zsk_join_xor_lane<4>(a.planar + job.planar, x.base + content, a.dst + job.dst, job.m, job.h, job.t, i0);
@@ -509,20 +496,6 @@ ZH_DEV void zsk_planes_join_xor_body(const ZskJoinXorArgs& x)
 // last element and the tails go byte by byte; nothing of the base or of a planar buffer outside the stored bytes is read.
 #define ZSK_CHAIN_MAX 16u
 struct ZskJoinChainArgs { ZskJoinArgs j; const uint8_t* planar[ZSK_CHAIN_MAX]; uint32_t nLinks; const uint8_t* base; const uint64_t* content; };      // j.planar is not read; base NULL: none, content not read
-// zsk_join16_words in its two halves: the K planes' words as they lie (plane p's four at w + 4 p), and their transposition into the 16 elements' words
-template <int K> ZH_DEV void zsk_planar_load16(const uint8_t* s, uint64_t plane, uint32_t* w)
-{
-#pragma unroll
-    for (int p = 0; p < K; p++) zsk_words(zh_ld128(s + p * plane), w + 4 * p);
-}
-template <int K> ZH_DEV void zsk_planar_words(const uint32_t* w, uint32_t* o)
-{
-#pragma unroll
-    for (int W = 0; W < 4 * K; W++) {                  // the output word: bytes 4W .. 4W + 3 of the 16 elements
-        if (K == 2) o[W] = zsk_perm(w[4 + (W >> 1)], w[W >> 1], W & 1 ? 0x07030602u : 0x05010400u);
-        else { const int per = K / 4, i = W / per, p0 = (W % per) * 4; o[W] = zsk_byte_of4(w[4 * p0 + (i >> 2)], w[4 * (p0 + 1) + (i >> 2)], w[4 * (p0 + 2) + (i >> 2)], w[4 * (p0 + 3) + (i >> 2)], i & 3); }
-    }
-}
 // at: the job's offset in every planar buffer; b: the base at the job's content offset, or NULL
 template <int K> ZH_DEV void zsk_join_chain_lane(const ZskJoinChainArgs& x, uint64_t at, const uint8_t* b, uint8_t* d, uint64_t m, uint32_t h, uint32_t t, uint64_t i0)
 {
@@ -567,16 +540,9 @@ ZH_DEV void zsk_planes_join_chain_body(const ZskJoinChainArgs& x)
     const ZskJoinArgs& a = x.j;
     const uint32_t tpg = (a.group + ZSK_PLANE_TILE - 1) / ZSK_PLANE_TILE;
     for (uint64_t t = zh_block(); t < a.tiles; t += zh_nblocks()) {
-        ZskJoinJob job; uint64_t content = 0;
-        if (a.jobs) {
-            uint32_t lo = 0, hi = a.nJobs;                                  // the last job whose tilePrefix <= t
-            while (hi - lo > 1) { const uint32_t mid = lo + (hi - lo) / 2; if (a.jobs[mid].tilePrefix <= t) lo = mid; else hi = mid; }
-            job = a.jobs[lo];
-            if (x.base) content = x.content[lo];
-        } else {
-            const uint64_t g = t / tpg;
-            job.planar = job.dst = content = g * a.group * a.k; job.m = zsk_group_len(a.elements, a.group, g); job.tilePrefix = g * tpg; job.h = job.t = 0;
-        }
+        uint64_t content = 0;
+        const ZskJoinJob job = zsk_join_job(a, tpg, t, [&](uint32_t j) { if (x.base) content = x.content[j]; });
+        if (!a.jobs) content = job.planar;
         const uint64_t i0 = (t - job.tilePrefix) * ZSK_PLANE_TILE + zh_lane() * 16;
         const uint8_t* const b = x.base ? x.base + content : nullptr;
         if (a.k == 2) zsk_join_chain_lane<2>(x, job.planar, b, a.dst + job.dst, job.m, job.h, job.t, i0);

@@ -1,7 +1,8 @@
 // zhip_seekable_typed_calls.hpp -- HOST side of the typed seekable calls, free of HIP, beside zhip_seekable_calls.hpp: the checks, the layouts and the
 // sequences as function templates over a backend. The typed calls are built AROUND the plain ones -- typed compress is the split kernel, the records call on
 // the staging buffer and the seal; a typed read is the many-ranges call into a planar buffer, the join kernel and the status reducer -- so zsk_compress_records,
-// zsk_open and zsk_ranges run as they are, with their own kernels, areas and traces, and nothing of zhip_seekable_calls.hpp changes.
+// zsk_open and zsk_ranges run as they are, with their own kernels, areas and traces, and nothing of zhip_seekable_calls.hpp changes. What the filters' entry
+// points share is written once: zsk_launch_split picks the split kernel, zsk_typed_read_setup plans a read and uploads its tables.
 //
 // The backend is one of zhip_seekable_calls.hpp's, extended by:
 //     int  reserve_typed(ZskTypedArea, size_t bytes, uint8_t** base)                    as reserve(); the areas are kept between calls like the others
@@ -71,18 +72,26 @@ static inline int zsk_base_check(const char* what, const void* d_base, uint64_t 
     return 0;
 }
 
+// the split kernels' arguments (records, d_base: NULL where there are none), and THE split of a filter: the xor kernel takes the struct, the other two its ZskPlanesArgs
+static inline ZskPlanesXorArgs zsk_split_args(const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst, const void* d_base, uint8_t* records)
+{
+    ZskPlanesXorArgs x; memset(&x, 0, sizeof x);
+    ZskPlanesArgs& a = x.p;
+    a.src = (const uint8_t*)d_src; a.dst = (uint8_t*)d_dst; a.elements = size / k; a.k = k; a.group = frameSize; a.nGroups = (uint32_t)zsk_frame_count(a.elements, frameSize);
+    a.records = (uint64_t*)records; x.base = (const uint8_t*)d_base;
+    return x;
+}
+template <class B> void zsk_launch_split(B& b, uint32_t filter, const ZskPlanesXorArgs& x, uint32_t grid)
+{
+    if (filter == ZSK_FILTER_XOR_BASE) b.launch_typed(ZSKT_K_PLANES_SPLIT_XOR, grid, &x);
+    else b.launch_typed(filter == ZSK_FILTER_DELTA ? ZSKT_K_PLANES_SPLIT_DELTA : ZSKT_K_PLANES_SPLIT, grid, &x.p);
+}
 // The whole-buffer kernels on their own: interleaved -> planar (no records) and back. d_base: the *_base_ calls' (filter ZSK_FILTER_XOR_BASE), `size` bytes
 template <class B> int zsk_planes_split(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, void* d_dst, uint32_t filter = ZSK_FILTER_NONE, const void* d_base = nullptr)
 {
     if (int rc = zsk_planes_check(ctx && (!size || (d_src && d_dst)), size, k, frameSize, b.err, filter, d_base != nullptr)) return rc;
     if (!size) return 0;
-    ZskPlanesXorArgs x; memset(&x, 0, sizeof x);
-    ZskPlanesArgs& a = x.p;
-    a.src = (const uint8_t*)d_src; a.dst = (uint8_t*)d_dst; a.elements = size / k; a.k = k; a.group = frameSize; a.nGroups = (uint32_t)zsk_frame_count(a.elements, frameSize);
-    x.base = (const uint8_t*)d_base;
-    const uint32_t grid = zsk_tile_grid(b.numCU, zsk_planes_tiles(a.elements, frameSize), 0);
-    if (filter == ZSK_FILTER_XOR_BASE) b.launch_typed(ZSKT_K_PLANES_SPLIT_XOR, grid, &x);
-    else b.launch_typed(filter == ZSK_FILTER_DELTA ? ZSKT_K_PLANES_SPLIT_DELTA : ZSKT_K_PLANES_SPLIT, grid, &a);
+    zsk_launch_split(b, filter, zsk_split_args(d_src, size, k, frameSize, d_dst, d_base, nullptr), zsk_tile_grid(b.numCU, zsk_planes_tiles(size / k, frameSize), 0));
     return b.check();
 }
 template <class B> int zsk_planes_split_base(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, const void* d_base, void* d_dst)
@@ -119,7 +128,6 @@ template <class B> int zsk_planes_join(B& b, bool ctx, const void* d_src, uint64
     zsk_launch_join(b, filter, a, zsk_frame_count(a.elements, frameSize), sums);
     return b.check();
 }
-
 template <class B> int zsk_planes_join_base(B& b, bool ctx, const void* d_src, uint64_t size, uint32_t k, uint32_t frameSize, const void* d_base, void* d_dst)
 {
     if (int rc = zsk_base_check("planes join", d_base, size, k, d_dst, size, b.err)) return rc;
@@ -141,13 +149,7 @@ template <class B> int zsk_typed_compress(B& b, bool ctx, const void* d_src, uin
     if (n) if (int rc = b.reserve_typed(ZSKT_A_RECORDS, (size_t)n * 16, &records)) return rc;
     if (int rc = b.reserve_typed(ZSKT_A_STASH, (size_t)zsk_seal_stash_bytes(n, checksum), &stash)) return rc;
     if (n) {
-        ZskPlanesXorArgs x; memset(&x, 0, sizeof x);
-        ZskPlanesArgs& a = x.p;
-        a.src = (const uint8_t*)d_src; a.dst = staging; a.elements = elements; a.k = k; a.group = frameSize; a.nGroups = (uint32_t)nGroups; a.records = (uint64_t*)records;
-        x.base = (const uint8_t*)d_base;
-        const uint32_t grid = zsk_tile_grid(b.numCU, zsk_planes_tiles(elements, frameSize), n);
-        if (filter == ZSK_FILTER_XOR_BASE) b.launch_typed(ZSKT_K_PLANES_SPLIT_XOR, grid, &x);
-        else b.launch_typed(filter == ZSK_FILTER_DELTA ? ZSKT_K_PLANES_SPLIT_DELTA : ZSKT_K_PLANES_SPLIT, grid, &a);
+        zsk_launch_split(b, filter, zsk_split_args(d_src, srcSize, k, frameSize, staging, d_base, records), zsk_tile_grid(b.numCU, zsk_planes_tiles(elements, frameSize), n));
         if (int rc = b.check()) return rc;
     }
     const uint64_t extra = ZSK_MARKER + zsk_entry_size(checksum);
@@ -199,6 +201,27 @@ static inline ZskTypedReadLayout zsk_typed_read_layout(size_t J, size_t R, size_
     return l;
 }
 
+// THE read setup, of the typed read and of the chain read: the plan under `filter` from h's offsets and scratch limit, the tables' layout, every planar range's place
+// in a status area of *statusInts ints (0 on entry), and the tables on the device at *t, uploaded through the pinned area. The other areas are the callers'
+template <class B> int zsk_typed_read_setup(B& b, const ZskTypedOpened* h, const uint64_t* rg, size_t R, uint32_t filter, ZskTypedPlan* out, ZskTypedReadLayout* layout, size_t* statusInts, uint8_t** t)
+{
+    ZskTypedPlan& plan = *out; size_t& ints = *statusInts;
+    zsk_typed_plan(h->dOff.data(), h->elementSize, h->groupElements, rg, R, h->scratchLimit, &plan, filter);
+    const size_t J = plan.jobs.size(), Q = plan.planar.size() / 3;
+    const ZskTypedReadLayout l = *layout = zsk_typed_read_layout(J, R, Q, plan.content.size());
+    std::vector<uint32_t> pairAt(Q); uint8_t* pin = nullptr;
+    for (const ZskTypedPass& p : plan.passes) { for (uint32_t q = p.q0; q < p.q1; q++) pairAt[q] = (uint32_t)(ints + 2 + 2 * (q - p.q0)); ints += 2 + 2 * (size_t)(p.q1 - p.q0); }
+    if (int rc = b.reserve_typed(ZSKT_A_TABLES, l.tableBytes, t)) return rc;
+    if (int rc = b.reserve(ZSK_A_PIN, l.tableBytes, &pin)) return rc;
+    memcpy(pin + l.oJobs, plan.jobs.data(), J * sizeof(ZskJoinJob));
+    memcpy(pin + l.oOwner, plan.owner.data(), R * 8);
+    memcpy(pin + l.oPairAt, pairAt.data(), Q * 4);
+    memcpy(pin + l.oContent, plan.content.data(), plan.content.size() * 8);
+    return b.copy(*t, pin, l.tableBytes, ZSK_COPY_FROM_PIN);
+}
+// a pass's many-ranges statistics into the typed call's (`passes` is the typed call's own count)
+static inline void zsk_add_stats(zhip_seekable_gather_stats* sum, const zhip_seekable_gather_stats& one) { if (sum) { sum->items += one.items; sum->inPlace += one.inPlace; sum->scratchBytes += one.scratchBytes; sum->copyJobs += one.copyJobs; } }
+
 // R user ranges in element order: per pass of the plan the many-ranges call into the planar buffer and the join kernel (the handle's filter picks it: under
 // delta the three launches of zsk_launch_join); then the status reducer.
 // stats (where given) receives the sums over the passes' many-ranges calls, `passes` counting the typed passes.
@@ -214,16 +237,10 @@ template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h,
     if (stats) memset(stats, 0, sizeof *stats);
     if (!any) return b.zero(d_status, (2 + 2 * R) * sizeof(int32_t));
 
-    ZskTypedPlan plan;
-    zsk_typed_plan(h->dOff.data(), h->elementSize, h->groupElements, rg, R, h->scratchLimit, &plan, h->filter);
-    const size_t J = plan.jobs.size(), Q = plan.planar.size() / 3, nPass = plan.passes.size();
-    const ZskTypedReadLayout l = zsk_typed_read_layout(J, R, Q, plan.content.size());
-    std::vector<uint32_t> pairAt(Q);
-    size_t statusInts = 0;
-    for (const ZskTypedPass& p : plan.passes) { for (uint32_t q = p.q0; q < p.q1; q++) pairAt[q] = (uint32_t)(statusInts + 2 + 2 * (q - p.q0)); statusInts += 2 + 2 * (size_t)(p.q1 - p.q0); }
-    uint8_t* P = nullptr; uint8_t* t = nullptr; uint8_t* st = nullptr; uint8_t* pin = nullptr;
+    ZskTypedPlan plan; ZskTypedReadLayout l; size_t statusInts = 0; uint8_t* t = nullptr;
+    if (int rc = zsk_typed_read_setup(b, h, rg, R, h->filter, &plan, &l, &statusInts, &t)) return rc;
+    uint8_t* P = nullptr; uint8_t* st = nullptr;
     if (int rc = b.reserve_typed(ZSKT_A_PLANAR, (size_t)plan.pMax, &P)) return rc;
-    if (int rc = b.reserve_typed(ZSKT_A_TABLES, l.tableBytes, &t)) return rc;
     if (int rc = b.reserve_typed(ZSKT_A_STATUS, statusInts * 4, &st)) return rc;
     uint8_t* sums = nullptr;
     if (h->filter == ZSK_FILTER_DELTA) {
@@ -231,20 +248,14 @@ template <class B> int zsk_typed_ranges(B& b, bool ctx, const ZskTypedOpened* h,
         for (const ZskTypedPass& p : plan.passes) if (p.tiles > most) most = p.tiles;
         if (int rc = b.reserve_typed(ZSKT_A_TILESUMS, (size_t)most * 8, &sums)) return rc;
     }
-    if (int rc = b.reserve(ZSK_A_PIN, l.tableBytes, &pin)) return rc;
-    memcpy(pin + l.oJobs, plan.jobs.data(), J * sizeof(ZskJoinJob));
-    memcpy(pin + l.oOwner, plan.owner.data(), R * 8);
-    memcpy(pin + l.oPairAt, pairAt.data(), Q * 4);
-    memcpy(pin + l.oContent, plan.content.data(), plan.content.size() * 8);
-    if (int rc = b.copy(t, pin, l.tableBytes, ZSK_COPY_FROM_PIN)) return rc;
 
     size_t at = 0;
-    for (size_t p = 0; p < nPass; p++) {
-        const ZskTypedPass& ps = plan.passes[p];
+    for (const ZskTypedPass& ps : plan.passes) {
         zhip_seekable_gather_stats one; size_t inner = 0;
         if (int rc = zsk_ranges(b, ctx, h, plan.planar.data() + 3 * (size_t)ps.q0, ps.q1 - ps.q0, P, ps.bytes, (int32_t*)st + at, &one, &inner)) return rc;
         at += 2 + 2 * (size_t)(ps.q1 - ps.q0);
-        if (stats) { stats->items += one.items; stats->inPlace += one.inPlace; stats->scratchBytes += one.scratchBytes; stats->copyJobs += one.copyJobs; stats->passes++; }
+        zsk_add_stats(stats, one);
+        if (stats) stats->passes++;
         ZskJoinArgs a; memset(&a, 0, sizeof a);
         a.planar = P; a.dst = (uint8_t*)d_dst; a.jobs = (const ZskJoinJob*)(t + l.oJobs) + ps.job0; a.nJobs = ps.job1 - ps.job0; a.tiles = ps.tiles; a.k = h->elementSize; a.group = h->groupElements;
         if (h->filter == ZSK_FILTER_XOR_BASE) zsk_launch_join_xor(b, a, d_base, t + l.oContent + 8 * (size_t)ps.job0);
@@ -349,33 +360,20 @@ template <class B> int zsk_typed_ranges_chain(B* const* bs, std::string& err, bo
         return b.check();
     }
 
-    ZskTypedPlan plan;
-    zsk_typed_plan(h->dOff.data(), h->elementSize, h->groupElements, rg, R, h->scratchLimit, &plan, d_base ? ZSK_FILTER_XOR_BASE : ZSK_FILTER_NONE);
-    const size_t J = plan.jobs.size(), Q = plan.planar.size() / 3, nPass = plan.passes.size();
-    const ZskTypedReadLayout l = zsk_typed_read_layout(J, R, Q, plan.content.size());
-    std::vector<uint32_t> pairAt(Q);
-    size_t statusInts = 0;
-    for (const ZskTypedPass& p : plan.passes) { for (uint32_t q = p.q0; q < p.q1; q++) pairAt[q] = (uint32_t)(statusInts + 2 + 2 * (q - p.q0)); statusInts += 2 + 2 * (size_t)(p.q1 - p.q0); }
-    uint8_t* P[ZSK_CHAIN_MAX]; uint8_t* st[ZSK_CHAIN_MAX]; uint8_t* t = nullptr; uint8_t* pin = nullptr;
+    ZskTypedPlan plan; ZskTypedReadLayout l; size_t statusInts = 0; uint8_t* t = nullptr;
+    if (int rc = zsk_typed_read_setup(b, h, rg, R, d_base ? ZSK_FILTER_XOR_BASE : ZSK_FILTER_NONE, &plan, &l, &statusInts, &t)) return rc;
+    uint8_t* P[ZSK_CHAIN_MAX]; uint8_t* st[ZSK_CHAIN_MAX];
     for (size_t i = 0; i < nLinks; i++) {
         if (int rc = bs[i]->reserve_typed(ZSKT_A_PLANAR, (size_t)plan.pMax, &P[i])) return rc;
         if (int rc = bs[i]->reserve_typed(ZSKT_A_STATUS, statusInts * 4, &st[i])) return rc;
     }
-    if (int rc = b.reserve_typed(ZSKT_A_TABLES, l.tableBytes, &t)) return rc;
-    if (int rc = b.reserve(ZSK_A_PIN, l.tableBytes, &pin)) return rc;
-    memcpy(pin + l.oJobs, plan.jobs.data(), J * sizeof(ZskJoinJob));
-    memcpy(pin + l.oOwner, plan.owner.data(), R * 8);
-    memcpy(pin + l.oPairAt, pairAt.data(), Q * 4);
-    memcpy(pin + l.oContent, plan.content.data(), plan.content.size() * 8);
-    if (int rc = b.copy(t, pin, l.tableBytes, ZSK_COPY_FROM_PIN)) return rc;
 
     size_t at = 0;
-    for (size_t p = 0; p < nPass; p++) {
-        const ZskTypedPass& ps = plan.passes[p];
+    for (const ZskTypedPass& ps : plan.passes) {
         for (size_t i = 0; i < nLinks; i++) {
             zhip_seekable_gather_stats one; size_t inner = 0;
             if (int rc = zsk_ranges(*bs[i], ctx, links[i], plan.planar.data() + 3 * (size_t)ps.q0, ps.q1 - ps.q0, P[i], ps.bytes, (int32_t*)st[i] + at, &one, &inner)) return rc;
-            if (stats) { stats->items += one.items; stats->inPlace += one.inPlace; stats->scratchBytes += one.scratchBytes; stats->copyJobs += one.copyJobs; }
+            zsk_add_stats(stats, one);
         }
         at += 2 + 2 * (size_t)(ps.q1 - ps.q0);
         if (stats) stats->passes++;
@@ -384,7 +382,7 @@ template <class B> int zsk_typed_ranges_chain(B* const* bs, std::string& err, bo
         a.planar = P[0]; a.dst = (uint8_t*)d_dst; a.jobs = (const ZskJoinJob*)(t + l.oJobs) + ps.job0; a.nJobs = ps.job1 - ps.job0; a.tiles = ps.tiles; a.k = h->elementSize; a.group = h->groupElements;
         for (size_t i = 0; i < nLinks; i++) x.planar[i] = P[i];
         x.nLinks = (uint32_t)nLinks; x.base = (const uint8_t*)d_base; x.content = d_base ? (const uint64_t*)(t + l.oContent) + ps.job0 : nullptr;
-        b.launch_typed(ZSKT_K_PLANES_JOIN_CHAIN, zsk_tile_grid(b.numCU, a.tiles, 0), &x);
+        b.launch_typed(ZSKT_K_PLANES_JOIN_CHAIN, zsk_tile_grid(b.numCU, ps.tiles, 0), &x);
         if (int rc = b.check()) return rc;
     }
     s.s.owner = (const uint32_t*)(t + l.oOwner); s.s.pairAt = (const uint32_t*)(t + l.oPairAt);

@@ -1,21 +1,15 @@
-// tests/emu/delta_planes_main.cpp -- the stand-alone sanitizer program of the delta filter's kernels (tests/emu/build_asan_delta.sh): the split-with-delta, tile
+// tests/emu/delta_planes_main.cpp -- the stand-alone sanitizer program of the delta filter's kernels (tests/emu/build_asan_planes.sh): the split-with-delta, tile
 // sums, tile offsets and join-scan-store bodies of python-zstandard_amd/csrc/zhip_seekable_typed.hpp under the host wave emulator, every buffer a heap
 // allocation of exactly the bytes the kernel may touch, at byte offsets 0, 1 and 3 from the allocation -- a read or a write one byte outside is the
 // sanitizer's finding. The results are checked against plain loops. Exit 0: every case held. Test infrastructure only.
 #include "emu_seekable_delta.cpp"
+#include "exact_buffers.hpp"
 
-static uint32_t g_seed = 54321;
-static uint8_t next_byte() { g_seed = g_seed * 1664525u + 1013904223u; return (uint8_t)(g_seed >> 24); }
-// `n` bytes at `offset` bytes into an allocation of exactly offset + n
-struct Exact {
-    std::unique_ptr<uint8_t[]> p; uint8_t* at;
-    Exact(size_t n, size_t offset, int fill) : p(new uint8_t[n + offset]), at(p.get() + offset) { for (size_t i = 0; i < n; i++) at[i] = fill == 0 ? 0x5A : fill == 1 ? next_byte() : 0xFF; }
-};
-static int fail(const char* what, uint32_t k, uint64_t m, uint32_t off) { fprintf(stderr, "%s: k = %u, m = %llu, offset %u\n", what, k, (unsigned long long)m, off); return 1; }
 static uint64_t element(const uint8_t* p, uint32_t k) { uint64_t v = 0; for (uint32_t b = 0; b < k; b++) v |= (uint64_t)p[b] << (8 * b); return v; }
 
 int main()
 {
+    g_seed = 54321;
     static const uint32_t sizes[] = {1, 15, 16, 17, 1023, 1024, 1025, 2067, 3077}, lasts[] = {1, 15, 17}, offsets[] = {0, 1, 3}, ks[] = {2, 4, 8};
     int cases = 0, shape = 0;
     for (uint32_t k : ks) for (uint32_t m : sizes) for (uint32_t last : lasts) for (int fill = 1; fill <= 2; fill++) {

@@ -1,21 +1,15 @@
-// tests/emu/typed_planes_main.cpp -- the stand-alone sanitizer program of the typed seekable kernels (tests/emu/build_asan_typed.sh): the split, join and seal
+// tests/emu/typed_planes_main.cpp -- the stand-alone sanitizer program of the typed seekable kernels (tests/emu/build_asan_planes.sh): the split, join and seal
 // bodies of python-zstandard_amd/csrc/zhip_seekable_typed.hpp under the host wave emulator, every buffer a heap allocation of exactly the bytes the kernel may
 // touch, at byte offsets 0, 1 and 3 from the allocation -- a read or a write one byte outside is the sanitizer's finding. The results are checked against
 // plain loops. Exit 0: every case held. Test infrastructure only.
 #include "emu_seekable_typed.cpp"
+#include "exact_buffers.hpp"
 
 static inline void zsk_wr32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
-static uint32_t g_seed = 12345;
-static uint8_t next_byte() { g_seed = g_seed * 1664525u + 1013904223u; return (uint8_t)(g_seed >> 24); }
-// `n` bytes at `offset` bytes into an allocation of exactly offset + n
-struct Exact {
-    std::unique_ptr<uint8_t[]> p; uint8_t* at;
-    Exact(size_t n, size_t offset, bool fill) : p(new uint8_t[n + offset]), at(p.get() + offset) { for (size_t i = 0; i < n; i++) at[i] = fill ? next_byte() : 0x5A; }
-};
-static int fail(const char* what, uint32_t k, uint64_t m, uint32_t off) { fprintf(stderr, "%s: k = %u, m = %llu, offset %u\n", what, k, (unsigned long long)m, off); return 1; }
 
 int main()
 {
+    g_seed = 12345;
     static const uint32_t sizes[] = {1, 15, 16, 17, 63, 64, 65, 1023, 1024, 1025}, offsets[] = {0, 1, 3}, ks[] = {2, 4, 8};
     int cases = 0;
     for (uint32_t k : ks) for (uint32_t m : sizes) for (uint32_t off : offsets) {

@@ -1,20 +1,13 @@
-// tests/emu/xor_planes_main.cpp -- the stand-alone sanitizer program of the xor-with-base filter's kernels (tests/emu/build_asan_xor.sh): the split-with-xor and
+// tests/emu/xor_planes_main.cpp -- the stand-alone sanitizer program of the xor-with-base filter's kernels (tests/emu/build_asan_planes.sh): the split-with-xor and
 // join-with-xor bodies of python-zstandard_amd/csrc/zhip_seekable_typed.hpp under the host wave emulator, every buffer -- the base among them -- a heap
 // allocation of exactly the bytes the kernel may touch, at byte offsets 0, 1 and 3 from the allocation: a read or a write one byte outside is the
 // sanitizer's finding. The results are checked against plain loops. Exit 0: every case held. Test infrastructure only.
 #include "emu_seekable_xor_base.cpp"
-
-static uint32_t g_seed = 97531;
-static uint8_t next_byte() { g_seed = g_seed * 1664525u + 1013904223u; return (uint8_t)(g_seed >> 24); }
-// `n` bytes at `offset` bytes into an allocation of exactly offset + n; fill 0: 0x5A, 1: random
-struct Exact {
-    std::unique_ptr<uint8_t[]> p; uint8_t* at;
-    Exact(size_t n, size_t offset, int fill) : p(new uint8_t[n + offset]), at(p.get() + offset) { for (size_t i = 0; i < n; i++) at[i] = fill == 0 ? 0x5A : next_byte(); }
-};
-static int fail(const char* what, uint32_t k, uint64_t m, uint32_t off) { fprintf(stderr, "%s: k = %u, m = %llu, offset %u\n", what, k, (unsigned long long)m, off); return 1; }
+#include "exact_buffers.hpp"
 
 int main()
 {
+    g_seed = 97531;
     static const uint32_t sizes[] = {1, 15, 16, 17, 1023, 1024, 1025, 2500}, lasts[] = {1, 15, 17}, offsets[] = {0, 1, 3}, ks[] = {2, 4, 8};
     int cases = 0, shape = 0;
     for (uint32_t k : ks) for (uint32_t m : sizes) for (uint32_t last : lasts) for (int kind = 0; kind < 3; kind++) {

@@ -481,7 +481,7 @@ def test_sanitizer_program(tmp_path):
     """tests/emu/chain_planes_main.cpp under AddressSanitizer and UBSan: the chain join body over the shapes above, every buffer -- every link's planar buffer
     and the base -- a heap allocation sized exactly. A program of its own, run as a subprocess"""
     exe = os.path.join(str(tmp_path), "chain_planes_asan")
-    subprocess.check_call(["sh", os.path.join(EMU, "build_asan_chain.sh"), exe])
+    subprocess.check_call(["sh", os.path.join(EMU, "build_asan_planes.sh"), "chain_planes_main.cpp", exe])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     assert r.returncode == 0, r.stdout.decode()[-2000:]
     assert b"cases" in r.stdout

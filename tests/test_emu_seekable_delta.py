@@ -398,7 +398,7 @@ def test_size_claim_with_libzstd_alone():
 def test_sanitizer_program(tmp_path):
     """tests/emu/delta_planes_main.cpp under AddressSanitizer and UBSan: the split, sums, offsets and join bodies over the shapes above, heap buffers sized exactly"""
     exe = os.path.join(str(tmp_path), "delta_planes_asan")
-    subprocess.check_call(["sh", os.path.join(EMU, "build_asan_delta.sh"), exe])
+    subprocess.check_call(["sh", os.path.join(EMU, "build_asan_planes.sh"), "delta_planes_main.cpp", exe])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     assert r.returncode == 0, r.stdout.decode()[-2000:]
     assert b"cases" in r.stdout

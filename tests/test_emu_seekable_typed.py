@@ -412,7 +412,7 @@ def test_refusals(lib):
 def test_sanitizer_program(tmp_path):
     """tests/emu/typed_planes_main.cpp under AddressSanitizer and UBSan: the split, join and seal bodies over the shapes above, heap buffers sized exactly"""
     exe = os.path.join(str(tmp_path), "typed_planes_asan")
-    subprocess.check_call(["sh", os.path.join(EMU, "build_asan_typed.sh"), exe])
+    subprocess.check_call(["sh", os.path.join(EMU, "build_asan_planes.sh"), "typed_planes_main.cpp", exe])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     assert r.returncode == 0, r.stdout.decode()[-2000:]
     assert b"cases" in r.stdout

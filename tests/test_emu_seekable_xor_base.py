@@ -450,7 +450,7 @@ def test_sanitizer_program(tmp_path):
     """tests/emu/xor_planes_main.cpp under AddressSanitizer and UBSan: the split and join bodies over the shapes above, every buffer -- the base too -- a heap
     allocation sized exactly. A program of its own, run as a subprocess"""
     exe = os.path.join(str(tmp_path), "xor_planes_asan")
-    subprocess.check_call(["sh", os.path.join(EMU, "build_asan_xor.sh"), exe])
+    subprocess.check_call(["sh", os.path.join(EMU, "build_asan_planes.sh"), "xor_planes_main.cpp", exe])
     r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     assert r.returncode == 0, r.stdout.decode()[-2000:]
     assert b"cases" in r.stdout
